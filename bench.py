@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the SIFT hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+results when --dump-outputs is given, and prints the headline JSON line.
+--full adds every side measurement listed below to that line.
 
 Workload (BASELINE.json configs[1], "C2"): synthetic 1920x1200 frames,
 detectAndCompute with numOctaveLayers=3 (5 DoG scales per octave), 3 octaves,
@@ -19,7 +23,7 @@ value = all frames' pixels / max-over-ranks wall time, in Mpix/s; the strictly
 serial one-frame-at-a-time rate and the synchronous per-frame latency are
 reported beside it.
 
-Side measurements in the same JSON line: 2000x2000x128 brute-force match (C3),
+Side measurements in the same JSON line (--full): 2000x2000x128 brute-force match (C3),
 the 8-way all-gather + pairwise match (C5) when N > 1, the per-kernel roofline of
 the dominant kernel (HIP events on the stream the kernels run on) and the CPU
 oracle on the host's cores (bounded sample).
@@ -69,6 +73,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=16,
                     help="frames per step: one launch per pipeline stage processes the whole batch "
                          "(sift_hip_set_batch); 1 = single-frame graphs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (single-stream, exact-descriptor and "
+                         "OpenCV-default legs, C4, host input, rooflines, C3/C5 match, CPU baseline, reference "
+                         "configurations) and report them in the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (keypoints, features, descriptors of its frames) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-oracle sample length")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-only", action="store_true",
@@ -515,6 +526,40 @@ def kernel_rooflines(det, timing, steps, B, pmc_path, first_octave=0):
                               "(L2-served windows: latency/VALU-bound)")
     return {k: v for k, v in out.items() if v}
 
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, det, B, suffix=""):
+    """--dump-outputs: what the last timed step left in its detector, as a
+    caller reads it back -- per frame the keypoints (x, y, response), the
+    features (octave word, size, response, angle) and the 128 descriptor
+    values, in the detector's own (deterministic) row order, frames
+    concatenated; `counts` holds the rows per frame.  All float32 except
+    counts (float64).  Past DUMP_LIMIT_BYTES a fixed seeded sample of the rows
+    is written, with their indices in `sample_rows`."""
+    if B == 1:
+        det.copyToHost(True)
+        per = [(det.final_kpts, det.final_features, det.descriptors)]
+    else:
+        per = [det.batch_copy_to_host(i, descriptor=True) for i in range(det.batch_frames())]
+    arrays = {"counts": np.array([len(k) for k, _, _ in per], np.float64),
+              "keypoints": np.concatenate([k for k, _, _ in per]).astype(np.float32),
+              "features": np.concatenate([f for _, f, _ in per]).astype(np.float32),
+              "descriptors": np.concatenate([d for _, _, d in per]).astype(np.float32)}
+    rows = len(arrays["keypoints"])
+    row_bytes = 4 * (3 + 4 + 128) + 8  # + its sample_rows entry
+    keep = (DUMP_LIMIT_BYTES - arrays["counts"].nbytes) // row_bytes
+    if rows > keep:
+        pick = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        for name in ("keypoints", "features", "descriptors"):
+            arrays[name] = arrays[name][pick]
+        arrays["sample_rows"] = pick.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -606,6 +651,43 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     value = world * a.steps * B * W * H / 1e6 / elapsed
     ms_per_frame = elapsed / (a.steps * B) * 1e3
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dets[(a.steps - 1) % len(dets)], B, "" if world == 1 else f"_rank{rank}")
+    head = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "library": sift.version(),
+        "config": {
+            "workload": f"C2: detectAndCompute on 1920x1200 frames, {B} per step per GPU (one launch per stage "
+                        "for the batch), numOctaveLayers=3 (5 DoG scales/octave), numOctaves=3, upscale=false, "
+                        "numFeatures=5000; frames HBM-resident",
+            "frames_per_step_per_gpu": B,
+            "frames_per_launch": B,
+            "streams_per_gpu": a.streams,
+            "parallelism": f"frame-sharded x{world}, no data-path collective",
+            "descriptor_mode": "exact" if a.exact_descriptors else "fixed-point (default)",
+            "keypoints_per_frame": kcount,
+        },
+        "ms_per_frame": round(ms_per_frame, 4),
+        "pipeline_hbm_frac": round(88.0 * sum_px / (ms_per_frame / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+    }
+    if not a.full:  # the plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     detb = dets[0]  # kept for the roofline pass (same frames per launch as the timed steps)
     del dets
 
@@ -1124,35 +1206,10 @@ def main():
 
     if rank == 0:
         line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "Mpix/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "library": sift.version(),
-            "config": {
-                "workload": f"C2: detectAndCompute on 1920x1200 frames, {B} per step per GPU (one launch per stage "
-                            "for the batch), numOctaveLayers=3 (5 DoG scales/octave), numOctaves=3, upscale=false, "
-                            "numFeatures=5000; frames HBM-resident",
-                "frames_per_step_per_gpu": B,
-                "frames_per_launch": B,
-                "streams_per_gpu": a.streams,
-                "parallelism": f"frame-sharded x{world}, no data-path collective",
-                "descriptor_mode": "exact" if a.exact_descriptors else "fixed-point (default)",
-                "keypoints_per_frame": kcount,
-            },
+            **head,
             "roofline": rl["roofline"],
             "roofline_kernels": rk,
             "cpu_baseline": cpu,
-            "ms_per_frame": round(ms_per_frame, 4),
-            "pipeline_hbm_frac": round(88.0 * sum_px / (ms_per_frame / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
             "sync_ms_per_frame": round(sync_ms, 4),
             "single_stream": {"value": round(single_value, 2), "ms_per_frame": round(single / n1 * 1e3, 4)},
             "exact_descriptors": exact_leg,

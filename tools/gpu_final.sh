@@ -5,10 +5,12 @@
 #                                    + a roctx marker trace of the eager stages
 #   tools/gpu_final.sh TAG bench  -- GPU tests, smoke, bench line, rocprof kernel stats of the bench,
 #                                    the roofline pass under rocprof
-# Outputs under gpurun_out/; summarise and copy into profiles/<round>/ (profiles/README.md).
+# The pmc session writes where tools/pmc.sh does, the bench session under $OUT (default profile_out/);
+# summarise and copy into profiles/<round>/ (profiles/README.md).
 set -o pipefail
 TAG=${1:-final}
 WHAT=${2:-bench}
+OUT=${OUT:-profile_out}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 if [ "$WHAT" = pmc ]; then
@@ -18,12 +20,13 @@ if [ "$WHAT" = pmc ]; then
   echo "pmc session done"
   exit 0
 fi
-timeout -k 10 600 python -u -m pytest tests/ -q -m gpu -x --timeout 120 --timeout-method thread > gpurun_out/pytest_$TAG.log 2>&1
-rc=$?; echo "pytest rc=$rc"; tail -3 gpurun_out/pytest_$TAG.log
+mkdir -p "$OUT"
+timeout -k 10 600 python -u -m pytest tests/ -q -m gpu -x --timeout 120 --timeout-method thread > $OUT/pytest_$TAG.log 2>&1
+rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_$TAG.log
 case $rc in 0|1) ;; *) exit $rc ;; esac
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.txt 2>&1 || { echo "smoke failed"; tail -5 gpurun_out/smoke_$TAG.txt; exit 1; }
-cat gpurun_out/smoke_$TAG.txt | tail -1
-timeout -k 10 400 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { echo "bench failed"; tail -20 gpurun_out/bench_$TAG.err; exit 1; }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline > gpurun_out/prof_$TAG.log 2>&1 || { echo "bench prof failed"; exit 1; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/roof_$TAG -o run --output-format csv -- python bench.py --roofline-only --steps 100 > gpurun_out/roof_$TAG.json 2> gpurun_out/roof_$TAG.err || { echo "roofline prof failed"; exit 1; }
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.txt 2>&1 || { echo "smoke failed"; tail -5 $OUT/smoke_$TAG.txt; exit 1; }
+cat $OUT/smoke_$TAG.txt | tail -1
+timeout -k 10 400 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench failed"; tail -20 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1 || { echo "bench prof failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/roof_$TAG -o run --output-format csv -- python bench.py --roofline-only --steps 100 > $OUT/roof_$TAG.json 2> $OUT/roof_$TAG.err || { echo "roofline prof failed"; exit 1; }
 echo "bench session done"
