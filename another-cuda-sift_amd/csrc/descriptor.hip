@@ -308,10 +308,18 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
         // Fixed-point scale 2^S with every bin < 2^31: a contribution is at most
         // the gradient magnitude <= sqrt(2) * range, and a bin collects samples
         // from a 2x2-cell rotated square of side 2*hist_width, i.e. at most
-        // (2*sqrt(2)*hist_width + 2)^2 samples.
+        // (2*sqrt(2)*hist_width + 2)^2 samples -- and never more than the
+        // plane's interior samples, the only ones that pass the oracle's test
+        // (0 < r < rows - 1, 0 < c < cols - 1).  The second bound matters where
+        // the window is larger than the plane (the coarsest octaves, and
+        // caller-supplied keypoints of any size): sized for the window alone,
+        // the scale left a 6 x 5 plane's twelve faint samples a percent of a bin
+        // of truncation each, and entries 2 off the oracle.  Where the plane
+        // holds the window (every plane of the C2 workload) S is unchanged.
         const float nb = 2.8285f * jb.hist_width + 2.f;
+        const float interior = (float)max(max(jb.rows - 2, 0) * max(jb.cols - 2, 0), 1);
         int e;
-        (void)frexpf(nb * nb * 1.4143f * range + 1.f, &e);
+        (void)frexpf(fminf(nb * nb, interior) * 1.4143f * range + 1.f, &e);
         const int S = min(31 - e, 40);
         const float fxs = ldexpf(1.f, S);
         lds_barrier();

@@ -542,6 +542,16 @@ void enqueue_descriptor(sift_hip_detector* d, int slot, int nf) {
     });
 }
 
+// Descriptor jobs of caller-supplied keypoints (one frame): stands in for
+// extrema .. order of the detect chain, their housekeeping included
+// (k_provided_jobs).
+void enqueue_provided(sift_hip_detector* d, int slot, const ProvidedKpt* kpts, int n) {
+    d->timed("provided_jobs", (double)n * (sizeof(ProvidedKpt) + sizeof(DescJob) + 28), [&] {
+        launch_provided_jobs(d->pyr, kpts, n, d->cfg.col_width, d->cfg.row_width, d->dCtr, range_keys(d, (slot & 1) ^ 1),
+                             d->dJobs, d->dKpts3[slot], d->dFeats4[slot], d->stream);
+    });
+}
+
 void enqueue_body(sift_hip_detector* d, int slot, int nf) {
     enqueue_pyramid(d, nf, slot & 1);  // kSlots is even, so slot parity = frame parity
     enqueue_extrema(d, nf);
@@ -638,11 +648,12 @@ int warm_lane(sift_hip_detector* d) {
 // micro-batch (`numbered`) takes nf numbers, frame d->submitted + i in arena i.  With stage dumps on (single frames after warm-up) the frame's
 // input is kept as float, the frame is completed synchronously and dumped.
 int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf, long sfs,
-              bool numbered) {
+              bool numbered, const ProvidedKpt* provided, int nProvided) {
     const long long f = d->submitted;
     Lane& L = d->lane();
     const int slot = (int)(L.launched % L.nslots);
-    const bool dump = !d->dgDir.empty() && nf == 1 && d->firstFrame > 0;
+    const bool compute = nProvided >= 0;  // (a stage dump records the detect chain: not for compute frames)
+    const bool dump = !d->dgDir.empty() && nf == 1 && d->firstFrame > 0 && !compute;
     const int W = d->cfg.col_width, H = d->cfg.row_width;
     if (dump) {
         if (!d->dDg && hipMalloc((void**)&d->dDg, sizeof(float) * (size_t)W * H) != hipSuccess)
@@ -653,7 +664,7 @@ int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEven
             HIPCHK(hipMemcpy2DAsync(d->dDg, sizeof(float) * W, img, sizeof(float) * (size_t)pitch, sizeof(float) * W,
                                     H, hipMemcpyDefault, d->stream));
     }
-    const bool graphs = d->useGraph && !d->timing;
+    const bool graphs = d->useGraph && !d->timing && !compute;
     hipGraphExec_t gh = !graphs || consumed || fmt != SIFT_HIP_F32 ? nullptr
                         : nf == L.B                                  ? L.execH[slot]
                         : nf == 1                                    ? L.execH1[slot]
@@ -679,6 +690,10 @@ int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEven
         hipGraphExec_t g = nf == L.B ? L.exec[slot] : (nf == 1 ? L.exec1[slot] : nullptr);
         if (graphs && g) {
             HIPCHK(hipGraphLaunch(g, d->stream));
+        } else if (compute) {  // caller-supplied keypoints: pyramid -> jobs -> descriptor, eagerly
+            enqueue_pyramid(d, 1, slot & 1);
+            enqueue_provided(d, slot, provided, nProvided);
+            enqueue_descriptor(d, slot, 1);
         } else {  // timing mode, or a partial batch: the same launches, eagerly
             enqueue_body(d, slot, nf);
         }
@@ -785,6 +800,43 @@ int batch_frames_of(sift_hip_detector* d) {
         HIPCHK(hipSetDevice((h)->device));                                                    \
         bind_lane((h), (h)->curLane, (h)->curIdx);                                            \
     } while (0)
+
+// ---- caller-supplied keypoints (sift_hip_check_keypoints / sift_hip_compute*) ----
+static_assert(sizeof(sift_hip_keypoint) == sizeof(ProvidedKpt) && offsetof(sift_hip_keypoint, octave) == offsetof(ProvidedKpt, octave),
+              "sift_hip_keypoint is the kernels' ProvidedKpt");
+static const ProvidedKpt* as_provided(const sift_hip_keypoint* k) { return reinterpret_cast<const ProvidedKpt*>(k); }
+
+static int check_keypoint_count(const sift_hip_detector* d, const sift_hip_keypoint* kpts, int n) {
+    if (n < 0) return fail(SIFT_HIP_ERR_INVALID, "negative keypoint count");
+    if ((unsigned)n > d->kp.capFinal)
+        return fail(SIFT_HIP_ERR_INVALID, "keypoint count " + std::to_string(n) + " above the result capacity " +
+                                              std::to_string(d->kp.capFinal) + " (sift_hip_capacities)");
+    if (n > 0 && !kpts) return fail(SIFT_HIP_ERR_INVALID, "null keypoints");
+    return SIFT_HIP_OK;
+}
+
+// Index of the first host keypoint that provided_kpt_valid rejects, or -1.
+static int first_bad_keypoint(const sift_hip_detector* d, const sift_hip_keypoint* kpts, int n) {
+    for (int i = 0; i < n; i++)
+        if (!provided_kpt_valid(as_provided(kpts)[i], d->firstOctave, d->nOct, d->L, d->cfg.col_width, d->cfg.row_width))
+            return i;
+    return -1;
+}
+
+// sift_hip_compute / sift_hip_compute_u8: keypoints validated here, then a
+// host-input frame of the compute chain, waited for (as sift_hip_detect).
+static int compute_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, const sift_hip_keypoint* kpts, int n) {
+    if (int rc = check_keypoint_count(d, kpts, n)) return rc;
+    const int bad = first_bad_keypoint(d, kpts, n);
+    if (bad >= 0)
+        return fail(SIFT_HIP_ERR_INVALID, "keypoint " + std::to_string(bad) + " is invalid (sift_hip_check_keypoints)");
+    if (!d->hKpts &&
+        hipHostMalloc((void**)&d->hKpts, sizeof(ProvidedKpt) * (size_t)d->kp.capFinal, hipHostMallocMapped) != hipSuccess)
+        return fail(SIFT_HIP_ERR_NOMEM, "hipHostMalloc of the keypoint staging failed");
+    long long f = 0;
+    const int rc = submit_host(d, img, stride, fmt, &f, as_provided(kpts), n);
+    return rc ? rc : wait_frame(d, f);
+}
 
 extern "C" {
 
@@ -943,6 +995,48 @@ int sift_hip_submit_device(sift_hip_t d, const void* img, size_t stride, int for
 
 int sift_hip_detect_device(sift_hip_t d, const float* img, size_t stride, void* stream) {
     return sift_hip_detect_device_fmt(d, img, stride, SIFT_HIP_F32, stream);
+}
+
+int sift_hip_check_keypoints(sift_hip_t d, const sift_hip_keypoint* kpts, int n, int* first_bad) {
+    if (!d) return fail(SIFT_HIP_ERR_INVALID, "null handle");
+    if (first_bad) *first_bad = -1;
+    if (int rc = check_keypoint_count(d, kpts, n)) return rc;
+    if (first_bad) *first_bad = first_bad_keypoint(d, kpts, n);
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_compute(sift_hip_t d, const float* img, size_t stride, const sift_hip_keypoint* kpts, int n) {
+    CHECK_HANDLE(d);
+    return compute_host(d, img, stride, SIFT_HIP_F32, kpts, n);
+}
+
+int sift_hip_compute_u8(sift_hip_t d, const uint8_t* img, size_t stride, const sift_hip_keypoint* kpts, int n) {
+    CHECK_HANDLE(d);
+    return compute_host(d, img, stride, SIFT_HIP_U8, kpts, n);
+}
+
+int sift_hip_compute_device(sift_hip_t d, const void* img, size_t stride, int format, const sift_hip_keypoint* dev_kpts,
+                            int n, void* stream) {
+    CHECK_HANDLE(d);
+    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
+    const int es = format_size(format);
+    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
+    const int W = d->cfg.col_width;
+    if (stride == 0) stride = (size_t)es * W;
+    if (stride % es || stride < (size_t)es * W)
+        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    if (int rc = check_keypoint_count(d, dev_kpts, n)) return rc;
+    if (int rc = check_in_flight(d)) return rc;
+    long long f = 0;
+    // The lane waits for `stream` before it reads the image or the keypoints
+    // (k_provided_jobs validates them: they cannot be read here).
+    if (int rc = submit_device(d, img, stride, format, stream, 1, 0, &f, false, as_provided(dev_kpts), n)) return rc;
+    make_current(d, f);
+    if (stream) {
+        HIPCHK(hipEventRecord(d->evOut, d->stream));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
+    }
+    return SIFT_HIP_OK;
 }
 
 int sift_hip_set_batch(sift_hip_t d, int frames) {

@@ -14,6 +14,8 @@
 #include <cstdlib>
 #include <iostream>
 #include <memory>
+#include <stdexcept>
+#include <string>
 
 #include "sift_hip.h"
 
@@ -94,11 +96,15 @@ void Detector::warnOverflow() {
     int flags = 0;
     if (!m_handle || sift_hip_overflow_flags(m_handle, &flags) != SIFT_HIP_OK || !flags) return;
     if ((flags & ~m_overflowWarned) == 0) return;
+    const int fresh = flags & ~m_overflowWarned;
     m_overflowWarned |= flags;
-    std::fprintf(stderr,
-                 "sift_cuda::Detector: capacity overflow (flags 0x%x: 1 candidates, 2 refined, 4 oriented, "
-                 "8 results); keypoints were dropped -- raise CudaSiftConfig::maxKeypoints\n",
-                 flags);
+    if (fresh & 15)
+        std::fprintf(stderr,
+                     "sift_cuda::Detector: capacity overflow (flags 0x%x: 1 candidates, 2 refined, 4 oriented, "
+                     "8 results); keypoints were dropped -- raise CudaSiftConfig::maxKeypoints\n",
+                     flags);
+    if (fresh & SIFT_HIP_FLAG_BAD_KEYPOINT)
+        std::fprintf(stderr, "sift_cuda::Detector: computeDevice met an invalid keypoint (flag 16); its descriptor row is zero\n");
 }
 
 void Detector::detectAndCompute(const Imagef& image) {
@@ -176,6 +182,57 @@ void Detector::detectAndComputeDevice(const float* dev, size_t stride, void* str
     if (!m_initialized && !gpuWarmUpAndAllocate()) return;
     check(sift_hip_detect_device(m_handle, dev, stride, stream), "detectAndComputeDevice");
     check(sift_hip_sync(m_handle), "detectAndComputeDevice sync");
+    refreshViews();
+}
+
+namespace {
+
+static_assert(sizeof(KeyPoint) == sizeof(sift_hip_keypoint), "sift_cuda::KeyPoint is sift_hip_keypoint");
+
+// compute / computeDevice report errors by exception (a bad keypoint list is
+// the caller's to handle, unlike a failed HIP call in the detect path).
+void check_throw(int rc, const char* what) {
+    if (rc == SIFT_HIP_OK) return;
+    const std::string msg = std::string(what) + ": " + sift_hip_last_error() + " (status " + std::to_string(rc) + ")";
+    if (rc == SIFT_HIP_ERR_INVALID) throw std::invalid_argument(msg);
+    throw std::runtime_error(msg);
+}
+
+const sift_hip_keypoint* abi_kpts(const KeyPoint* k) { return reinterpret_cast<const sift_hip_keypoint*>(k); }
+
+template <class T>
+void check_shape_throw(const Image<T>& image, const CudaSiftConfig& c) {
+    if (!image.m_data || image.cols() != c.col_width || image.rows() != c.row_width)
+        throw std::invalid_argument("compute: image is " + std::to_string(image.cols()) + "x" + std::to_string(image.rows()) +
+                                    ", detector configured for " + std::to_string(c.col_width) + "x" +
+                                    std::to_string(c.row_width));
+}
+
+}  // namespace
+
+void Detector::compute(const Imagef& image, const std::vector<KeyPoint>& keypoints) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) throw std::runtime_error("compute: detector not initialised");
+    check_shape_throw(image, m_config);
+    check_throw(sift_hip_compute(m_handle, image.m_data->data(), sizeof(float) * (size_t)image.cols(),
+                                 abi_kpts(keypoints.data()), (int)keypoints.size()),
+                "compute");
+    refreshViews();
+}
+
+void Detector::compute(const Image8U& image, const std::vector<KeyPoint>& keypoints) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) throw std::runtime_error("compute: detector not initialised");
+    check_shape_throw(image, m_config);
+    check_throw(sift_hip_compute_u8(m_handle, image.m_data->data(), (size_t)image.cols(), abi_kpts(keypoints.data()),
+                                    (int)keypoints.size()),
+                "compute");
+    refreshViews();
+}
+
+void Detector::computeDevice(const void* dev, size_t stride, bool u8, const KeyPoint* dev_kpts, int n, void* stream) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) throw std::runtime_error("computeDevice: detector not initialised");
+    check_throw(sift_hip_compute_device(m_handle, dev, stride, u8 ? SIFT_HIP_U8 : SIFT_HIP_F32, abi_kpts(dev_kpts), n, stream),
+                "computeDevice");
+    check_throw(sift_hip_sync(m_handle), "computeDevice sync");
     refreshViews();
 }
 

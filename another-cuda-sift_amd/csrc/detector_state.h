@@ -340,6 +340,10 @@ struct sift_hip_detector {
     bool useGraph = true;
 
     CopyPool* pool = nullptr;  // staging copies of large host frames (created at the first one)
+    // Pinned staging of host keypoints (sift_hip_compute): capFinal entries,
+    // allocated at the first compute call (a detect-only caller pays nothing).
+    // One buffer: the call is synchronous, so its kernel has read it on return.
+    ProvidedKpt* hKpts = nullptr;
     // The most the caller's sift_hip_copy_to_host / sift_hip_results_host
     // calls took (0 nothing yet, 1 keypoints, 2 keypoints + descriptors):
     // host-input frames have their descriptor kernel write that much to
@@ -431,6 +435,7 @@ struct sift_hip_detector {
                 if (L.stream) (void)hipStreamDestroy(L.stream);
             }
             if (dDg) (void)hipFree(dDg);
+            if (hKpts) (void)hipHostFree(hKpts);
             for (auto e : evPool) (void)hipEventDestroy(e);
             if (hstBlock) (void)hipHostFree(hstBlock);
             for (hipEvent_t e : hstRead) (void)hipEventDestroy(e);
@@ -468,9 +473,12 @@ void enqueue_refine(sift_hip_detector* d, int nf);
 void enqueue_orientation(sift_hip_detector* d, int nf);
 void enqueue_order(sift_hip_detector* d, int slot, int nf);
 void enqueue_descriptor(sift_hip_detector* d, int slot, int nf);
+void enqueue_provided(sift_hip_detector* d, int slot, const ProvidedKpt* kpts, int n);
 bool event_done(hipEvent_t e);
+// nProvided >= 0 (<= capFinal): the frame describes the nProvided
+// device-readable keypoints `provided` instead of detecting (sift_hip_compute*).
 int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf = 1, long sfs = 0,
-              bool numbered = false);
+              bool numbered = false, const ProvidedKpt* provided = nullptr, int nProvided = -1);
 void make_current(sift_hip_detector* d, long long f);
 void complete_counts(sift_hip_detector* d);
 int ensure_counts(sift_hip_detector* d);
@@ -488,10 +496,12 @@ int check_in_flight(sift_hip_detector* d);
 size_t host_res_bytes(const sift_hip_detector* d);
 void host_res(const sift_hip_detector* d, char* base, int region, float** k3, float** f4, uint16_t** desc);
 int ensure_host_res(sift_hip_detector* d, Lane& L);
-int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket);
+// n >= 0: a compute frame of the n host keypoints `kpts` (already validated).
+int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
+                const ProvidedKpt* kpts = nullptr, int n = -1);
 int run_group(sift_hip_detector* d);
 int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue = false);
+                  long long* ticket, bool queue = false, const ProvidedKpt* devKpts = nullptr, int n = -1);
 int wait_frame(sift_hip_detector* d, long long f);
 
 // ---- datagen.hip ----

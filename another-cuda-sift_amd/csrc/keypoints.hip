@@ -787,20 +787,23 @@ bool launch_order(const PyrDesc& pyr, const OriKpt* kpts, Counters* ctr, unsigne
 // octave scale, angle flip 360 - angle) and the head of calcSIFTDescriptor
 // (cos/sin / hist_width, radius clamped to the image diagonal), computed once
 // per keypoint here so the descriptor workgroup starts from scalar loads.
-__device__ DescJob make_desc_job(const PyrDesc& pyr, const OriKpt& kpt, long foff) {
+// One body for both callers: the detector's final keypoints (make_desc_job)
+// and caller-supplied ones (k_provided_jobs).
+__device__ __forceinline__ DescJob desc_job_of(const PyrDesc& pyr, float x, float y, float ksize, float kangle,
+                                               int packed_octave, long foff) {
     DescJob j;
-    int octave = kpt.octave & 255;
-    const int layer = (kpt.octave >> 8) & 255;
+    int octave = packed_octave & 255;
+    const int layer = (packed_octave >> 8) & 255;
     octave = octave < 128 ? octave : (-128 | octave);
     const float scale = octave >= 0 ? 1.f / (float)(1 << octave) : (float)(1 << -octave);
-    const float size = kpt.size * scale;
-    const float ptfx = kpt.x * scale, ptfy = kpt.y * scale;
+    const float size = ksize * scale;
+    const float ptfx = x * scale, ptfy = y * scale;
     const OctGeom& g = pyr.oct[octave - pyr.firstOctave];
     j.img = fptr(g.base, foff) + (size_t)layer * g.planeStride;
     j.pitch = g.pitch;
     j.rows = g.H;
     j.cols = g.W;
-    float angle = 360.f - kpt.angle;
+    float angle = 360.f - kangle;
     if (fabsf(angle - 360.f) < FLT_EPSILON) angle = 0.f;
     j.angle = angle;
     const float scl = size * 0.5f;
@@ -816,6 +819,9 @@ __device__ DescJob make_desc_job(const PyrDesc& pyr, const OriKpt& kpt, long fof
     j.out = 0;
     j.pad[0] = j.pad[1] = j.pad[2] = 0;
     return j;
+}
+__device__ __forceinline__ DescJob make_desc_job(const PyrDesc& pyr, const OriKpt& kpt, long foff) {
+    return desc_job_of(pyr, kpt.x, kpt.y, kpt.size, kpt.angle, kpt.octave, foff);
 }
 
 // Final order inside each row bucket (rank by sub key), then write the
@@ -936,6 +942,67 @@ void launch_bucket_rank(const PyrDesc& pyr, const OriKpt* kpts, unsigned* bcount
                         const KeypointParams& kp, const Frames& fr, hipStream_t s) {
     hipLaunchKernelGGL(k_bucket_rank, dim3(per_frame_blocks(256, fr.nf), fr.nf), dim3(256), 0, s, pyr, kpts, bcount,
                        boff, order, ctr, jobs, kpts3, feats4, kp, fr.stride);
+}
+
+// ---------------------------------------------------------------------------
+// Descriptor jobs of caller-supplied keypoints (sift_hip_compute*): the chain
+// pyramid -> k_provided_jobs -> descriptor, without extrema / refine /
+// orientation / order.  Thread i: jobs[i] (output row i, the caller's order),
+// kpts3 and feats4 from the input.  An invalid keypoint (device keypoints
+// cannot be checked on the host) gets a null job -- an empty window (radius 0
+// over a plane of 0 rows: no row passes 0 < r < rows - 1 and every buffer load
+// is out of range), whose histogram stays zero through the norm, clip and x512
+// steps: a zero descriptor row -- and sets kFlagBadKeypoint.
+// Workgroup 0 also does the frame's housekeeping that k_order / k_select do on
+// the detect path: final_n, the host-results request moved to its level half,
+// and the other parity's range keys zeroed for the next frame.  (The dedupe
+// bitmap and the bucket counts are not touched on this path and stay zero.)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_provided_jobs(PyrDesc pyr, const ProvidedKpt* __restrict__ kpts, unsigned n, int W,
+                                                       int H, Counters* __restrict__ ctr,
+                                                       unsigned* __restrict__ zero_range, DescJob* __restrict__ jobs,
+                                                       float* __restrict__ kpts3, float* __restrict__ feats4) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0) {
+        for (int i = tid; i < 2 * kRangeSlots; i += 256) zero_range[i] = 0u;  // next frame's range keys
+        if (tid == 0) {
+            ctr->final_n = n;
+            ctr->pad[1] >>= kHostReqShift;  // host results request -> level (HostOut)
+        }
+    }
+    const unsigned i = blockIdx.x * 256u + tid;
+    if (i >= n) return;
+    const ProvidedKpt k = kpts[i];
+    DescJob j;
+    if (provided_kpt_valid(k, pyr.firstOctave, pyr.nOct, pyr.L, W, H)) {
+        j = desc_job_of(pyr, k.x, k.y, k.size, k.angle, k.octave, 0);
+    } else {
+        const OctGeom& g = pyr.oct[0];
+        j.img = g.base;
+        j.cos_t = 1.f;
+        j.sin_t = 0.f;
+        j.angle = 0.f;
+        j.hist_width = 1.f;
+        j.ptx = j.pty = 0;
+        j.rows = j.cols = 0;
+        j.pitch = g.pitch;
+        j.radius = 0;
+        j.pad[0] = j.pad[1] = j.pad[2] = 0;
+        atomicOr(&ctr->overflow, kFlagBadKeypoint);
+    }
+    j.out = (int)i;
+    jobs[i] = j;
+    kpts3[3 * (size_t)i + 0] = k.x;
+    kpts3[3 * (size_t)i + 1] = k.y;
+    kpts3[3 * (size_t)i + 2] = (float)((k.octave >> 8) & 255);
+    reinterpret_cast<float4*>(feats4)[i] = make_float4((float)k.octave, k.size, k.response, k.angle);
+}
+
+void launch_provided_jobs(const PyrDesc& pyr, const ProvidedKpt* kpts, int n, int W, int H, Counters* ctr,
+                          unsigned* zero_range, DescJob* jobs, float* kpts3, float* feats4, hipStream_t s) {
+    const unsigned blocks = (unsigned)std::max(1, (n + 255) / 256);  // n = 0: the housekeeping alone
+    hipLaunchKernelGGL(k_provided_jobs, dim3(blocks), dim3(256), 0, s, pyr, kpts, (unsigned)n, W, H, ctr, zero_range,
+                       jobs, kpts3, feats4);
 }
 
 // ---------------------------------------------------------------------------

@@ -236,7 +236,8 @@ int queue_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, lo
 // return) -> device staging by a small-grid copy kernel on the lane's stream
 // -> pipeline on the frame's lane -> results to pinned host memory.  On a
 // micro-batching handle the frame joins the pending group (queue_host).
-int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket) {
+int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
+                const ProvidedKpt* kpts, int n) {
     const int es = format_size(fmt);
     if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
     if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
@@ -245,7 +246,7 @@ int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, l
     if (stride == 0) stride = rowB;
     if (stride < rowB) return fail(SIFT_HIP_ERR_INVALID, "row stride smaller than width");
     if (int rc = check_in_flight(d)) return rc;
-    if (queue_frame(d)) return queue_host(d, img, stride, fmt, ticket);
+    if (n < 0 && queue_frame(d)) return queue_host(d, img, stride, fmt, ticket);
     if (int rc = run_group(d)) return rc;  // pending micro-batch frames keep their submission order
     if (int rc = pick_lane(d)) return rc;
     Lane& L = d->lane();
@@ -265,7 +266,12 @@ int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, l
     L.uploads++;
     d->uploads++;
     const long long f = d->submitted;
-    if (int rc = run_frame(d, L.dStage[k], d->inPitch, fmt, nullptr)) return rc;
+    const ProvidedKpt* devKpts = nullptr;
+    if (n > 0) {  // host keypoints: through the pinned staging, read by k_provided_jobs over PCIe (24 B each)
+        memcpy(d->hKpts, kpts, sizeof(ProvidedKpt) * (size_t)n);
+        HIPCHK(hipHostGetDevicePointer((void**)&devKpts, d->hKpts, 0));
+    }
+    if (int rc = run_frame(d, L.dStage[k], d->inPitch, fmt, nullptr, 1, 0, false, devKpts, n)) return rc;
     if (reqAt) mark_host_results(d, f);
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;
@@ -336,7 +342,7 @@ int run_group(sift_hip_detector* d) {
 // frame of sift_hip_submit_device on a micro-batching handle joins the pending
 // group instead.
 int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue) {
+                  long long* ticket, bool queue, const ProvidedKpt* devKpts, int n) {
     hipStream_t ext = (hipStream_t)stream;
     if (queue && nf == 1 && queue_frame(d)) {
         const int i = d->npend;
@@ -359,7 +365,8 @@ int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt,
         HIPCHK(hipStreamWaitEvent(d->stream, d->evIn, 0));
     }
     const long long f = d->submitted;
-    if (int rc = run_frame(d, img, (int)(stride / format_size(fmt)), fmt, nullptr, nf, (long)fstride)) return rc;
+    if (int rc = run_frame(d, img, (int)(stride / format_size(fmt)), fmt, nullptr, nf, (long)fstride, false, devKpts, n))
+        return rc;
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;
 }

@@ -224,6 +224,43 @@ static_assert(sizeof(DescJob) == 64, "DescJob is one 64-byte scalar load");
 void launch_rank_final(const PyrDesc& pyr, const OriKpt* kpts, const unsigned* bcount, const unsigned* boff,
                        const int* order, const Counters* ctr, const JobOrder* jord, DescJob* jobs, float* kpts3, float* feats4,
                        const KeypointParams& kp, const Frames& fr, hipStream_t s);
+
+// Caller-supplied keypoints (sift_hip_compute*): cv::KeyPoint minus class_id,
+// the layout of sift_hip_keypoint (include/sift_hip.h).
+struct ProvidedKpt {
+    float x, y, size, angle, response;
+    int octave;  // OpenCV's packed form: octave & 255 | layer << 8 | xi << 16
+};
+static_assert(sizeof(ProvidedKpt) == 24, "ProvidedKpt is sift_hip_keypoint");
+constexpr unsigned kFlagBadKeypoint = 16u;  // Counters.overflow bit 4 (SIFT_HIP_FLAG_BAD_KEYPOINT)
+
+// Validity of a caller-supplied keypoint for a pyramid of nOct octaves from
+// firstOctave with L + 3 planes each, over a W x H input image: the one rule
+// of sift_hip_check_keypoints (host) and k_provided_jobs (device keypoints).
+// Octave and layer address a Gaussian plane; x, y, size finite and size > 0;
+// 0 <= angle <= 360 (the descriptor kernels need obin in (-8, 8)); the point
+// within one image size of the frame (-W <= x <= 2W, -H <= y <= 2H), which
+// bounds the integer position arithmetic.  NaN fails every comparison.
+__host__ __device__ inline bool provided_kpt_valid(const ProvidedKpt& k, int firstOctave, int nOct, int L, int W, int H) {
+    int o = k.octave & 255;
+    o = o < 128 ? o : (-128 | o);
+    const int layer = (k.octave >> 8) & 255;
+    const float big = 3.402823466e+38f;  // FLT_MAX: |v| <= big is false for inf and NaN
+    return o >= firstOctave && o <= firstOctave + nOct - 1 && layer <= L + 2 &&
+           (k.x < 0 ? -k.x : k.x) <= big && (k.y < 0 ? -k.y : k.y) <= big && k.size <= big && k.size > 0.f &&
+           k.angle >= 0.f && k.angle <= 360.f && k.x >= -(float)W && k.x <= 2.f * (float)W && k.y >= -(float)H &&
+           k.y <= 2.f * (float)H;
+}
+
+// One thread per caller-supplied keypoint i: its descriptor job (make_desc_job's
+// body) into jobs[i] with out = i, kpts3 {x, y, layer} and feats4 {(float)octave,
+// size, response, angle} from the input; an invalid keypoint gets a null job
+// (an empty window: a zero descriptor row) and sets kFlagBadKeypoint.  It also
+// does what the stages it stands in for do for the frame and its successor:
+// final_n = n, the host-results request -> level (Counters.pad[1]), and the
+// other parity's range keys zeroed (zero_range).  n <= capFinal (host-checked).
+void launch_provided_jobs(const PyrDesc& pyr, const ProvidedKpt* kpts, int n, int W, int H, Counters* ctr,
+                          unsigned* zero_range, DescJob* jobs, float* kpts3, float* feats4, hipStream_t s);
 // Results of a finished frame -> mapped pinned host buffers (host-input frames).
 // Frame rows (rowB bytes, `rows` of them, pitches in bytes) copied by `wgs`
 // 256-thread workgroups on the lane stream: host staging -> device, and

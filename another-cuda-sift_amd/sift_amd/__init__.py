@@ -35,6 +35,10 @@ LIB_PATH = os.environ.get("SIFT_HIP_LIB") or os.path.join(LIB_DIR, "libsift_hip.
 SIFT_HIP_OK = 0
 SIFT_HIP_F32, SIFT_HIP_U8 = 0, 1  # pixel formats (include/sift_hip.h)
 SIFT_HIP_DESC_FAST, SIFT_HIP_DESC_EXACT = 0, 1  # descriptor modes (sift_hip_set_descriptor_mode)
+SIFT_HIP_FLAG_BAD_KEYPOINT = 16  # overflow_flags() bit: computeDevice met an invalid keypoint
+# sift_hip_keypoint (cv::KeyPoint minus class_id, 24 bytes): the records Detector.compute takes.
+# octave is OpenCV's packed form (octave & 255 | layer << 8 | xi << 16).
+KPT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
 _lib = None
 
 
@@ -44,6 +48,10 @@ class SiftHipError(RuntimeError):
 
 class SiftCapacityWarning(RuntimeWarning):
     """A per-frame capacity (candidates, refined, oriented, results) overflowed; see overflow_flags()."""
+
+
+class SiftKeypointWarning(RuntimeWarning):
+    """computeDevice met an invalid keypoint (overflow_flags() bit 16): its descriptor row is zero."""
 
 
 class _Config(ctypes.Structure):
@@ -92,6 +100,10 @@ def lib() -> ctypes.CDLL:
         "sift_hip_detect_device": (i, [vp, vp, sz, vp]),
         "sift_hip_detect_u8": (i, [vp, vp, sz]),
         "sift_hip_detect_device_fmt": (i, [vp, vp, sz, i, vp]),
+        "sift_hip_check_keypoints": (i, [vp, vp, i, ip]),
+        "sift_hip_compute": (i, [vp, vp, sz, vp, i]),
+        "sift_hip_compute_u8": (i, [vp, vp, sz, vp, i]),
+        "sift_hip_compute_device": (i, [vp, vp, sz, i, vp, i, vp]),
         "sift_hip_submit": (i, [vp, vp, sz, i, ctypes.POINTER(ctypes.c_longlong)]),
         "sift_hip_wait": (i, [vp, ctypes.c_longlong]),
         "sift_hip_submit_device": (i, [vp, vp, sz, i, vp, ctypes.POINTER(ctypes.c_longlong)]),
@@ -332,6 +344,10 @@ class Detector:
         new = flags & ~getattr(self, "_overflow_warned", 0)
         if new:
             self._overflow_warned = getattr(self, "_overflow_warned", 0) | flags
+        if new & SIFT_HIP_FLAG_BAD_KEYPOINT:
+            warnings.warn("computeDevice met an invalid keypoint (flag 16, check_keypoints names it); its descriptor "
+                          "row is zero", SiftKeypointWarning, stacklevel=3)
+        if new & 15:
             warnings.warn(f"capacity overflow (flags {flags:#x}: 1 candidates, 2 refined, 4 oriented, 8 results); "
                           f"keypoints were dropped -- raise CudaSiftConfig.maxKeypoints", SiftCapacityWarning, stacklevel=3)
 
@@ -354,6 +370,47 @@ class Detector:
         else:
             _check(lib().sift_hip_detect(self._h, _ptr(img), img.strides[0]), "detectAndCompute")
         self._refresh()
+
+    # --- descriptors for the caller's own keypoints (cv::Feature2D::compute) ------
+    @staticmethod
+    def _kpt_records(kpts) -> np.ndarray:
+        k = np.ascontiguousarray(kpts, dtype=KPT_DTYPE) if not isinstance(kpts, np.ndarray) or kpts.dtype != KPT_DTYPE \
+            else np.ascontiguousarray(kpts)
+        return k.reshape(-1)
+
+    def check_keypoints(self, kpts) -> int:
+        """Index of the first keypoint (KPT_DTYPE records) compute would refuse, or -1 (sift_hip_check_keypoints;
+        host-only, valid before warm-up).  More keypoints than the result capacity raise SiftHipError."""
+        k = self._kpt_records(kpts)
+        bad = ctypes.c_int(-1)
+        _check(lib().sift_hip_check_keypoints(self._h, _ptr(k) if len(k) else None, len(k), ctypes.byref(bad)),
+               "check_keypoints")
+        return bad.value
+
+    def compute(self, image: np.ndarray, kpts) -> None:
+        """Descriptors of the caller's keypoints on `image` (float32 or uint8, as detectAndCompute):
+        sift_hip_compute / sift_hip_compute_u8.  `kpts`: KPT_DTYPE records (sift_amd.cv.keypoint_records /
+        from_cv_keypoints build them).  Counts as a frame: total_size = len(kpts), rows in the caller's order,
+        device_kpts / device_features hold the input, prev_descriptor the previous frame's rows.  An invalid
+        keypoint or more than the result capacity raises SiftHipError and leaves the previous results current."""
+        self.gpuWarmUpAndAllocate()
+        img, fmt = self._host_frame(image)
+        k = self._kpt_records(kpts)
+        fn = lib().sift_hip_compute_u8 if fmt == SIFT_HIP_U8 else lib().sift_hip_compute
+        _check(fn(self._h, _ptr(img), img.strides[0], _ptr(k) if len(k) else None, len(k)), "compute")
+        self._refresh()
+
+    def computeDevice(self, dev_ptr: int, row_stride_bytes: int, kpts_dev_ptr: int, n: int, stream: Optional[int] = None,
+                      u8: bool = False, sync: bool = True) -> None:
+        """The same for a device image and n device keypoints (24-byte KPT_DTYPE records), enqueued after `stream`
+        (sift_hip_compute_device).  Device keypoints are validated on the GPU: an invalid one gets an all-zero row
+        and sets overflow_flags() bit 16."""
+        self.gpuWarmUpAndAllocate()
+        fmt = SIFT_HIP_U8 if u8 else SIFT_HIP_F32
+        _check(lib().sift_hip_compute_device(self._h, dev_ptr, row_stride_bytes, fmt, kpts_dev_ptr or None, n, stream),
+               "computeDevice")
+        if sync:
+            self.sync()
 
     def submit(self, image: np.ndarray) -> int:
         """Pipelined input (sift_hip_submit): stage + upload + enqueue, no wait.  Returns the frame ticket."""

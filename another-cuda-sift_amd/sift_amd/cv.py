@@ -21,6 +21,30 @@ def keypoint_fields(final_kpts: np.ndarray, final_features: np.ndarray, size: in
             "size": f[:n, 1], "response": f[:n, 2], "angle": f[:n, 3]}
 
 
+def keypoint_records(fields_or_kpts, final_features=None) -> np.ndarray:
+    """The inverse of keypoint_fields: KPT_DTYPE records (what Detector.compute takes) from its field dict, or from
+    (final_kpts, final_features) as a detector returns them."""
+    from . import KPT_DTYPE
+
+    f = fields_or_kpts if isinstance(fields_or_kpts, dict) else keypoint_fields(fields_or_kpts, final_features)
+    out = np.zeros(len(f["x"]), KPT_DTYPE)
+    for name in KPT_DTYPE.names:
+        out[name] = f[name]
+    return out
+
+
+def from_cv_keypoints(kpts) -> np.ndarray:
+    """list of cv2.KeyPoint -> KPT_DTYPE records (class_id dropped)."""
+    import cv2  # noqa: F401  (the objects are cv2's; absent OpenCV is an ImportError, as in to_cv_keypoints)
+
+    from . import KPT_DTYPE
+
+    out = np.zeros(len(kpts), KPT_DTYPE)
+    for i, k in enumerate(kpts):
+        out[i] = (k.pt[0], k.pt[1], k.size, k.angle, k.response, k.octave)
+    return out
+
+
 def descriptor_matrix(descriptors: np.ndarray, num_pts: int) -> np.ndarray:
     """ConversionImpl.hpp:66-82: row-major 128-wide descriptors -> float32 (n, 128)."""
     d = np.asarray(descriptors).reshape(-1, 128)

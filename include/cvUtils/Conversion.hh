@@ -94,6 +94,15 @@ inline std::vector<cv::KeyPoint> localKptToCvKpt(const std::vector<sift_cuda::Fl
     return out;
 }
 
+// The inverse, for Detector::compute: cv::KeyPoint -> sift_cuda::KeyPoint
+// (class_id dropped; the packed octave as cv::SIFT writes it).
+inline std::vector<sift_cuda::KeyPoint> cvKptToLocalKpt(const std::vector<cv::KeyPoint>& kpts) {
+    std::vector<sift_cuda::KeyPoint> out;
+    out.reserve(kpts.size());
+    for (const cv::KeyPoint& k : kpts) out.push_back({k.pt.x, k.pt.y, k.size, k.angle, k.response, k.octave});
+    return out;
+}
+
 // ConversionImpl.hpp:66-82: row-major 128-wide descriptors -> CV_32F (n x 128).
 template <typename Data_T>
 cv::Mat descriptorToCvMat(const std::vector<Data_T>& descriptors, int num_pts) {

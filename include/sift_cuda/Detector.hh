@@ -61,6 +61,23 @@ public:
     // Extra: image already in device memory (fp32, row stride in bytes).
     void detectAndComputeDevice(const float* device_image, size_t row_stride_bytes, void* hip_stream = nullptr);
 
+    // Extra: descriptors for the caller's own keypoints (cv::Feature2D::compute;
+    // sift_hip_compute / sift_hip_compute_u8): the frame's pyramid is built and
+    // the keypoints described in the caller's order -- total_size =
+    // keypoints.size(), device_kpts / device_features hold the input,
+    // prev_descriptor the previous frame's rows.  Synchronous.  Throws
+    // std::invalid_argument when a keypoint is invalid or there are more than
+    // the result capacity (nothing runs), std::runtime_error on any other error.
+    void compute(const Imagef& image, const std::vector<KeyPoint>& keypoints);
+    void compute(const Image8U& image, const std::vector<KeyPoint>& keypoints);
+    // Extra: the same for a device image (fp32 or 8-bit, row stride in bytes)
+    // and n device keypoints, read after `hip_stream` reaches the call;
+    // returns when the results are ready.  Device keypoints are validated on
+    // the GPU: an invalid one gets an all-zero row and sets overflow flag 16
+    // (reported on stderr like a capacity overflow).
+    void computeDevice(const void* device_image, size_t row_stride_bytes, bool u8, const KeyPoint* device_keypoints,
+                       int n, void* hip_stream = nullptr);
+
     // Detector.cu:606-634: copies total_size results (+ descriptors) to host.
     void copyToHost(bool descriptor);
     // Extra: the same rows without the copy into final_kpts / final_features /

@@ -43,6 +43,16 @@ struct Half {
 };
 static_assert(sizeof(Float3) == 12 && sizeof(Float4) == 16 && sizeof(Half) == 2, "layout");
 
+// A caller-supplied keypoint for Detector::compute: cv::KeyPoint minus
+// class_id, layout-identical to sift_hip_keypoint (include/sift_hip.h).
+// x, y, size in input-image pixels, angle in degrees (0..360), octave in
+// OpenCV's packed form (octave & 255 | layer << 8 | xi << 16).
+struct KeyPoint {
+    float x, y, size, angle, response;
+    int octave;
+};
+static_assert(sizeof(KeyPoint) == 24 && offsetof(KeyPoint, octave) == 20, "layout of sift_hip_keypoint");
+
 // Non-owning view of a device array owned by a Detector (stands in for the
 // reference's thrust::device_vector members, Detector.hh:54-57; data()/size()
 // as there).  data() is read-only: the detector derives data from what it

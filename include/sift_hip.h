@@ -97,6 +97,69 @@ int sift_hip_detect_device_fmt(sift_hip_t h, const void* dev_img, size_t row_str
                                void* stream);
 int sift_hip_sync(sift_hip_t h);
 
+/* Descriptors for caller-supplied keypoints: cv::Feature2D::compute, i.e.
+ * cv::SIFT::detectAndCompute(img, mask, kpts, desc, useProvidedKeypoints =
+ * true) -- tracked points of the previous frame, re-projected map points,
+ * another detector's corners.  The call builds the Gaussian pyramid of the
+ * frame and describes the n keypoints on it (OpenCV's calcDescriptors: each
+ * keypoint's packed octave picks its plane, no orientation is assigned);
+ * extrema, refinement, orientation and ordering do not run.
+ *
+ * sift_hip_keypoint is cv::KeyPoint minus class_id (24 bytes).  `octave` is
+ * OpenCV's packed form: octave & 255 | layer << 8 | xi << 16 (the value
+ * feats4[0] holds as a float); x, y, size in input-image pixels, angle in
+ * degrees.
+ *
+ * The call counts as a frame like a single-frame detect: it takes the next
+ * frame number and results slot, and every result accessor works unchanged --
+ * sift_hip_num_keypoints gives n, rows are in the caller's order, kpts3 =
+ * {x, y, layer} and feats4 = {(float)octave, size, response, angle} are
+ * written from the input, prev_desc is the previous frame's rows and the
+ * matcher sidecar is that of the new rows.  On a batch handle it uses frame
+ * 0's arena.  Not available as submit / micro-batch / batch variants.
+ *
+ * A keypoint is valid when: its octave lies in [firstOctave, firstOctave +
+ * nOctaves - 1] of this handle (firstOctave = -1 with upscale, else 0) and
+ * its layer in [0, numOctaveLayers + 2] (every Gaussian plane, as in OpenCV);
+ * x, y and size are finite and size > 0; 0 <= angle <= 360; and -W <= x <= 2W,
+ * -H <= y <= 2H (points a little outside the frame are legitimate and give
+ * partial or all-zero rows; further out the integer window arithmetic is not
+ * defended).
+ *
+ * In the default descriptor mode the +-1 contract against OpenCV is stated for
+ * keypoints in the detector's scale range (size * scale / 2 <= sigma *
+ * 2^((L + 0.5) / L), scale = 2^-octave).  Larger windows (12 to 200 px on
+ * every plane of a 96 x 80 frame) also measured +-1, with a lower share of
+ * exact bytes (0.9905 against 0.998).
+ * SIFT_HIP_DESC_EXACT is bit-identical to OpenCV for every valid keypoint. */
+typedef struct { float x, y, size, angle, response; int octave; } sift_hip_keypoint;
+
+/* Host-only (valid right after sift_hip_create, no device call): *first_bad =
+ * index of the first invalid keypoint, or -1 when all n are valid; returns
+ * SIFT_HIP_OK either way.  n < 0 or n above the result capacity
+ * (sift_hip_capacities) is SIFT_HIP_ERR_INVALID. */
+int sift_hip_check_keypoints(sift_hip_t h, const sift_hip_keypoint* kpts, int n, int* first_bad);
+
+/* Host image and host keypoints; synchronous, as sift_hip_detect.  Keypoints
+ * are validated first: an invalid one, n < 0 or n above the result capacity
+ * returns SIFT_HIP_ERR_INVALID (the index in sift_hip_last_error) and nothing
+ * is launched -- the previous results stay current.  n = 0 is legal (count 0). */
+int sift_hip_compute   (sift_hip_t h, const float*   host_img, size_t row_stride_bytes,
+                        const sift_hip_keypoint* kpts, int n);
+int sift_hip_compute_u8(sift_hip_t h, const uint8_t* host_img, size_t row_stride_bytes,
+                        const sift_hip_keypoint* kpts, int n);
+
+/* Device image (SIFT_HIP_F32 / SIFT_HIP_U8) and device keypoints, enqueued
+ * after `stream` and NOT synchronised, as sift_hip_detect_device_fmt; both
+ * buffers must stay unchanged until sift_hip_sync.  The keypoints cannot be
+ * checked on the host: the job kernel validates them, an invalid keypoint gets
+ * an all-zero descriptor row (and the sidecar codes of a zero row) and sets
+ * SIFT_HIP_FLAG_BAD_KEYPOINT in the frame's sift_hip_overflow_flags.  n is
+ * checked on the host as above. */
+#define SIFT_HIP_FLAG_BAD_KEYPOINT 16
+int sift_hip_compute_device(sift_hip_t h, const void* dev_img, size_t row_stride_bytes, int format,
+                            const sift_hip_keypoint* dev_kpts, int n, void* stream);
+
 /* Frame batches (C4: many frames per GPU).  sift_hip_set_batch(h, B), called
  * before sift_hip_warmup, gives the handle B frame arenas (pyramid, keypoint
  * lists, counters and result slots per frame) and a pipeline graph whose every
@@ -223,7 +286,9 @@ int sift_hip_num_keypoints(sift_hip_t h, int* n);
  * overrides the result capacity); NULL arguments are skipped. */
 int sift_hip_capacities(sift_hip_t h, int* candidates, int* refined, int* oriented, int* results);
 
-/* Non-zero when a capacity (candidates / keypoints / results) overflowed. */
+/* Non-zero when a capacity overflowed (1 candidates, 2 refined, 4 oriented,
+ * 8 results) or sift_hip_compute_device met an invalid keypoint
+ * (SIFT_HIP_FLAG_BAD_KEYPOINT, 16). */
 int sift_hip_overflow_flags(sift_hip_t h, int* flags);
 
 /* Device result arrays (Detector.hh:54-57): kpts = float3 {x, y, layer}
