@@ -501,7 +501,7 @@ void enqueue_refine(sift_hip_detector* d, int nf) {
 void enqueue_orientation(sift_hip_detector* d, int nf) {
     const Frames fr{nf, d->afs};
     d->timed("orientation", 0,
-             [&] { launch_orientation(d->pyr, d->dRef, d->dCtr, d->dOri, d->dBitmap, d->kp, fr, d->stream); });
+             [&] { launch_orientation(d->pyr, d->dRef, d->dCtr, d->dOri, d->dBitmap, d->kp, fr, d->stream, d->mask); });
 }
 
 void enqueue_order(sift_hip_detector* d, int slot, int nf) {
@@ -511,12 +511,12 @@ void enqueue_order(sift_hip_detector* d, int slot, int nf) {
     if (d->kp.numBuckets <= kOrderMaxBuckets) {
         d->timed("order", 0, [&] {
             launch_order(d->pyr, d->dOri, d->dCtr, range_keys(d, parity ^ 1), d->dBcount, d->dBoff, d->dSlot, d->dOrder,
-                         d->dJord, d->kp, fr, s);
+                         d->dJord, d->kp, fr, s, d->mask);
         });
     } else {
         d->timed("select", 0, [&] { launch_select(d->dOri, d->dCtr, range_keys(d, parity ^ 1), d->kp, fr, s); });
         d->timed("bucket_count", 0,
-                 [&] { launch_bucket_count(d->dOri, d->dCtr, d->dBcount, d->dSlot, d->kp, fr, s); });
+                 [&] { launch_bucket_count(d->dOri, d->dCtr, d->dBcount, d->dSlot, d->kp, fr, s, d->mask); });
         d->timed("bucket_scan", 0, [&] { launch_bucket_scan(d->dBcount, d->dBoff, d->dCtr, d->kp, fr, s); });
         d->timed("bucket_scatter", 0,
                  [&] { launch_bucket_scatter(d->dOri, d->dCtr, d->dBoff, d->dSlot, d->dOrder, d->kp, fr, s); });
@@ -648,7 +648,7 @@ int warm_lane(sift_hip_detector* d) {
 // micro-batch (`numbered`) takes nf numbers, frame d->submitted + i in arena i.  With stage dumps on (single frames after warm-up) the frame's
 // input is kept as float, the frame is completed synchronously and dumped.
 int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf, long sfs,
-              bool numbered, const ProvidedKpt* provided, int nProvided) {
+              bool numbered, const ProvidedKpt* provided, int nProvided, const MaskArg* mask) {
     const long long f = d->submitted;
     Lane& L = d->lane();
     const int slot = (int)(L.launched % L.nslots);
@@ -664,7 +664,11 @@ int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEven
             HIPCHK(hipMemcpy2DAsync(d->dDg, sizeof(float) * W, img, sizeof(float) * (size_t)pitch, sizeof(float) * W,
                                     H, hipMemcpyDefault, d->stream));
     }
-    const bool graphs = d->useGraph && !d->timing && !compute;
+    // A masked frame takes the eager launches below with the mask as a kernel
+    // argument (the captured graphs carry none); sift_hip_detect_masked*
+    // refuse it while stage dumps are on.
+    const bool masked = mask && mask->p && !compute;
+    const bool graphs = d->useGraph && !d->timing && !compute && !masked;
     hipGraphExec_t gh = !graphs || consumed || fmt != SIFT_HIP_F32 ? nullptr
                         : nf == L.B                                  ? L.execH[slot]
                         : nf == 1                                    ? L.execH1[slot]
@@ -694,8 +698,10 @@ int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEven
             enqueue_pyramid(d, 1, slot & 1);
             enqueue_provided(d, slot, provided, nProvided);
             enqueue_descriptor(d, slot, 1);
-        } else {  // timing mode, or a partial batch: the same launches, eagerly
+        } else {  // timing mode, a partial batch or a masked frame: the same launches, eagerly
+            if (masked) d->mask = *mask;
             enqueue_body(d, slot, nf);
+            d->mask = MaskArg{};
         }
     }
     HIPCHK(hipEventRecord(L.evFrame[slot], d->stream));
@@ -838,6 +844,79 @@ static int compute_host(sift_hip_detector* d, const void* img, size_t stride, in
     return rc ? rc : wait_frame(d, f);
 }
 
+// ---- detection mask (sift_hip_detect_masked*) ----
+// The mask's row stride (0 = packed) checked against the width, and the state
+// a masked call needs: no stage dumps (the dump format has no mask, so a
+// replay of `order` could not reproduce the frame).
+static int check_mask(const sift_hip_detector* d, size_t* maskStride) {
+    const size_t W = (size_t)d->cfg.col_width;
+    if (*maskStride == 0) *maskStride = W;
+    if (*maskStride < W) return fail(SIFT_HIP_ERR_INVALID, "mask row stride smaller than width");
+    if (!d->dgDir.empty())
+        return fail(SIFT_HIP_ERR_STATE, "masked detect while sift_hip_set_datagen is active (stage dumps hold no mask)");
+    return SIFT_HIP_OK;
+}
+
+// sift_hip_detect_device_fmt / sift_hip_detect_device_masked (mask nullable).
+static int detect_device(sift_hip_detector* d, const void* img, size_t stride, int format, const uint8_t* mask,
+                         size_t maskStride, void* stream) {
+    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
+    const int es = format_size(format);
+    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
+    const int W = d->cfg.col_width, H = d->cfg.row_width;
+    if (stride == 0) stride = (size_t)es * W;
+    if (stride % es || stride < (size_t)es * W)
+        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    if (mask)
+        if (int rc = check_mask(d, &maskStride)) return rc;
+    if (int rc = check_in_flight(d)) return rc;
+    long long f = 0;
+    const MaskArg m{mask, (int)maskStride, W, H, 0};
+    if (int rc = submit_device(d, img, stride, format, stream, 1, 0, &f, false, nullptr, -1, mask ? &m : nullptr)) return rc;
+    // Device-ordered consumers see this frame's buffers at once; counts
+    // follow at sift_hip_sync / sift_hip_wait.
+    make_current(d, f);
+    if (stream) {
+        HIPCHK(hipEventRecord(d->evOut, d->stream));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
+    }
+    return SIFT_HIP_OK;
+}
+
+// sift_hip_detect_batch_device / sift_hip_detect_batch_device_masked (masks nullable).
+static int detect_batch_device(sift_hip_detector* d, const void* frames, int n, size_t stride, size_t frame_stride,
+                               int format, const uint8_t* masks, size_t maskStride, size_t maskFrameStride,
+                               void* stream) {
+    if (!frames) return fail(SIFT_HIP_ERR_INVALID, "null frames");
+    if (n < 1 || n > d->B) return fail(SIFT_HIP_ERR_INVALID, "frame count outside 1..batch capacity");
+    const int es = format_size(format);
+    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
+    const int W = d->cfg.col_width, H = d->cfg.row_width;
+    if (stride == 0) stride = (size_t)es * W;
+    if (stride % es || stride < (size_t)es * W)
+        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    if (frame_stride == 0) frame_stride = stride * H;
+    if (n > 1 && frame_stride < stride * (H - 1) + (size_t)es * W)
+        return fail(SIFT_HIP_ERR_INVALID, "frame stride smaller than one frame");
+    if (masks) {
+        if (int rc = check_mask(d, &maskStride)) return rc;
+        if (maskFrameStride == 0) maskFrameStride = maskStride * H;
+        if (n > 1 && maskFrameStride < maskStride * (H - 1) + (size_t)W)
+            return fail(SIFT_HIP_ERR_INVALID, "mask frame stride smaller than one mask");
+    }
+    if (int rc = check_in_flight(d)) return rc;
+    long long f = 0;
+    const MaskArg m{masks, (int)maskStride, W, H, (long)maskFrameStride};
+    if (int rc = submit_device(d, frames, stride, format, stream, n, frame_stride, &f, false, nullptr, -1, masks ? &m : nullptr))
+        return rc;
+    make_current(d, f);
+    if (stream) {
+        HIPCHK(hipEventRecord(d->evOut, d->stream));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
+    }
+    return SIFT_HIP_OK;
+}
+
 extern "C" {
 
 void sift_hip_default_config(sift_hip_config* c, int w, int h) {
@@ -960,24 +1039,32 @@ int sift_hip_wait(sift_hip_t d, long long ticket) {
 
 int sift_hip_detect_device_fmt(sift_hip_t d, const void* img, size_t stride, int format, void* stream) {
     CHECK_HANDLE(d);
-    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
-    if (int rc = check_in_flight(d)) return rc;
-    long long f = 0;
-    if (int rc = submit_device(d, img, stride, format, stream, 1, 0, &f)) return rc;
-    // Device-ordered consumers see this frame's buffers at once; counts
-    // follow at sift_hip_sync / sift_hip_wait.
-    make_current(d, f);
-    if (stream) {
-        HIPCHK(hipEventRecord(d->evOut, d->stream));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
+    return detect_device(d, img, stride, format, nullptr, 0, stream);
+}
+
+int sift_hip_detect_masked(sift_hip_t d, const void* img, size_t stride, int format, const uint8_t* mask,
+                           size_t mask_stride) {
+    CHECK_HANDLE(d);
+    if (mask) {  // (submit_host checks the image arguments itself; nothing is launched before it has)
+        if (!format_size(format)) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
+        if (int rc = check_mask(d, &mask_stride)) return rc;
     }
-    return SIFT_HIP_OK;
+    long long f = 0;
+    int rc = submit_host(d, img, stride, format, &f, nullptr, -1, mask, mask_stride);
+    return rc ? rc : wait_frame(d, f);
+}
+
+int sift_hip_detect_device_masked(sift_hip_t d, const void* img, size_t stride, int format, const uint8_t* mask,
+                                  size_t mask_stride, void* stream) {
+    CHECK_HANDLE(d);
+    return detect_device(d, img, stride, format, mask, mask_stride, stream);
+}
+
+int sift_hip_detect_batch_device_masked(sift_hip_t d, const void* frames, int n, size_t stride, size_t frame_stride,
+                                        int format, const uint8_t* masks, size_t mask_stride, size_t mask_frame_stride,
+                                        void* stream) {
+    CHECK_HANDLE(d);
+    return detect_batch_device(d, frames, n, stride, frame_stride, format, masks, mask_stride, mask_frame_stride, stream);
 }
 
 int sift_hip_submit_device(sift_hip_t d, const void* img, size_t stride, int format, void* stream, long long* ticket) {
@@ -1115,26 +1202,7 @@ int sift_hip_batch_capacity(sift_hip_t d, int* frames) {
 int sift_hip_detect_batch_device(sift_hip_t d, const void* frames, int n, size_t stride, size_t frame_stride,
                                  int format, void* stream) {
     CHECK_HANDLE(d);
-    if (!frames) return fail(SIFT_HIP_ERR_INVALID, "null frames");
-    if (n < 1 || n > d->B) return fail(SIFT_HIP_ERR_INVALID, "frame count outside 1..batch capacity");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width, H = d->cfg.row_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
-    if (frame_stride == 0) frame_stride = stride * H;
-    if (n > 1 && frame_stride < stride * (H - 1) + (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "frame stride smaller than one frame");
-    if (int rc = check_in_flight(d)) return rc;
-    long long f = 0;
-    if (int rc = submit_device(d, frames, stride, format, stream, n, frame_stride, &f)) return rc;
-    make_current(d, f);
-    if (stream) {
-        HIPCHK(hipEventRecord(d->evOut, d->stream));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
-    }
-    return SIFT_HIP_OK;
+    return detect_batch_device(d, frames, n, stride, frame_stride, format, nullptr, 0, 0, stream);
 }
 
 int sift_hip_batch_frames(sift_hip_t d, int* n) {

@@ -236,6 +236,47 @@ void Detector::computeDevice(const void* dev, size_t stride, bool u8, const KeyP
     refreshViews();
 }
 
+namespace {
+
+void check_mask_throw(const Image8U& mask, const CudaSiftConfig& c) {
+    if (!mask.m_data || mask.cols() != c.col_width || mask.rows() != c.row_width)
+        throw std::invalid_argument("detectAndCompute: mask is " + std::to_string(mask.cols()) + "x" +
+                                    std::to_string(mask.rows()) + ", detector configured for " +
+                                    std::to_string(c.col_width) + "x" + std::to_string(c.row_width));
+}
+
+}  // namespace
+
+void Detector::detectAndCompute(const Imagef& image, const Image8U& mask) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) return;
+    check_shape(image, m_config, "detectAndCompute");
+    check_mask_throw(mask, m_config);
+    check_throw(sift_hip_detect_masked(m_handle, image.m_data->data(), sizeof(float) * (size_t)image.cols(), SIFT_HIP_F32,
+                                       mask.m_data->data(), (size_t)mask.cols()),
+                "detectAndCompute");
+    refreshViews();
+}
+
+void Detector::detectAndCompute(const Image8U& image, const Image8U& mask) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) return;
+    check_shape(image, m_config, "detectAndCompute");
+    check_mask_throw(mask, m_config);
+    check_throw(sift_hip_detect_masked(m_handle, image.m_data->data(), (size_t)image.cols(), SIFT_HIP_U8,
+                                       mask.m_data->data(), (size_t)mask.cols()),
+                "detectAndCompute");
+    refreshViews();
+}
+
+void Detector::detectAndComputeDevice(const void* dev, size_t stride, bool u8, const uint8_t* dev_mask, size_t mask_stride,
+                                      void* stream) {
+    if (!m_initialized && !gpuWarmUpAndAllocate()) return;
+    check_throw(sift_hip_detect_device_masked(m_handle, dev, stride, u8 ? SIFT_HIP_U8 : SIFT_HIP_F32, dev_mask, mask_stride,
+                                              stream),
+                "detectAndComputeDevice");
+    check_throw(sift_hip_sync(m_handle), "detectAndComputeDevice sync");
+    refreshViews();
+}
+
 void Detector::setDataGen(const std::string& path) {
     m_debug_path = path;
     if (m_handle) check(sift_hip_set_datagen(m_handle, path.c_str()), "setDataGen");

@@ -344,6 +344,16 @@ struct sift_hip_detector {
     // allocated at the first compute call (a detect-only caller pays nothing).
     // One buffer: the call is synchronous, so its kernel has read it on return.
     ProvidedKpt* hKpts = nullptr;
+    // Detection mask (sift_hip_detect_masked*).  `mask`: the mask of the launch
+    // group being enqueued (run_frame sets it around the eager launches; null
+    // otherwise, so every captured graph is mask-free).  Host masks go through
+    // hMask (pinned, packed rows) into dMask (device) on the frame's lane
+    // stream; both are allocated at the first host-mask call (a caller who
+    // never passes a mask pays nothing) and one of each is enough: the call is
+    // synchronous, so its kernels have read them on return.
+    MaskArg mask{};
+    uint8_t* hMask = nullptr;
+    uint8_t* dMask = nullptr;
     // The most the caller's sift_hip_copy_to_host / sift_hip_results_host
     // calls took (0 nothing yet, 1 keypoints, 2 keypoints + descriptors):
     // host-input frames have their descriptor kernel write that much to
@@ -436,6 +446,8 @@ struct sift_hip_detector {
             }
             if (dDg) (void)hipFree(dDg);
             if (hKpts) (void)hipHostFree(hKpts);
+            if (hMask) (void)hipHostFree(hMask);
+            if (dMask) (void)hipFree(dMask);
             for (auto e : evPool) (void)hipEventDestroy(e);
             if (hstBlock) (void)hipHostFree(hstBlock);
             for (hipEvent_t e : hstRead) (void)hipEventDestroy(e);
@@ -477,8 +489,11 @@ void enqueue_provided(sift_hip_detector* d, int slot, const ProvidedKpt* kpts, i
 bool event_done(hipEvent_t e);
 // nProvided >= 0 (<= capFinal): the frame describes the nProvided
 // device-readable keypoints `provided` instead of detecting (sift_hip_compute*).
+// mask (nullable; p != nullptr): the detect chain runs eagerly with the mask
+// test in its orientation and order stages (sift_hip_detect_masked*).
 int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf = 1, long sfs = 0,
-              bool numbered = false, const ProvidedKpt* provided = nullptr, int nProvided = -1);
+              bool numbered = false, const ProvidedKpt* provided = nullptr, int nProvided = -1,
+              const MaskArg* mask = nullptr);
 void make_current(sift_hip_detector* d, long long f);
 void complete_counts(sift_hip_detector* d);
 int ensure_counts(sift_hip_detector* d);
@@ -497,11 +512,14 @@ size_t host_res_bytes(const sift_hip_detector* d);
 void host_res(const sift_hip_detector* d, char* base, int region, float** k3, float** f4, uint16_t** desc);
 int ensure_host_res(sift_hip_detector* d, Lane& L);
 // n >= 0: a compute frame of the n host keypoints `kpts` (already validated).
+// mask (nullable): a host detection mask, rows maskStride bytes apart
+// (validated); the frame is launched at once, never queued.
 int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
-                const ProvidedKpt* kpts = nullptr, int n = -1);
+                const ProvidedKpt* kpts = nullptr, int n = -1, const uint8_t* mask = nullptr, size_t maskStride = 0);
 int run_group(sift_hip_detector* d);
 int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue = false, const ProvidedKpt* devKpts = nullptr, int n = -1);
+                  long long* ticket, bool queue = false, const ProvidedKpt* devKpts = nullptr, int n = -1,
+                  const MaskArg* mask = nullptr);
 int wait_frame(sift_hip_detector* d, long long f);
 
 // ---- datagen.hip ----

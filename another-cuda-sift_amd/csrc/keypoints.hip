@@ -341,10 +341,14 @@ constexpr int kOriAhead = 1;
 // round-robin over blockIdx.x, put every frame's neighbouring keypoints on all
 // 8 XCDs), against 192.1 MB for a perfect cache at 128-byte lines
 // (tools/window_line_model.py).
-__global__ __launch_bounds__(64) void k_orientation(PyrDesc pyr, const RefKpt* __restrict__ in,
-                                                    Counters* __restrict__ ctr, OriKpt* __restrict__ out,
-                                                    uint32_t* __restrict__ bitmap, KeypointParams kp, long fs,
-                                                    unsigned nf) {
+// kMask: the launch of a masked frame (sift_hip_detect_masked*); frames without
+// a mask -- every captured graph -- run the <false> instantiation, whose code
+// has no trace of the mask.
+template <bool kMask>
+__device__ __forceinline__ void orientation_body(const PyrDesc& pyr, const RefKpt* __restrict__ in,
+                                                 Counters* __restrict__ ctr, OriKpt* __restrict__ out,
+                                                 uint32_t* __restrict__ bitmap, const KeypointParams& kp, long fs,
+                                                 unsigned nf, const MaskArg& mask) {
     __shared__ __attribute__((aligned(16))) float chunk[64 + 3 * kOriBins];  // bin runs padded to 4
     // Below 8 frames a frame's keypoints stay round-robin over its XCDs
     // (q = 1): single frames are latency-bound and contiguous per-XCD ranges
@@ -366,12 +370,26 @@ __global__ __launch_bounds__(64) void k_orientation(PyrDesc pyr, const RefKpt* _
     for (int bit = 0; bit < 6; bit++) lane_nb[bit] = ((lane >> bit) & 1) ? 0ull : ~0ull;
     const unsigned n = min(ctr->refined, kp.capRefined);
     const int fo = pyr.firstOctave;
+    // Detection mask, early: without retainBest (numFeatures <= 0) a masked-out
+    // keypoint can be dropped before its window is fetched (the duplicate
+    // filter commutes with the mask: duplicates share pt).  With retainBest its
+    // response still counts towards the threshold, so only k_order tests it.
+    const bool early = kMask && kp.numFeatures <= 0;
+    const float mscale = fo < 0 ? 1.f / (float)(1 << -fo) : 1.f;  // ori_emit's rescale: the floats OriKpt.x/y hold
     const unsigned span = (n + q - 1) / q, kend = min(n, (range + 1) * span);
     for (unsigned k = range * span + j; k < kend; k += step) {
         const RefKpt kpt = load_ref(in, k);
         const OctGeom* gp;
         const OriWin wn = ori_window(pyr, kpt, foff, gp);
         if (lane == 0) ori_clear_bit(bitmap, *gp, kpt);
+        if (early && !mask_ok(mask, frame, fo < 0 ? kpt.x * mscale : kpt.x, fo < 0 ? kpt.y * mscale : kpt.y)) {
+            if (lane == 0) {
+                OriKpt hole{};
+                hole.bucket = kHoleBucket;
+                out[k] = hole;
+            }
+            continue;
+        }
         float acc = 0.f;  // temphist[lane] for lane < 36
         // Loads run kOriAhead chunks ahead of the chunk being sorted (ring of
         // fetches): a large keypoint's chunks are a dependent chain, and
@@ -395,16 +413,33 @@ __global__ __launch_bounds__(64) void k_orientation(PyrDesc pyr, const RefKpt* _
     }
 }
 
+__global__ __launch_bounds__(64) void k_orientation(PyrDesc pyr, const RefKpt* __restrict__ in,
+                                                    Counters* __restrict__ ctr, OriKpt* __restrict__ out,
+                                                    uint32_t* __restrict__ bitmap, KeypointParams kp, long fs,
+                                                    unsigned nf) {
+    orientation_body<false>(pyr, in, ctr, out, bitmap, kp, fs, nf, MaskArg{});
+}
+__global__ __launch_bounds__(64) void k_orientation_masked(PyrDesc pyr, const RefKpt* __restrict__ in,
+                                                           Counters* __restrict__ ctr, OriKpt* __restrict__ out,
+                                                           uint32_t* __restrict__ bitmap, KeypointParams kp, long fs,
+                                                           unsigned nf, MaskArg mask) {
+    orientation_body<true>(pyr, in, ctr, out, bitmap, kp, fs, nf, mask);
+}
+
 void launch_orientation(const PyrDesc& pyr, const RefKpt* in, Counters* ctr, OriKpt* out, uint32_t* bitmap,
-                        const KeypointParams& kp, const Frames& fr, hipStream_t s) {
+                        const KeypointParams& kp, const Frames& fr, hipStream_t s, const MaskArg& mask) {
     // One-wave workgroups per frame: 8192 for a single frame, 1024 at 8 frames.
     // Grids that fill every wave slot keep the other stream's pyramid kernels
     // out; this size lets them co-reside (+2-4 % frame rate, tools/grid_sweep.sh).
     // (512 per frame at 16 frames; 256 measured equal, round 2.)  per is a
     // multiple of 8: every XCD range gets the same number of workgroups.
     const int per = fr.nf <= 1 ? 8192 : std::max(256, 8192 / fr.nf) & ~7;
-    hipLaunchKernelGGL(k_orientation, dim3(per * fr.nf), dim3(64), 0, s, pyr, in, ctr, out, bitmap, kp, fr.stride,
-                       (unsigned)fr.nf);
+    if (mask.p)
+        hipLaunchKernelGGL(k_orientation_masked, dim3(per * fr.nf), dim3(64), 0, s, pyr, in, ctr, out, bitmap, kp,
+                           fr.stride, (unsigned)fr.nf, mask);
+    else
+        hipLaunchKernelGGL(k_orientation, dim3(per * fr.nf), dim3(64), 0, s, pyr, in, ctr, out, bitmap, kp, fr.stride,
+                           (unsigned)fr.nf);
 }
 
 // ---------------------------------------------------------------------------
@@ -504,9 +539,10 @@ void launch_select(const OriKpt* kpts, Counters* ctr, unsigned* zero_range, cons
 // Atomic compaction upstream makes arrival order nondeterministic; this makes
 // the output order a pure function of the keypoint set.
 // ---------------------------------------------------------------------------
+template <bool kMask>
 __global__ __launch_bounds__(256) void k_bucket_count(const OriKpt* __restrict__ kpts, const Counters* __restrict__ ctr,
                                                       unsigned* __restrict__ bcount, int* __restrict__ slot,
-                                                      KeypointParams kp, long fs) {
+                                                      KeypointParams kp, long fs, MaskArg mask) {
     const long foff = blockIdx.y * fs;  // frame blockIdx.y
     kpts = fptr(kpts, foff);
     ctr = fptr(ctr, foff);
@@ -516,13 +552,20 @@ __global__ __launch_bounds__(256) void k_bucket_count(const OriKpt* __restrict__
     const float thr = __uint_as_float(ctr->thr_bits);
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const OriKpt k = kpts[i];
-        slot[i] = k.bucket != kHoleBucket && k.response >= thr ? (int)atomicAdd(&bcount[k.bucket], 1u) : -1;
+        const bool keep = (unsigned)k.bucket != kHoleBucket && k.response >= thr &&
+                          (!kMask || mask_ok(mask, blockIdx.y, k.x, k.y));
+        slot[i] = keep ? (int)atomicAdd(&bcount[k.bucket], 1u) : -1;
     }
 }
 
 void launch_bucket_count(const OriKpt* kpts, const Counters* ctr, unsigned* bcount, int* slot,
-                         const KeypointParams& kp, const Frames& fr, hipStream_t s) {
-    hipLaunchKernelGGL(k_bucket_count, dim3(256, fr.nf), dim3(256), 0, s, kpts, ctr, bcount, slot, kp, fr.stride);
+                         const KeypointParams& kp, const Frames& fr, hipStream_t s, const MaskArg& mask) {
+    if (mask.p)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_count<true>), dim3(256, fr.nf), dim3(256), 0, s, kpts, ctr, bcount,
+                           slot, kp, fr.stride, mask);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_count<false>), dim3(256, fr.nf), dim3(256), 0, s, kpts, ctr, bcount,
+                           slot, kp, fr.stride, mask);
 }
 
 __global__ __launch_bounds__(1024) void k_bucket_scan(const unsigned* __restrict__ bcount, unsigned* __restrict__ boff,
@@ -604,11 +647,12 @@ __device__ __forceinline__ int lpt_seg(int packed_octave, int fo, int L) {
     return o * L + layer - 1;
 }
 
+template <bool kMask>
 __global__ __launch_bounds__(1024) void k_order(PyrDesc pyr, const OriKpt* __restrict__ kpts, Counters* __restrict__ ctr,
                                                 unsigned* __restrict__ zero_range, unsigned* __restrict__ bcount,
                                                 unsigned* __restrict__ boff, int* __restrict__ slot,
                                                 int* __restrict__ order, JobOrder* __restrict__ jord,
-                                                KeypointParams kp, long fs) {
+                                                KeypointParams kp, long fs, MaskArg mask) {
     extern __shared__ unsigned s_bucket[];  // counts, then exclusive offsets
     __shared__ unsigned hist[256], wsum[16];
     __shared__ unsigned s_prefix, s_k;
@@ -680,11 +724,26 @@ __global__ __launch_bounds__(1024) void k_order(PyrDesc pyr, const OriKpt* __res
         const float4* kq = reinterpret_cast<const float4*>(kpts);
 #pragma unroll
         for (int u = 0; u < kOrderRegs; u++) q[u] = kq[2 * min(tid + 1024u * u, n - 1) + 1];
+        // Masked frames: every entry's {x, y}, then its mask byte, as two
+        // rounds of loads in flight (inside the loop below they would be 16
+        // dependent round trips).  The stage costs ~5 us more with a mask
+        // (10.5 -> 15.6 us on C2).
+        bool mok[kOrderRegs];
+#pragma unroll
+        for (int u = 0; u < kOrderRegs; u++) mok[u] = true;
+        if (kMask) {
+            float2 xy[kOrderRegs];
+            const float2* kx = reinterpret_cast<const float2*>(kpts);
+#pragma unroll
+            for (int u = 0; u < kOrderRegs; u++) xy[u] = kx[4 * min(tid + 1024u * u, n - 1)];
+#pragma unroll
+            for (int u = 0; u < kOrderRegs; u++) mok[u] = mask_ok(mask, blockIdx.y, xy[u].x, xy[u].y);
+        }
 #pragma unroll
         for (int u = 0; u < kOrderRegs; u++) {
             const unsigned i = tid + 1024u * u;
             rbk[u] = __float_as_int(q[u].z);
-            const bool keep = i < n && (unsigned)rbk[u] != kHoleBucket && q[u].x >= thr;
+            const bool keep = i < n && (unsigned)rbk[u] != kHoleBucket && q[u].x >= thr && mok[u];
             rsl[u] = keep ? (int)atomicAdd(&s_bucket[rbk[u]], 1u) : -1;
             if (keep && lpt) atomicAdd(&s_seg[lpt_seg(__float_as_int(q[u].y), fo, L)], 1u);
         }
@@ -692,6 +751,7 @@ __global__ __launch_bounds__(1024) void k_order(PyrDesc pyr, const OriKpt* __res
         for (unsigned i0 = tid; i0 < n; i0 += 4 * 1024) {
             int bk[4], oc[4];
             float rs[4];
+            bool mok[4] = {true, true, true, true};
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const unsigned i = min(i0 + 1024u * u, n - 1);
@@ -699,11 +759,18 @@ __global__ __launch_bounds__(1024) void k_order(PyrDesc pyr, const OriKpt* __res
                 rs[u] = kpts[i].response;
                 oc[u] = kpts[i].octave;
             }
+            if (kMask) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = min(i0 + 1024u * u, n - 1);
+                    mok[u] = mask_ok(mask, blockIdx.y, kpts[i].x, kpts[i].y);
+                }
+            }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const unsigned i = i0 + 1024u * u;
                 if (i < n) {
-                    const bool keep = (unsigned)bk[u] != kHoleBucket && rs[u] >= thr;
+                    const bool keep = (unsigned)bk[u] != kHoleBucket && rs[u] >= thr && mok[u];
                     slot[i] = keep ? (int)atomicAdd(&s_bucket[bk[u]], 1u) : -1;
                     if (keep && lpt) atomicAdd(&s_seg[lpt_seg(oc[u], fo, L)], 1u);
                 }
@@ -776,10 +843,16 @@ __global__ __launch_bounds__(1024) void k_order(PyrDesc pyr, const OriKpt* __res
 
 bool launch_order(const PyrDesc& pyr, const OriKpt* kpts, Counters* ctr, unsigned* zero_range, unsigned* bcount,
                   unsigned* boff, int* slot, int* order, JobOrder* jord, const KeypointParams& kp, const Frames& fr,
-                  hipStream_t s) {
+                  hipStream_t s, const MaskArg& mask) {
     if (kp.numBuckets > kOrderMaxBuckets) return false;
-    hipLaunchKernelGGL(k_order, dim3(1, fr.nf), dim3(1024), sizeof(unsigned) * (size_t)kp.numBuckets, s, pyr, kpts,
-                       ctr, zero_range, bcount, boff, slot, order, jord, kp, fr.stride);
+    if (mask.p)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_order<true>), dim3(1, fr.nf), dim3(1024),
+                           sizeof(unsigned) * (size_t)kp.numBuckets, s, pyr, kpts, ctr, zero_range, bcount, boff, slot,
+                           order, jord, kp, fr.stride, mask);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_order<false>), dim3(1, fr.nf), dim3(1024),
+                           sizeof(unsigned) * (size_t)kp.numBuckets, s, pyr, kpts, ctr, zero_range, bcount, boff, slot,
+                           order, jord, kp, fr.stride, mask);
     return true;
 }
 

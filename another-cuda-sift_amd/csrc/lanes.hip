@@ -237,7 +237,7 @@ int queue_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, lo
 // -> pipeline on the frame's lane -> results to pinned host memory.  On a
 // micro-batching handle the frame joins the pending group (queue_host).
 int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
-                const ProvidedKpt* kpts, int n) {
+                const ProvidedKpt* kpts, int n, const uint8_t* mask, size_t maskStride) {
     const int es = format_size(fmt);
     if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
     if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
@@ -246,7 +246,13 @@ int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, l
     if (stride == 0) stride = rowB;
     if (stride < rowB) return fail(SIFT_HIP_ERR_INVALID, "row stride smaller than width");
     if (int rc = check_in_flight(d)) return rc;
-    if (n < 0 && queue_frame(d)) return queue_host(d, img, stride, fmt, ticket);
+    if (mask) {  // first host mask: pinned staging and its device copy (packed rows)
+        if (!d->hMask && hipHostMalloc((void**)&d->hMask, (size_t)W * H, hipHostMallocMapped) != hipSuccess)
+            return fail(SIFT_HIP_ERR_NOMEM, "hipHostMalloc of the mask staging failed");
+        if (!d->dMask && hipMalloc((void**)&d->dMask, (size_t)W * H) != hipSuccess)
+            return fail(SIFT_HIP_ERR_NOMEM, "hipMalloc of the device mask failed");
+    }
+    if (n < 0 && !mask && queue_frame(d)) return queue_host(d, img, stride, fmt, ticket);
     if (int rc = run_group(d)) return rc;  // pending micro-batch frames keep their submission order
     if (int rc = pick_lane(d)) return rc;
     Lane& L = d->lane();
@@ -271,7 +277,15 @@ int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, l
         memcpy(d->hKpts, kpts, sizeof(ProvidedKpt) * (size_t)n);
         HIPCHK(hipHostGetDevicePointer((void**)&devKpts, d->hKpts, 0));
     }
-    if (int rc = run_frame(d, L.dStage[k], d->inPitch, fmt, nullptr, 1, 0, false, devKpts, n)) return rc;
+    MaskArg m{};
+    if (mask) {  // host mask: pinned staging -> device on the lane's stream, ahead of the frame
+        copy_rows(nullptr, (char*)d->hMask, (size_t)W, (const char*)mask, maskStride, (size_t)W, H);
+        void* msrc = nullptr;
+        HIPCHK(hipHostGetDevicePointer(&msrc, d->hMask, 0));
+        launch_copy_rows(msrc, (size_t)W, d->dMask, (size_t)W, (size_t)W, H, kStageWg, d->stream);
+        m = MaskArg{d->dMask, W, W, H, 0};
+    }
+    if (int rc = run_frame(d, L.dStage[k], d->inPitch, fmt, nullptr, 1, 0, false, devKpts, n, mask ? &m : nullptr)) return rc;
     if (reqAt) mark_host_results(d, f);
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;
@@ -342,7 +356,7 @@ int run_group(sift_hip_detector* d) {
 // frame of sift_hip_submit_device on a micro-batching handle joins the pending
 // group instead.
 int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue, const ProvidedKpt* devKpts, int n) {
+                  long long* ticket, bool queue, const ProvidedKpt* devKpts, int n, const MaskArg* mask) {
     hipStream_t ext = (hipStream_t)stream;
     if (queue && nf == 1 && queue_frame(d)) {
         const int i = d->npend;
@@ -365,7 +379,7 @@ int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt,
         HIPCHK(hipStreamWaitEvent(d->stream, d->evIn, 0));
     }
     const long long f = d->submitted;
-    if (int rc = run_frame(d, img, (int)(stride / format_size(fmt)), fmt, nullptr, nf, (long)fstride, false, devKpts, n))
+    if (int rc = run_frame(d, img, (int)(stride / format_size(fmt)), fmt, nullptr, nf, (long)fstride, false, devKpts, n, mask))
         return rc;
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;

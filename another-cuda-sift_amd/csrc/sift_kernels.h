@@ -165,12 +165,33 @@ struct KeypointParams {
     int descNrec;           // LDS record bound of the descriptor's counting sort
     int descExact;          // 1: OpenCV's sequential float histogram (k_descriptor_exact)
 };
+// Detection mask (cv::SIFT::detectAndCompute's mask argument; OpenCV's
+// KeyPointsFilter::runByPixelsMask): W x H bytes in device-readable memory,
+// rows `stride` bytes apart, frame f's mask at p + f * fstride.  A keypoint is
+// kept when mask[(int)(y + 0.5f)][(int)(x + 0.5f)] != 0 on its final
+// (rescaled) coordinates.  p == nullptr: no mask (every captured graph).
+struct MaskArg {
+    const uint8_t* p = nullptr;
+    int stride = 0, W = 0, H = 0;
+    long fstride = 0;
+};
+__device__ __forceinline__ bool mask_ok(const MaskArg& m, unsigned frame, float x, float y) {
+    if (!m.p) return true;
+    // float32 add, truncating cast (runByPixelsMask); the index is clamped
+    // defensively -- detector keypoints lie inside the frame.
+    const int ix = min(max((int)__fadd_rn(x, 0.5f), 0), m.W - 1);
+    const int iy = min(max((int)__fadd_rn(y, 0.5f), 0), m.H - 1);
+    return m.p[(size_t)frame * (size_t)m.fstride + (size_t)iy * (size_t)m.stride + (size_t)ix] != 0;
+}
+
 void launch_refine(const PyrDesc& pyr, const uint2* cand, unsigned capCand, Counters* ctr, uint32_t* bitmap,
                    RefKpt* out, const KeypointParams& kp, const Frames& fr, hipStream_t s);
 // Also clears each refined keypoint's dedupe bit (k_refine set it), so the
-// bitmap is zero again for the next frame without a memset.
+// bitmap is zero again for the next frame without a memset.  With a mask and
+// numFeatures <= 0 (no retainBest) a masked-out keypoint is left a hole before
+// its window is fetched.
 void launch_orientation(const PyrDesc& pyr, const RefKpt* in, Counters* ctr, OriKpt* out, uint32_t* bitmap,
-                        const KeypointParams& kp, const Frames& fr, hipStream_t s);
+                        const KeypointParams& kp, const Frames& fr, hipStream_t s, const MaskArg& mask = MaskArg{});
 // zero_range: the other frame buffer's 2 * kRangeSlots range keys (zeroed here
 // for the next frame, so no memset node is needed).
 void launch_select(const OriKpt* kpts, Counters* ctr, unsigned* zero_range, const KeypointParams& kp, const Frames& fr,
@@ -196,10 +217,13 @@ struct JobOrder {
     int jobBase[kLptSegs];
 };
 
+// mask: applied after the retainBest threshold (which still comes from every
+// oriented entry), as OpenCV filters by mask after retainBest.
 bool launch_order(const PyrDesc& pyr, const OriKpt* kpts, Counters* ctr, unsigned* zero_range, unsigned* bcount, unsigned* boff, int* slot,
-                  int* order, JobOrder* jord, const KeypointParams& kp, const Frames& fr, hipStream_t s);
+                  int* order, JobOrder* jord, const KeypointParams& kp, const Frames& fr, hipStream_t s,
+                  const MaskArg& mask = MaskArg{});
 void launch_bucket_count(const OriKpt* kpts, const Counters* ctr, unsigned* bcount, int* slot,
-                         const KeypointParams& kp, const Frames& fr, hipStream_t s);
+                         const KeypointParams& kp, const Frames& fr, hipStream_t s, const MaskArg& mask = MaskArg{});
 void launch_bucket_scan(unsigned* bcount, unsigned* boff, Counters* ctr, const KeypointParams& kp, const Frames& fr,
                         hipStream_t s);
 void launch_bucket_scatter(const OriKpt* kpts, const Counters* ctr, const unsigned* boff, const int* slot,

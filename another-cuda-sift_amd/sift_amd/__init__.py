@@ -100,6 +100,9 @@ def lib() -> ctypes.CDLL:
         "sift_hip_detect_device": (i, [vp, vp, sz, vp]),
         "sift_hip_detect_u8": (i, [vp, vp, sz]),
         "sift_hip_detect_device_fmt": (i, [vp, vp, sz, i, vp]),
+        "sift_hip_detect_masked": (i, [vp, vp, sz, i, vp, sz]),
+        "sift_hip_detect_device_masked": (i, [vp, vp, sz, i, vp, sz, vp]),
+        "sift_hip_detect_batch_device_masked": (i, [vp, vp, i, sz, sz, i, vp, sz, sz, vp]),
         "sift_hip_check_keypoints": (i, [vp, vp, i, ip]),
         "sift_hip_compute": (i, [vp, vp, sz, vp, i]),
         "sift_hip_compute_u8": (i, [vp, vp, sz, vp, i]),
@@ -361,8 +364,31 @@ class Detector:
             raise SiftHipError(f"image shape {img.shape} != configured {(self.config.row_width, self.config.col_width)}")
         return img, fmt
 
-    def detectAndCompute(self, image: np.ndarray) -> None:
-        """Detector.cu:133-233.  `image`: (rows, cols) float32 0..255 (Imagef) or uint8 (Image8U)."""
+    def _host_mask(self, mask) -> np.ndarray:
+        """A detection mask as the C ABI takes it: a 2-D uint8 array of the frame's shape whose last axis is
+        contiguous (a strided view is passed with its row stride, not copied).  Host-only check."""
+        if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8:
+            raise SiftHipError(f"mask must be a uint8 numpy array, got {getattr(mask, 'dtype', type(mask))}")
+        shape = (self.config.row_width, self.config.col_width)
+        if mask.ndim != 2 or mask.shape != shape:
+            raise SiftHipError(f"mask shape {mask.shape} != configured {shape}")
+        if mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
+            mask = np.ascontiguousarray(mask)
+        return mask
+
+    def detectAndCompute(self, image: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
+        """Detector.cu:133-233.  `image`: (rows, cols) float32 0..255 (Imagef) or uint8 (Image8U).
+        `mask` (cv::SIFT's mask argument; sift_hip_detect_masked): uint8 (rows, cols); a keypoint is dropped when
+        mask[int(y + 0.5), int(x + 0.5)] == 0 in float32 (sift_amd.cv.mask_keep), after retainBest(numFeatures)
+        as in OpenCV, and every result holds the kept rows only.  None: the unmasked call."""
+        if mask is not None:
+            m = self._host_mask(mask)
+            self.gpuWarmUpAndAllocate()
+            img, fmt = self._host_frame(image)
+            _check(lib().sift_hip_detect_masked(self._h, _ptr(img), img.strides[0], fmt, _ptr(m), m.strides[0]),
+                   "detectAndCompute")
+            self._refresh()
+            return
         self.gpuWarmUpAndAllocate()
         img, fmt = self._host_frame(image)
         if fmt == SIFT_HIP_U8:
@@ -453,10 +479,16 @@ class Detector:
         self._refresh()
 
     def detectAndComputeDevice(self, dev_ptr: int, row_stride_bytes: int, stream: Optional[int] = None, sync: bool = True,
-                               u8: bool = False) -> None:
+                               u8: bool = False, mask_ptr: Optional[int] = None, mask_stride: int = 0) -> None:
+        """mask_ptr: a device detection mask (col_width x row_width bytes, rows mask_stride bytes apart, 0 = packed),
+        read in place -- unchanged until sync, like the image (sift_hip_detect_device_masked)."""
         self.gpuWarmUpAndAllocate()
         fmt = SIFT_HIP_U8 if u8 else SIFT_HIP_F32
-        _check(lib().sift_hip_detect_device_fmt(self._h, dev_ptr, row_stride_bytes, fmt, stream), "detectAndComputeDevice")
+        if mask_ptr:
+            _check(lib().sift_hip_detect_device_masked(self._h, dev_ptr, row_stride_bytes, fmt, mask_ptr, mask_stride, stream),
+                   "detectAndComputeDevice")
+        else:
+            _check(lib().sift_hip_detect_device_fmt(self._h, dev_ptr, row_stride_bytes, fmt, stream), "detectAndComputeDevice")
         if sync:
             self.sync()
 
@@ -466,12 +498,20 @@ class Detector:
 
     # --- frame batches ----------------------------------------------------------
     def detectBatchDevice(self, dev_ptr: int, n: int, row_stride_bytes: int = 0, frame_stride_bytes: int = 0,
-                          stream: Optional[int] = None, sync: bool = True, u8: bool = False) -> None:
-        """n (<= batch) device frames at dev_ptr + i * frame_stride_bytes, one launch per stage for all."""
+                          stream: Optional[int] = None, sync: bool = True, u8: bool = False,
+                          masks_ptr: Optional[int] = None, mask_stride: int = 0, mask_frame_stride: int = 0) -> None:
+        """n (<= batch) device frames at dev_ptr + i * frame_stride_bytes, one launch per stage for all.
+        masks_ptr: n device detection masks, mask i at masks_ptr + i * mask_frame_stride (0 = mask_stride * rows),
+        rows mask_stride bytes apart (0 = packed): sift_hip_detect_batch_device_masked."""
         self.gpuWarmUpAndAllocate()
         fmt = SIFT_HIP_U8 if u8 else SIFT_HIP_F32
-        _check(lib().sift_hip_detect_batch_device(self._h, dev_ptr, n, row_stride_bytes, frame_stride_bytes, fmt, stream),
-               "detectBatchDevice")
+        if masks_ptr:
+            _check(lib().sift_hip_detect_batch_device_masked(self._h, dev_ptr, n, row_stride_bytes, frame_stride_bytes, fmt,
+                                                             masks_ptr, mask_stride, mask_frame_stride, stream),
+                   "detectBatchDevice")
+        else:
+            _check(lib().sift_hip_detect_batch_device(self._h, dev_ptr, n, row_stride_bytes, frame_stride_bytes, fmt, stream),
+                   "detectBatchDevice")
         if sync:
             self.sync()
 

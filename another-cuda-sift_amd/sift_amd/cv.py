@@ -45,6 +45,23 @@ def from_cv_keypoints(kpts) -> np.ndarray:
     return out
 
 
+def mask_keep(x, y, mask: np.ndarray) -> np.ndarray:
+    """KeyPointsFilter::runByPixelsMask in numpy (the rule of Detector.detectAndCompute(image, mask)): keypoint i is
+    kept when mask[int(y[i] + 0.5f), int(x[i] + 0.5f)] != 0 -- float32 add, truncating cast, any non-zero byte keeps.
+    `mask`: 2-D uint8 (any strides).  Returns a bool array; kpts[mask_keep(kpts[:, 0], kpts[:, 1], mask)] is the
+    kept list in its order.  The index is clamped to the mask (detector keypoints never need it)."""
+    m = np.asarray(mask)
+    if m.ndim != 2 or m.dtype != np.uint8:
+        raise ValueError("mask must be a 2-D uint8 array")
+    xs = np.asarray(x, np.float32).reshape(-1)
+    ys = np.asarray(y, np.float32).reshape(-1)
+    if len(xs) != len(ys):
+        raise ValueError("x and y differ in length")
+    ix = np.clip((xs + np.float32(0.5)).astype(np.int32), 0, m.shape[1] - 1)
+    iy = np.clip((ys + np.float32(0.5)).astype(np.int32), 0, m.shape[0] - 1)
+    return m[iy, ix] != 0
+
+
 def descriptor_matrix(descriptors: np.ndarray, num_pts: int) -> np.ndarray:
     """ConversionImpl.hpp:66-82: row-major 128-wide descriptors -> float32 (n, 128)."""
     d = np.asarray(descriptors).reshape(-1, 128)

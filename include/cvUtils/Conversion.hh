@@ -24,6 +24,7 @@
 namespace OpencvUtils {
 
 // ConversionImpl.hpp:8-31: single-channel CV_8U / CV_32F / CV_64F -> Image<T>.
+// A cv::SIFT mask goes the same way: det.detectAndCompute(img, cvMatToImage<unsigned char>(mask)).
 template <typename DataType_T>
 Image<DataType_T> cvMatToImage(const cv::Mat& mat) {
     if (mat.channels() > 1) throw std::runtime_error("More channels than expected");

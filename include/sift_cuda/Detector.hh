@@ -61,6 +61,25 @@ public:
     // Extra: image already in device memory (fp32, row stride in bytes).
     void detectAndComputeDevice(const float* device_image, size_t row_stride_bytes, void* hip_stream = nullptr);
 
+    // Extra: cv::SIFT::detectAndCompute(image, mask, ...) -- a detection mask
+    // (Image8U of the frame's size; sift_hip_detect_masked).  A keypoint is
+    // dropped when mask[(int)(y + 0.5f)][(int)(x + 0.5f)] == 0 (OpenCV's
+    // KeyPointsFilter::runByPixelsMask; any non-zero byte keeps it), after
+    // retainBest(numFeatures) as in OpenCV: total_size, the device buffers,
+    // prev_descriptor of the next frame and the host results hold the kept rows
+    // only, in the unmasked order.  Synchronous.  A mask of the wrong size
+    // throws std::invalid_argument (nothing runs).  No submit / submitDevice
+    // variants take a mask, and compute() takes none (OpenCV ignores the mask
+    // for provided keypoints).
+    void detectAndCompute(const Imagef& image, const Image8U& mask);
+    void detectAndCompute(const Image8U& image, const Image8U& mask);
+    // Extra: the same for a device image (fp32 or 8-bit) and a device mask
+    // (col_width x row_width bytes, row stride in bytes, 0 = packed), read in
+    // place after `hip_stream` reaches the call; returns when the results are
+    // ready.  A null mask is the unmasked call.
+    void detectAndComputeDevice(const void* device_image, size_t row_stride_bytes, bool u8, const uint8_t* device_mask,
+                                size_t mask_stride_bytes, void* hip_stream = nullptr);
+
     // Extra: descriptors for the caller's own keypoints (cv::Feature2D::compute;
     // sift_hip_compute / sift_hip_compute_u8): the frame's pyramid is built and
     // the keypoints described in the caller's order -- total_size =

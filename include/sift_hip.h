@@ -160,6 +160,59 @@ int sift_hip_compute_u8(sift_hip_t h, const uint8_t* host_img, size_t row_stride
 int sift_hip_compute_device(sift_hip_t h, const void* dev_img, size_t row_stride_bytes, int format,
                             const sift_hip_keypoint* dev_kpts, int n, void* stream);
 
+/* Detection mask: cv::SIFT::detectAndCompute(img, mask, kpts, desc) with a
+ * non-empty mask.  The mask is an 8-bit image of the frame's size (col_width x
+ * row_width bytes, row stride in bytes, 0 = packed).  OpenCV applies it to the
+ * detector's final keypoint list (KeyPointsFilter::runByPixelsMask) -- after
+ * the duplicate filter, after retainBest(numFeatures) and after the upscale
+ * rescale of pt -- and so does this build: a keypoint is REMOVED when
+ *     mask[(int)(pt.y + 0.5f)][(int)(pt.x + 0.5f)] == 0
+ * (float32 add, truncating cast, on the coordinates kpts3 holds; any non-zero
+ * byte keeps it; the index is clamped to the mask, which detector keypoints
+ * never need).  The kept keypoints keep their order, and everything downstream
+ * sees the kept rows only: sift_hip_num_keypoints, kpts3 / feats4 / desc, the
+ * matcher sidecar, prev_desc of the next frame, the host results.  The result
+ * capacity (overflow flag 8) is judged on the kept count.
+ *
+ * The mask acts AFTER retainBest: with numFeatures = N a masked frame returns
+ * the kept subset of the unmasked frame's N best -- usually fewer than N, not
+ * the N best of the masked region.  With numFeatures = 0 (keep all) masked-out
+ * keypoints are dropped before their orientation histogram is built, so their
+ * orientation and descriptor work is saved.
+ *
+ * A masked call is a frame like any other single-frame (or batch) detect: next
+ * frame number and results slot, prev_desc = the previous frame's rows, fresh
+ * sidecars; on a batch handle the single-frame calls use frame 0's arena; on a
+ * micro-batching / auto-group handle queued frames are launched first.  It
+ * launches the detect chain's kernels eagerly with the mask as an argument;
+ * frames without a mask launch the captured graphs as before.  mask == NULL
+ * makes each call identical to its unmasked counterpart.  A mask stride below
+ * the width (or an unknown format) is SIFT_HIP_ERR_INVALID, and a masked call
+ * while sift_hip_set_datagen is active is SIFT_HIP_ERR_STATE (the dump format
+ * holds no mask, so a replay could not reproduce the frame); in both cases
+ * nothing is launched and the previous results stay current.  Timing mode works.
+ * There are no pipelined (sift_hip_submit / sift_hip_submit_device /
+ * micro-batch) variants.  sift_hip_compute* take no mask: OpenCV ignores the
+ * mask when useProvidedKeypoints is set.
+ *
+ * Host image (SIFT_HIP_F32 / SIFT_HIP_U8) and host mask; synchronous.  The mask
+ * goes through handle-owned staging allocated at the first such call; both
+ * buffers are free on return. */
+int sift_hip_detect_masked(sift_hip_t h, const void* host_img, size_t row_stride_bytes, int format,
+                           const uint8_t* host_mask, size_t mask_stride_bytes);
+/* Device image and device mask, enqueued after `stream`, not synchronised (as
+ * sift_hip_detect_device_fmt).  The mask is read in place: like the image it
+ * must stay unchanged until sift_hip_sync. */
+int sift_hip_detect_device_masked(sift_hip_t h, const void* dev_img, size_t row_stride_bytes, int format,
+                                  const uint8_t* dev_mask, size_t mask_stride_bytes, void* stream);
+/* n device frames and n device masks (mask i at dev_masks + i *
+ * mask_frame_stride_bytes, 0 = mask stride * height), as
+ * sift_hip_detect_batch_device.  Each frame's results are those of the
+ * single-frame masked call on it, bit for bit. */
+int sift_hip_detect_batch_device_masked(sift_hip_t h, const void* dev_frames, int n, size_t row_stride_bytes,
+                                        size_t frame_stride_bytes, int format, const uint8_t* dev_masks,
+                                        size_t mask_stride_bytes, size_t mask_frame_stride_bytes, void* stream);
+
 /* Frame batches (C4: many frames per GPU).  sift_hip_set_batch(h, B), called
  * before sift_hip_warmup, gives the handle B frame arenas (pyramid, keypoint
  * lists, counters and result slots per frame) and a pipeline graph whose every

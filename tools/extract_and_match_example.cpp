@@ -11,6 +11,9 @@
 // --ahead N (with --pipelined): N frames submitted past the one waited for
 // (default 1, or 2N with --micro-batch); past 2 per lane the default handle
 // runs them in automatic launch groups (sift_hip_set_auto_micro_batch).
+// --mask-border N (synchronous loop only): every frame is detected with a
+// mask that zeroes an N-pixel frame border (cv::SIFT's mask argument,
+// Detector::detectAndCompute(image, mask)); no keypoint may come from it.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -22,7 +25,7 @@
 int main(int argc, char** argv) {
     int W = 752, H = 480, frames = 4, dx = 3, dy = 2;
     bool pipelined = false, exact = false;
-    int micro = 1, ahead_arg = 0;
+    int micro = 1, ahead_arg = 0, border = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--pipelined") pipelined = true;
@@ -32,6 +35,7 @@ int main(int argc, char** argv) {
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--micro-batch" && i + 1 < argc) micro = std::atoi(argv[++i]);
         else if (a == "--ahead" && i + 1 < argc) ahead_arg = std::atoi(argv[++i]);
+        else if (a == "--mask-border" && i + 1 < argc) border = std::atoi(argv[++i]);
     }
     const int PW = W + frames * dx, PH = H + frames * dy;
     std::vector<float> big((size_t)PW * PH);
@@ -49,6 +53,14 @@ int main(int argc, char** argv) {
         detector.setMicroBatch(micro);
     }
     detector.gpuWarmUpAndAllocate();
+    if (border > 0 && pipelined) {
+        std::fprintf(stderr, "--mask-border needs the synchronous loop (no pipelined masked variant)\n");
+        return 1;
+    }
+    Image8U mask(H, W);
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+            mask.at(y, x) = x >= border && x < W - border && y >= border && y < H - border ? 255 : 0;
     int prev_size = 0;
     std::vector<sift_cuda::Float3> prev_kpts;
     int failures = 0;
@@ -72,10 +84,20 @@ int main(int argc, char** argv) {
         } else {
             Imagef img(H, W);
             frame(f, img);
-            detector.detectAndCompute(img);
+            if (border > 0)
+                detector.detectAndCompute(img, mask);
+            else
+                detector.detectAndCompute(img);
         }
         detector.copyToHost(false);
         const int curr_size = detector.total_size;
+        if (border > 0)
+            for (const auto& k : detector.final_kpts)
+                if (!mask.at((int)(k.y + 0.5f), (int)(k.x + 0.5f))) {
+                    std::printf("frame %d: keypoint (%g, %g) lies in the masked border\n", f, k.x, k.y);
+                    failures++;
+                    break;
+                }
         if (f > 0) {
             const auto matches = sift_cuda::matchBruteForce(detector.prev_descriptor, prev_size,
                                                             detector.device_descriptor, curr_size);
