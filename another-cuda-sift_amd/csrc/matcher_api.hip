@@ -90,9 +90,17 @@ struct sift_hip_matcher {
     long codeRows = 0;
     unsigned epoch = 0;
     bool sidecars = true;  // single pairs of detector buffers: match their sidecar codes (k_match_direct)
+    // Match lists (sift_hip_match_list_*), allocated at the first such call: the top-2 arrays of the forward pairs
+    // (rows 0 .. sum nq) and of the reverse pairs (after them), 2 maxP maxQ rows of two entries each; the records
+    // and the count of sift_hip_match_list_host.
+    int* dSelIdx = nullptr;
+    float* dSelD = nullptr;
+    MatchRecord* dList = nullptr;
+    int* dCount = nullptr;
     ~sift_hip_matcher() {
         (void)hipSetDevice(device);
-        for (void* p : {(void*)dKeys, (void*)dDone, (void*)dMatch, (void*)dCodes, (void*)dRowKeys, (void*)dFlags})
+        for (void* p : {(void*)dKeys, (void*)dDone, (void*)dMatch, (void*)dCodes, (void*)dRowKeys, (void*)dFlags,
+                        (void*)dSelIdx, (void*)dSelD, (void*)dList, (void*)dCount})
             if (p) (void)hipFree(p);
     }
 };
@@ -259,6 +267,187 @@ int sift_hip_match_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const u
     int rc = sift_hip_match_device(m, q, nq, t, nt, ratio, ratio_on_squared, nullptr, nullptr, m->dMatch, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(out, m->dMatch, sizeof(int) * nq, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+}  // extern "C"
+
+// --- Match lists -------------------------------------------------------------
+static_assert(sizeof(sift_hip_dmatch) == sizeof(MatchRecord) && sizeof(sift_hip_dmatch) == 16, "cv::DMatch layout");
+static_assert(sizeof(sift_hip_match_filter) == sizeof(MatchFilter), "the filter is passed to the kernel as it is");
+
+namespace {
+
+bool needs_reverse(const sift_hip_match_filter& f) { return f.cross_check || f.ratio_both_ways; }
+
+// The select scratch, at the first list call of a matcher (not under stream capture).
+int ensure_select_scratch(sift_hip_matcher* m) {
+    if (m->dSelIdx) return SIFT_HIP_OK;
+    const size_t rows = 2 * (size_t)m->maxP * m->maxQ;
+    HIPCHK(hipSetDevice(m->device));
+    if (hipMalloc((void**)&m->dSelIdx, sizeof(int) * 2 * rows) != hipSuccess ||
+        hipMalloc((void**)&m->dSelD, sizeof(float) * 2 * rows) != hipSuccess ||
+        hipMalloc((void**)&m->dList, sizeof(MatchRecord) * (size_t)m->maxQ) != hipSuccess ||
+        hipMalloc((void**)&m->dCount, sizeof(int) * (size_t)m->maxP) != hipSuccess) {
+        for (void** p : {(void**)&m->dSelIdx, (void**)&m->dSelD, (void**)&m->dList, (void**)&m->dCount}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return fail(SIFT_HIP_ERR_NOMEM, "match list scratch allocation failed");
+    }
+    return SIFT_HIP_OK;
+}
+
+// Argument rules shared by the list entry points (nothing is launched on a failure).
+int check_list_args(sift_hip_matcher* m, int P, const int* nq, const int* nt, const sift_hip_match_filter* filter,
+                    const void* out, const void* counts) {
+    if (!m || !filter || !out || !counts || P <= 0 || P > m->maxP || !nq || !nt)
+        return fail(SIFT_HIP_ERR_INVALID, "bad match list arguments");
+    const bool rev = needs_reverse(*filter);
+    for (int p = 0; p < P; p++) {
+        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
+            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
+        if (rev && (nt[p] > m->maxQ || nq[p] > m->maxT))
+            return fail(SIFT_HIP_ERR_INVALID, "the reverse pair (roles swapped) exceeds matcher limits");
+    }
+    return SIFT_HIP_OK;
+}
+
+// Filter and compact the top-2 arrays in the select scratch: forward pair p at row sum_{r<p} nq[r], reverse pair p at
+// row sum nq + sum_{r<p} nt[r].
+int select_lists(sift_hip_matcher* m, int P, const int* nq, const int* nt, const sift_hip_match_filter& filter,
+                 sift_hip_dmatch* out, int* counts, hipStream_t stream) {
+    SelectBatch sb{};
+    int totq = 0;
+    for (int p = 0; p < P; p++) totq += nq[p];
+    int fwd = 0, rev = totq;
+    for (int p = 0; p < P; p++) {
+        // a pair without train rows keeps nothing (its top-2 rows hold no entry)
+        sb.pair[p] = SelectPair{nt[p] > 0 ? nq[p] : 0, nt[p], fwd, rev, fwd};
+        fwd += nq[p];
+        rev += nt[p];
+    }
+    const MatchFilter f{filter.ratio, filter.ratio_on_squared, filter.ratio_both_ways, filter.max_distance,
+                        filter.cross_check};
+    launch_match_select(sb, P, m->dSelIdx, m->dSelD, f, reinterpret_cast<MatchRecord*>(out), counts, stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+bool any_pair(int P, const int* nq, const int* nt) {
+    for (int p = 0; p < P; p++)
+        if (nq[p] > 0 && nt[p] > 0) return true;
+    return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sift_hip_default_match_filter(sift_hip_match_filter* f) {
+    if (!f) return;
+    f->ratio = 0.8f;
+    f->ratio_on_squared = 0;
+    f->ratio_both_ways = 0;
+    f->max_distance = 0.f;
+    f->cross_check = 1;
+}
+
+int sift_hip_match_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                const uint16_t* const* t, const int* nt, const sift_hip_match_filter* filter,
+                                sift_hip_dmatch* out, int* counts, void* stream) {
+    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
+    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "bad match list arguments");
+    for (int p = 0; p < P; p++)
+        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
+    if (int rc = ensure_select_scratch(m)) return rc;
+    const bool rev = needs_reverse(*filter);
+    if (any_pair(P, nq, nt)) {
+        int totq = 0;
+        for (int p = 0; p < P; p++) totq += nq[p];
+        Sidecar sq{}, st{};
+        // A single pair of detector buffers goes through its sidecars in both directions (two direct launches).
+        const bool direct = P == 1 && m->sidecars && find_sidecar(q[0], nq[0], &sq) && find_sidecar(t[0], nt[0], &st);
+        if (rev && 2 * P <= m->maxP && !direct) {
+            // Forward and reverse pairs in one launch; the sets are deduplicated by pointer, so each is converted once.
+            const uint16_t *q2[kMaxMatchPairs], *t2[kMaxMatchPairs];
+            int nq2[kMaxMatchPairs], nt2[kMaxMatchPairs];
+            for (int p = 0; p < P; p++) {
+                q2[p] = q[p], t2[p] = t[p], nq2[p] = nq[p], nt2[p] = nt[p];
+                q2[P + p] = t[p], t2[P + p] = q[p], nq2[P + p] = nt[p], nt2[P + p] = nq[p];
+            }
+            if (int rc = sift_hip_match_batched(m, 2 * P, q2, nq2, t2, nt2, 0.f, 0, m->dSelIdx, m->dSelD, nullptr, stream))
+                return rc;
+        } else {
+            // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
+            if (int rc = sift_hip_match_batched(m, P, q, nq, t, nt, 0.f, 0, m->dSelIdx, m->dSelD, nullptr, stream))
+                return rc;
+            if (rev)
+                if (int rc = sift_hip_match_batched(m, P, t, nt, q, nq, 0.f, 0, m->dSelIdx + 2 * (size_t)totq,
+                                                    m->dSelD + 2 * (size_t)totq, nullptr, stream))
+                    return rc;
+        }
+    }
+    HIPCHK(hipSetDevice(m->device));
+    return select_lists(m, P, nq, nt, *filter, out, counts, (hipStream_t)stream);
+}
+
+int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                      const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                      const int* tkey0, const int* nt, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* counts, void* stream) {
+    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
+    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
+    for (int p = 0; p < P; p++)
+        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
+            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
+    if (int rc = ensure_select_scratch(m)) return rc;
+    const bool rev = needs_reverse(*filter);
+    if (any_pair(P, nq, nt)) {
+        int totq = 0;
+        for (int p = 0; p < P; p++) totq += nq[p];
+        if (rev && 2 * P <= m->maxP) {
+            int a[6][kMaxMatchPairs];  // qrow0, qkey0, nq, trow0, tkey0, nt of the 2P pairs
+            for (int p = 0; p < P; p++) {
+                a[0][p] = qrow0[p], a[1][p] = qkey0[p], a[2][p] = nq[p], a[3][p] = trow0[p], a[4][p] = tkey0[p], a[5][p] = nt[p];
+                a[0][P + p] = trow0[p], a[1][P + p] = tkey0[p], a[2][P + p] = nt[p];
+                a[3][P + p] = qrow0[p], a[4][P + p] = qkey0[p], a[5][P + p] = nq[p];
+            }
+            if (int rc = sift_hip_match_codes_batched(m, codes, keys, 2 * P, a[0], a[1], a[2], a[3], a[4], a[5], 0.f, 0,
+                                                      m->dSelIdx, m->dSelD, nullptr, stream))
+                return rc;
+        } else {
+            if (int rc = sift_hip_match_codes_batched(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, 0.f, 0,
+                                                      m->dSelIdx, m->dSelD, nullptr, stream))
+                return rc;
+            if (rev)
+                if (int rc = sift_hip_match_codes_batched(m, codes, keys, P, trow0, tkey0, nt, qrow0, qkey0, nq, 0.f, 0,
+                                                          m->dSelIdx + 2 * (size_t)totq, m->dSelD + 2 * (size_t)totq,
+                                                          nullptr, stream))
+                    return rc;
+        }
+    }
+    HIPCHK(hipSetDevice(m->device));
+    return select_lists(m, P, nq, nt, *filter, out, counts, (hipStream_t)stream);
+}
+
+int sift_hip_match_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, void* stream) {
+    return sift_hip_match_list_batched(m, 1, &q, &nq, &t, &nt, filter, out, count, stream);
+}
+
+int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                             const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count) {
+    if (!m || !filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
+    *count = 0;
+    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
+    if (int rc = ensure_select_scratch(m)) return rc;
+    if (int rc = sift_hip_match_list_device(m, q, nq, t, nt, filter, reinterpret_cast<sift_hip_dmatch*>(m->dList),
+                                            m->dCount, nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
     return SIFT_HIP_OK;
 }
 

@@ -77,4 +77,38 @@ void launch_match_codes(MatchBatch& batch, const MatchPlan& plan, int nq_stride,
                         const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
                         int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s);
 
+// --- Match lists (sift_hip_match_list_*): filter + ordered compaction of the
+// top-2 arrays the launchers above wrote (k_match_select).
+//
+// One record per kept query, cv::DMatch's layout (sift_hip_dmatch).
+struct MatchRecord {
+    int queryIdx, trainIdx, imgIdx;
+    float distance;
+};
+static_assert(sizeof(MatchRecord) == 16, "cv::DMatch layout");
+
+// The keep rule's parameters (sift_hip_match_filter; the rule is in include/sift_hip.h).
+struct MatchFilter {
+    float ratio;
+    int ratio_on_squared, ratio_both_ways;
+    float max_distance;
+    int cross_check;
+};
+
+// Pair p of a select launch: the forward top-2 of its query i is row fwd + i of
+// idx2 / d2, the reverse top-2 of its train row t is row rev + t (read only when
+// the filter needs the reverse direction), its records go to out + out_off.
+struct SelectPair {
+    int nq, nt, fwd, rev, out_off;
+};
+// Passed by value (64 x 20 B of kernarg).
+struct SelectBatch {
+    SelectPair pair[kMaxMatchPairs];
+};
+
+// One 1024-thread workgroup per pair: records of the kept queries in ascending
+// query order at out + out_off, their number in counts[p].
+void launch_match_select(const SelectBatch& batch, int P, const int* idx2, const float* d2, const MatchFilter& filter,
+                         MatchRecord* out, int* counts, hipStream_t s);
+
 }  // namespace sift_amd

@@ -39,6 +39,8 @@ SIFT_HIP_FLAG_BAD_KEYPOINT = 16  # overflow_flags() bit: computeDevice met an in
 # sift_hip_keypoint (cv::KeyPoint minus class_id, 24 bytes): the records Detector.compute takes.
 # octave is OpenCV's packed form (octave & 255 | layer << 8 | xi << 16).
 KPT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
+# sift_hip_dmatch (cv::DMatch's fields in its order, 16 bytes): the records of Matcher.match_list_*.
+DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
 _lib = None
 
 
@@ -67,6 +69,23 @@ class _Config(ctypes.Structure):
         ("numOctaves", ctypes.c_int),
         ("maxKeypoints", ctypes.c_int),
     ]
+
+
+class _MatchFilter(ctypes.Structure):
+    _fields_ = [
+        ("ratio", ctypes.c_float),
+        ("ratio_on_squared", ctypes.c_int),
+        ("ratio_both_ways", ctypes.c_int),
+        ("max_distance", ctypes.c_float),
+        ("cross_check", ctypes.c_int),
+    ]
+
+
+def _match_filter(ratio: float = 0.8, ratio_on_squared: bool = False, ratio_both_ways: bool = False,
+                  max_distance: float = 0.0, cross_check: bool = True) -> _MatchFilter:
+    """sift_hip_match_filter with sift_hip_default_match_filter's defaults."""
+    return _MatchFilter(ratio, int(bool(ratio_on_squared)), int(bool(ratio_both_ways)), max_distance,
+                        int(bool(cross_check)))
 
 
 def lib() -> ctypes.CDLL:
@@ -150,6 +169,12 @@ def lib() -> ctypes.CDLL:
         "sift_hip_match_batched": (i, [vp, i, vp, vp, vp, vp, f, i, vp, vp, vp, vp]),
         "sift_hip_match_host": (i, [vp, vp, i, vp, i, f, i, vp]),
         "sift_hip_match_plan": (i, [i, i, i, ip, ip]),
+        "sift_hip_default_match_filter": (None, [ctypes.POINTER(_MatchFilter)]),
+        "sift_hip_match_list_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_MatchFilter),
+                                                  vp, vp, vp]),
+        "sift_hip_match_list_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchFilter), vp, i, ip]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -699,7 +724,72 @@ class Matcher:
         return out
 
 
+    # --- match lists: match -> filter -> ordered compaction on the device (the rule: include/sift_hip.h, and in
+    # numpy sift_amd.cv.filter_matches).  `filter` keywords: ratio=0.8, ratio_on_squared=False,
+    # ratio_both_ways=False, max_distance=0 (off), cross_check=True.  The first list call of a matcher allocates its
+    # scratch (not under stream capture).
+
+    def match_list_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, out_ptr: int, count_ptr: int,
+                          stream: Optional[int] = None, **filter) -> None:
+        """DMATCH_DTYPE records of the kept queries, ascending queryIdx, at out_ptr (device, room for nq) and their
+        number at count_ptr (device int32); enqueued on `stream` (sift_hip_match_list_device)."""
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_device(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(f), out_ptr or None,
+                                                count_ptr or None, stream), "match_list_device")
+
+    def match_list_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int], nts: Sequence[int],
+                           out_ptr: int, counts_ptr: int, stream: Optional[int] = None, **filter) -> None:
+        """P pairs: pair p's records at row sum(nqs[:p]) of out_ptr with imgIdx = p, its count at counts_ptr[p]
+        (sift_hip_match_list_batched)."""
+        P = len(q_ptrs)
+        qa = (ctypes.c_void_p * P)(*q_ptrs)
+        ta = (ctypes.c_void_p * P)(*t_ptrs)
+        na = (ctypes.c_int * P)(*nqs)
+        ma = (ctypes.c_int * P)(*nts)
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_batched(self._m, P, qa, na, ta, ma, ctypes.byref(f), out_ptr or None,
+                                                 counts_ptr or None, stream), "match_list_batched")
+
+    def match_list_codes_batched(self, codes_ptr: int, keys_ptr: int, pairs: Sequence, out_ptr: int, counts_ptr: int,
+                                 stream: Optional[int] = None, **filter) -> None:
+        """The same for pairs (qrow0, qkey0, nq, trow0, tkey0, nt) of ready code sets, as match_codes_batched takes
+        them (sift_hip_match_list_codes_batched)."""
+        P = len(pairs)
+        qr, qk, nq, tr, tk, nt = ((ctypes.c_int * P)(*[p[k] for p in pairs]) for k in range(6))
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_codes_batched(self._m, codes_ptr, keys_ptr, P, qr, qk, nq, tr, tk, nt,
+                                                       ctypes.byref(f), out_ptr or None, counts_ptr or None, stream),
+               "match_list_codes_batched")
+
+    def match_list_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, **filter) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_list_host)."""
+        out = np.zeros(max(nq, 0), DMATCH_DTYPE)
+        f = _match_filter(**filter)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_list_host(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(f), _ptr(out), len(out),
+                                              ctypes.byref(n)), "match_list_host")
+        return out[: n.value]
+
+
 _default_matcher: Optional[Matcher] = None
+
+
+def matchList(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src: int, **filter) -> np.ndarray:
+    """The usable match list of des against src in one device operation: DMATCH_DTYPE records (queryIdx, trainIdx,
+    imgIdx 0, L2 distance) of the rows that pass the filter -- by default Lowe's ratio 0.8 on distances and the cross
+    check of cv::BFMatcher(NORM_L2, crossCheck=True) -- in ascending queryIdx.  `filter` keywords as
+    Matcher.match_list_*; the rule is sift_amd.cv.filter_matches."""
+    global _default_matcher
+    need = max(num_des, num_src, 1)  # the reverse direction swaps the roles: both limits hold both sets
+    if (_default_matcher is None or need > min(_default_matcher.max_query, _default_matcher.max_train)
+            or _default_matcher.max_pairs < 2):
+        cap = max(need, _default_matcher.max_query if _default_matcher else 0,
+                  _default_matcher.max_train if _default_matcher else 0)
+        # two pairs: foreign buffers match both directions in one launch (detector buffers use their sidecars)
+        _default_matcher = Matcher(cap, cap, max_pairs=2)
+    if num_des <= 0 or num_src <= 0:
+        return np.zeros(0, DMATCH_DTYPE)
+    return _default_matcher.match_list_host(des.data(), num_des, src.data(), num_src, **filter)
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

@@ -3,6 +3,8 @@ cvUtils/Conversion.hh:12-70 (``OpencvUtils::localKptToCvKpt``,
 ``descriptorToCvMat``, ``cvtMatchToDMatch``).  The field mapping is plain
 numpy so it is usable (and tested) without OpenCV; the ``cv2`` object builders
 import cv2 lazily and raise ImportError where OpenCV is absent.
+``filter_matches`` is the match-list rule (cross check, ratio test, distance
+cap; ``sift_amd.matchList``) on the host.
 """
 from typing import List, Sequence
 
@@ -74,6 +76,68 @@ def dmatch_triples(match: Sequence[int]) -> List[tuple]:
     return [(i, int(m), 0.0) for i, m in enumerate(match) if m != -1]
 
 
+def _ratio_pass(idx2: np.ndarray, d2: np.ndarray, ratio, ratio_on_squared: bool) -> np.ndarray:
+    """The ratio test of sift_hip_match_device's `match` output, per row of a top-2 array, in float32."""
+    a1, a2 = idx2[:, 0], idx2[:, 1]
+    r = np.float32(ratio)
+    if not r > 0:
+        return a1 >= 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        if ratio_on_squared:
+            test = d2[:, 0] < r * d2[:, 1]
+        else:
+            test = np.sqrt(d2[:, 0]) < r * np.sqrt(d2[:, 1])
+    return (a1 >= 0) & ((a2 < 0) | test)
+
+
+def filter_matches(idx2_fwd, d2_fwd, idx2_rev=None, d2_rev=None, ratio: float = 0.8, ratio_on_squared: bool = False,
+                   ratio_both_ways: bool = False, max_distance: float = 0.0, cross_check: bool = True,
+                   img_idx: int = 0) -> np.ndarray:
+    """The match-list rule of include/sift_hip.h (Matcher.match_list_*, matchList) in numpy, float32 arithmetic: the
+    reference the tests hold the device operation to.
+
+    idx2_fwd / d2_fwd: (nq, 2) top-2 train indices (-1: none) and squared distances of every query, as
+    Matcher.match_device(Q, T) writes them; idx2_rev / d2_rev: (nt, 2), the same for match_device(T, Q) (needed with
+    cross_check or ratio_both_ways only).  Query i with forward (i1, e1, i2, e2) is kept when i1 >= 0, the ratio
+    test passes on its forward pair (it passes when i2 < 0; ratio <= 0: no test; on e or on sqrt(e)),
+    max_distance <= 0 or sqrt(e1) <= max_distance, with cross_check idx2_rev[i1, 0] == i, and with ratio_both_ways
+    the ratio test passes on row i1 of the reverse arrays.  Returns DMATCH_DTYPE records (i, i1, img_idx, sqrt(e1))
+    of the kept queries in ascending i."""
+    from . import DMATCH_DTYPE
+
+    fi = np.asarray(idx2_fwd, np.int32).reshape(-1, 2)
+    fd = np.asarray(d2_fwd, np.float32).reshape(-1, 2)
+    if len(fi) != len(fd):
+        raise ValueError("idx2_fwd and d2_fwd differ in length")
+    i1 = fi[:, 0]
+    with np.errstate(invalid="ignore"):
+        dist = np.sqrt(fd[:, 0])
+    keep = (i1 >= 0) & _ratio_pass(fi, fd, ratio, ratio_on_squared)
+    if np.float32(max_distance) > 0:
+        keep &= dist <= np.float32(max_distance)
+    if cross_check or ratio_both_ways:
+        if idx2_rev is None or d2_rev is None:
+            raise ValueError("cross_check / ratio_both_ways need the reverse top-2 arrays")
+        ri = np.asarray(idx2_rev, np.int32).reshape(-1, 2)
+        rd = np.asarray(d2_rev, np.float32).reshape(-1, 2)
+        if len(ri) != len(rd):
+            raise ValueError("idx2_rev and d2_rev differ in length")
+        if keep.any() and i1[keep].max() >= len(ri):
+            raise ValueError("a forward index lies outside the reverse arrays")
+        row = np.where(keep, i1, 0)  # rows of queries already dropped are not looked at
+        if len(ri) == 0:
+            keep &= False
+        else:
+            if cross_check:
+                keep &= ri[row, 0] == np.arange(len(fi))
+            if ratio_both_ways:
+                keep &= _ratio_pass(ri, rd, ratio, ratio_on_squared)[row]
+    q = np.flatnonzero(keep)
+    out = np.zeros(len(q), DMATCH_DTYPE)
+    out["queryIdx"], out["trainIdx"], out["imgIdx"], out["distance"] = q, i1[q], img_idx, dist[q]
+    return out
+
+
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     import cv2
 
@@ -86,7 +150,12 @@ def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     return out
 
 
-def to_cv_dmatches(match: Sequence[int]):
+def to_cv_dmatches(match):
+    """list of cv2.DMatch from DMATCH_DTYPE records (matchList, Matcher.match_list_*: real distances and imgIdx), or
+    from a match index per query (matchBruteForce: distance 0, -1 skipped)."""
     import cv2
 
+    names = getattr(getattr(match, "dtype", None), "names", None)
+    if names and "queryIdx" in names:
+        return [cv2.DMatch(int(r["queryIdx"]), int(r["trainIdx"]), int(r["imgIdx"]), float(r["distance"])) for r in match]
     return [cv2.DMatch(q, t, d) for q, t, d in dmatch_triples(match)]

@@ -123,4 +123,12 @@ inline std::vector<cv::DMatch> cvtMatchToDMatch(const std::vector<int>& match) {
     return out;
 }
 
+// sift_cuda::matchList records -> cv::DMatch with their real distances.
+inline std::vector<cv::DMatch> cvtMatchToDMatch(const std::vector<sift_cuda::DMatch>& matches) {
+    std::vector<cv::DMatch> out;
+    out.reserve(matches.size());
+    for (const sift_cuda::DMatch& m : matches) out.emplace_back(m.queryIdx, m.trainIdx, m.imgIdx, m.distance);
+    return out;
+}
+
 }  // namespace OpencvUtils

@@ -157,4 +157,14 @@ private:
 std::vector<int> matchBruteForce(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
                                  int num_src);
 
+// Extra: the usable match list in one device operation (sift_hip_match_list_host)
+// -- top-2 search in both directions, the filter (ratio test, distance cap,
+// cross check = cv::BFMatcher(NORM_L2, crossCheck = true)) and compaction on the
+// GPU: the kept (queryIdx, trainIdx, distance) records in ascending queryIdx,
+// imgIdx 0.  The rule is spelled out in include/sift_hip.h.  Synchronous; a
+// thread-local matcher as matchBruteForce's, sized so both directions fit.
+// OpencvUtils::cvtMatchToDMatch turns the result into std::vector<cv::DMatch>.
+std::vector<DMatch> matchList(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                              const MatchFilter& filter = {});
+
 }  // namespace sift_cuda

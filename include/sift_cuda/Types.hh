@@ -53,6 +53,25 @@ struct KeyPoint {
 };
 static_assert(sizeof(KeyPoint) == 24 && offsetof(KeyPoint, octave) == 20, "layout of sift_hip_keypoint");
 
+// One match of matchList: cv::DMatch's fields in its order, layout-identical to
+// sift_hip_dmatch.  distance is the L2 distance (not squared).
+struct DMatch {
+    int queryIdx, trainIdx, imgIdx;
+    float distance;
+};
+static_assert(sizeof(DMatch) == 16 && offsetof(DMatch, distance) == 12, "layout of sift_hip_dmatch");
+
+// The keep rule of matchList (sift_hip_match_filter, include/sift_hip.h; the
+// defaults are sift_hip_default_match_filter's).
+struct MatchFilter {
+    float ratio = 0.8f;            // Lowe's ratio; <= 0: no ratio test
+    int ratio_on_squared = 0;      // the ratio applies to squared distances (matchBruteForce's convention)
+    int ratio_both_ways = 0;       // the reverse top-2 of the matched row passes the ratio test too
+    float max_distance = 0.f;      // cap on the L2 distance; <= 0: none
+    int cross_check = 1;           // mutual nearest neighbours only (cv::BFMatcher's crossCheck)
+};
+static_assert(sizeof(MatchFilter) == 20, "layout of sift_hip_match_filter");
+
 // Non-owning view of a device array owned by a Detector (stands in for the
 // reference's thrust::device_vector members, Detector.hh:54-57; data()/size()
 // as there).  data() is read-only: the detector derives data from what it

@@ -495,6 +495,99 @@ int sift_hip_match_host(sift_hip_matcher_t m, const uint16_t* query, int nq,
                         const uint16_t* train, int nt, float ratio, int ratio_on_squared,
                         int* out);
 
+/* --- Match lists: match -> filter -> ordered compaction on the device -------
+ *
+ * What a caller of sift_hip_match_* does next (cv::BFMatcher(NORM_L2,
+ * crossCheck = true), COLMAP / SiftGPU's cross_check, "mutual nearest
+ * neighbour") in one enqueued operation: the top-2 search in both directions,
+ * the filter below, and the surviving matches as cv::DMatch-layout records in
+ * query order with their count -- nothing returns to the host in between.
+ *
+ * The rule.  For a pair (query set Q of nq rows, train set T of nt rows):
+ *   forward top-2  (i1, e1, i2, e2)[i] is what sift_hip_match_device(Q, T)
+ *                  writes to idx2 / d2 for query i (squared distances, ties to
+ *                  the lower train index, -1: none);
+ *   reverse top-2  (j1, f1, j2, f2)[t] is what sift_hip_match_device(T, Q)
+ *                  writes for train row t (ties to the lower query index);
+ *   ratio_pass(a1, d1, a2, d2): the ratio test of sift_hip_match_device's
+ *                  `match` output -- a1 >= 0 is required; it passes if a2 < 0;
+ *                  with ratio_on_squared the test is d1 < ratio * d2, else
+ *                  sqrtf(d1) < ratio * sqrtf(d2) in float32; ratio <= 0
+ *                  switches the test off (only a1 >= 0 remains).
+ * Query i is kept when all of these hold:
+ *   1. i1 >= 0;
+ *   2. ratio_pass(forward[i]);
+ *   3. max_distance <= 0, or sqrtf(e1) <= max_distance (float32);
+ *   4. if cross_check: j1[i1] == i;
+ *   5. if ratio_both_ways: ratio_pass(reverse[i1]).
+ * The output is the kept queries in ascending queryIdx, one record each:
+ * {queryIdx = i, trainIdx = i1, imgIdx = the pair's index p in the call,
+ * distance = sqrtf(e1)}, and the number of records.  The bytes are the same in
+ * every run (slots are assigned by prefix sums, not by atomics).  With neither
+ * cross_check nor ratio_both_ways the reverse direction is not computed: the
+ * call is a compacting form of sift_hip_match_device's ratio test.  The rule
+ * consumes whatever top-2 the match kernels produce, so it holds unchanged for
+ * sets with non-integer fp16 values (the general path, float d2).
+ *
+ * A mutual list (cross_check) is symmetric: the list of (b, a) is the list of
+ * (a, b) with queryIdx and trainIdx swapped (in trainIdx order).  An all-pairs
+ * exchange over 8 sets therefore needs the 28 unordered pairs, not the 56
+ * ordered ones.
+ *
+ * Scratch: the top-2 arrays of both directions live in matcher-owned scratch
+ * that is allocated at the first sift_hip_match_list_* call on the matcher, so
+ * a matcher that never makes one keeps its footprint.  That FIRST call
+ * allocates device memory and must not run under stream capture; later calls
+ * only launch kernels.  Calls on one matcher must be ordered, as for
+ * sift_hip_match_*. */
+typedef struct {
+    int queryIdx, trainIdx, imgIdx;
+    float distance;
+} sift_hip_dmatch; /* 16 bytes, cv::DMatch's fields in its order */
+
+typedef struct {
+    float ratio;          /* Lowe's ratio; <= 0: no ratio test */
+    int ratio_on_squared; /* the ratio applies to squared distances (matchBruteForce's convention) */
+    int ratio_both_ways;  /* the reverse top-2 of the matched train row passes the ratio test too */
+    float max_distance;   /* cap on the L2 distance (not squared); <= 0: none */
+    int cross_check;      /* keep mutual nearest neighbours only */
+} sift_hip_match_filter;
+
+/* ratio 0.8 on distances, one way, no distance cap, cross_check on. */
+void sift_hip_default_match_filter(sift_hip_match_filter* filter);
+
+/* One pair.  out: device, room for nq records; count: device int.  When the
+ * filter needs the reverse direction (cross_check or ratio_both_ways) the pair
+ * is also matched with the roles swapped, so nt <= max_query and
+ * nq <= max_train must hold besides sift_hip_match_device's limits.  A pair of
+ * detector buffers with fresh sidecars matches their codes directly in both
+ * directions.  A null matcher, filter, out or count, or a size over a limit:
+ * SIFT_HIP_ERR_INVALID, nothing is launched.  nq == 0 or nt == 0: count 0. */
+int sift_hip_match_list_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, void* stream);
+
+/* P pairs (host arrays as sift_hip_match_batched; P <= max_pairs).  Pair p's
+ * records start at row sum_{r<p} nq[r] of out (device, sum nq rows) and carry
+ * imgIdx = p; counts: device, P ints.  With the reverse direction needed and
+ * 2 P <= max_pairs the forward and reverse pairs run in one 2P-pair launch
+ * (each distinct set is converted once), otherwise in two P-pair launches on
+ * the stream; the results are the same bytes. */
+int sift_hip_match_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                const uint16_t* const* train, const int* nt, const sift_hip_match_filter* filter,
+                                sift_hip_dmatch* out, int* counts, void* stream);
+
+/* The same for pairs of ready code sets (sift_hip_match_codes_batched's
+ * arguments). */
+int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                      const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                      const int* tkey0, const int* nt, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* counts, void* stream);
+
+/* Synchronous, one pair, records to host memory: copies min(count, cap)
+ * records to out_host and sets *count to the full count. */
+int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                             const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count);
+
 /* The launch plan a match call of this shape gets: train splits S per query
  * block (S > 1: split workgroups merge their top-2 through the scratch's
  * atomics) and waves per workgroup.  Host-only (no GPU call beyond reading the

@@ -14,6 +14,10 @@
 // --mask-border N (synchronous loop only): every frame is detected with a
 // mask that zeroes an N-pixel frame border (cv::SIFT's mask argument,
 // Detector::detectAndCompute(image, mask)); no keypoint may come from it.
+// --cross-check / --max-distance D: the frame pairs are matched with
+// sift_cuda::matchList instead (filter + compaction on the GPU: Lowe's ratio,
+// the mutual-nearest-neighbour test with --cross-check, an L2 distance cap of
+// D with --max-distance) and its count is printed.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +30,8 @@ int main(int argc, char** argv) {
     int W = 752, H = 480, frames = 4, dx = 3, dy = 2;
     bool pipelined = false, exact = false;
     int micro = 1, ahead_arg = 0, border = 0;
+    bool cross_check = false;
+    float max_distance = 0.f;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--pipelined") pipelined = true;
@@ -36,6 +42,8 @@ int main(int argc, char** argv) {
         else if (a == "--micro-batch" && i + 1 < argc) micro = std::atoi(argv[++i]);
         else if (a == "--ahead" && i + 1 < argc) ahead_arg = std::atoi(argv[++i]);
         else if (a == "--mask-border" && i + 1 < argc) border = std::atoi(argv[++i]);
+        else if (a == "--cross-check") cross_check = true;
+        else if (a == "--max-distance" && i + 1 < argc) max_distance = (float)std::atof(argv[++i]);
     }
     const int PW = W + frames * dx, PH = H + frames * dy;
     std::vector<float> big((size_t)PW * PH);
@@ -98,7 +106,23 @@ int main(int argc, char** argv) {
                     failures++;
                     break;
                 }
-        if (f > 0) {
+        if (f > 0 && (cross_check || max_distance > 0.f)) {
+            sift_cuda::MatchFilter filter;  // ratio 0.8 on squared distances, as matchBruteForce below
+            filter.ratio_on_squared = 1;
+            filter.cross_check = cross_check;
+            filter.max_distance = max_distance;
+            const auto list = sift_cuda::matchList(detector.prev_descriptor, prev_size, detector.device_descriptor,
+                                                   curr_size, filter);
+            int consistent = 0;
+            for (const auto& m : list) {
+                const auto& a = prev_kpts[m.queryIdx];
+                const auto& b = detector.final_kpts[m.trainIdx];
+                if (std::fabs((a.x - dx) - b.x) < 1.5f && std::fabs((a.y - dy) - b.y) < 1.5f) consistent++;
+            }
+            std::printf("frame %d: %d kpts, %zu list matches, %d consistent with the (%d,%d) shift\n", f, curr_size,
+                        list.size(), consistent, -dx, -dy);
+            if (list.empty() || consistent * 10 < (int)list.size() * 8) failures++;
+        } else if (f > 0) {
             const auto matches = sift_cuda::matchBruteForce(detector.prev_descriptor, prev_size,
                                                             detector.device_descriptor, curr_size);
             int good = 0, consistent = 0;
