@@ -498,25 +498,25 @@ void enqueue_refine(sift_hip_detector* d, int nf) {
     });
 }
 
-void enqueue_orientation(sift_hip_detector* d, int nf) {
+void enqueue_orientation(sift_hip_detector* d, int nf, const MaskArg& mask) {
     const Frames fr{nf, d->afs};
     d->timed("orientation", 0,
-             [&] { launch_orientation(d->pyr, d->dRef, d->dCtr, d->dOri, d->dBitmap, d->kp, fr, d->stream, d->mask); });
+             [&] { launch_orientation(d->pyr, d->dRef, d->dCtr, d->dOri, d->dBitmap, d->kp, fr, d->stream, mask); });
 }
 
-void enqueue_order(sift_hip_detector* d, int slot, int nf) {
+void enqueue_order(sift_hip_detector* d, int slot, int nf, const MaskArg& mask) {
     hipStream_t s = d->stream;
     const int parity = slot & 1;
     const Frames fr{nf, d->afs};
     if (d->kp.numBuckets <= kOrderMaxBuckets) {
         d->timed("order", 0, [&] {
             launch_order(d->pyr, d->dOri, d->dCtr, range_keys(d, parity ^ 1), d->dBcount, d->dBoff, d->dSlot, d->dOrder,
-                         d->dJord, d->kp, fr, s, d->mask);
+                         d->dJord, d->kp, fr, s, mask);
         });
     } else {
         d->timed("select", 0, [&] { launch_select(d->dOri, d->dCtr, range_keys(d, parity ^ 1), d->kp, fr, s); });
         d->timed("bucket_count", 0,
-                 [&] { launch_bucket_count(d->dOri, d->dCtr, d->dBcount, d->dSlot, d->kp, fr, s, d->mask); });
+                 [&] { launch_bucket_count(d->dOri, d->dCtr, d->dBcount, d->dSlot, d->kp, fr, s, mask); });
         d->timed("bucket_scan", 0, [&] { launch_bucket_scan(d->dBcount, d->dBoff, d->dCtr, d->kp, fr, s); });
         d->timed("bucket_scatter", 0,
                  [&] { launch_bucket_scatter(d->dOri, d->dCtr, d->dBoff, d->dSlot, d->dOrder, d->kp, fr, s); });
@@ -552,23 +552,14 @@ void enqueue_provided(sift_hip_detector* d, int slot, const ProvidedKpt* kpts, i
     });
 }
 
-void enqueue_body(sift_hip_detector* d, int slot, int nf) {
+// mask: only an eager masked frame passes one, so no captured graph carries a mask.
+void enqueue_body(sift_hip_detector* d, int slot, int nf, const MaskArg& mask = MaskArg{}) {
     enqueue_pyramid(d, nf, slot & 1);  // kSlots is even, so slot parity = frame parity
     enqueue_extrema(d, nf);
     enqueue_refine(d, nf);
-    enqueue_orientation(d, nf);
-    enqueue_order(d, slot, nf);
+    enqueue_orientation(d, nf, mask);
+    enqueue_order(d, slot, nf, mask);
     enqueue_descriptor(d, slot, nf);
-}
-
-int capture(sift_hip_detector* d, int slot, int nf, hipGraphExec_t* out) {
-    hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_body(d, slot, nf);
-    HIPCHK(hipStreamEndCapture(d->stream, &g));
-    HIPCHK(hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-    HIPCHK(hipGraphDestroy(g));
-    return SIFT_HIP_OK;
 }
 
 // The head for f32 device input (the frame's first blur, or the 2x upsample)
@@ -585,36 +576,37 @@ void head_node(sift_hip_detector* d, HeadNode& h, const float* img, int pitch, i
     }
 }
 
-// head + body captured together; the graph is kept for its head node.
-int capture_with_head(sift_hip_detector* d, int slot, int nf, hipGraphExec_t* out, hipGraph_t* graph,
-                      hipGraphNode_t* head) {
+// Fills G with the graphs of nf frames into results slot `slot` of the bound
+// lane: the body alone, then head + body captured together, the head reading
+// the lane's blank input until a frame re-points it.
+int capture(sift_hip_detector* d, int slot, int nf, FrameGraph& G) {
+    hipGraph_t body = nullptr;
     HIPCHK(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_head(d, d->dInput, d->inPitch, SIFT_HIP_F32, slot & 1, nf, d->afs);
     enqueue_body(d, slot, nf);
-    HIPCHK(hipStreamEndCapture(d->stream, graph));
+    HIPCHK(hipStreamEndCapture(d->stream, &body));
+    HIPCHK(hipGraphInstantiate(&G.exec, body, nullptr, nullptr, 0));
+    HIPCHK(hipGraphDestroy(body));
+    G.in = HeadIn{d->dInput, d->inPitch, d->afs};
+    HIPCHK(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
+    enqueue_head(d, G.in.img, G.in.pitch, SIFT_HIP_F32, slot & 1, nf, G.in.sfs);
+    enqueue_body(d, slot, nf);
+    HIPCHK(hipStreamEndCapture(d->stream, &G.graphH));
     size_t nroot = 0;
-    HIPCHK(hipGraphGetRootNodes(*graph, nullptr, &nroot));
+    HIPCHK(hipGraphGetRootNodes(G.graphH, nullptr, &nroot));
     if (nroot != 1) return fail(SIFT_HIP_ERR_RUNTIME, "captured frame graph: expected one root (the head)");
-    HIPCHK(hipGraphGetRootNodes(*graph, head, &nroot));
+    HIPCHK(hipGraphGetRootNodes(G.graphH, &G.head, &nroot));
     hipGraphNodeType ty;
-    HIPCHK(hipGraphNodeGetType(*head, &ty));
+    HIPCHK(hipGraphNodeGetType(G.head, &ty));
     if (ty != hipGraphNodeTypeKernel) return fail(SIFT_HIP_ERR_RUNTIME, "captured frame graph: the head is not a kernel");
-    HIPCHK(hipGraphInstantiate(out, *graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphInstantiate(&G.execH, G.graphH, nullptr, nullptr, 0));
     return SIFT_HIP_OK;
 }
 
 int build_graphs(sift_hip_detector* d) {
     Lane& L = d->lane();
-    for (int b = 0; b < L.nslots; b++) {
-        if (int rc = capture(d, b, L.B, &L.exec[b])) return rc;
-        if (int rc = capture_with_head(d, b, L.B, &L.execH[b], &L.graphH[b], &L.headH[b])) return rc;
-        L.headIn[b][0] = Lane::HeadIn{d->dInput, d->inPitch, d->afs};
-        if (L.B > 1) {
-            if (int rc = capture(d, b, 1, &L.exec1[b])) return rc;
-            if (int rc = capture_with_head(d, b, 1, &L.execH1[b], &L.graphH1[b], &L.headH1[b])) return rc;
-            L.headIn[b][1] = Lane::HeadIn{d->dInput, d->inPitch, d->afs};
-        }
-    }
+    for (int b = 0; b < L.nslots; b++)
+        for (int kind = 0; kind < (L.B > 1 ? 2 : 1); kind++)
+            if (int rc = capture(d, b, kind == 0 ? L.B : 1, L.graphs[b][kind])) return rc;
     return SIFT_HIP_OK;
 }
 
@@ -631,28 +623,27 @@ bool event_done(hipEvent_t e) {
 // range-key parity alternating, and the lane's next frame takes slot 0.
 int warm_lane(sift_hip_detector* d) {
     Lane& L = d->lane();
-    const int nb = L.B > 1 ? 2 : 1;
-    for (int r = 0; r < nb; r++)
+    const int kinds = L.B > 1 ? 2 : 1;
+    for (int kind = 0; kind < kinds; kind++)
         for (int b = 0; b < L.nslots; b++) {
-            HIPCHK(hipGraphLaunch(r == 0 ? L.execH[b] : L.execH1[b], L.stream));
+            HIPCHK(hipGraphLaunch(L.graphs[b][kind].execH, L.stream));
             HIPCHK(hipEventRecord(L.evFrame[b], L.stream));
-            L.nfOf[b] = r == 0 ? L.B : 1;
+            L.nfOf[b] = kind == 0 ? L.B : 1;
         }
-    L.launched = (long long)nb * L.nslots;
+    L.launched = (long long)kinds * L.nslots;
     return SIFT_HIP_OK;
 }
 
-// Enqueues launch group d->submitted (nf frames at byte stride sfs) on the
-// bound lane (pick_lane); `consumed` (nullable) is recorded once the input has
-// been read.  A batch (sift_hip_detect_batch_device) is one frame number; a
-// micro-batch (`numbered`) takes nf numbers, frame d->submitted + i in arena i.  With stage dumps on (single frames after warm-up) the frame's
-// input is kept as float, the frame is completed synchronously and dumped.
-int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf, long sfs,
-              bool numbered, const ProvidedKpt* provided, int nProvided, const MaskArg* mask) {
+// Enqueues launch group d->submitted (FrameJob) on the bound lane (pick_lane).
+// With stage dumps on (single frames after warm-up) the frame's input is kept
+// as float, the frame is completed synchronously and dumped.
+int run_frame(sift_hip_detector* d, const FrameJob& job) {
+    const void* img = job.img;
+    const int pitch = job.pitch, fmt = job.fmt, nf = job.nf;
     const long long f = d->submitted;
     Lane& L = d->lane();
     const int slot = (int)(L.launched % L.nslots);
-    const bool compute = nProvided >= 0;  // (a stage dump records the detect chain: not for compute frames)
+    const bool compute = job.nProvided >= 0;  // (a stage dump records the detect chain: not for compute frames)
     const bool dump = !d->dgDir.empty() && nf == 1 && d->firstFrame > 0 && !compute;
     const int W = d->cfg.col_width, H = d->cfg.row_width;
     if (dump) {
@@ -667,45 +658,36 @@ int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEven
     // A masked frame takes the eager launches below with the mask as a kernel
     // argument (the captured graphs carry none); sift_hip_detect_masked*
     // refuse it while stage dumps are on.
-    const bool masked = mask && mask->p && !compute;
-    const bool graphs = d->useGraph && !d->timing && !compute && !masked;
-    hipGraphExec_t gh = !graphs || consumed || fmt != SIFT_HIP_F32 ? nullptr
-                        : nf == L.B                                  ? L.execH[slot]
-                        : nf == 1                                    ? L.execH1[slot]
-                                                                     : nullptr;
-    // The head node of execH[slot] is re-pointed only once that exec's last
-    // launch (whose completion evFrame[slot] still records) has finished: a
-    // queued launch never sees its kernel arguments change.  Otherwise the
-    // frame takes the separate head launch and the plain exec.
-    if (gh && !event_done(L.evFrame[slot])) gh = nullptr;
-    if (gh) {  // device f32 input: one launch for the whole frame, the head re-pointed at img
-        const Lane::HeadIn in{img, pitch, sfs};
-        Lane::HeadIn& cur = L.headIn[slot][nf == L.B ? 0 : 1];
-        if (!(cur == in)) {
+    const bool replay = d->useGraph && !d->timing && !compute && !job.mask.p;
+    FrameGraph* G = replay ? L.graph(slot, nf) : nullptr;
+    // Device f32 input: one launch for the whole frame, the head re-pointed at
+    // img -- but only once execH's last launch (whose completion evFrame[slot]
+    // still records) has finished: a queued launch never sees its kernel
+    // arguments change.  Otherwise the frame takes the separate head launch
+    // and the plain exec.
+    if (G && fmt == SIFT_HIP_F32 && event_done(L.evFrame[slot])) {
+        const HeadIn in{img, pitch, job.sfs};
+        if (!(G->in == in)) {
             HeadNode& h = d->headNode;
-            head_node(d, h, static_cast<const float*>(img), pitch, slot & 1, nf, sfs);
-            HIPCHK(hipGraphExecKernelNodeSetParams(gh, nf == L.B ? L.headH[slot] : L.headH1[slot], &h.p));
-            cur = in;
+            head_node(d, h, static_cast<const float*>(img), pitch, slot & 1, nf, job.sfs);
+            HIPCHK(hipGraphExecKernelNodeSetParams(G->execH, G->head, &h.p));
+            G->in = in;
         }
-        HIPCHK(hipGraphLaunch(gh, d->stream));
+        HIPCHK(hipGraphLaunch(G->execH, d->stream));
     } else {
-        enqueue_head(d, img, pitch, fmt, slot & 1, nf, sfs);
-        if (consumed) HIPCHK(hipEventRecord(consumed, d->stream));
-        hipGraphExec_t g = nf == L.B ? L.exec[slot] : (nf == 1 ? L.exec1[slot] : nullptr);
-        if (graphs && g) {
-            HIPCHK(hipGraphLaunch(g, d->stream));
+        enqueue_head(d, img, pitch, fmt, slot & 1, nf, job.sfs);
+        if (G) {
+            HIPCHK(hipGraphLaunch(G->exec, d->stream));
         } else if (compute) {  // caller-supplied keypoints: pyramid -> jobs -> descriptor, eagerly
             enqueue_pyramid(d, 1, slot & 1);
-            enqueue_provided(d, slot, provided, nProvided);
+            enqueue_provided(d, slot, job.provided, job.nProvided);
             enqueue_descriptor(d, slot, 1);
         } else {  // timing mode, a partial batch or a masked frame: the same launches, eagerly
-            if (masked) d->mask = *mask;
-            enqueue_body(d, slot, nf);
-            d->mask = MaskArg{};
+            enqueue_body(d, slot, nf, job.mask);
         }
     }
     HIPCHK(hipEventRecord(L.evFrame[slot], d->stream));
-    const int nums = numbered ? nf : 1;
+    const int nums = job.numbered ? nf : 1;
     L.nfOf[slot] = nf;
     L.slotFrame[slot] = f;
     L.slotNum[slot] = nums;
@@ -807,6 +789,87 @@ int batch_frames_of(sift_hip_detector* d) {
         bind_lane((h), (h)->curLane, (h)->curIdx);                                            \
     } while (0)
 
+// The same for the two accessors that also answer before warm-up (with zeros):
+// on a warmed handle they bind and wait for the current frame's counts.
+static int bind_counts_if_warm(sift_hip_detector* d) {
+    if (!d->allocated || !d->lanes[0].ready) return SIFT_HIP_OK;
+    HIPCHK(hipSetDevice(d->device));
+    bind_lane(d, d->curLane, d->curIdx);
+    return ensure_counts(d);
+}
+
+// Host counters of the current frame (frame i of a batch), valid after ensure_counts.
+static const Counters& current_counters(sift_hip_detector* d, int i = 0) {
+    return d->hCtr[(size_t)d->cur * d->lane().B + i];
+}
+
+// n result rows of `slot` of the bound lane (the arena at byte offset `off`)
+// into host memory, on the copy stream, ordered after that slot's frame only:
+// frames submitted after it keep running.  Null destinations are skipped.
+static int copy_results_d2h(sift_hip_detector* d, int slot, long off, int n, float* k3, float* f4, uint16_t* desc) {
+    hipStream_t s;
+    if (int rc = copy_stream(d, &s)) return rc;
+    HIPCHK(hipStreamWaitEvent(s, d->lane().evFrame[slot], 0));
+    if (n > 0) {
+        if (k3) HIPCHK(hipMemcpyAsync(k3, fptr(d->dKpts3[slot], off), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, s));
+        if (f4) HIPCHK(hipMemcpyAsync(f4, fptr(d->dFeats4[slot], off), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, s));
+        if (desc)
+            HIPCHK(hipMemcpyAsync(desc, fptr(d->dDesc[slot], off), sizeof(uint16_t) * 128 * n, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return SIFT_HIP_OK;
+}
+
+// A caller reads results back (sift_hip_copy_to_host / sift_hip_results_host):
+// from the first such call every ready lane has host regions, and host-input
+// frames write that much to them (hostWant).
+static int want_host_results(sift_hip_detector* d, bool desc) {
+    if (!d->hostWant)
+        for (int k = 0; k < d->nLanes; k++)
+            if (d->lanes[k].ready)
+                if (int rc = ensure_host_res(d, d->lanes[k])) return rc;
+    d->hostWant = std::max(d->hostWant, desc ? 2 : 1);
+    return SIFT_HIP_OK;
+}
+
+// Whether host region `region` of the current frame's lane holds that frame
+// (with its descriptors when `desc`).
+static bool region_holds_current(const sift_hip_detector* d, const Lane& L, int region, bool desc) {
+    return L.hostFrame[region] == d->current && d->current >= d->firstFrame && (!desc || L.hostDesc[region]);
+}
+
+// A host frame (submit_host's arguments), waited for.
+static int detect_host(sift_hip_detector* d, const FrameJob& job, size_t stride, const uint8_t* mask = nullptr,
+                       size_t maskStride = 0) {
+    long long f = 0;
+    const int rc = submit_host(d, job, stride, &f, mask, maskStride);
+    return rc ? rc : wait_frame(d, f);
+}
+
+// The image arguments of a device entry point; *stride (bytes, 0 = packed) is
+// the row stride on return.
+static int check_device_image(const sift_hip_detector* d, const void* img, int format, size_t* stride) {
+    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
+    const size_t es = (size_t)format_size(format);
+    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
+    if (*stride == 0) *stride = es * d->cfg.col_width;
+    if (*stride % es || *stride < es * d->cfg.col_width)
+        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    return SIFT_HIP_OK;
+}
+
+// Exposes the launched frame f at once (device-ordered consumers see its
+// buffers; counts follow at sift_hip_sync / sift_hip_wait) and orders the
+// caller's stream after the frame's lane.
+static int publish(sift_hip_detector* d, long long f, void* stream) {
+    make_current(d, f);
+    if (stream) {
+        HIPCHK(hipEventRecord(d->evOut, d->stream));
+        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
+    }
+    return SIFT_HIP_OK;
+}
+
 // ---- caller-supplied keypoints (sift_hip_check_keypoints / sift_hip_compute*) ----
 static_assert(sizeof(sift_hip_keypoint) == sizeof(ProvidedKpt) && offsetof(sift_hip_keypoint, octave) == offsetof(ProvidedKpt, octave),
               "sift_hip_keypoint is the kernels' ProvidedKpt");
@@ -839,9 +902,7 @@ static int compute_host(sift_hip_detector* d, const void* img, size_t stride, in
     if (!d->hKpts &&
         hipHostMalloc((void**)&d->hKpts, sizeof(ProvidedKpt) * (size_t)d->kp.capFinal, hipHostMallocMapped) != hipSuccess)
         return fail(SIFT_HIP_ERR_NOMEM, "hipHostMalloc of the keypoint staging failed");
-    long long f = 0;
-    const int rc = submit_host(d, img, stride, fmt, &f, as_provided(kpts), n);
-    return rc ? rc : wait_frame(d, f);
+    return detect_host(d, {.img = img, .fmt = fmt, .provided = as_provided(kpts), .nProvided = n}, stride);
 }
 
 // ---- detection mask (sift_hip_detect_masked*) ----
@@ -854,66 +915,6 @@ static int check_mask(const sift_hip_detector* d, size_t* maskStride) {
     if (*maskStride < W) return fail(SIFT_HIP_ERR_INVALID, "mask row stride smaller than width");
     if (!d->dgDir.empty())
         return fail(SIFT_HIP_ERR_STATE, "masked detect while sift_hip_set_datagen is active (stage dumps hold no mask)");
-    return SIFT_HIP_OK;
-}
-
-// sift_hip_detect_device_fmt / sift_hip_detect_device_masked (mask nullable).
-static int detect_device(sift_hip_detector* d, const void* img, size_t stride, int format, const uint8_t* mask,
-                         size_t maskStride, void* stream) {
-    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width, H = d->cfg.row_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
-    if (mask)
-        if (int rc = check_mask(d, &maskStride)) return rc;
-    if (int rc = check_in_flight(d)) return rc;
-    long long f = 0;
-    const MaskArg m{mask, (int)maskStride, W, H, 0};
-    if (int rc = submit_device(d, img, stride, format, stream, 1, 0, &f, false, nullptr, -1, mask ? &m : nullptr)) return rc;
-    // Device-ordered consumers see this frame's buffers at once; counts
-    // follow at sift_hip_sync / sift_hip_wait.
-    make_current(d, f);
-    if (stream) {
-        HIPCHK(hipEventRecord(d->evOut, d->stream));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
-    }
-    return SIFT_HIP_OK;
-}
-
-// sift_hip_detect_batch_device / sift_hip_detect_batch_device_masked (masks nullable).
-static int detect_batch_device(sift_hip_detector* d, const void* frames, int n, size_t stride, size_t frame_stride,
-                               int format, const uint8_t* masks, size_t maskStride, size_t maskFrameStride,
-                               void* stream) {
-    if (!frames) return fail(SIFT_HIP_ERR_INVALID, "null frames");
-    if (n < 1 || n > d->B) return fail(SIFT_HIP_ERR_INVALID, "frame count outside 1..batch capacity");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width, H = d->cfg.row_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
-    if (frame_stride == 0) frame_stride = stride * H;
-    if (n > 1 && frame_stride < stride * (H - 1) + (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "frame stride smaller than one frame");
-    if (masks) {
-        if (int rc = check_mask(d, &maskStride)) return rc;
-        if (maskFrameStride == 0) maskFrameStride = maskStride * H;
-        if (n > 1 && maskFrameStride < maskStride * (H - 1) + (size_t)W)
-            return fail(SIFT_HIP_ERR_INVALID, "mask frame stride smaller than one mask");
-    }
-    if (int rc = check_in_flight(d)) return rc;
-    long long f = 0;
-    const MaskArg m{masks, (int)maskStride, W, H, (long)maskFrameStride};
-    if (int rc = submit_device(d, frames, stride, format, stream, n, frame_stride, &f, false, nullptr, -1, masks ? &m : nullptr))
-        return rc;
-    make_current(d, f);
-    if (stream) {
-        HIPCHK(hipEventRecord(d->evOut, d->stream));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
-    }
     return SIFT_HIP_OK;
 }
 
@@ -991,7 +992,8 @@ int sift_hip_warmup(sift_hip_t d) {
     const int ns = d->lanes[0].nslots;
     for (int i = 0; i < ns * (d->B > 1 ? 2 : 1); i++) {
         const int nf = i < ns ? d->B : 1;
-        if ((rc = run_frame(d, d->dInput, d->inPitch, SIFT_HIP_F32, nullptr, nf, d->afs))) return rc;
+        if ((rc = run_frame(d, {.img = d->dInput, .pitch = d->inPitch, .fmt = SIFT_HIP_F32, .nf = nf, .sfs = d->afs})))
+            return rc;
         if ((rc = finish_frame(d))) return rc;
     }
     d->firstFrame = d->submitted;
@@ -1015,21 +1017,17 @@ int sift_hip_octave_dims(sift_hip_t h, int o, int* w, int* hh, int* pitch) {
 
 int sift_hip_detect(sift_hip_t d, const float* img, size_t stride) {
     CHECK_HANDLE(d);
-    long long f = 0;
-    int rc = submit_host(d, img, stride, SIFT_HIP_F32, &f);
-    return rc ? rc : wait_frame(d, f);
+    return detect_host(d, {.img = img, .fmt = SIFT_HIP_F32}, stride);
 }
 
 int sift_hip_detect_u8(sift_hip_t d, const uint8_t* img, size_t stride) {
     CHECK_HANDLE(d);
-    long long f = 0;
-    int rc = submit_host(d, img, stride, SIFT_HIP_U8, &f);
-    return rc ? rc : wait_frame(d, f);
+    return detect_host(d, {.img = img, .fmt = SIFT_HIP_U8}, stride);
 }
 
 int sift_hip_submit(sift_hip_t d, const void* img, size_t stride, int format, long long* ticket) {
     CHECK_HANDLE(d);
-    return submit_host(d, img, stride, format, ticket);
+    return submit_host(d, {.img = img, .fmt = format}, stride, ticket);
 }
 
 int sift_hip_wait(sift_hip_t d, long long ticket) {
@@ -1038,8 +1036,7 @@ int sift_hip_wait(sift_hip_t d, long long ticket) {
 }
 
 int sift_hip_detect_device_fmt(sift_hip_t d, const void* img, size_t stride, int format, void* stream) {
-    CHECK_HANDLE(d);
-    return detect_device(d, img, stride, format, nullptr, 0, stream);
+    return sift_hip_detect_device_masked(d, img, stride, format, nullptr, 0, stream);
 }
 
 int sift_hip_detect_masked(sift_hip_t d, const void* img, size_t stride, int format, const uint8_t* mask,
@@ -1049,35 +1046,53 @@ int sift_hip_detect_masked(sift_hip_t d, const void* img, size_t stride, int for
         if (!format_size(format)) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
         if (int rc = check_mask(d, &mask_stride)) return rc;
     }
-    long long f = 0;
-    int rc = submit_host(d, img, stride, format, &f, nullptr, -1, mask, mask_stride);
-    return rc ? rc : wait_frame(d, f);
+    return detect_host(d, {.img = img, .fmt = format}, stride, mask, mask_stride);
 }
 
 int sift_hip_detect_device_masked(sift_hip_t d, const void* img, size_t stride, int format, const uint8_t* mask,
                                   size_t mask_stride, void* stream) {
     CHECK_HANDLE(d);
-    return detect_device(d, img, stride, format, mask, mask_stride, stream);
+    if (int rc = check_device_image(d, img, format, &stride)) return rc;
+    if (mask)
+        if (int rc = check_mask(d, &mask_stride)) return rc;
+    if (int rc = check_in_flight(d)) return rc;
+    long long f = 0;
+    const FrameJob job{.img = img, .pitch = (int)(stride / format_size(format)), .fmt = format,
+                       .mask = {mask, (int)mask_stride, d->cfg.col_width, d->cfg.row_width, 0}};  // (null mask: none)
+    if (int rc = submit_device(d, job, stream, &f)) return rc;
+    return publish(d, f, stream);
 }
 
 int sift_hip_detect_batch_device_masked(sift_hip_t d, const void* frames, int n, size_t stride, size_t frame_stride,
                                         int format, const uint8_t* masks, size_t mask_stride, size_t mask_frame_stride,
                                         void* stream) {
     CHECK_HANDLE(d);
-    return detect_batch_device(d, frames, n, stride, frame_stride, format, masks, mask_stride, mask_frame_stride, stream);
+    if (!frames) return fail(SIFT_HIP_ERR_INVALID, "null frames");
+    if (n < 1 || n > d->B) return fail(SIFT_HIP_ERR_INVALID, "frame count outside 1..batch capacity");
+    if (int rc = check_device_image(d, frames, format, &stride)) return rc;
+    const int es = format_size(format), W = d->cfg.col_width, H = d->cfg.row_width;
+    if (frame_stride == 0) frame_stride = stride * H;
+    if (n > 1 && frame_stride < stride * (H - 1) + (size_t)es * W)
+        return fail(SIFT_HIP_ERR_INVALID, "frame stride smaller than one frame");
+    if (masks) {
+        if (int rc = check_mask(d, &mask_stride)) return rc;
+        if (mask_frame_stride == 0) mask_frame_stride = mask_stride * H;
+        if (n > 1 && mask_frame_stride < mask_stride * (H - 1) + (size_t)W)
+            return fail(SIFT_HIP_ERR_INVALID, "mask frame stride smaller than one mask");
+    }
+    if (int rc = check_in_flight(d)) return rc;
+    long long f = 0;
+    const FrameJob job{.img = frames, .pitch = (int)(stride / es), .fmt = format, .nf = n, .sfs = (long)frame_stride,
+                       .mask = {masks, (int)mask_stride, W, H, (long)mask_frame_stride}};  // (null masks: none)
+    if (int rc = submit_device(d, job, stream, &f)) return rc;
+    return publish(d, f, stream);
 }
 
 int sift_hip_submit_device(sift_hip_t d, const void* img, size_t stride, int format, void* stream, long long* ticket) {
     CHECK_HANDLE(d);
-    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    if (int rc = check_device_image(d, img, format, &stride)) return rc;
     if (int rc = check_in_flight(d)) return rc;
-    return submit_device(d, img, stride, format, stream, 1, 0, ticket, true);
+    return submit_device(d, {.img = img, .pitch = (int)(stride / format_size(format)), .fmt = format}, stream, ticket, true);
 }
 
 int sift_hip_detect_device(sift_hip_t d, const float* img, size_t stride, void* stream) {
@@ -1105,25 +1120,16 @@ int sift_hip_compute_u8(sift_hip_t d, const uint8_t* img, size_t stride, const s
 int sift_hip_compute_device(sift_hip_t d, const void* img, size_t stride, int format, const sift_hip_keypoint* dev_kpts,
                             int n, void* stream) {
     CHECK_HANDLE(d);
-    if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
-    const int es = format_size(format);
-    if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
-    const int W = d->cfg.col_width;
-    if (stride == 0) stride = (size_t)es * W;
-    if (stride % es || stride < (size_t)es * W)
-        return fail(SIFT_HIP_ERR_INVALID, "row stride must be a multiple of the pixel size and >= width");
+    if (int rc = check_device_image(d, img, format, &stride)) return rc;
     if (int rc = check_keypoint_count(d, dev_kpts, n)) return rc;
     if (int rc = check_in_flight(d)) return rc;
     long long f = 0;
     // The lane waits for `stream` before it reads the image or the keypoints
     // (k_provided_jobs validates them: they cannot be read here).
-    if (int rc = submit_device(d, img, stride, format, stream, 1, 0, &f, false, as_provided(dev_kpts), n)) return rc;
-    make_current(d, f);
-    if (stream) {
-        HIPCHK(hipEventRecord(d->evOut, d->stream));
-        HIPCHK(hipStreamWaitEvent((hipStream_t)stream, d->evOut, 0));
-    }
-    return SIFT_HIP_OK;
+    const FrameJob job{.img = img, .pitch = (int)(stride / format_size(format)), .fmt = format,
+                       .provided = as_provided(dev_kpts), .nProvided = n};
+    if (int rc = submit_device(d, job, stream, &f)) return rc;
+    return publish(d, f, stream);
 }
 
 int sift_hip_set_batch(sift_hip_t d, int frames) {
@@ -1201,8 +1207,7 @@ int sift_hip_batch_capacity(sift_hip_t d, int* frames) {
 
 int sift_hip_detect_batch_device(sift_hip_t d, const void* frames, int n, size_t stride, size_t frame_stride,
                                  int format, void* stream) {
-    CHECK_HANDLE(d);
-    return detect_batch_device(d, frames, n, stride, frame_stride, format, nullptr, 0, 0, stream);
+    return sift_hip_detect_batch_device_masked(d, frames, n, stride, frame_stride, format, nullptr, 0, 0, stream);
 }
 
 int sift_hip_batch_frames(sift_hip_t d, int* n) {
@@ -1218,7 +1223,7 @@ int sift_hip_batch_results_device(sift_hip_t d, int i, int* count, int* overflow
     if (i < 0 || i >= batch_frames_of(d)) return fail(SIFT_HIP_ERR_INVALID, "no such frame in the current batch");
     if (count || overflow)
         if (int rc = ensure_counts(d)) return rc;
-    const Counters& c = d->hCtr[(size_t)d->cur * d->lane().B + i];
+    const Counters& c = current_counters(d, i);
     const long o = (long)i * d->afs;
     if (count) *count = (int)std::min<unsigned>(c.final_n, d->kp.capFinal);
     if (overflow) *overflow = (int)c.overflow;
@@ -1230,21 +1235,10 @@ int sift_hip_batch_results_device(sift_hip_t d, int i, int* count, int* overflow
 
 int sift_hip_batch_copy_to_host(sift_hip_t d, int i, float* k3, float* f4, uint16_t* desc, int cap, int* count) {
     int n = 0;
-    const float *dk = nullptr, *df = nullptr;
-    const uint16_t* dd = nullptr;
-    if (int rc = sift_hip_batch_results_device(d, i, &n, nullptr, &dk, &df, &dd)) return rc;
+    if (int rc = sift_hip_batch_results_device(d, i, &n, nullptr, nullptr, nullptr, nullptr)) return rc;
     n = std::min(n, cap);
     if (count) *count = n;
-    hipStream_t s;
-    if (int rc = copy_stream(d, &s)) return rc;
-    HIPCHK(hipStreamWaitEvent(s, d->lane().evFrame[d->cur], 0));
-    if (n > 0) {
-        if (k3) HIPCHK(hipMemcpyAsync(k3, dk, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, s));
-        if (f4) HIPCHK(hipMemcpyAsync(f4, df, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, s));
-        if (desc) HIPCHK(hipMemcpyAsync(desc, dd, sizeof(uint16_t) * 128 * n, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return SIFT_HIP_OK;
+    return copy_results_d2h(d, d->cur, (long)i * d->afs, n, k3, f4, desc);
 }
 
 int sift_hip_sync(sift_hip_t d) {
@@ -1254,23 +1248,15 @@ int sift_hip_sync(sift_hip_t d) {
 
 int sift_hip_num_keypoints(sift_hip_t d, int* n) {
     if (!d || !n) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    if (d->allocated && d->lanes[0].ready) {
-        HIPCHK(hipSetDevice(d->device));
-        bind_lane(d, d->curLane, d->curIdx);
-        if (int rc = ensure_counts(d)) return rc;
-    }
+    if (int rc = bind_counts_if_warm(d)) return rc;
     *n = d->count;
     return SIFT_HIP_OK;
 }
 
 int sift_hip_overflow_flags(sift_hip_t d, int* flags) {
     if (!d || !flags) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    if (d->allocated && d->lanes[0].ready) {
-        HIPCHK(hipSetDevice(d->device));
-        bind_lane(d, d->curLane, d->curIdx);
-        if (int rc = ensure_counts(d)) return rc;
-    }
-    *flags = d->hCtr ? (int)d->hCtr[(size_t)d->cur * d->lane().B].overflow : 0;
+    if (int rc = bind_counts_if_warm(d)) return rc;
+    *flags = d->hCtr ? (int)current_counters(d).overflow : 0;
     return SIFT_HIP_OK;
 }
 
@@ -1302,13 +1288,9 @@ int sift_hip_copy_to_host(sift_hip_t d, float* k3, float* f4, uint16_t* desc, in
     if (int rc = ensure_counts(d)) return rc;
     const int n = std::min(d->count, cap);
     Lane& L = d->lane();
-    if (!d->hostWant)
-        for (int k = 0; k < d->nLanes; k++)
-            if (d->lanes[k].ready)
-                if (int rc = ensure_host_res(d, d->lanes[k])) return rc;
-    d->hostWant = std::max(d->hostWant, desc ? 2 : 1);
-    const int region = d->cur * d->lane().B + d->curIdx;
-    if (L.hRes && L.hostFrame[region] == d->current && d->current >= d->firstFrame && (!desc || L.hostDesc[region])) {
+    if (int rc = want_host_results(d, desc != nullptr)) return rc;
+    const int region = d->cur * L.B + d->curIdx;
+    if (L.hRes && region_holds_current(d, L, region, desc != nullptr)) {
         // A host-input frame: its descriptor kernel wrote them to pinned host memory.
         HIPCHK(hipEventSynchronize(L.evFrame[d->cur]));
         float *hk3, *hf4;
@@ -1324,19 +1306,7 @@ int sift_hip_copy_to_host(sift_hip_t d, float* k3, float* f4, uint16_t* desc, in
         }
         return SIFT_HIP_OK;
     }
-    // On the copy stream, ordered after the current frame only: frames
-    // submitted after it keep running.
-    hipStream_t s;
-    if (int rc = copy_stream(d, &s)) return rc;
-    HIPCHK(hipStreamWaitEvent(s, d->lane().evFrame[d->cur], 0));
-    if (n > 0) {
-        if (k3) HIPCHK(hipMemcpyAsync(k3, d->dKpts3[d->cur], sizeof(float) * 3 * n, hipMemcpyDeviceToHost, s));
-        if (f4) HIPCHK(hipMemcpyAsync(f4, d->dFeats4[d->cur], sizeof(float) * 4 * n, hipMemcpyDeviceToHost, s));
-        if (desc)
-            HIPCHK(hipMemcpyAsync(desc, d->dDesc[d->cur], sizeof(uint16_t) * 128 * n, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return SIFT_HIP_OK;
+    return copy_results_d2h(d, d->cur, 0, n, k3, f4, desc);
 }
 
 // The current frame's results in the handle's pinned host region (the lane's
@@ -1348,28 +1318,15 @@ int sift_hip_results_host(sift_hip_t d, const float** k3, const float** f4, cons
     if (int rc = ensure_counts(d)) return rc;
     const int n = std::min(d->count, (int)d->kp.capFinal);
     Lane& L = d->lane();
-    if (!d->hostWant)
-        for (int k = 0; k < d->nLanes; k++)
-            if (d->lanes[k].ready)
-                if (int rc = ensure_host_res(d, d->lanes[k])) return rc;
-    d->hostWant = std::max(d->hostWant, desc ? 2 : 1);
-    const int region = d->cur * d->lane().B + d->curIdx;
+    if (int rc = want_host_results(d, desc != nullptr)) return rc;
+    const int region = d->cur * L.B + d->curIdx;
     float *hk3, *hf4;
     uint16_t* hdesc;
     host_res(d, L.hRes, region, &hk3, &hf4, &hdesc);
-    if (L.hostFrame[region] == d->current && d->current >= d->firstFrame && (!desc || L.hostDesc[region])) {
+    if (region_holds_current(d, L, region, desc != nullptr)) {
         HIPCHK(hipEventSynchronize(L.evFrame[d->cur]));
     } else {
-        hipStream_t s;
-        if (int rc = copy_stream(d, &s)) return rc;
-        HIPCHK(hipStreamWaitEvent(s, L.evFrame[d->cur], 0));
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync(hk3, d->dKpts3[d->cur], sizeof(float) * 3 * n, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(hf4, d->dFeats4[d->cur], sizeof(float) * 4 * n, hipMemcpyDeviceToHost, s));
-            if (desc)
-                HIPCHK(hipMemcpyAsync(hdesc, d->dDesc[d->cur], sizeof(uint16_t) * 128 * n, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
+        if (int rc = copy_results_d2h(d, d->cur, 0, n, hk3, hf4, desc ? hdesc : nullptr)) return rc;
         L.hostFrame[region] = d->current;
         L.hostDesc[region] = desc != nullptr;
     }
@@ -1451,7 +1408,7 @@ int sift_hip_debug_gaussian(sift_hip_t d, int o, int layer, float* out) {
 int sift_hip_debug_candidates(sift_hip_t d, int* quads, int cap, int* count) {
     CHECK_HANDLE(d);
     if (int rc = ensure_counts(d)) return rc;
-    const Counters& c = d->hCtr[(size_t)d->cur * d->lane().B];
+    const Counters& c = current_counters(d);
     const int n = (int)std::min<unsigned>(c.cand, d->capCand);
     if (count) *count = (int)c.cand;
     const int m = std::min(n, cap);

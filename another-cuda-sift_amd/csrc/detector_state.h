@@ -132,6 +132,30 @@ constexpr int kLaneSlots = 4;
 constexpr int kMaxLanes = 4;
 constexpr int kFrameRing = 256;  // per-frame (lane, slot, arena) records: > 2 x kMaxLanes x kMaxMicroBatch (frames in flight) + the two readable
 
+// The input a captured head node reads (image, pitch in floats, byte stride
+// between frames).
+struct HeadIn {
+    const void* img = nullptr;
+    int pitch = 0;
+    long sfs = 0;
+    bool operator==(const HeadIn& o) const { return img == o.img && pitch == o.pitch && sfs == o.sfs; }
+};
+
+// The captured graphs of one (results slot, group kind) of a lane.  exec: the
+// pipeline after the head.  execH: the same with the f32 head captured in
+// (device input); its head node is re-pointed at each frame's image
+// (hipGraphExecKernelNodeSetParams), so the frame is ONE graph launch -- a
+// separate head launch left ~6 us between the head and the graph's first
+// kernel on every single frame.  graphH is kept for that node, `head`; `in` is
+// what the node reads now: a frame from the same buffer as the record's last
+// one launches without re-pointing it.
+struct FrameGraph {
+    hipGraphExec_t exec = nullptr, execH = nullptr;
+    hipGraph_t graphH = nullptr;
+    hipGraphNode_t head = nullptr;
+    HeadIn in;
+};
+
 // A compute lane: one HIP stream, its B frame arenas (every per-frame buffer of
 // the pipeline, sift_kernels.h Frames), the graphs captured on them and a ring
 // of kResultSlots results slots.  A lane runs its frames in order; frames on
@@ -151,29 +175,16 @@ struct Lane {
     Counters* hCtr = nullptr;     // kResultSlots x B pinned host copies of the counters (written by k_descriptor)
     Counters* hCtrDev = nullptr;  // their device-side address
     hipEvent_t evFrame[kResultSlots] = {};  // recorded after each slot's last frame
-    hipGraphExec_t exec[kResultSlots] = {};   // B frames per launch
-    hipGraphExec_t exec1[kResultSlots] = {};  // one frame (B > 1 only; exec when B = 1)
-    // The same graphs with the f32 head captured in (device input): the head
-    // node is re-pointed at each frame's image (hipGraphExecKernelNodeSetParams),
-    // so the frame is ONE graph launch -- a separate head launch left ~6 us
-    // between the head and the graph's first kernel on every single frame.
-    hipGraphExec_t execH[kResultSlots] = {}, execH1[kResultSlots] = {};
-    hipGraph_t graphH[kResultSlots] = {}, graphH1[kResultSlots] = {};
-    hipGraphNode_t headH[kResultSlots] = {}, headH1[kResultSlots] = {};
-    // The input each exec's head node reads now (image, pitch, frame stride;
-    // [slot][0]: execH, [1]: execH1): a frame from the same buffer as that
-    // exec's last one launches without re-pointing the node.
-    struct HeadIn {
-        const void* img = nullptr;
-        int pitch = 0;
-        long sfs = 0;
-        bool operator==(const HeadIn& o) const { return img == o.img && pitch == o.pitch && sfs == o.sfs; }
-    };
-    HeadIn headIn[kResultSlots][2];
+    // Per slot: [0] the graphs of a full group (B frames), [1] those of a
+    // single frame on a lane with B > 1 (with B = 1 a single frame is [0]).
+    FrameGraph graphs[kResultSlots][2];
+    // The graphs a launch group of nf frames replays in `slot`, or null for a
+    // partial group (1 < nf < B), which runs the same launches eagerly.
+    FrameGraph* graph(int slot, int nf) { return nf == B ? &graphs[slot][0] : (nf == 1 ? &graphs[slot][1] : nullptr); }
     int nfOf[kResultSlots] = {};  // frames of the launch group that wrote each slot
     long long slotFrame[kResultSlots] = {-1, -1, -1, -1, -1, -1, -1, -1};  // the (first) frame whose results each slot holds
     int slotNum[kResultSlots] = {};  // frame numbers in that slot (> 1: a micro-batch, frame slotFrame + i in arena i)
-    long long launched = 0;  // launch groups run on this lane; the next takes slot launched % kResultSlots
+    long long launched = 0;  // launch groups run on this lane; the next takes slot launched % nslots
     long long last = -1;     // the last frame launched here (-1: none since warm-up)
     char* mbIn = nullptr;    // micro-batch input copies: mb frames of f32 rows (created at the first micro-batch)
     // Host-input frames: results written to mapped pinned host memory by the
@@ -218,6 +229,25 @@ struct ArenaLayout {
     size_t k3[kResultSlots] = {}, f4[kResultSlots] = {}, desc[kResultSlots] = {};
     size_t codes[kResultSlots] = {}, ckeys[kResultSlots] = {};  // matcher sidecar of desc (Sidecar)
     size_t octave[kMaxOctaves] = {};  // float offset of each octave's planes inside the pyramid
+};
+
+// What run_frame launches: one launch group on the bound lane.
+struct FrameJob {
+    const void* img = nullptr;  // device-readable input: nf frames, sfs bytes apart
+    int pitch = 0;              // row pitch in elements of fmt (bytes for SIFT_HIP_U8)
+    int fmt = SIFT_HIP_F32;
+    int nf = 1;
+    long sfs = 0;
+    // A batch (sift_hip_detect_batch_device) is one frame number; a micro-batch
+    // (numbered) takes nf numbers, frame d->submitted + i in arena i.
+    bool numbered = false;
+    // nProvided >= 0 (<= capFinal): the frame describes the nProvided
+    // device-readable keypoints `provided` instead of detecting (sift_hip_compute*).
+    const ProvidedKpt* provided = nullptr;
+    int nProvided = -1;
+    // mask.p != nullptr: the detect chain runs eagerly with the mask test in its
+    // orientation and order stages (sift_hip_detect_masked*).
+    MaskArg mask{};
 };
 
 }  // namespace det
@@ -344,14 +374,11 @@ struct sift_hip_detector {
     // allocated at the first compute call (a detect-only caller pays nothing).
     // One buffer: the call is synchronous, so its kernel has read it on return.
     ProvidedKpt* hKpts = nullptr;
-    // Detection mask (sift_hip_detect_masked*).  `mask`: the mask of the launch
-    // group being enqueued (run_frame sets it around the eager launches; null
-    // otherwise, so every captured graph is mask-free).  Host masks go through
-    // hMask (pinned, packed rows) into dMask (device) on the frame's lane
-    // stream; both are allocated at the first host-mask call (a caller who
-    // never passes a mask pays nothing) and one of each is enough: the call is
-    // synchronous, so its kernels have read them on return.
-    MaskArg mask{};
+    // Host detection masks (sift_hip_detect_masked) go through hMask (pinned,
+    // packed rows) into dMask (device) on the frame's lane stream; both are
+    // allocated at the first host-mask call (a caller who never passes a mask
+    // pays nothing) and one of each is enough: the call is synchronous, so its
+    // kernels have read them on return.
     uint8_t* hMask = nullptr;
     uint8_t* dMask = nullptr;
     // The most the caller's sift_hip_copy_to_host / sift_hip_results_host
@@ -426,10 +453,11 @@ struct sift_hip_detector {
                 Lane& L = lanes[k];
                 if (L.stream) (void)hipStreamSynchronize(L.stream);
                 for (int b = 0; b < kSlots; b++) {
-                    for (hipGraphExec_t e : {L.exec[b], L.exec1[b], L.execH[b], L.execH1[b]})
-                        if (e) (void)hipGraphExecDestroy(e);
-                    for (hipGraph_t g : {L.graphH[b], L.graphH1[b]})
-                        if (g) (void)hipGraphDestroy(g);
+                    for (FrameGraph& g : L.graphs[b]) {
+                        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+                        if (g.execH) (void)hipGraphExecDestroy(g.execH);
+                        if (g.graphH) (void)hipGraphDestroy(g.graphH);
+                    }
                     if (L.evFrame[b]) (void)hipEventDestroy(L.evFrame[b]);
                 }
                 if (L.arena) (void)hipFree(L.arena);
@@ -482,18 +510,14 @@ void enqueue_head(sift_hip_detector* d, const void* img, int pitch, int fmt, int
 void enqueue_pyramid(sift_hip_detector* d, int nf, int parity);
 void enqueue_extrema(sift_hip_detector* d, int nf);
 void enqueue_refine(sift_hip_detector* d, int nf);
-void enqueue_orientation(sift_hip_detector* d, int nf);
-void enqueue_order(sift_hip_detector* d, int slot, int nf);
+// mask: the detection mask of an eager masked frame; captured graphs and stage
+// replays pass none.
+void enqueue_orientation(sift_hip_detector* d, int nf, const MaskArg& mask = MaskArg{});
+void enqueue_order(sift_hip_detector* d, int slot, int nf, const MaskArg& mask = MaskArg{});
 void enqueue_descriptor(sift_hip_detector* d, int slot, int nf);
 void enqueue_provided(sift_hip_detector* d, int slot, const ProvidedKpt* kpts, int n);
 bool event_done(hipEvent_t e);
-// nProvided >= 0 (<= capFinal): the frame describes the nProvided
-// device-readable keypoints `provided` instead of detecting (sift_hip_compute*).
-// mask (nullable; p != nullptr): the detect chain runs eagerly with the mask
-// test in its orientation and order stages (sift_hip_detect_masked*).
-int run_frame(sift_hip_detector* d, const void* img, int pitch, int fmt, hipEvent_t consumed, int nf = 1, long sfs = 0,
-              bool numbered = false, const ProvidedKpt* provided = nullptr, int nProvided = -1,
-              const MaskArg* mask = nullptr);
+int run_frame(sift_hip_detector* d, const FrameJob& job);
 void make_current(sift_hip_detector* d, long long f);
 void complete_counts(sift_hip_detector* d);
 int ensure_counts(sift_hip_detector* d);
@@ -511,15 +535,16 @@ int check_in_flight(sift_hip_detector* d);
 size_t host_res_bytes(const sift_hip_detector* d);
 void host_res(const sift_hip_detector* d, char* base, int region, float** k3, float** f4, uint16_t** desc);
 int ensure_host_res(sift_hip_detector* d, Lane& L);
-// n >= 0: a compute frame of the n host keypoints `kpts` (already validated).
-// mask (nullable): a host detection mask, rows maskStride bytes apart
-// (validated); the frame is launched at once, never queued.
-int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
-                const ProvidedKpt* kpts = nullptr, int n = -1, const uint8_t* mask = nullptr, size_t maskStride = 0);
+// job: the host image and format, and for a compute frame the host keypoints
+// (already validated); stride: the image's row stride in bytes.  mask
+// (nullable): a host detection mask, rows maskStride bytes apart (validated);
+// such a frame is launched at once, never queued.
+int submit_host(sift_hip_detector* d, FrameJob job, size_t stride, long long* ticket, const uint8_t* mask = nullptr,
+                size_t maskStride = 0);
 int run_group(sift_hip_detector* d);
-int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue = false, const ProvidedKpt* devKpts = nullptr, int n = -1,
-                  const MaskArg* mask = nullptr);
+// job: a device launch group; the lane waits for `stream` before it reads it.
+// queue: a single frame may join the pending queue (sift_hip_submit_device).
+int submit_device(sift_hip_detector* d, const FrameJob& job, void* stream, long long* ticket, bool queue = false);
 int wait_frame(sift_hip_detector* d, long long f);
 
 // ---- datagen.hip ----

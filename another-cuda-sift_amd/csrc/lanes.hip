@@ -189,6 +189,24 @@ bool launch_now(sift_hip_detector* d) {
     return (shallow || d->npend >= auto_min_group(d)) && lane_available(d, d->npend);
 }
 
+// Appends frame p to the pending queue (its ticket: the frame number it will
+// take) and runs the queue when launch_now says so.  If that launch fails with
+// the frame still queued, the frame is taken off again -- and a host frame's
+// staging slot is free again.
+static int queue_pending(sift_hip_detector* d, const sift_hip_detector::PendingFrame& p, long long* ticket) {
+    const int i = d->npend;
+    d->pend[i] = p;
+    d->npend = i + 1;
+    if (ticket) *ticket = d->submitted + i;
+    if (!launch_now(d)) return SIFT_HIP_OK;
+    const int rc = run_group(d);
+    if (rc && d->npend == i + 1) {
+        d->npend = i;
+        if (p.hslot >= 0) d->hstNext--;
+    }
+    return rc;
+}
+
 // A host frame on a micro-batching handle: into the next pinned staging slot
 // of the handle's ring (the caller's buffer is free on return), pending until
 // its group runs (run_group copies it to the lane's group input).
@@ -219,25 +237,17 @@ int queue_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, lo
     copy_rows(d->pool, slot, pitchB, (const char*)img, stride, rowB, H);
     void* dev = nullptr;
     HIPCHK(hipHostGetDevicePointer(&dev, slot, 0));
-    const int i = d->npend;
-    d->pend[i] = sift_hip_detector::PendingFrame{dev, pitchB, fmt, false, hs};
-    d->npend = i + 1;
-    if (ticket) *ticket = d->submitted + i;
-    if (!launch_now(d)) return SIFT_HIP_OK;
-    const int rc = run_group(d);
-    if (rc && d->npend == i + 1) {  // the group did not launch: this call's frame is not queued either
-        d->npend = i;
-        d->hstNext--;  // (its staging slot is free again)
-    }
-    return rc;
+    return queue_pending(d, {.img = dev, .stride = pitchB, .fmt = fmt, .ordered = false, .hslot = hs}, ticket);
 }
 
 // Host frame -> the lane's pinned staging (the caller's buffer is free on
 // return) -> device staging by a small-grid copy kernel on the lane's stream
 // -> pipeline on the frame's lane -> results to pinned host memory.  On a
 // micro-batching handle the frame joins the pending group (queue_host).
-int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, long long* ticket,
-                const ProvidedKpt* kpts, int n, const uint8_t* mask, size_t maskStride) {
+int submit_host(sift_hip_detector* d, FrameJob job, size_t stride, long long* ticket, const uint8_t* mask,
+                size_t maskStride) {
+    const void* img = job.img;
+    const int fmt = job.fmt, n = job.nProvided;
     const int es = format_size(fmt);
     if (!es) return fail(SIFT_HIP_ERR_INVALID, "unknown pixel format");
     if (!img) return fail(SIFT_HIP_ERR_INVALID, "null image");
@@ -272,20 +282,24 @@ int submit_host(sift_hip_detector* d, const void* img, size_t stride, int fmt, l
     L.uploads++;
     d->uploads++;
     const long long f = d->submitted;
-    const ProvidedKpt* devKpts = nullptr;
+    // From here the job is the device frame: the lane's staging, and the
+    // device addresses of the keypoints and the mask.
+    job.img = L.dStage[k];
+    job.pitch = d->inPitch;
+    const ProvidedKpt* kpts = job.provided;
+    job.provided = nullptr;
     if (n > 0) {  // host keypoints: through the pinned staging, read by k_provided_jobs over PCIe (24 B each)
         memcpy(d->hKpts, kpts, sizeof(ProvidedKpt) * (size_t)n);
-        HIPCHK(hipHostGetDevicePointer((void**)&devKpts, d->hKpts, 0));
+        HIPCHK(hipHostGetDevicePointer((void**)&job.provided, d->hKpts, 0));
     }
-    MaskArg m{};
     if (mask) {  // host mask: pinned staging -> device on the lane's stream, ahead of the frame
         copy_rows(nullptr, (char*)d->hMask, (size_t)W, (const char*)mask, maskStride, (size_t)W, H);
         void* msrc = nullptr;
         HIPCHK(hipHostGetDevicePointer(&msrc, d->hMask, 0));
         launch_copy_rows(msrc, (size_t)W, d->dMask, (size_t)W, (size_t)W, H, kStageWg, d->stream);
-        m = MaskArg{d->dMask, W, W, H, 0};
+        job.mask = MaskArg{d->dMask, W, W, H, 0};
     }
-    if (int rc = run_frame(d, L.dStage[k], d->inPitch, fmt, nullptr, 1, 0, false, devKpts, n, mask ? &m : nullptr)) return rc;
+    if (int rc = run_frame(d, job)) return rc;
     if (reqAt) mark_host_results(d, f);
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;
@@ -306,7 +320,7 @@ int run_group(sift_hip_detector* d) {
         const auto& p = d->pend[0];
         if (p.ordered) HIPCHK(hipStreamWaitEvent(d->stream, d->evPend[0], 0));
         d->npend = 0;
-        return run_frame(d, p.img, (int)(p.stride / format_size(p.fmt)), p.fmt, nullptr);
+        return run_frame(d, {.img = p.img, .pitch = (int)(p.stride / format_size(p.fmt)), .fmt = p.fmt});
     }
     // One format per launch group: the frames' own, or f32 when they mix (an
     // 8-bit frame converted exactly, as the 8-bit head does).
@@ -345,42 +359,37 @@ int run_group(sift_hip_detector* d) {
     }
     d->npend = 0;
     const long long f = d->submitted;
-    if (int rc = run_frame(d, L.mbIn, d->inPitch, fmt, nullptr, n, (long)fb, true)) return rc;
+    if (int rc = run_frame(d, {.img = L.mbIn, .pitch = d->inPitch, .fmt = fmt, .nf = n, .sfs = (long)fb, .numbered = true}))
+        return rc;
     for (int i = 0; i < n; i++)
         if (host[i]) mark_host_results(d, f + i);
     return SIFT_HIP_OK;
 }
 
-// Device frame (HBM-resident, fp32 or u8) -> the frame's lane; the lane waits
-// for `stream` (the caller's producer) before reading it.  `queue`: a single
-// frame of sift_hip_submit_device on a micro-batching handle joins the pending
-// group instead.
-int submit_device(sift_hip_detector* d, const void* img, size_t stride, int fmt, void* stream, int nf, size_t fstride,
-                  long long* ticket, bool queue, const ProvidedKpt* devKpts, int n, const MaskArg* mask) {
+// Device launch group (HBM-resident, fp32 or u8) -> a lane; the lane waits for
+// `stream` (the caller's producer) before reading it.  `queue`: a single frame
+// of sift_hip_submit_device on a micro-batching handle joins the pending queue
+// instead.
+int submit_device(sift_hip_detector* d, const FrameJob& job, void* stream, long long* ticket, bool queue) {
     hipStream_t ext = (hipStream_t)stream;
-    if (queue && nf == 1 && queue_frame(d)) {
-        const int i = d->npend;
+    if (queue && job.nf == 1 && queue_frame(d)) {
+        hipEvent_t& ev = d->evPend[d->npend];
         if (ext) {
-            if (!d->evPend[i]) HIPCHK(hipEventCreateWithFlags(&d->evPend[i], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(d->evPend[i], ext));
+            if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(ev, ext));
         }
-        d->pend[i] = sift_hip_detector::PendingFrame{img, stride, fmt, ext != nullptr, -1};
-        d->npend = i + 1;
-        if (ticket) *ticket = d->submitted + i;
-        if (!launch_now(d)) return SIFT_HIP_OK;
-        const int rc = run_group(d);
-        if (rc && d->npend == i + 1) d->npend = i;  // the group did not launch: this call's frame is not queued
-        return rc;
+        const size_t stride = (size_t)job.pitch * format_size(job.fmt);
+        return queue_pending(d, {.img = job.img, .stride = stride, .fmt = job.fmt, .ordered = ext != nullptr, .hslot = -1},
+                             ticket);
     }
     if (int rc = run_group(d)) return rc;  // frames are numbered (and launched) in submission order
-    if (int rc = pick_lane(d, nf)) return rc;
+    if (int rc = pick_lane(d, job.nf)) return rc;
     if (ext) {
         HIPCHK(hipEventRecord(d->evIn, ext));
         HIPCHK(hipStreamWaitEvent(d->stream, d->evIn, 0));
     }
     const long long f = d->submitted;
-    if (int rc = run_frame(d, img, (int)(stride / format_size(fmt)), fmt, nullptr, nf, (long)fstride, false, devKpts, n, mask))
-        return rc;
+    if (int rc = run_frame(d, job)) return rc;
     if (ticket) *ticket = f;
     return SIFT_HIP_OK;
 }
