@@ -372,4 +372,68 @@ std::vector<DMatch> matchList(const DeviceBuffer<Half>& des, int num_des, const 
     return out;
 }
 
+namespace {
+
+sift_hip_match_gate abi_gate(const MatchGate& g) {
+    return sift_hip_match_gate{g.query_xy, g.query_stride, g.train_xy, g.train_stride, g.radius};
+}
+
+struct DeviceFree {
+    void operator()(void* p) const { sift_hip_free(p); }
+};
+
+}  // namespace
+
+std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                    int num_src, const MatchGate& gate, const MatchFilter& filter) {
+    thread_local std::unique_ptr<sift_hip_matcher, MatcherDeleter> matcher;
+    thread_local int cap = 0;  // both limits: the reverse direction swaps the roles
+    std::vector<DMatch> out;
+    if (num_des <= 0 || num_src <= 0) return out;
+    if (!matcher || std::max(num_des, num_src) > cap) {
+        cap = std::max(std::max(num_des, num_src), cap);
+        sift_hip_matcher_t m = nullptr;
+        check(sift_hip_matcher_create(-1, cap, cap, 2, &m), "matchListGuided");
+        matcher.reset(m);
+    }
+    const sift_hip_match_gate g = abi_gate(gate);
+    const sift_hip_match_filter f{filter.ratio, filter.ratio_on_squared, filter.ratio_both_ways, filter.max_distance,
+                                  filter.cross_check};
+    out.resize((size_t)num_des);
+    int count = 0;
+    check_throw(sift_hip_match_list_guided_host(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                                                reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, &f,
+                                                reinterpret_cast<sift_hip_dmatch*>(out.data()), num_des, &count),
+                "matchListGuided");
+    out.resize((size_t)count);
+    return out;
+}
+
+std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                             const MatchGate& gate) {
+    thread_local std::unique_ptr<sift_hip_matcher, MatcherDeleter> matcher;
+    thread_local std::unique_ptr<void, DeviceFree> dmatch;  // capQ ints
+    thread_local int capQ = 0, capT = 0;
+    std::vector<int> out((size_t)std::max(num_des, 0), -1);
+    if (num_des <= 0) return out;
+    if (!matcher || num_des > capQ || num_src > capT) {
+        capQ = std::max(num_des, capQ);
+        capT = std::max(std::max(num_src, 1), capT);
+        sift_hip_matcher_t m = nullptr;
+        check(sift_hip_matcher_create(-1, capQ, capT, 1, &m), "matchGuided");
+        matcher.reset(m);
+        void* p = nullptr;
+        check(sift_hip_malloc(&p, sizeof(int) * (size_t)capQ), "matchGuided");
+        dmatch.reset(p);
+    }
+    const sift_hip_match_gate g = abi_gate(gate);
+    check_throw(sift_hip_match_guided_device(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                                             reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, 0.8f, 1, nullptr,
+                                             nullptr, static_cast<int*>(dmatch.get()), nullptr),
+                "matchGuided");
+    check(sift_hip_device_sync(), "matchGuided");
+    check(sift_hip_memcpy_d2h(out.data(), dmatch.get(), sizeof(int) * (size_t)num_des), "matchGuided");
+    return out;
+}
+
 }  // namespace sift_cuda

@@ -19,6 +19,9 @@
 //                  of one per tile); per 32-row tile 8 MFMAs per wave.
 //  k_match_single  one pair without the prep launch: each workgroup (256
 //                  queries) converts its own query rows and train tiles.
+//  k_match_guided  one pair of ready code sets under a search window: the
+//                  direct kernel with the train positions staged beside the
+//                  keys and a per-key gate in the top-2 fold.
 //  k_match_select  match lists: the top-2 arrays of both directions filtered
 //                  (ratio test, distance cap, cross check) and compacted in
 //                  query order into cv::DMatch records, one workgroup per pair.
@@ -777,6 +780,259 @@ void launch_match_direct(const MatchPair& pr, const int8_t* qc, const int* qk, c
     dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1);
     hipLaunchKernelGGL((k_match_direct<kDirectNW, kDirectQBW>), g, dim3(64 * kDirectNW), 0, s, pr, qc, qk, tc, tk, zc,
                        zk, S, keys, done, ratio, ratio_on_squared, idx2, d2, match);
+}
+
+// ---------------------------------------------------------------------------
+// Guided matching (k_match_guided): the top-2 of a query over the train rows
+// inside its search window -- train row t is a candidate of query i when
+// fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius (float32, one
+// subtraction per axis, inclusive; a NaN coordinate is a candidate of nothing).
+// The distance matrix still lives in the accumulator only: the gate is a
+// per-key predicate in the top-2 fold.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool in_gate(float tx, float ty, float qx, float qy, float radius) {
+    return __builtin_fabsf(tx - qx) <= radius && __builtin_fabsf(ty - qy) <= radius;
+}
+
+// The positions of train rows [row0, row0 + 32 nc) into the chunk's two float
+// planes by 4-byte LDS-DMA, 64 rows per instruction as the keys.  Rows past nt
+// read row nt - 1 (their padding key loses whatever the gate says): nothing
+// past the caller's nt rows is touched.
+template <int NW>
+__device__ __forceinline__ void stage_pos_dma(const float* __restrict__ txy, int tstride, int nt, int row0, int nc,
+                                              float* sx, float* sy, int w, int lane) {
+    const int wv = __builtin_amdgcn_readfirstlane(w);
+    for (int b = wv; b < (nc * kMatchTileRows + 63) / 64; b += NW) {
+        const float* src = txy + (size_t)min(row0 + 64 * b + lane, nt - 1) * tstride;
+        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sx + 64 * b), 4, 0,
+                                         0);
+        __builtin_amdgcn_global_load_lds((const void*)(src + 1), (__attribute__((address_space(3))) void*)(sy + 64 * b),
+                                         4, 0, 0);
+    }
+}
+
+// chunk_top2 under a gate: the key of a (query, row) outside the window becomes
+// INT_MIN before the fold -- below kInvalidKey, so fold_group reads it as
+// "none".  The positions are read as the keys are (the same address across the
+// lanes of a half: broadcast reads); a lane holds its queries' (qx, qy).
+template <int QBW>
+__device__ __forceinline__ void chunk_top2_gated(const int8_t* sc, const int* sk, const float* sx, const float* sy,
+                                                 int nc, int t0, int col, int h, const i32x4 (&bq)[QBW][4],
+                                                 const float (&qx)[QBW], const float (&qy)[QBW], float radius,
+                                                 Best (&best)[QBW]) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    int m1e[QBW], m2e[QBW], m1o[QBW], m2o[QBW];  // registers 0-7 / 8-15
+#pragma unroll
+    for (int qb = 0; qb < QBW; qb++) m1e[qb] = m2e[qb] = m1o[qb] = m2o[qb] = INT_MIN;
+    const int sw = (col >> 1) & 7;
+    const int8_t* const ta0 = sc + col * 128;
+    const int* const tk1 = sk + 4 * h;
+    const float* const tx1 = sx + 4 * h;
+    const float* const ty1 = sy + 4 * h;
+#pragma unroll
+    for (int j = 0; j < kChunkTiles; j++) {
+        if (j < nc) {
+            i32x4 a[4], tk[4];
+            f32x4 px[4], py[4];
+#pragma unroll
+            for (int kb = 0; kb < 4; kb++)
+                a[kb] = *reinterpret_cast<const i32x4*>(ta0 + j * kTileBytes + 16 * ((4 * h + kb) ^ sw));
+            // accumulator register i holds train row (i & 3) + 8 (i >> 2) + 4 h
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                tk[g] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * g);
+                px[g] = *reinterpret_cast<const f32x4*>(tx1 + j * kMatchTileRows + 8 * g);
+                py[g] = *reinterpret_cast<const f32x4*>(ty1 + j * kMatchTileRows + 8 * g);
+            }
+            i32x16 acc[QBW] = {};
+#pragma unroll
+            for (int qb = 0; qb < QBW; qb++)
+#pragma unroll
+                for (int kb = 0; kb < 4; kb++)
+                    acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kb], bq[qb][kb], acc[qb], 0, 0, 0);
+#pragma unroll
+            for (int qb = 0; qb < QBW; qb++) {
+                auto key = [&](int i) {
+                    const int k = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
+                    return in_gate(px[i >> 2][i & 3], py[i >> 2][i & 3], qx[qb], qy[qb], radius) ? k : INT_MIN;
+                };
+#pragma unroll
+                for (int i = 0; i < 8; i += 2) {
+                    const int x0 = key(i), y0 = key(i + 1), x1 = key(i + 8), y1 = key(i + 9);
+                    m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
+                    m1e[qb] = max3_i32(m1e[qb], x0, y0);
+                    m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
+                    m1o[qb] = max3_i32(m1o[qb], x1, y1);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < QBW; qb++) {
+        const int a1 = m1e[qb], a2 = m2e[qb], b1 = m1o[qb], b2 = m2o[qb];
+        best[qb] = fold_group(best[qb], max(a1, b1), max(min(a1, b1), max(a2, b2)), t0);
+    }
+}
+
+// match_f16_block under a gate (sets with fp16 values that are not integers
+// 0..255): the insert also requires the row to lie in the query's window.
+// Lane col carries the position of train row t0 + col, as it carries its norm.
+__device__ Top2 match_f16_block_gated(const MatchPair& pr, const MatchGate& g, int q0, int tbeg, int tend, int col,
+                                      int h) {
+    const int qrow = q0 + col;
+    const bool qvalid = qrow < pr.nq;
+    half8 bq[8];
+#pragma unroll
+    for (int s = 0; s < 8; s++) bq[s] = qvalid ? load_frag(pr.q + (size_t)qrow * 128, 16 * s + 8 * h) : half8{};
+    const float qx = qvalid ? g.qxy[(size_t)qrow * g.qstride] : NAN;
+    const float qy = qvalid ? g.qxy[(size_t)qrow * g.qstride + 1] : NAN;
+    float qn = sumsq8(bq);
+    qn += __shfl_xor(qn, 32);
+    Top2 best{INFINITY, INFINITY, kNone, kNone};
+    for (int tile = tbeg; tile < tend; tile++) {
+        const int t0 = tile * kMatchTileRows, trow = t0 + col;
+        const bool tvalid = trow < pr.nt;
+        half8 a[8];
+#pragma unroll
+        for (int s = 0; s < 8; s++) a[s] = tvalid ? load_frag(pr.t + (size_t)trow * 128, 16 * s + 8 * h) : half8{};
+        const float tx = tvalid ? g.txy[(size_t)trow * g.tstride] : NAN;
+        const float ty = tvalid ? g.txy[(size_t)trow * g.tstride + 1] : NAN;
+        float tn = sumsq8(a);
+        tn += __shfl_xor(tn, 32);
+        f32x16 acc = {}, acc2 = {};
+#pragma unroll
+        for (int s = 0; s < 8; s += 2) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], bq[s], acc, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s + 1], bq[s + 1], acc2, 0, 0, 0);
+        }
+        acc += acc2;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const float d = __shfl(tn, row) - 2.f * acc[i];
+            const bool cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
+            if (t0 + row < pr.nt && cand && d < best.d2) {
+                if (d < best.d1) {
+                    best.d2 = best.d1;
+                    best.i2 = best.i1;
+                    best.d1 = d;
+                    best.i1 = t0 + row;
+                } else {
+                    best.d2 = d;
+                    best.i2 = t0 + row;
+                }
+            }
+        }
+    }
+    best = merge_top2(best, shfl_top2(best, 32));
+    best.d1 += qn;
+    best.d2 += qn;
+    return best;
+}
+
+// k_match_guided: one pair of ready code sets (sidecars, or the matcher's
+// prepared codes) under a gate.  k_match_direct with the train positions of
+// each chunk staged beside its keys (two float planes of kChunkRows per buffer:
+// 70 KiB of LDS per workgroup, still two per CU) and the gated fold; a pair
+// with a flagged set takes the gated fp16 path.
+// grid = (query blocks of 32 QBW NW, splits S of whole key groups).
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_guided(  // registers for two workgroups per CU
+    MatchPair pr, MatchGate g, const int8_t* __restrict__ qc, const int* __restrict__ qk,
+    const int8_t* __restrict__ tc, const int* __restrict__ tk, const int8_t* __restrict__ zc,
+    const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch, int S,
+    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
+    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
+    constexpr int QB = 32 * QBW * NW;
+    static_assert(QB <= 64 * NW, "the write-out gives each thread one query: at most 2 query blocks per wave");
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ unsigned s_last;
+    static_assert(sizeof(Top2) * QB <= sizeof(s_codes), "results alias the code tiles");
+    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
+    const int q0 = blockIdx.x * QB;
+    if (q0 >= pr.nq) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+    const int ntiles = (pr.nt + kMatchTileRows - 1) / kMatchTileRows;
+    const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;  // whole key groups
+    const int tb = min(ntiles, (int)blockIdx.y * tps), te = min(ntiles, tb + tps);
+    const int q0w = q0 + 32 * QBW * w;
+    Top2 res[QBW];
+    if (!flags || (flags[pr.qset] != epoch && flags[pr.tset] != epoch)) {
+        // ---- integer path ----
+        auto stage = [&](int c0, int buf) {
+            const int nc = min(kChunkTiles, te - c0);
+            stage_dma<NW>(tc, tk, pr.nt, c0 * kMatchTileRows, nc, zc, zk, s_codes[buf], s_key[buf], w, lane);
+            stage_pos_dma<NW>(g.txy, g.tstride, pr.nt, c0 * kMatchTileRows, nc, s_px[buf], s_py[buf], w, lane);
+        };
+        if (tb < te) stage(tb, 0);  // the first chunk's DMA before the query loads: both round trips overlap
+        i32x4 bq[QBW][4];
+        int qn[QBW];
+        load_queries<QBW>(qc, qk, pr.nq, q0w, col, h, bq, qn);
+        float qx[QBW], qy[QBW];
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) {
+            const float* p = g.qxy + (size_t)min(q0w + 32 * qb + col, pr.nq - 1) * g.qstride;
+            qx[qb] = p[0];
+            qy[qb] = p[1];
+        }
+        Best best[QBW];
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
+        int buf = 0;
+        for (int c0 = tb; c0 < te; c0 += kChunkTiles, buf ^= 1) {
+            // this wave's copies of the chunk have landed (LDS-DMA writes are counted by vmcnt); the barrier
+            // publishes every wave's, and every wave is done with the other buffer
+            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (c0 + kChunkTiles < te) stage(c0 + kChunkTiles, buf ^ 1);
+            chunk_top2_gated(s_codes[buf], s_key[buf], s_px[buf], s_py[buf], min(kChunkTiles, te - c0),
+                             c0 * kMatchTileRows, col, h, bq, qx, qy, g.radius, best);
+        }
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
+    } else {
+        // ---- general path: fp16 values that are not integers 0..255 ----
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block_gated(pr, g, q0w + 32 * qb, tb, te, col, h);
+    }
+    __syncthreads();  // s_res aliases the code tiles
+    if (h == 0) {
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) s_res[32 * QBW * w + 32 * qb + col] = res[qb];
+    }
+    __syncthreads();
+    const int q = q0 + tid;
+    const bool qv = tid < QB && q < pr.nq;
+    const size_t o = (size_t)pr.out_off + q;
+    if (S == 1) {
+        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);
+        return;
+    }
+    merge_contribution(s_res, &s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, ratio,
+                       ratio_on_squared, idx2, d2out, match);
+}
+
+void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, unsigned* flags, unsigned epoch,
+                       hipStream_t s) {
+    if (sets.maxn > 0)
+        hipLaunchKernelGGL(k_match_prep, dim3((sets.maxn + 31) / 32, sets.nsets), dim3(256), 0, s, sets, codes, rowkeys,
+                           flags, epoch);
+}
+
+// The direct kernel's shape (8 waves x 1 query block, one key group per split
+// up to kDirectWgTarget workgroups): the gate adds VALU work per key, not
+// traffic, so the split that balances the ungated kernel balances this one.
+void launch_match_guided(const MatchPair& pr, const MatchGate& gate, const int8_t* qc, const int* qk, const int8_t* tc,
+                         const int* tk, const int8_t* zc, const int* zk, const unsigned* flags, unsigned epoch,
+                         unsigned long long* keys, unsigned* done, float ratio, int ratio_on_squared, int* idx2,
+                         float* d2, int* match, hipStream_t s) {
+    const int S = match_direct_splits(pr.nq, pr.nt);
+    dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1);
+    hipLaunchKernelGGL((k_match_guided<kDirectNW, kDirectQBW>), g, dim3(64 * kDirectNW), 0, s, pr, gate, qc, qk, tc, tk,
+                       zc, zk, flags, epoch, S, keys, done, ratio, ratio_on_squared, idx2, d2, match);
 }
 
 // Single pairs of foreign buffers (k_match_single): workgroups a launch aims

@@ -451,6 +451,127 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, co
     return SIFT_HIP_OK;
 }
 
+}  // extern "C"
+
+// --- Guided matching -----------------------------------------------------------
+namespace {
+
+// The gate's own rules first (they need no matcher), then the matcher's.  Nothing is launched on a failure.
+int check_guided_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                      const sift_hip_match_gate* g) {
+    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null match gate");
+    if (g->query_stride < 2 || g->train_stride < 2)
+        return fail(SIFT_HIP_ERR_INVALID, "match gate: a position stride below 2 floats");
+    if (!(g->radius > 0.f)) return fail(SIFT_HIP_ERR_INVALID, "match gate: the radius must be > 0");
+    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
+    if (nq < 0 || nt < 0 || nq > m->maxQ || nt > m->maxT)
+        return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
+    if ((nq && !q) || (nt && !t)) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
+    if ((nq && !g->query_xy) || (nt && !g->train_xy))
+        return fail(SIFT_HIP_ERR_INVALID, "match gate: null position pointer");
+    return SIFT_HIP_OK;
+}
+
+// The guided top-2 of (q, t) into idx2 / d2 / match and, with rev_idx2, of (t, q) under the swapped gate into
+// rev_idx2 / rev_d2.  Arguments are checked by the caller; nq > 0.  Detector buffers with fresh sidecars: one launch
+// per direction on their codes.  Otherwise k_match_prep once for both sets, then one launch per direction.
+int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const sift_hip_match_gate& g,
+                float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, int* rev_idx2, float* rev_d2,
+                hipStream_t stream) {
+    const int8_t* const zc = m->dCodes + (size_t)m->codeRows * 128;
+    const int* const zk = m->dRowKeys + m->codeRows;
+    const int8_t *qc, *tc;
+    const int *qk, *tk;
+    const unsigned* flags = nullptr;
+    int qs = 0, ts = 0;
+    Sidecar sq{}, st{};
+    HIPCHK(hipSetDevice(m->device));
+    if (m->sidecars && nt > 0 && find_sidecar(q, nq, &sq) && find_sidecar(t, nt, &st)) {
+        qc = sq.codes, qk = sq.keys, tc = st.codes, tk = st.keys;
+    } else {
+        MatchSets sets{};
+        sets.set[sets.nsets++] = MatchSet{q, nq, 0};
+        if (t == q)
+            sets.set[0].n = std::max(nq, nt);
+        else
+            sets.set[ts = sets.nsets++] = MatchSet{t, nt, nq};
+        sets.maxn = std::max(nq, nt);
+        if ((long)nq + nt > m->codeRows)
+            return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
+        m->epoch = m->epoch + 1 == 0 ? 1 : m->epoch + 1;  // flags from earlier calls never equal it
+        launch_match_prep(sets, m->dCodes, m->dRowKeys, m->dFlags, m->epoch, stream);
+        HIPCHK(hipGetLastError());
+        const int trow0 = sets.set[ts].row0;
+        qc = m->dCodes, qk = m->dRowKeys, tc = m->dCodes + (size_t)trow0 * 128, tk = m->dRowKeys + trow0;
+        flags = m->dFlags;
+    }
+    const MatchPair fwd{q, t, nq, nt, 0, qs, ts, 0, 0, 0, 0};
+    launch_match_guided(fwd, MatchGate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius}, qc, qk, tc, tk,
+                        zc, zk, flags, m->epoch, m->dKeys, m->dDone, ratio, ratio_on_squared, idx2, d2, match, stream);
+    HIPCHK(hipGetLastError());
+    if (rev_idx2 && nt > 0) {
+        // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
+        const MatchPair rev{t, q, nt, nq, 0, ts, qs, 0, 0, 0, 0};
+        launch_match_guided(rev, MatchGate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius}, tc, tk, qc,
+                            qk, zc, zk, flags, m->epoch, m->dKeys, m->dDone, 0.f, 0, rev_idx2, rev_d2, nullptr, stream);
+        HIPCHK(hipGetLastError());
+    }
+    return SIFT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_hip_match_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                 const sift_hip_match_gate* gate, float ratio, int ratio_on_squared, int* idx2,
+                                 float* d2, int* match, void* stream) {
+    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
+    if (nq == 0) return SIFT_HIP_OK;
+    return guided_top2(m, q, nq, t, nt, *gate, ratio, ratio_on_squared, idx2, d2, match, nullptr, nullptr,
+                       (hipStream_t)stream);
+}
+
+int sift_hip_match_guided_plan(int nq, int nt, int* splits) {
+    if (nq < 0 || nt < 0 || !splits) return fail(SIFT_HIP_ERR_INVALID, "bad match shape");
+    *splits = match_direct_splits(nq, nt);
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_match_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                      const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* count, void* stream) {
+    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
+    if (int rc = check_list_args(m, 1, &nq, &nt, filter, out, count)) return rc;
+    if (int rc = ensure_select_scratch(m)) return rc;
+    if (nq > 0 && nt > 0) {
+        const bool rev = needs_reverse(*filter);
+        if (int rc = guided_top2(m, q, nq, t, nt, *gate, 0.f, 0, m->dSelIdx, m->dSelD, nullptr,
+                                 rev ? m->dSelIdx + 2 * (size_t)nq : nullptr, m->dSelD + 2 * (size_t)nq,
+                                 (hipStream_t)stream))
+            return rc;
+    }
+    HIPCHK(hipSetDevice(m->device));
+    return select_lists(m, 1, &nq, &nt, *filter, out, count, (hipStream_t)stream);
+}
+
+int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                    const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                    sift_hip_dmatch* out_host, int cap, int* count) {
+    if (!filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
+    *count = 0;
+    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
+    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
+    if (int rc = ensure_select_scratch(m)) return rc;
+    if (int rc = sift_hip_match_list_guided_device(m, q, nq, t, nt, gate, filter,
+                                                   reinterpret_cast<sift_hip_dmatch*>(m->dList), m->dCount, nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
 int sift_hip_device_count(int* n) {
     if (!n) return fail(SIFT_HIP_ERR_INVALID, "null argument");
     if (hipGetDeviceCount(n) != hipSuccess) *n = 0;

@@ -77,6 +77,32 @@ void launch_match_codes(MatchBatch& batch, const MatchPlan& plan, int nq_stride,
                         const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
                         int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s);
 
+// --- Guided matching (sift_hip_match_guided_*): the top-2 of a query over the
+// train rows inside its search window (the rule is in include/sift_hip.h).
+//
+// The gate as the kernel takes it (sift_hip_match_gate): row i of a set has its
+// position at xy[i * stride + {0, 1}].
+struct MatchGate {
+    const float* qxy;
+    const float* txy;
+    int qstride, tstride;
+    float radius;
+};
+
+// k_match_prep alone: the call's distinct sets into codes / rowkeys / flags.
+void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, unsigned* flags, unsigned epoch,
+                       hipStream_t s);
+
+// One pair of ready code sets -- sidecars, or what launch_match_prep wrote --
+// under a gate: k_match_guided, match_direct_splits(nq, nt) splits.  flags ==
+// nullptr: integer sets by construction (sidecars); otherwise a set whose flag
+// (flags[pr.qset], flags[pr.tset]) equals epoch sends the pair down the fp16
+// path on pr.q / pr.t.
+void launch_match_guided(const MatchPair& pr, const MatchGate& gate, const int8_t* qc, const int* qk, const int8_t* tc,
+                         const int* tk, const int8_t* zc, const int* zk, const unsigned* flags, unsigned epoch,
+                         unsigned long long* keys, unsigned* done, float ratio, int ratio_on_squared, int* idx2,
+                         float* d2, int* match, hipStream_t s);
+
 // --- Match lists (sift_hip_match_list_*): filter + ordered compaction of the
 // top-2 arrays the launchers above wrote (k_match_select).
 //

@@ -71,6 +71,17 @@ class _Config(ctypes.Structure):
     ]
 
 
+class _MatchGate(ctypes.Structure):
+    """sift_hip_match_gate: device position rows (x, y first) of both sets and the window's half-size in pixels."""
+    _fields_ = [
+        ("query_xy", ctypes.c_void_p),
+        ("query_stride", ctypes.c_int),
+        ("train_xy", ctypes.c_void_p),
+        ("train_stride", ctypes.c_int),
+        ("radius", ctypes.c_float),
+    ]
+
+
 class _MatchFilter(ctypes.Structure):
     _fields_ = [
         ("ratio", ctypes.c_float),
@@ -175,6 +186,12 @@ def lib() -> ctypes.CDLL:
         "sift_hip_match_list_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_MatchFilter),
                                                   vp, vp, vp]),
         "sift_hip_match_list_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchFilter), vp, i, ip]),
+        "sift_hip_match_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), f, i, vp, vp, vp, vp]),
+        "sift_hip_match_guided_plan": (i, [i, i, ip]),
+        "sift_hip_match_list_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate),
+                                                  ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_guided_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate),
+                                                ctypes.POINTER(_MatchFilter), vp, i, ip]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -770,6 +787,48 @@ class Matcher:
                                               ctypes.byref(n)), "match_list_host")
         return out[: n.value]
 
+    # --- guided matching: the same operations restricted to a search window (the rule: include/sift_hip.h, and in
+    # numpy sift_amd.cv.gate_mask / guided_top2).  q_xy_ptr / t_xy_ptr: device float rows with x, y first (stride 3
+    # passes a detector's device_kpts as it is); train row t is a candidate of query i when |tx - qx| <= radius and
+    # |ty - qy| <= radius.  One pair per call.
+
+    @staticmethod
+    def guided_plan(nq: int, nt: int) -> int:
+        """Train splits a guided call of this shape launches with (sift_hip_match_guided_plan; host-only)."""
+        S = ctypes.c_int()
+        _check(lib().sift_hip_match_guided_plan(nq, nt, ctypes.byref(S)), "match_guided_plan")
+        return S.value
+
+    def match_guided_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, radius: float,
+                            q_stride: int = 3, t_stride: int = 3, ratio: float = 0.8, ratio_on_squared: bool = False,
+                            idx2_ptr: int = 0, d2_ptr: int = 0, match_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """match_device over each query's candidates only (sift_hip_match_guided_device)."""
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        _check(lib().sift_hip_match_guided_device(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ratio,
+                                                  int(ratio_on_squared), idx2_ptr or None, d2_ptr or None,
+                                                  match_ptr or None, stream), "match_guided_device")
+
+    def match_list_guided_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                                 radius: float, out_ptr: int, count_ptr: int, q_stride: int = 3, t_stride: int = 3,
+                                 stream: Optional[int] = None, **filter) -> None:
+        """match_list_device with the guided top-2 of both directions (sift_hip_match_list_guided_device)."""
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_guided_device(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ctypes.byref(f),
+                                                       out_ptr or None, count_ptr or None, stream),
+               "match_list_guided_device")
+
+    def match_list_guided_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                               radius: float, q_stride: int = 3, t_stride: int = 3, **filter) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_list_guided_host)."""
+        out = np.zeros(max(nq, 0), DMATCH_DTYPE)
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        f = _match_filter(**filter)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_list_guided_host(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ctypes.byref(f),
+                                                     _ptr(out), len(out), ctypes.byref(n)), "match_list_guided_host")
+        return out[: n.value]
+
 
 _default_matcher: Optional[Matcher] = None
 
@@ -779,6 +838,13 @@ def matchList(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src: i
     imgIdx 0, L2 distance) of the rows that pass the filter -- by default Lowe's ratio 0.8 on distances and the cross
     check of cv::BFMatcher(NORM_L2, crossCheck=True) -- in ascending queryIdx.  `filter` keywords as
     Matcher.match_list_*; the rule is sift_amd.cv.filter_matches."""
+    m = _list_matcher(num_des, num_src)
+    if num_des <= 0 or num_src <= 0:
+        return np.zeros(0, DMATCH_DTYPE)
+    return m.match_list_host(des.data(), num_des, src.data(), num_src, **filter)
+
+
+def _list_matcher(num_des: int, num_src: int) -> Matcher:
     global _default_matcher
     need = max(num_des, num_src, 1)  # the reverse direction swaps the roles: both limits hold both sets
     if (_default_matcher is None or need > min(_default_matcher.max_query, _default_matcher.max_train)
@@ -787,9 +853,22 @@ def matchList(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src: i
                   _default_matcher.max_train if _default_matcher else 0)
         # two pairs: foreign buffers match both directions in one launch (detector buffers use their sidecars)
         _default_matcher = Matcher(cap, cap, max_pairs=2)
+    return _default_matcher
+
+
+def matchListGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, radius: float,
+                    des_stride: int = 3, src_stride: int = 3, **filter) -> np.ndarray:
+    """matchList inside a search window: row t of src is a candidate of row i of des when both coordinates of their
+    positions differ by at most `radius` pixels (the rule: sift_amd.cv.gate_mask), and the top-2 search of both
+    directions, the ratio test and the cross check see candidates only.  des_xy / src_xy: DeviceBuffers or raw device
+    pointers of float rows with x, y first -- det.device_kpts (stride 3) for a detector's current frame, the
+    previous frame's positions or the caller's predictions for the other side.  `filter` keywords as matchList."""
+    m = _list_matcher(num_des, num_src)
     if num_des <= 0 or num_src <= 0:
         return np.zeros(0, DMATCH_DTYPE)
-    return _default_matcher.match_list_host(des.data(), num_des, src.data(), num_src, **filter)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    return m.match_list_guided_host(des.data(), num_des, src.data(), num_src, qxy, txy, radius, des_stride, src_stride,
+                                    **filter)
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

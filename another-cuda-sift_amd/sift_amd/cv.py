@@ -4,7 +4,8 @@ cvUtils/Conversion.hh:12-70 (``OpencvUtils::localKptToCvKpt``,
 numpy so it is usable (and tested) without OpenCV; the ``cv2`` object builders
 import cv2 lazily and raise ImportError where OpenCV is absent.
 ``filter_matches`` is the match-list rule (cross check, ratio test, distance
-cap; ``sift_amd.matchList``) on the host.
+cap; ``sift_amd.matchList``) on the host; ``gate_mask`` and ``guided_top2``
+are the guided-matching rule (``sift_amd.matchListGuided``) there.
 """
 from typing import List, Sequence
 
@@ -136,6 +137,48 @@ def filter_matches(idx2_fwd, d2_fwd, idx2_rev=None, d2_rev=None, ratio: float = 
     out = np.zeros(len(q), DMATCH_DTYPE)
     out["queryIdx"], out["trainIdx"], out["imgIdx"], out["distance"] = q, i1[q], img_idx, dist[q]
     return out
+
+
+def gate_mask(q_xy, t_xy, radius) -> np.ndarray:
+    """The guided-matching gate of include/sift_hip.h in numpy float32: an (nq, nt) bool array, True where train row
+    t is a candidate of query i -- fabsf(tx - qx) <= radius and fabsf(ty - qy) <= radius, one float32 subtraction per
+    axis and an inclusive compare.  A NaN coordinate makes its row a candidate of nothing; radius = inf is no gate.
+    q_xy / t_xy: (n, >= 2) arrays with x, y in the first two columns (further columns are ignored)."""
+    q = np.asarray(q_xy, np.float32).reshape(len(q_xy), -1)[:, :2]
+    t = np.asarray(t_xy, np.float32).reshape(len(t_xy), -1)[:, :2]
+    r = np.float32(radius)
+    with np.errstate(invalid="ignore"):
+        dx = np.abs(t[None, :, 0] - q[:, None, 0])
+        dy = np.abs(t[None, :, 1] - q[:, None, 1])
+        return (dx <= r) & (dy <= r)
+
+
+def guided_top2(q, t, q_xy, t_xy, radius):
+    """Matcher.match_guided_device in numpy: (idx2, d2), (nq, 2) int32 / float32 laid out as match_device writes
+    them -- the two nearest candidates (gate_mask) of every query, ties to the lower train index, -1 / FLT_MAX where
+    there is none.  Squared distances come from an exact integer product when both sets hold integers, otherwise
+    from float64 (exact for the values the tests use), and are rounded to float32 once.  filter_matches consumes the
+    output unchanged."""
+    q, t = np.asarray(q), np.asarray(t)
+    nq, nt = len(q), len(t)
+    idx2 = np.full((nq, 2), -1, np.int32)
+    d2 = np.full((nq, 2), np.finfo(np.float32).max, np.float32)
+    if nq == 0 or nt == 0:
+        return idx2, d2
+    exact = np.int64 if (np.all(q == np.rint(q)) and np.all(t == np.rint(t))) else np.float64
+    a, b = q.astype(exact), t.astype(exact)
+    dist = (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2 * (a @ b.T)
+    cand = gate_mask(q_xy, t_xy, radius)
+    if cand.shape != dist.shape:
+        raise ValueError("positions and descriptor sets differ in length")
+    order = np.argsort(np.where(cand, dist, np.inf), axis=1, kind="stable")[:, :2]  # stable: ties to the lower index
+    rows = np.arange(nq)
+    for k in range(order.shape[1]):
+        j = order[:, k]
+        ok = cand[rows, j]
+        idx2[ok, k] = j[ok]
+        d2[ok, k] = dist[rows, j][ok]
+    return idx2, d2
 
 
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):

@@ -167,4 +167,27 @@ std::vector<int> matchBruteForce(const DeviceBuffer<Half>& des, int num_des, con
 std::vector<DMatch> matchList(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
                               const MatchFilter& filter = {});
 
+// Extra: matchList inside a search window (sift_hip_match_list_guided_host) --
+// row t of src is a candidate of row i of des when both coordinates of their
+// positions differ by at most gate.radius pixels, and the top-2 search of both
+// directions, the ratio test and the cross check see candidates only
+// (ORB-SLAM's search by projection, COLMAP's guided match).  The tracker loop:
+//     gate.query_xy = the previous frame's positions (a device copy of its
+//                     device_kpts) or the caller's predictions,
+//     gate.train_xy = reinterpret_cast<const float*>(det.device_kpts.data()),
+//     both strides 3, gate.radius = the search radius in pixels;
+//     matchListGuided(det.prev_descriptor, n0, det.device_descriptor, n1, gate).
+// Synchronous; the thread-local matcher is sized as matchList's.  A bad gate
+// (null positions, a stride below 2, a radius that is not > 0) throws
+// std::invalid_argument.
+std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                    int num_src, const MatchGate& gate, const MatchFilter& filter = {});
+
+// Extra: matchBruteForce inside the same window, with its ratio convention
+// (0.8 on squared distances): the nearest candidate of each des row if it
+// passes the test against the second-nearest candidate, else -1; a row with one
+// candidate matches it.
+std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                             const MatchGate& gate);
+
 }  // namespace sift_cuda

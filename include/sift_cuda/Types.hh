@@ -72,6 +72,19 @@ struct MatchFilter {
 };
 static_assert(sizeof(MatchFilter) == 20, "layout of sift_hip_match_filter");
 
+// The search window of matchListGuided / matchGuided (sift_hip_match_gate,
+// include/sift_hip.h): device rows of floats with x, y first for both sets --
+// row i of the query set at query_xy[i * query_stride + {0, 1}] -- and the
+// window's half-size: a train row is a candidate of a query when both
+// coordinates differ by at most radius pixels.
+struct MatchGate {
+    const float* query_xy = nullptr;
+    int query_stride = 3;          // floats per row, >= 2; 3: a Detector's device_kpts as it is
+    const float* train_xy = nullptr;
+    int train_stride = 3;
+    float radius = 0.f;            // pixels, > 0; infinity: no gate
+};
+
 // Non-owning view of a device array owned by a Detector (stands in for the
 // reference's thrust::device_vector members, Detector.hh:54-57; data()/size()
 // as there).  data() is read-only: the detector derives data from what it

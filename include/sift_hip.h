@@ -588,6 +588,76 @@ int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes,
 int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
                              const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count);
 
+/* --- Guided matching: top-2 and match lists inside a search window ----------
+ *
+ * A tracker matches a point near its previous position, an SfM front end a
+ * re-projected map point near where it should land (ORB-SLAM's search by
+ * projection, SiftGPU's and COLMAP's guided match, the mask argument of
+ * cv::DescriptorMatcher::knnMatch).  The best and second-best rows inside the
+ * window are in general not the global top-2, so this cannot be derived from
+ * sift_hip_match_device's output; here the window is a predicate inside the
+ * matcher's top-2 fold and no nq x nt matrix ever exists.
+ *
+ * The rule.  A gate gives every row of both sets a position:
+ *   query i at (qx, qy) = query_xy[i * query_stride + {0, 1}],
+ *   train t at (tx, ty) = train_xy[t * train_stride + {0, 1}].
+ * Train row t is a candidate of query i when
+ *   fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius
+ * evaluated in float32: one subtraction per axis and an inclusive compare (no
+ * product, so no contraction can change it).  A NaN coordinate makes its row a
+ * candidate of nothing; radius = +inf is no gate.  The predicate is symmetric
+ * in the two rows, so the reverse direction of a cross check is the same gate
+ * with the roles swapped.
+ * The guided top-2 of query i is sift_hip_match_device's top-2 restricted to
+ * i's candidates: the same squared distances, ties to the lower train index, an
+ * absent neighbour -1 / FLT_MAX.  The `match` output's ratio test is unchanged:
+ * a query with one candidate matches it, a query with none gets -1.
+ * The guided match list is the match-list rule above with both top-2 arrays
+ * replaced by the guided ones.
+ *
+ * Positions are device arrays of float rows; a stride of 3 passes a detector's
+ * keypoint buffer ({x, y, layer} rows, sift_hip_results_device's kpts3) as it
+ * is.  Exactly nq and nt rows are read.
+ *
+ * One pair per call.  Two detector descriptor buffers with fresh sidecars are
+ * matched on their codes in one launch; any other pair is converted first (two
+ * launches); a set with non-integer fp16 values takes the general path, as in
+ * sift_hip_match_device.  Batched, code-set (sift_hip_match_codes_batched) and
+ * multi-GPU guided forms do not exist. */
+typedef struct {
+    const float* query_xy; /* device; query i's predicted position is query_xy[i*query_stride + {0,1}] */
+    int query_stride;      /* floats per row, >= 2 (3 passes a detector's kpts3 buffer as it is) */
+    const float* train_xy; /* device; the same for train rows */
+    int train_stride;
+    float radius;          /* pixels, > 0; +inf = no gate */
+} sift_hip_match_gate;
+
+/* sift_hip_match_device under a gate.  SIFT_HIP_ERR_INVALID, with nothing
+ * launched, for: a null matcher or gate, a stride < 2, a radius that is not
+ * > 0 (NaN included), a size over the matcher's limits, a null descriptor or
+ * position pointer of a non-empty set.  nq == 0: nothing is written.  nt == 0:
+ * every query gets -1 / FLT_MAX. */
+int sift_hip_match_guided_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                 const sift_hip_match_gate* gate, float ratio, int ratio_on_squared, int* idx2,
+                                 float* d2, int* match, void* stream);
+
+/* The train splits S a guided call of this shape launches with (host-only, as
+ * sift_hip_match_plan). */
+int sift_hip_match_guided_plan(int nq, int nt, int* splits);
+
+/* sift_hip_match_list_device under a gate: the forward guided top-2, with
+ * cross_check or ratio_both_ways the reverse guided top-2 (the gate's roles
+ * swapped), then the filter and the compaction.  Outputs, size limits and the
+ * first call's scratch allocation as sift_hip_match_list_device. */
+int sift_hip_match_list_guided_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                      int nt, const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* count, void* stream);
+
+/* Synchronous, records to host memory, as sift_hip_match_list_host. */
+int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                    const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                    sift_hip_dmatch* out_host, int cap, int* count);
+
 /* The launch plan a match call of this shape gets: train splits S per query
  * block (S > 1: split workgroups merge their top-2 through the scratch's
  * atomics) and waves per workgroup.  Host-only (no GPU call beyond reading the
