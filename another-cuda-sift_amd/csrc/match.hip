@@ -19,9 +19,12 @@
 //                  of one per tile); per 32-row tile 8 MFMAs per wave.
 //  k_match_single  one pair without the prep launch: each workgroup (256
 //                  queries) converts its own query rows and train tiles.
+//  k_match_direct  one pair of ready code sets (detector sidecars): the
+//                  integer path of k_match_batch with no prep and no flags.
 //  k_match_guided  one pair of ready code sets under a search window: the
 //                  direct kernel with the train positions staged beside the
-//                  keys and a per-key gate in the top-2 fold.
+//                  keys and a per-key gate in the top-2 fold.  Both are
+//                  wrappers around one body, match_pair.
 //  k_match_select  match lists: the top-2 arrays of both directions filtered
 //                  (ratio test, distance cap, cross check) and compacted in
 //                  query order into cv::DMatch records, one workgroup per pair.
@@ -42,6 +45,13 @@
 // reference's own unrounded x512 descriptors) runs the general path in the
 // same launch: v_mfma_f32_32x32x16_f16 dot products (exact products, fp32
 // sums), fp32 norms, a float top-2 in train order.
+//
+// Shared core: one integer fold (chunk_top2) and one fp16 block
+// (match_f16_block), both templates on a gate policy (NoGate, or the gate of
+// guided matching: in_gate is the window rule); one split rule for the kernels
+// that split by whole key groups (GroupSplit, host and device); one merge
+// (merge_contribution).  The bit-exactness rules -- the tie order, INT_MIN
+// against kPadBias, rows past nt losing -- live there and nowhere else.
 //
 // Splits of the train rows merge through 64-bit atomicMin keys (d^2 bits << 32 |
 // train index) in the matcher's scratch; the last split of a query block (a
@@ -229,16 +239,42 @@ __device__ __forceinline__ float sumsq8(const half8 (&v)[8]) {
     return (c[0] + c[1]) + (c[2] + c[3]);
 }
 
+// ---------------------------------------------------------------------------
+// The gate (guided matching, k_match_guided) as a compile-time policy of the
+// two match cores, chunk_top2 and match_f16_block.  Train row t is a candidate
+// of query i when fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius
+// (float32, one subtraction per axis, inclusive; a NaN coordinate is a
+// candidate of nothing).  The distance matrix still lives in the accumulator
+// only: the gate is a per-key predicate in the top-2 fold.  Instantiated with
+// NoGate a core carries no position, query position or radius at all.
+// ---------------------------------------------------------------------------
+struct NoGate {};
+template <class Gate>
+constexpr bool kGated = !std::is_same<Gate, NoGate>::value;
+
+__device__ __forceinline__ bool in_gate(float tx, float ty, float qx, float qy, float radius) {
+    return __builtin_fabsf(tx - qx) <= radius && __builtin_fabsf(ty - qy) <= radius;
+}
+
 // One wave's 32 queries (rows q0 + col of the pair) against train tiles
 // [tbeg, tend): f16 MFMA (train rows as A, queries as B, so the accumulator's
 // lane is the query and its 16 registers are train rows in increasing order),
-// float top-2 with a strict '<' insert.  Returns the full d^2.
-__device__ Top2 match_f16_block(const MatchPair& pr, int q0, int tbeg, int tend, int col, int h) {
+// float top-2 with a strict '<' insert.  Returns the full d^2.  Under a gate
+// (Gate = MatchGate) the insert also requires the row to lie in the query's
+// window; lane col carries the position of train row t0 + col, as it carries
+// its norm.
+template <class Gate>
+__device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int tbeg, int tend, int col, int h) {
     const int qrow = q0 + col;
     const bool qvalid = qrow < pr.nq;
     half8 bq[8];
 #pragma unroll
     for (int s = 0; s < 8; s++) bq[s] = qvalid ? load_frag(pr.q + (size_t)qrow * 128, 16 * s + 8 * h) : half8{};
+    float qx = NAN, qy = NAN;
+    if constexpr (kGated<Gate>) {
+        qx = qvalid ? g.qxy[(size_t)qrow * g.qstride] : NAN;
+        qy = qvalid ? g.qxy[(size_t)qrow * g.qstride + 1] : NAN;
+    }
     float qn = sumsq8(bq);
     qn += __shfl_xor(qn, 32);
     Top2 best{INFINITY, INFINITY, kNone, kNone};
@@ -248,6 +284,11 @@ __device__ Top2 match_f16_block(const MatchPair& pr, int q0, int tbeg, int tend,
         half8 a[8];
 #pragma unroll
         for (int s = 0; s < 8; s++) a[s] = tvalid ? load_frag(pr.t + (size_t)trow * 128, 16 * s + 8 * h) : half8{};
+        float tx = NAN, ty = NAN;
+        if constexpr (kGated<Gate>) {
+            tx = tvalid ? g.txy[(size_t)trow * g.tstride] : NAN;
+            ty = tvalid ? g.txy[(size_t)trow * g.tstride + 1] : NAN;
+        }
         float tn = sumsq8(a);
         tn += __shfl_xor(tn, 32);
         f32x16 acc = {}, acc2 = {};
@@ -261,7 +302,9 @@ __device__ Top2 match_f16_block(const MatchPair& pr, int q0, int tbeg, int tend,
         for (int i = 0; i < 16; i++) {
             const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
             const float d = __shfl(tn, row) - 2.f * acc[i];
-            if (t0 + row < pr.nt && d < best.d2) {
+            bool cand = true;
+            if constexpr (kGated<Gate>) cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
+            if (t0 + row < pr.nt && cand && d < best.d2) {
                 if (d < best.d1) {
                     best.d2 = best.d1;
                     best.i2 = best.i1;
@@ -284,30 +327,28 @@ __device__ __forceinline__ unsigned long long match_key(float d2, int idx) {
     return idx == kNone ? ~0ull : ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx;
 }
 
-__device__ __forceinline__ void write_match(int i1, float e1, int i2, float e2, size_t o, float ratio,
-                                            int ratio_on_squared, int* idx2, float* d2out, int* match) {
-    if (idx2) {
-        idx2[2 * o] = i1;
-        idx2[2 * o + 1] = i2;
+__device__ __forceinline__ void write_match(int i1, float e1, int i2, float e2, size_t o, const MatchOut& out) {
+    if (out.idx2) {
+        out.idx2[2 * o] = i1;
+        out.idx2[2 * o + 1] = i2;
     }
-    if (d2out) {
-        d2out[2 * o] = e1;
-        d2out[2 * o + 1] = e2;
+    if (out.d2) {
+        out.d2[2 * o] = e1;
+        out.d2[2 * o + 1] = e2;
     }
-    if (match) {
+    if (out.match) {
         int m = -1;
         if (i1 >= 0) {
             if (i2 < 0)
                 m = i1;
-            else if (ratio_on_squared)
-                m = e1 < ratio * e2 ? i1 : -1;
+            else if (out.ratio_on_squared)
+                m = e1 < out.ratio * e2 ? i1 : -1;
             else
-                m = __builtin_sqrtf(e1) < ratio * __builtin_sqrtf(e2) ? i1 : -1;
+                m = __builtin_sqrtf(e1) < out.ratio * __builtin_sqrtf(e2) ? i1 : -1;
         }
-        match[o] = m;
+        out.match[o] = m;
     }
 }
-
 
 // ---------------------------------------------------------------------------
 // Integer-path building blocks shared by both kernels.
@@ -374,6 +415,45 @@ __device__ __forceinline__ void stage_dma(const int8_t* __restrict__ tc, const i
     }
 }
 
+// The positions of train rows [row0, row0 + 32 nc) into the chunk's two float
+// planes by 4-byte LDS-DMA, 64 rows per instruction as the keys.  Rows past nt
+// read row nt - 1 (their padding key loses whatever the gate says): nothing
+// past the caller's nt rows is touched.
+template <int NW>
+__device__ __forceinline__ void stage_pos_dma(const float* __restrict__ txy, int tstride, int nt, int row0, int nc,
+                                              float* sx, float* sy, int w, int lane) {
+    const int wv = __builtin_amdgcn_readfirstlane(w);
+    for (int b = wv; b < (nc * kMatchTileRows + 63) / 64; b += NW) {
+        const float* src = txy + (size_t)min(row0 + 64 * b + lane, nt - 1) * tstride;
+        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sx + 64 * b), 4, 0,
+                                         0);
+        __builtin_amdgcn_global_load_lds((const void*)(src + 1), (__attribute__((address_space(3))) void*)(sy + 64 * b),
+                                         4, 0, 0);
+    }
+}
+
+// A lane's side of the gate in the integer fold: the positions of its queries.
+template <int QBW>
+struct LaneGate {
+    float qx[QBW], qy[QBW], radius;
+};
+template <int QBW>
+__device__ __forceinline__ LaneGate<QBW> lane_gate(const MatchGate& g, int nq, int q0w, int col) {
+    LaneGate<QBW> lg;
+    lg.radius = g.radius;
+#pragma unroll
+    for (int qb = 0; qb < QBW; qb++) {
+        const float* p = g.qxy + (size_t)min(q0w + 32 * qb + col, nq - 1) * g.qstride;
+        lg.qx[qb] = p[0];
+        lg.qy[qb] = p[1];
+    }
+    return lg;
+}
+template <int QBW>
+__device__ __forceinline__ NoGate lane_gate(const NoGate&, int, int, int) {
+    return {};
+}
+
 // One staged chunk of nc tiles (rows t0 ...) against a wave's two query
 // blocks: per tile 8 MFMAs from LDS fragments, then each lane folds its 32
 // keys into a per-block running key top-2 -- two at a time: for a pair (x, y)
@@ -382,9 +462,15 @@ __device__ __forceinline__ void stage_dma(const int8_t* __restrict__ tc, const i
 // block (accumulator registers 0-7 / 8-15).  The chunk lies in one key group
 // (r = row - t0 < 256), so its top-2 is decoded once into (e, train index) and
 // merged into the running pair (earlier groups win ties).
-template <int QBW>
-__device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, int nc, int t0, int col, int h,
-                                           const i32x4 (&bq)[QBW][4], Best (&best)[QBW]) {
+// Under a gate (Gate = LaneGate, planes sx / sy) the key of a (query, row)
+// outside the window becomes INT_MIN before the fold -- below kInvalidKey, so
+// fold_group reads it as "none".  The positions are read as the keys are (the
+// same address across the lanes of a half: broadcast reads).
+template <int QBW, class Gate>
+__device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, const float* sx, const float* sy, int nc,
+                                           int t0, int col, int h, const i32x4 (&bq)[QBW][4], const Gate& g,
+                                           Best (&best)[QBW]) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
     int m1e[QBW], m2e[QBW], m1o[QBW], m2o[QBW];  // registers 0-7 / 8-15
 #pragma unroll
     for (int qb = 0; qb < QBW; qb++) m1e[qb] = m2e[qb] = m1o[qb] = m2o[qb] = INT_MIN;
@@ -395,12 +481,19 @@ __device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, int 
     for (int j = 0; j < kChunkTiles; j++) {
         if (j < nc) {
             i32x4 a[4], tk[4];
+            f32x4 px[4], py[4];  // gated only
 #pragma unroll
             for (int kb = 0; kb < 4; kb++)
                 a[kb] = *reinterpret_cast<const i32x4*>(ta0 + j * kTileBytes + 16 * ((4 * h + kb) ^ sw));
             // accumulator register i holds train row (i & 3) + 8 (i >> 2) + 4 h
 #pragma unroll
-            for (int g = 0; g < 4; g++) tk[g] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * g);
+            for (int r = 0; r < 4; r++) {
+                tk[r] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * r);
+                if constexpr (kGated<Gate>) {
+                    px[r] = *reinterpret_cast<const f32x4*>(sx + 4 * h + j * kMatchTileRows + 8 * r);
+                    py[r] = *reinterpret_cast<const f32x4*>(sy + 4 * h + j * kMatchTileRows + 8 * r);
+                }
+            }
             i32x16 acc[QBW] = {};
 #pragma unroll
             for (int qb = 0; qb < QBW; qb++)
@@ -408,18 +501,23 @@ __device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, int 
                 for (int kb = 0; kb < 4; kb++)
                     acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kb], bq[qb][kb], acc[qb], 0, 0, 0);
 #pragma unroll
-            for (int qb = 0; qb < QBW; qb++)
+            for (int qb = 0; qb < QBW; qb++) {
+                auto key = [&](int i) {
+                    const int k = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
+                    if constexpr (kGated<Gate>)
+                        return in_gate(px[i >> 2][i & 3], py[i >> 2][i & 3], g.qx[qb], g.qy[qb], g.radius) ? k : INT_MIN;
+                    else
+                        return k;
+                };
 #pragma unroll
                 for (int i = 0; i < 8; i += 2) {
-                    const int x0 = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
-                    const int y0 = (acc[qb][i + 1] << 9) + tk[i >> 2][(i & 3) + 1];
-                    const int x1 = (acc[qb][i + 8] << 9) + tk[(i + 8) >> 2][i & 3];
-                    const int y1 = (acc[qb][i + 9] << 9) + tk[(i + 8) >> 2][(i & 3) + 1];
+                    const int x0 = key(i), y0 = key(i + 1), x1 = key(i + 8), y1 = key(i + 9);
                     m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
                     m1e[qb] = max3_i32(m1e[qb], x0, y0);
                     m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
                     m1o[qb] = max3_i32(m1o[qb], x1, y1);
                 }
+            }
         }
     }
 #pragma unroll
@@ -446,11 +544,9 @@ __device__ __forceinline__ Top2 finish_best(const Best b, int qn) {
     return t;
 }
 
-__device__ __forceinline__ void write_top2(const Top2 r, size_t o, float ratio, int ratio_on_squared, int* idx2,
-                                           float* d2out, int* match) {
+__device__ __forceinline__ void write_top2(const Top2 r, size_t o, const MatchOut& out) {
     const int i1 = r.i1 == kNone ? -1 : r.i1, i2 = r.i2 == kNone ? -1 : r.i2;
-    write_match(i1, i1 >= 0 ? r.d1 : FLT_MAX, i2, i2 >= 0 ? r.d2 : FLT_MAX, o, ratio, ratio_on_squared, idx2, d2out,
-                match);
+    write_match(i1, i1 >= 0 ? r.d1 : FLT_MAX, i2, i2 >= 0 ? r.d2 : FLT_MAX, o, out);
 }
 
 // Global top-2 of a query over several contributions (train ranges):
@@ -465,8 +561,7 @@ __device__ __forceinline__ void write_top2(const Top2 r, size_t o, float ratio, 
 // thread of the workgroup, thread t for query q0 + t (s_res[t]).
 __device__ __forceinline__ void merge_contribution(const Top2* s_res, unsigned* s_last, unsigned long long* K0,
                                                    unsigned* cnt, unsigned units, unsigned total, bool qv, size_t o,
-                                                   float ratio, int ratio_on_squared, int* idx2, float* d2out,
-                                                   int* match) {
+                                                   const MatchOut& out) {
     const int tid = threadIdx.x;
     unsigned long long* K = K0 + 2 * tid;
     if (qv) {
@@ -488,9 +583,39 @@ __device__ __forceinline__ void merge_contribution(const Top2* s_res, unsigned* 
         const int i1 = k1 == ~0ull ? -1 : (int)(unsigned)k1, i2 = k2 == ~0ull ? -1 : (int)(unsigned)k2;
         const float e1 = i1 >= 0 ? __uint_as_float((unsigned)(k1 >> 32)) : FLT_MAX;
         const float e2 = i2 >= 0 ? __uint_as_float((unsigned)(k2 >> 32)) : FLT_MAX;
-        write_match(i1, e1, i2, e2, o, ratio, ratio_on_squared, idx2, d2out, match);
+        write_match(i1, e1, i2, e2, o, out);
     }
     if (tid == 0) atomicExch(cnt, 0u);
+}
+
+// Splits of whole key groups: S splits of ntiles train tiles, split s owning
+// tiles [begin(s), end(s)).  The one rule that keeps a kernel's tile range and
+// the host's split count in agreement (tps rounded up can leave trailing
+// splits empty: count() is the number that are not).
+struct GroupSplit {
+    int ntiles, tps;  // tiles per split
+    __host__ __device__ GroupSplit(int ntiles, int S)
+        : ntiles(ntiles), tps(((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles) {}
+    __host__ __device__ int begin(int s) const { return min(ntiles, s * tps); }
+    __host__ __device__ int end(int s) const { return min(ntiles, begin(s) + tps); }
+    int count() const { return tps > 0 ? max(1, (ntiles + tps - 1) / tps) : 1; }
+};
+__host__ __device__ inline int match_tiles(int nt) { return (nt + kMatchTileRows - 1) / kMatchTileRows; }
+
+// Queries per workgroup of NW waves with QBW 32-query blocks each.  Every match
+// kernel ends the same way: each wave's h == 0 half parks the top-2 of its
+// queries (over the workgroup's split) in s_res, which aliases the code tiles;
+// thread t then owns query q0 + t and, with one split, writes its outputs,
+// else merges them into the query block's keys (merge_contribution).  That
+// ending and the LDS-DMA streaming loop before it are written out in
+// k_match_single, k_match_batch and match_pair: as shared functions both
+// compile to other instructions than the kernels measured in profiles/.
+template <int NW, int QBW>
+constexpr int block_queries() {
+    constexpr int QB = 32 * QBW * NW;
+    static_assert(QB <= 64 * NW, "the write-out gives each thread one query: at most 2 query blocks per wave");
+    static_assert(sizeof(Top2) * QB <= kChunkTiles * kTileBytes, "results alias the code tiles");
+    return QB;
 }
 
 // ---------------------------------------------------------------------------
@@ -502,23 +627,23 @@ __device__ __forceinline__ void merge_contribution(const Top2* s_res, unsigned* 
 // any of them holds a non-integer value.  Mixing paths across workgroups is
 // exact: on integer values 0..255 the fp16 path's dot products and norms are
 // exact integers below 2^24, so both paths return the same (d^2, index) pairs
-// with the same tie order.  Key groups start at the split's first tile.
+// with the same tie order.  The splits are plain ceil(ntiles / S) tile ranges,
+// not GroupSplit's whole key groups: the workgroup computes the key biases
+// itself, so its key groups start at the split's first tile, wherever that is,
+// and the split may be as small as the conversion cost allows (match_plan).
 // ---------------------------------------------------------------------------
 template <int NW, int QBW>
 __global__ __launch_bounds__(64 * NW, (kMatchWgPerCu * NW) / 4) void k_match_single(
     MatchPair pr, int S, unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio,
     int ratio_on_squared, int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
-    constexpr int NT = 64 * NW, QB = 32 * QBW * NW;  // threads, queries per workgroup (QBW 32-query blocks per wave)
+    constexpr int NT = 64 * NW, QB = block_queries<NW, QBW>();  // threads, queries per workgroup
     __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
     __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
     __shared__ unsigned s_last;
-    static_assert(sizeof(Top2) * QB <= sizeof(s_codes), "results alias the code tiles");
-    static_assert(QB <= NT, "the write-out gives each thread one query: at most 2 query blocks per wave");
-    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
     const int q0 = blockIdx.x * QB;
     if (q0 >= pr.nq) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
-    const int ntiles = (pr.nt + kMatchTileRows - 1) / kMatchTileRows, tps = (ntiles + S - 1) / S;
+    const int ntiles = match_tiles(pr.nt), tps = (ntiles + S - 1) / S;
     const int tbeg = min(ntiles, (int)blockIdx.y * tps), tend = min(ntiles, tbeg + tps);
     const int q0w = q0 + 32 * QBW * w;
     Top2 res[QBW];
@@ -577,7 +702,8 @@ __global__ __launch_bounds__(64 * NW, (kMatchWgPerCu * NW) / 4) void k_match_sin
         for (int c0 = tbeg; c0 < tend; c0 += kChunkTiles, buf ^= 1) {
             __syncthreads();  // chunk c0 is staged; every wave is done with the other buffer
             if (c0 + kChunkTiles < tend) stage(c0 + kChunkTiles, buf ^ 1);
-            chunk_top2(s_codes[buf], s_key[buf], min(kChunkTiles, tend - c0), c0 * kMatchTileRows, col, h, bq, best);
+            chunk_top2(s_codes[buf], s_key[buf], nullptr, nullptr, min(kChunkTiles, tend - c0), c0 * kMatchTileRows, col,
+                       h, bq, NoGate{}, best);
         }
 #pragma unroll
         for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
@@ -585,8 +711,10 @@ __global__ __launch_bounds__(64 * NW, (kMatchWgPerCu * NW) / 4) void k_match_sin
     if (__syncthreads_or(bad)) {
         // ---- general path: fp16 values that are not integers 0..255 ----
 #pragma unroll
-        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, q0w + 32 * qb, tbeg, tend, col, h);
+        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, NoGate{}, q0w + 32 * qb, tbeg, tend, col, h);
     }
+    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
+    const MatchOut out{ratio, ratio_on_squared, idx2, d2out, match};
     __syncthreads();  // s_res aliases the code tiles
     if (h == 0) {
 #pragma unroll
@@ -597,11 +725,10 @@ __global__ __launch_bounds__(64 * NW, (kMatchWgPerCu * NW) / 4) void k_match_sin
     const bool qv = tid < QB && q < pr.nq;
     const size_t o = (size_t)pr.out_off + q;
     if (S == 1) {
-        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);
+        if (qv) write_top2(s_res[tid], o, out);
         return;
     }
-    merge_contribution(s_res, &s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, ratio,
-                       ratio_on_squared, idx2, d2out, match);
+    merge_contribution(s_res, &s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -620,21 +747,17 @@ __global__ __launch_bounds__(64 * NW, (kMatchBatchWgPerCu * NW) / 4) void k_matc
     unsigned long long* __restrict__ keys,
     unsigned* __restrict__ done, float ratio, int ratio_on_squared, int* __restrict__ idx2, float* __restrict__ d2out,
     int* __restrict__ match) {
-    constexpr int QB = 32 * QBW * NW;  // queries per workgroup
-    static_assert(QB <= 64 * NW, "the write-out gives each thread one query: at most 2 query blocks per wave");
+    constexpr int QB = block_queries<NW, QBW>();
     __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
     __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
     __shared__ unsigned s_last;
-    static_assert(sizeof(Top2) * QB <= sizeof(s_codes), "results alias the code tiles");
-    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
     const int p = blockIdx.z;
     const MatchPair& pr = batch.pair[p];
     const int q0 = blockIdx.x * QB;
     if (q0 >= pr.nq) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
-    const int ntiles = (pr.nt + kMatchTileRows - 1) / kMatchTileRows;
-    const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;  // whole key groups
-    const int tb = min(ntiles, (int)blockIdx.y * tps), te = min(ntiles, tb + tps);
+    const GroupSplit split(match_tiles(pr.nt), S);
+    const int tb = split.begin(blockIdx.y), te = split.end(blockIdx.y);
     const int q0w = q0 + 32 * QBW * w;
     Top2 res[QBW];
     // flags == nullptr: code sets handed over ready (sift_hip_match_codes_batched), integers by construction.
@@ -642,15 +765,17 @@ __global__ __launch_bounds__(64 * NW, (kMatchBatchWgPerCu * NW) / 4) void k_matc
         // ---- integer path (zc / zk: the zero code row and padding key) ----
         const int8_t* __restrict__ tc = codes + (size_t)pr.trow0 * 128;
         const int* __restrict__ tk = rowkeys + pr.tkrow0;
+        auto stage = [&](int c0, int buf) {
+            stage_dma<NW>(tc, tk, pr.nt, c0 * kMatchTileRows, min(kChunkTiles, te - c0), zc, zk, s_codes[buf], s_key[buf],
+                          w, lane);
+        };
         i32x4 bq[QBW][4];
         int qn[QBW];
         load_queries<QBW>(codes + (size_t)pr.qrow0 * 128, rowkeys + pr.qkrow0, pr.nq, q0w, col, h, bq, qn);
         Best best[QBW];
 #pragma unroll
         for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
-        if (tb < te)
-            stage_dma<NW>(tc, tk, pr.nt, tb * kMatchTileRows, min(kChunkTiles, te - tb), zc, zk, s_codes[0], s_key[0],
-                          w, lane);
+        if (tb < te) stage(tb, 0);
         int buf = 0;
         for (int c0 = tb; c0 < te; c0 += kChunkTiles, buf ^= 1) {
             // LDS-DMA writes are counted by vmcnt: this wave's copies of the
@@ -658,88 +783,19 @@ __global__ __launch_bounds__(64 * NW, (kMatchBatchWgPerCu * NW) / 4) void k_matc
             // wave is done with the other buffer.
             __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            const int c1 = c0 + kChunkTiles;
-            if (c1 < te)
-                stage_dma<NW>(tc, tk, pr.nt, c1 * kMatchTileRows, min(kChunkTiles, te - c1), zc, zk, s_codes[buf ^ 1],
-                              s_key[buf ^ 1], w, lane);
-            chunk_top2(s_codes[buf], s_key[buf], min(kChunkTiles, te - c0), c0 * kMatchTileRows, col, h, bq, best);
+            if (c0 + kChunkTiles < te) stage(c0 + kChunkTiles, buf ^ 1);
+            chunk_top2(s_codes[buf], s_key[buf], nullptr, nullptr, min(kChunkTiles, te - c0), c0 * kMatchTileRows, col, h,
+                       bq, NoGate{}, best);
         }
 #pragma unroll
         for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
     } else {
         // ---- general path: fp16 values that are not integers 0..255 ----
 #pragma unroll
-        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, q0w + 32 * qb, tb, te, col, h);
+        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, NoGate{}, q0w + 32 * qb, tb, te, col, h);
     }
-    __syncthreads();  // s_res aliases the code tiles
-    if (h == 0) {
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) s_res[32 * QBW * w + 32 * qb + col] = res[qb];
-    }
-    __syncthreads();
-    const int q = q0 + tid;
-    const bool qv = tid < QB && q < pr.nq;  // (64 NW threads >= QB queries)
-    const size_t o = (size_t)pr.out_off + q;
-    if (S == 1) {
-        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);
-        return;
-    }
-    merge_contribution(s_res, &s_last, keys + 2 * ((size_t)p * nq_stride + q0), done + (size_t)p * gridDim.x + blockIdx.x,
-                       1u, (unsigned)S, qv, o, ratio, ratio_on_squared, idx2, d2out, match);
-}
-
-// ---------------------------------------------------------------------------
-// k_match_direct: one pair of detector-produced descriptor sets, read through
-// their sidecars (int8 codes + key bias, written by the descriptor kernels:
-// no conversion, no prep launch).  The integer path of k_match_batch with the
-// codes and keys addressed directly: query operands from the query sidecar,
-// the split's train key groups streamed through two LDS chunks by LDS-DMA.
-// grid = (query blocks of 32 QBW NW, splits S of whole key groups).
-// ---------------------------------------------------------------------------
-template <int NW, int QBW>
-__global__ __launch_bounds__(64 * NW) void k_match_direct(
-    MatchPair pr, const int8_t* __restrict__ qc, const int* __restrict__ qk, const int8_t* __restrict__ tc,
-    const int* __restrict__ tk, const int8_t* __restrict__ zc, const int* __restrict__ zk, int S,
-    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
-    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
-    constexpr int QB = 32 * QBW * NW;
-    static_assert(QB <= 64 * NW, "the write-out gives each thread one query: at most 2 query blocks per wave");
-    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
-    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
-    __shared__ unsigned s_last;
-    static_assert(sizeof(Top2) * QB <= sizeof(s_codes), "results alias the code tiles");
+    const MatchOut out{ratio, ratio_on_squared, idx2, d2out, match};
     Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
-    const int q0 = blockIdx.x * QB;
-    if (q0 >= pr.nq) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
-    const int ntiles = (pr.nt + kMatchTileRows - 1) / kMatchTileRows;
-    const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;  // whole key groups
-    const int tb = min(ntiles, (int)blockIdx.y * tps), te = min(ntiles, tb + tps);
-    const int q0w = q0 + 32 * QBW * w;
-    Top2 res[QBW];
-    {
-        if (tb < te)  // the first chunk's DMA before the query loads: both round trips overlap
-            stage_dma<NW>(tc, tk, pr.nt, tb * kMatchTileRows, min(kChunkTiles, te - tb), zc, zk, s_codes[0], s_key[0],
-                          w, lane);
-        i32x4 bq[QBW][4];
-        int qn[QBW];
-        load_queries<QBW>(qc, qk, pr.nq, q0w, col, h, bq, qn);
-        Best best[QBW];
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
-        int buf = 0;
-        for (int c0 = tb; c0 < te; c0 += kChunkTiles, buf ^= 1) {
-            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            const int c1 = c0 + kChunkTiles;
-            if (c1 < te)
-                stage_dma<NW>(tc, tk, pr.nt, c1 * kMatchTileRows, min(kChunkTiles, te - c1), zc, zk, s_codes[buf ^ 1],
-                              s_key[buf ^ 1], w, lane);
-            chunk_top2(s_codes[buf], s_key[buf], min(kChunkTiles, te - c0), c0 * kMatchTileRows, col, h, bq, best);
-        }
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
-    }
     __syncthreads();  // s_res aliases the code tiles
     if (h == 0) {
 #pragma unroll
@@ -750,11 +806,127 @@ __global__ __launch_bounds__(64 * NW) void k_match_direct(
     const bool qv = tid < QB && q < pr.nq;
     const size_t o = (size_t)pr.out_off + q;
     if (S == 1) {
-        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);
+        if (qv) write_top2(s_res[tid], o, out);
         return;
     }
-    merge_contribution(s_res, &s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, ratio,
-                       ratio_on_squared, idx2, d2out, match);
+    merge_contribution(s_res, &s_last, keys + 2 * ((size_t)p * nq_stride + q0), done + (size_t)p * gridDim.x + blockIdx.x,
+                       1u, (unsigned)S, qv, o, out);
+}
+
+// ---------------------------------------------------------------------------
+// match_pair: the body of the two kernels on one pair of ready code sets,
+// k_match_direct (Gate = NoGate) and k_match_guided (Gate = MatchGate).  The
+// integer path of k_match_batch with the codes and keys addressed directly:
+// query operands from the query set, the split's train key groups streamed
+// through the two LDS chunks by LDS-DMA -- under a gate with the train
+// positions beside the keys and the queries' positions in registers.  A
+// flagged set (flags != nullptr: the matcher's prepared sets) sends the pair
+// down the fp16 path; with flags == nullptr that branch folds away.
+// ---------------------------------------------------------------------------
+template <int NW, int QBW, class Gate>
+__device__ __forceinline__ void match_pair(int8_t (&s_codes)[2][kChunkTiles * kTileBytes], int (&s_key)[2][kChunkRows],
+                                           float (*s_px)[kChunkRows], float (*s_py)[kChunkRows], unsigned* s_last,
+                                           const MatchPair& pr, const Gate& g, const CodeSet& qs, const CodeSet& ts,
+                                           const CodeSet& zero, const unsigned* flags, unsigned epoch, int S,
+                                           unsigned long long* keys, unsigned* done, const MatchOut& out) {
+    constexpr int QB = block_queries<NW, QBW>();
+    const int q0 = blockIdx.x * QB;
+    if (q0 >= pr.nq) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+    const GroupSplit split(match_tiles(pr.nt), S);
+    const int tb = split.begin(blockIdx.y), te = split.end(blockIdx.y);
+    const int q0w = q0 + 32 * QBW * w;
+    Top2 res[QBW];
+    if (!flags || (flags[pr.qset] != epoch && flags[pr.tset] != epoch)) {
+        // ---- integer path ----
+        auto stage = [&](int c0, int buf) {
+            const int nc = min(kChunkTiles, te - c0);
+            stage_dma<NW>(ts.codes, ts.keys, pr.nt, c0 * kMatchTileRows, nc, zero.codes, zero.keys, s_codes[buf],
+                          s_key[buf], w, lane);
+            if constexpr (kGated<Gate>)
+                stage_pos_dma<NW>(g.txy, g.tstride, pr.nt, c0 * kMatchTileRows, nc, s_px[buf], s_py[buf], w, lane);
+        };
+        if (tb < te) stage(tb, 0);  // the first chunk's DMA before the query loads: both round trips overlap
+        i32x4 bq[QBW][4];
+        int qn[QBW];
+        load_queries<QBW>(qs.codes, qs.keys, pr.nq, q0w, col, h, bq, qn);
+        const auto lg = lane_gate<QBW>(g, pr.nq, q0w, col);
+        Best best[QBW];
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
+        int buf = 0;
+        for (int c0 = tb; c0 < te; c0 += kChunkTiles, buf ^= 1) {
+            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // as in k_match_batch
+            __syncthreads();
+            if (c0 + kChunkTiles < te) stage(c0 + kChunkTiles, buf ^ 1);
+            const float *sx = nullptr, *sy = nullptr;
+            if constexpr (kGated<Gate>) sx = s_px[buf], sy = s_py[buf];
+            chunk_top2(s_codes[buf], s_key[buf], sx, sy, min(kChunkTiles, te - c0), c0 * kMatchTileRows, col, h, bq, lg,
+                       best);
+        }
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
+    } else {
+        // ---- general path: fp16 values that are not integers 0..255 ----
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, g, q0w + 32 * qb, tb, te, col, h);
+    }
+    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
+    __syncthreads();  // s_res aliases the code tiles
+    if (h == 0) {
+#pragma unroll
+        for (int qb = 0; qb < QBW; qb++) s_res[32 * QBW * w + 32 * qb + col] = res[qb];
+    }
+    __syncthreads();
+    const int q = q0 + tid;
+    const bool qv = tid < QB && q < pr.nq;
+    const size_t o = (size_t)pr.out_off + q;
+    if (S == 1) {
+        if (qv) write_top2(s_res[tid], o, out);
+        return;
+    }
+    merge_contribution(s_res, s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, out);
+}
+
+// k_match_direct: one pair of detector-produced descriptor sets, read through
+// their sidecars (int8 codes + key bias, written by the descriptor kernels:
+// no conversion, no prep launch).  No gate, no flags, no position planes.
+// grid = (query blocks of 32 QBW NW, splits S of whole key groups).
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW) void k_match_direct(
+    MatchPair pr, const int8_t* __restrict__ qc, const int* __restrict__ qk, const int8_t* __restrict__ tc,
+    const int* __restrict__ tk, const int8_t* __restrict__ zc, const int* __restrict__ zk, int S,
+    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
+    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ unsigned s_last;
+    match_pair<NW, QBW>(s_codes, s_key, nullptr, nullptr, &s_last, pr, NoGate{}, CodeSet{qc, qk},
+                        CodeSet{tc, tk}, CodeSet{zc, zk}, nullptr, 0u, S, keys, done,
+                        MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
+}
+
+// k_match_guided: one pair of ready code sets (sidecars, or the matcher's
+// prepared codes) under a gate.  match_pair with the train positions of each
+// chunk staged beside its keys (two float planes of kChunkRows per buffer:
+// 70 KiB of LDS per workgroup, still two per CU) and the gated cores; a pair
+// with a flagged set takes the gated fp16 path.
+// grid = (query blocks of 32 QBW NW, splits S of whole key groups).
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_guided(  // registers for two workgroups per CU
+    MatchPair pr, MatchGate g, const int8_t* __restrict__ qc, const int* __restrict__ qk,
+    const int8_t* __restrict__ tc, const int* __restrict__ tk, const int8_t* __restrict__ zc,
+    const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch, int S,
+    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
+    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ unsigned s_last;
+    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, &s_last, pr, g, CodeSet{qc, qk}, CodeSet{tc, tk},
+                        CodeSet{zc, zk}, flags, epoch, S, keys, done,
+                        MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
 }
 
 // Direct single pairs: 8 waves x 1 query block (256 queries per workgroup),
@@ -766,273 +938,31 @@ __global__ __launch_bounds__(64 * NW) void k_match_direct(
 constexpr int kDirectNW = 8, kDirectQBW = 1, kDirectQB = 32 * kDirectNW * kDirectQBW, kDirectWgTarget = 256;
 
 int match_direct_splits(int nq, int nt) {
-    const int ntiles = (nt + kMatchTileRows - 1) / kMatchTileRows, groups = (ntiles + kGroupTiles - 1) / kGroupTiles;
+    const int ntiles = match_tiles(nt), groups = (ntiles + kGroupTiles - 1) / kGroupTiles;
     const int qblocks = (max(nq, 1) + kDirectQB - 1) / kDirectQB;
-    int S = max(1, min(groups, kDirectWgTarget / max(qblocks, 1)));
-    const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;
-    return tps > 0 ? max(1, (ntiles + tps - 1) / tps) : 1;
+    return GroupSplit(ntiles, max(1, min(groups, kDirectWgTarget / max(qblocks, 1)))).count();
 }
 
-void launch_match_direct(const MatchPair& pr, const int8_t* qc, const int* qk, const int8_t* tc, const int* tk,
-                         const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
-                         int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s) {
+// The gated kernel takes the direct kernel's shape: the gate adds VALU work
+// per key, not traffic, so the split that balances the one balances the other.
+void launch_match_pair(const MatchPair& pr, const MatchGate* gate, const CodeSet& q, const CodeSet& t,
+                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
     const int S = match_direct_splits(pr.nq, pr.nt);
-    dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1);
-    hipLaunchKernelGGL((k_match_direct<kDirectNW, kDirectQBW>), g, dim3(64 * kDirectNW), 0, s, pr, qc, qk, tc, tk, zc,
-                       zk, S, keys, done, ratio, ratio_on_squared, idx2, d2, match);
+    const dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1), b(64 * kDirectNW);
+    if (gate)
+        hipLaunchKernelGGL((k_match_guided<kDirectNW, kDirectQBW>), g, b, 0, s, pr, *gate, q.codes, q.keys, t.codes,
+                           t.keys, sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, S, sc.keys, sc.done, out.ratio,
+                           out.ratio_on_squared, out.idx2, out.d2, out.match);
+    else
+        hipLaunchKernelGGL((k_match_direct<kDirectNW, kDirectQBW>), g, b, 0, s, pr, q.codes, q.keys, t.codes, t.keys,
+                           sc.zero.codes, sc.zero.keys, S, sc.keys, sc.done, out.ratio, out.ratio_on_squared, out.idx2,
+                           out.d2, out.match);
 }
 
-// ---------------------------------------------------------------------------
-// Guided matching (k_match_guided): the top-2 of a query over the train rows
-// inside its search window -- train row t is a candidate of query i when
-// fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius (float32, one
-// subtraction per axis, inclusive; a NaN coordinate is a candidate of nothing).
-// The distance matrix still lives in the accumulator only: the gate is a
-// per-key predicate in the top-2 fold.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool in_gate(float tx, float ty, float qx, float qy, float radius) {
-    return __builtin_fabsf(tx - qx) <= radius && __builtin_fabsf(ty - qy) <= radius;
-}
-
-// The positions of train rows [row0, row0 + 32 nc) into the chunk's two float
-// planes by 4-byte LDS-DMA, 64 rows per instruction as the keys.  Rows past nt
-// read row nt - 1 (their padding key loses whatever the gate says): nothing
-// past the caller's nt rows is touched.
-template <int NW>
-__device__ __forceinline__ void stage_pos_dma(const float* __restrict__ txy, int tstride, int nt, int row0, int nc,
-                                              float* sx, float* sy, int w, int lane) {
-    const int wv = __builtin_amdgcn_readfirstlane(w);
-    for (int b = wv; b < (nc * kMatchTileRows + 63) / 64; b += NW) {
-        const float* src = txy + (size_t)min(row0 + 64 * b + lane, nt - 1) * tstride;
-        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(sx + 64 * b), 4, 0,
-                                         0);
-        __builtin_amdgcn_global_load_lds((const void*)(src + 1), (__attribute__((address_space(3))) void*)(sy + 64 * b),
-                                         4, 0, 0);
-    }
-}
-
-// chunk_top2 under a gate: the key of a (query, row) outside the window becomes
-// INT_MIN before the fold -- below kInvalidKey, so fold_group reads it as
-// "none".  The positions are read as the keys are (the same address across the
-// lanes of a half: broadcast reads); a lane holds its queries' (qx, qy).
-template <int QBW>
-__device__ __forceinline__ void chunk_top2_gated(const int8_t* sc, const int* sk, const float* sx, const float* sy,
-                                                 int nc, int t0, int col, int h, const i32x4 (&bq)[QBW][4],
-                                                 const float (&qx)[QBW], const float (&qy)[QBW], float radius,
-                                                 Best (&best)[QBW]) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    int m1e[QBW], m2e[QBW], m1o[QBW], m2o[QBW];  // registers 0-7 / 8-15
-#pragma unroll
-    for (int qb = 0; qb < QBW; qb++) m1e[qb] = m2e[qb] = m1o[qb] = m2o[qb] = INT_MIN;
-    const int sw = (col >> 1) & 7;
-    const int8_t* const ta0 = sc + col * 128;
-    const int* const tk1 = sk + 4 * h;
-    const float* const tx1 = sx + 4 * h;
-    const float* const ty1 = sy + 4 * h;
-#pragma unroll
-    for (int j = 0; j < kChunkTiles; j++) {
-        if (j < nc) {
-            i32x4 a[4], tk[4];
-            f32x4 px[4], py[4];
-#pragma unroll
-            for (int kb = 0; kb < 4; kb++)
-                a[kb] = *reinterpret_cast<const i32x4*>(ta0 + j * kTileBytes + 16 * ((4 * h + kb) ^ sw));
-            // accumulator register i holds train row (i & 3) + 8 (i >> 2) + 4 h
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                tk[g] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * g);
-                px[g] = *reinterpret_cast<const f32x4*>(tx1 + j * kMatchTileRows + 8 * g);
-                py[g] = *reinterpret_cast<const f32x4*>(ty1 + j * kMatchTileRows + 8 * g);
-            }
-            i32x16 acc[QBW] = {};
-#pragma unroll
-            for (int qb = 0; qb < QBW; qb++)
-#pragma unroll
-                for (int kb = 0; kb < 4; kb++)
-                    acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kb], bq[qb][kb], acc[qb], 0, 0, 0);
-#pragma unroll
-            for (int qb = 0; qb < QBW; qb++) {
-                auto key = [&](int i) {
-                    const int k = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
-                    return in_gate(px[i >> 2][i & 3], py[i >> 2][i & 3], qx[qb], qy[qb], radius) ? k : INT_MIN;
-                };
-#pragma unroll
-                for (int i = 0; i < 8; i += 2) {
-                    const int x0 = key(i), y0 = key(i + 1), x1 = key(i + 8), y1 = key(i + 9);
-                    m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
-                    m1e[qb] = max3_i32(m1e[qb], x0, y0);
-                    m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
-                    m1o[qb] = max3_i32(m1o[qb], x1, y1);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int qb = 0; qb < QBW; qb++) {
-        const int a1 = m1e[qb], a2 = m2e[qb], b1 = m1o[qb], b2 = m2o[qb];
-        best[qb] = fold_group(best[qb], max(a1, b1), max(min(a1, b1), max(a2, b2)), t0);
-    }
-}
-
-// match_f16_block under a gate (sets with fp16 values that are not integers
-// 0..255): the insert also requires the row to lie in the query's window.
-// Lane col carries the position of train row t0 + col, as it carries its norm.
-__device__ Top2 match_f16_block_gated(const MatchPair& pr, const MatchGate& g, int q0, int tbeg, int tend, int col,
-                                      int h) {
-    const int qrow = q0 + col;
-    const bool qvalid = qrow < pr.nq;
-    half8 bq[8];
-#pragma unroll
-    for (int s = 0; s < 8; s++) bq[s] = qvalid ? load_frag(pr.q + (size_t)qrow * 128, 16 * s + 8 * h) : half8{};
-    const float qx = qvalid ? g.qxy[(size_t)qrow * g.qstride] : NAN;
-    const float qy = qvalid ? g.qxy[(size_t)qrow * g.qstride + 1] : NAN;
-    float qn = sumsq8(bq);
-    qn += __shfl_xor(qn, 32);
-    Top2 best{INFINITY, INFINITY, kNone, kNone};
-    for (int tile = tbeg; tile < tend; tile++) {
-        const int t0 = tile * kMatchTileRows, trow = t0 + col;
-        const bool tvalid = trow < pr.nt;
-        half8 a[8];
-#pragma unroll
-        for (int s = 0; s < 8; s++) a[s] = tvalid ? load_frag(pr.t + (size_t)trow * 128, 16 * s + 8 * h) : half8{};
-        const float tx = tvalid ? g.txy[(size_t)trow * g.tstride] : NAN;
-        const float ty = tvalid ? g.txy[(size_t)trow * g.tstride + 1] : NAN;
-        float tn = sumsq8(a);
-        tn += __shfl_xor(tn, 32);
-        f32x16 acc = {}, acc2 = {};
-#pragma unroll
-        for (int s = 0; s < 8; s += 2) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s], bq[s], acc, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s + 1], bq[s + 1], acc2, 0, 0, 0);
-        }
-        acc += acc2;
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const float d = __shfl(tn, row) - 2.f * acc[i];
-            const bool cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
-            if (t0 + row < pr.nt && cand && d < best.d2) {
-                if (d < best.d1) {
-                    best.d2 = best.d1;
-                    best.i2 = best.i1;
-                    best.d1 = d;
-                    best.i1 = t0 + row;
-                } else {
-                    best.d2 = d;
-                    best.i2 = t0 + row;
-                }
-            }
-        }
-    }
-    best = merge_top2(best, shfl_top2(best, 32));
-    best.d1 += qn;
-    best.d2 += qn;
-    return best;
-}
-
-// k_match_guided: one pair of ready code sets (sidecars, or the matcher's
-// prepared codes) under a gate.  k_match_direct with the train positions of
-// each chunk staged beside its keys (two float planes of kChunkRows per buffer:
-// 70 KiB of LDS per workgroup, still two per CU) and the gated fold; a pair
-// with a flagged set takes the gated fp16 path.
-// grid = (query blocks of 32 QBW NW, splits S of whole key groups).
-template <int NW, int QBW>
-__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_guided(  // registers for two workgroups per CU
-    MatchPair pr, MatchGate g, const int8_t* __restrict__ qc, const int* __restrict__ qk,
-    const int8_t* __restrict__ tc, const int* __restrict__ tk, const int8_t* __restrict__ zc,
-    const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch, int S,
-    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
-    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
-    constexpr int QB = 32 * QBW * NW;
-    static_assert(QB <= 64 * NW, "the write-out gives each thread one query: at most 2 query blocks per wave");
-    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
-    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
-    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
-    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
-    __shared__ unsigned s_last;
-    static_assert(sizeof(Top2) * QB <= sizeof(s_codes), "results alias the code tiles");
-    Top2* const s_res = reinterpret_cast<Top2*>(&s_codes[0][0]);
-    const int q0 = blockIdx.x * QB;
-    if (q0 >= pr.nq) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
-    const int ntiles = (pr.nt + kMatchTileRows - 1) / kMatchTileRows;
-    const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;  // whole key groups
-    const int tb = min(ntiles, (int)blockIdx.y * tps), te = min(ntiles, tb + tps);
-    const int q0w = q0 + 32 * QBW * w;
-    Top2 res[QBW];
-    if (!flags || (flags[pr.qset] != epoch && flags[pr.tset] != epoch)) {
-        // ---- integer path ----
-        auto stage = [&](int c0, int buf) {
-            const int nc = min(kChunkTiles, te - c0);
-            stage_dma<NW>(tc, tk, pr.nt, c0 * kMatchTileRows, nc, zc, zk, s_codes[buf], s_key[buf], w, lane);
-            stage_pos_dma<NW>(g.txy, g.tstride, pr.nt, c0 * kMatchTileRows, nc, s_px[buf], s_py[buf], w, lane);
-        };
-        if (tb < te) stage(tb, 0);  // the first chunk's DMA before the query loads: both round trips overlap
-        i32x4 bq[QBW][4];
-        int qn[QBW];
-        load_queries<QBW>(qc, qk, pr.nq, q0w, col, h, bq, qn);
-        float qx[QBW], qy[QBW];
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) {
-            const float* p = g.qxy + (size_t)min(q0w + 32 * qb + col, pr.nq - 1) * g.qstride;
-            qx[qb] = p[0];
-            qy[qb] = p[1];
-        }
-        Best best[QBW];
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
-        int buf = 0;
-        for (int c0 = tb; c0 < te; c0 += kChunkTiles, buf ^= 1) {
-            // this wave's copies of the chunk have landed (LDS-DMA writes are counted by vmcnt); the barrier
-            // publishes every wave's, and every wave is done with the other buffer
-            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (c0 + kChunkTiles < te) stage(c0 + kChunkTiles, buf ^ 1);
-            chunk_top2_gated(s_codes[buf], s_key[buf], s_px[buf], s_py[buf], min(kChunkTiles, te - c0),
-                             c0 * kMatchTileRows, col, h, bq, qx, qy, g.radius, best);
-        }
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) res[qb] = finish_best(best[qb], qn[qb]);
-    } else {
-        // ---- general path: fp16 values that are not integers 0..255 ----
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block_gated(pr, g, q0w + 32 * qb, tb, te, col, h);
-    }
-    __syncthreads();  // s_res aliases the code tiles
-    if (h == 0) {
-#pragma unroll
-        for (int qb = 0; qb < QBW; qb++) s_res[32 * QBW * w + 32 * qb + col] = res[qb];
-    }
-    __syncthreads();
-    const int q = q0 + tid;
-    const bool qv = tid < QB && q < pr.nq;
-    const size_t o = (size_t)pr.out_off + q;
-    if (S == 1) {
-        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);
-        return;
-    }
-    merge_contribution(s_res, &s_last, keys + 2 * (size_t)q0, done + blockIdx.x, 1u, (unsigned)S, qv, o, ratio,
-                       ratio_on_squared, idx2, d2out, match);
-}
-
-void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, unsigned* flags, unsigned epoch,
-                       hipStream_t s) {
+void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, const SetFlags& flags, hipStream_t s) {
     if (sets.maxn > 0)
         hipLaunchKernelGGL(k_match_prep, dim3((sets.maxn + 31) / 32, sets.nsets), dim3(256), 0, s, sets, codes, rowkeys,
-                           flags, epoch);
-}
-
-// The direct kernel's shape (8 waves x 1 query block, one key group per split
-// up to kDirectWgTarget workgroups): the gate adds VALU work per key, not
-// traffic, so the split that balances the ungated kernel balances this one.
-void launch_match_guided(const MatchPair& pr, const MatchGate& gate, const int8_t* qc, const int* qk, const int8_t* tc,
-                         const int* tk, const int8_t* zc, const int* zk, const unsigned* flags, unsigned epoch,
-                         unsigned long long* keys, unsigned* done, float ratio, int ratio_on_squared, int* idx2,
-                         float* d2, int* match, hipStream_t s) {
-    const int S = match_direct_splits(pr.nq, pr.nt);
-    dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1);
-    hipLaunchKernelGGL((k_match_guided<kDirectNW, kDirectQBW>), g, dim3(64 * kDirectNW), 0, s, pr, gate, qc, qk, tc, tk,
-                       zc, zk, flags, epoch, S, keys, done, ratio, ratio_on_squared, idx2, d2, match);
+                           flags.flags, flags.epoch);
 }
 
 // Single pairs of foreign buffers (k_match_single): workgroups a launch aims
@@ -1064,7 +994,7 @@ static int device_cus() {
 
 MatchPlan match_plan(int max_nq, int max_nt, int P) {
     MatchPlan pl;
-    const int ntiles = (max_nt + kMatchTileRows - 1) / kMatchTileRows;
+    const int ntiles = match_tiles(max_nt);
     if (P == 1) {
         pl.nw = kMatchNWSingle;
         const int qblocks = (max_nq + kMatchSingleQB - 1) / kMatchSingleQB;
@@ -1095,12 +1025,11 @@ MatchPlan match_plan(int max_nq, int max_nt, int P) {
         int best = 1;
         long best_cost = -1;
         for (int S = 1; S <= groups; S++) {
-            const int tps = ((ntiles + S - 1) / S + kGroupTiles - 1) / kGroupTiles * kGroupTiles;
-            const int s_eff = (ntiles + tps - 1) / tps;
-            if (s_eff != S) continue;  // same split sizes as a smaller S
+            const GroupSplit split(ntiles, S);
+            if (split.count() != S) continue;  // same split sizes as a smaller S
             const long wgs = (long)units * S;
             if (S > 1 && wgs > (long)kMatchBatchWgPerCu * cus) break;  // one round only
-            const long cost = (wgs + cus - 1) / cus * tps + (S > 1 ? kMergeTiles : 0);
+            const long cost = (wgs + cus - 1) / cus * split.tps + (S > 1 ? kMergeTiles : 0);
             if (best_cost < 0 || cost < best_cost) {
                 best_cost = cost;
                 best = S;
@@ -1111,36 +1040,20 @@ MatchPlan match_plan(int max_nq, int max_nt, int P) {
     return pl;
 }
 
-void launch_match(const MatchSets& sets, MatchBatch& batch, const MatchPlan& plan, int nq_stride, int8_t* codes,
-                  int* rowkeys, int sentinel, unsigned* flags, unsigned epoch, unsigned long long* keys,
-                  unsigned* done, float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s) {
-    if (batch.P == 1) {
-        const MatchPair& pr = batch.pair[0];
-        dim3 g((max(pr.nq, 1) + kMatchSingleQB - 1) / kMatchSingleQB, plan.S, 1);
-        hipLaunchKernelGGL((k_match_single<kMatchNWSingle, kMatchQBWSingle>), g, dim3(64 * kMatchNWSingle),
-                           0, s, pr, plan.S, keys, done, ratio, ratio_on_squared, idx2, d2, match);
-        return;
-    }
-    if (sets.maxn > 0)
-        hipLaunchKernelGGL(k_match_prep, dim3((sets.maxn + 31) / 32, sets.nsets), dim3(256), 0, s, sets, codes, rowkeys,
-                           flags, epoch);
-    int max_nq = 1;
-    for (int p = 0; p < batch.P; p++) max_nq = max(max_nq, batch.pair[p].nq);
-    dim3 g((max_nq + kMatchBatchQB - 1) / kMatchBatchQB, plan.S, batch.P);
-    hipLaunchKernelGGL((k_match_batch<kMatchBatchNW, kMatchBatchQBW>), g, dim3(64 * kMatchBatchNW), 0, s, batch, plan.S, nq_stride, codes,
-                       rowkeys, codes + (size_t)sentinel * 128, rowkeys + sentinel, flags, epoch, keys, done, ratio,
-                       ratio_on_squared, idx2, d2, match);
+void launch_match_single(const MatchPair& pr, int S, const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
+    const dim3 g((max(pr.nq, 1) + kMatchSingleQB - 1) / kMatchSingleQB, S, 1);
+    hipLaunchKernelGGL((k_match_single<kMatchNWSingle, kMatchQBWSingle>), g, dim3(64 * kMatchNWSingle), 0, s, pr, S,
+                       sc.keys, sc.done, out.ratio, out.ratio_on_squared, out.idx2, out.d2, out.match);
 }
 
-void launch_match_codes(MatchBatch& batch, const MatchPlan& plan, int nq_stride, const int8_t* codes, const int* rowkeys,
-                        const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
-                        int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s) {
+void launch_match_codes(const MatchBatch& batch, int S, const CodeSet& set, const SetFlags& flags,
+                        const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
     int max_nq = 1;
     for (int p = 0; p < batch.P; p++) max_nq = max(max_nq, batch.pair[p].nq);
-    dim3 g((max_nq + kMatchBatchQB - 1) / kMatchBatchQB, plan.S, batch.P);
-    hipLaunchKernelGGL((k_match_batch<kMatchBatchNW, kMatchBatchQBW>), g, dim3(64 * kMatchBatchNW), 0, s, batch, plan.S,
-                       nq_stride, codes, rowkeys, zc, zk, (const unsigned*)nullptr, 0u, keys, done, ratio, ratio_on_squared,
-                       idx2, d2, match);
+    const dim3 g((max_nq + kMatchBatchQB - 1) / kMatchBatchQB, S, batch.P);
+    hipLaunchKernelGGL((k_match_batch<kMatchBatchNW, kMatchBatchQBW>), g, dim3(64 * kMatchBatchNW), 0, s, batch, S,
+                       sc.nq_stride, set.codes, set.keys, sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, sc.keys,
+                       sc.done, out.ratio, out.ratio_on_squared, out.idx2, out.d2, out.match);
 }
 
 // ---------------------------------------------------------------------------

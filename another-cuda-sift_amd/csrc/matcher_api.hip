@@ -103,7 +103,19 @@ struct sift_hip_matcher {
                         (void*)dSelIdx, (void*)dSelD, (void*)dList, (void*)dCount})
             if (p) (void)hipFree(p);
     }
+    // The sentinel row (row codeRows of dCodes / dRowKeys): zero codes with the padding key, written at creation.
+    CodeSet sentinel() const { return CodeSet{dCodes + (size_t)codeRows * 128, dRowKeys + codeRows}; }
+    MatchScratch scratch() const { return MatchScratch{dKeys, dDone, maxQ, sentinel()}; }
+    // The prepared sets of a call get a new epoch: flags from earlier calls never equal it.
+    SetFlags next_epoch() {
+        epoch = epoch + 1 == 0 ? 1 : epoch + 1;
+        return SetFlags{dFlags, epoch};
+    }
 };
+
+namespace {
+const SetFlags kNoFlags{nullptr, 0u};  // ready code sets: integers by construction
+}
 
 extern "C" {
 
@@ -130,8 +142,8 @@ int sift_hip_matcher_create(int device, int max_query, int max_train, int max_pa
         hipMalloc((void**)&m->dMatch, sizeof(int) * (size_t)max_pairs * max_query) != hipSuccess ||
         hipMalloc((void**)&m->dCodes, (size_t)(m->codeRows + 1) * 128) != hipSuccess ||
         hipMalloc((void**)&m->dRowKeys, sizeof(int) * (size_t)(m->codeRows + 1)) != hipSuccess ||
-        hipMemset(m->dCodes + (size_t)m->codeRows * 128, 0, 128) != hipSuccess ||
-        hipMemcpy(m->dRowKeys + m->codeRows, &kMatchPadKey, sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset((void*)m->sentinel().codes, 0, 128) != hipSuccess ||
+        hipMemcpy((void*)m->sentinel().keys, &kMatchPadKey, sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
         hipMalloc((void**)&m->dFlags, sizeof(unsigned) * 2 * kMaxMatchPairs) != hipSuccess ||
         hipMemset(m->dKeys, 0xff, sizeof(unsigned long long) * nkeys) != hipSuccess ||
         hipMemset(m->dDone, 0, sizeof(unsigned) * nblk) != hipSuccess ||
@@ -159,15 +171,15 @@ int sift_hip_match_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q
                            const uint16_t* const* t, const int* nt, float ratio, int ratio_on_squared, int* idx2,
                            float* d2, int* match, void* stream) {
     if (!m || P <= 0 || P > m->maxP || !q || !nq || !t || !nt) return fail(SIFT_HIP_ERR_INVALID, "bad batch");
+    const MatchOut out{ratio, ratio_on_squared, idx2, d2, match};
     Sidecar sq{}, st{};
     if (P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && nq[0] <= m->maxQ && nt[0] <= m->maxT &&
         find_sidecar(q[0], nq[0], &sq) && find_sidecar(t[0], nt[0], &st)) {
         // Both sets are detector buffers: their codes are ready (no conversion).
         HIPCHK(hipSetDevice(m->device));
         const MatchPair pr{q[0], t[0], nq[0], nt[0], 0, 0, 0, 0, 0, 0, 0};
-        launch_match_direct(pr, sq.codes, sq.keys, st.codes, st.keys, m->dCodes + (size_t)m->codeRows * 128,
-                            m->dRowKeys + m->codeRows, m->dKeys, m->dDone, ratio, ratio_on_squared, idx2, d2, match,
-                            (hipStream_t)stream);
+        launch_match_pair(pr, nullptr, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags, m->scratch(), out,
+                          (hipStream_t)stream);
         HIPCHK(hipGetLastError());
         return SIFT_HIP_OK;
     }
@@ -206,11 +218,16 @@ int sift_hip_match_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q
         b.pair[p].qrow0 = b.pair[p].qkrow0 = sets.set[b.pair[p].qset].row0;
         b.pair[p].trow0 = b.pair[p].tkrow0 = sets.set[b.pair[p].tset].row0;
     }
-    m->epoch = m->epoch + 1 == 0 ? 1 : m->epoch + 1;  // flags from earlier calls never equal it
+    const SetFlags flags = m->next_epoch();
     HIPCHK(hipSetDevice(m->device));
-    const MatchPlan plan = match_plan(maxq, maxt, P);
-    launch_match(sets, b, plan, m->maxQ, m->dCodes, m->dRowKeys, (int)m->codeRows, m->dFlags, m->epoch, m->dKeys, m->dDone, ratio,
-                 ratio_on_squared, idx2, d2, match, (hipStream_t)stream);
+    const int S = match_plan(maxq, maxt, P).S;
+    if (P == 1) {
+        // One pair of foreign buffers: the fused kernel converts as it goes (no prep launch).
+        launch_match_single(b.pair[0], S, m->scratch(), out, (hipStream_t)stream);
+    } else {
+        launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, (hipStream_t)stream);
+        launch_match_codes(b, S, CodeSet{m->dCodes, m->dRowKeys}, flags, m->scratch(), out, (hipStream_t)stream);
+    }
     HIPCHK(hipGetLastError());
     return SIFT_HIP_OK;
 }
@@ -234,9 +251,9 @@ int sift_hip_match_codes_batched(sift_hip_matcher_t m, const int8_t* codes, cons
         maxt = std::max(maxt, nt[p]);
     }
     HIPCHK(hipSetDevice(m->device));
-    const MatchPlan plan = match_plan(maxq, maxt, std::max(P, 2));  // the batched kernel's plan, also for one pair
-    launch_match_codes(b, plan, m->maxQ, codes, keys, m->dCodes + (size_t)m->codeRows * 128, m->dRowKeys + m->codeRows,
-                       m->dKeys, m->dDone, ratio, ratio_on_squared, idx2, d2, match, (hipStream_t)stream);
+    const int S = match_plan(maxq, maxt, std::max(P, 2)).S;  // the batched kernel's plan, also for one pair
+    launch_match_codes(b, S, CodeSet{codes, keys}, kNoFlags, m->scratch(),
+                       MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SIFT_HIP_OK;
 }
@@ -338,6 +355,14 @@ bool any_pair(int P, const int* nq, const int* nt) {
     for (int p = 0; p < P; p++)
         if (nq[p] > 0 && nt[p] > 0) return true;
     return false;
+}
+
+// The matcher's own list (dList, dCount: one pair) back to the host: the count, then min(count, cap) records.
+int read_list(sift_hip_matcher* m, sift_hip_dmatch* out_host, int cap, int* count) {
+    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
 }
 
 }  // namespace
@@ -445,10 +470,7 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, co
     if (int rc = sift_hip_match_list_device(m, q, nq, t, nt, filter, reinterpret_cast<sift_hip_dmatch*>(m->dList),
                                             m->dCount, nullptr))
         return rc;
-    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min(*count, cap);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
+    return read_list(m, out_host, cap, count);
 }
 
 }  // extern "C"
@@ -478,16 +500,13 @@ int check_guided_args(const sift_hip_matcher* m, const uint16_t* q, int nq, cons
 int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const sift_hip_match_gate& g,
                 float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, int* rev_idx2, float* rev_d2,
                 hipStream_t stream) {
-    const int8_t* const zc = m->dCodes + (size_t)m->codeRows * 128;
-    const int* const zk = m->dRowKeys + m->codeRows;
-    const int8_t *qc, *tc;
-    const int *qk, *tk;
-    const unsigned* flags = nullptr;
+    CodeSet qc, tc;
+    SetFlags flags = kNoFlags;
     int qs = 0, ts = 0;
     Sidecar sq{}, st{};
     HIPCHK(hipSetDevice(m->device));
     if (m->sidecars && nt > 0 && find_sidecar(q, nq, &sq) && find_sidecar(t, nt, &st)) {
-        qc = sq.codes, qk = sq.keys, tc = st.codes, tk = st.keys;
+        qc = CodeSet{sq.codes, sq.keys}, tc = CodeSet{st.codes, st.keys};
     } else {
         MatchSets sets{};
         sets.set[sets.nsets++] = MatchSet{q, nq, 0};
@@ -498,22 +517,22 @@ int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* 
         sets.maxn = std::max(nq, nt);
         if ((long)nq + nt > m->codeRows)
             return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-        m->epoch = m->epoch + 1 == 0 ? 1 : m->epoch + 1;  // flags from earlier calls never equal it
-        launch_match_prep(sets, m->dCodes, m->dRowKeys, m->dFlags, m->epoch, stream);
+        flags = m->next_epoch();
+        launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
         HIPCHK(hipGetLastError());
         const int trow0 = sets.set[ts].row0;
-        qc = m->dCodes, qk = m->dRowKeys, tc = m->dCodes + (size_t)trow0 * 128, tk = m->dRowKeys + trow0;
-        flags = m->dFlags;
+        qc = CodeSet{m->dCodes, m->dRowKeys}, tc = CodeSet{m->dCodes + (size_t)trow0 * 128, m->dRowKeys + trow0};
     }
     const MatchPair fwd{q, t, nq, nt, 0, qs, ts, 0, 0, 0, 0};
-    launch_match_guided(fwd, MatchGate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius}, qc, qk, tc, tk,
-                        zc, zk, flags, m->epoch, m->dKeys, m->dDone, ratio, ratio_on_squared, idx2, d2, match, stream);
+    const MatchGate fgate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius};
+    launch_match_pair(fwd, &fgate, qc, tc, flags, m->scratch(), MatchOut{ratio, ratio_on_squared, idx2, d2, match},
+                      stream);
     HIPCHK(hipGetLastError());
     if (rev_idx2 && nt > 0) {
         // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
         const MatchPair rev{t, q, nt, nq, 0, ts, qs, 0, 0, 0, 0};
-        launch_match_guided(rev, MatchGate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius}, tc, tk, qc,
-                            qk, zc, zk, flags, m->epoch, m->dKeys, m->dDone, 0.f, 0, rev_idx2, rev_d2, nullptr, stream);
+        const MatchGate rgate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius};
+        launch_match_pair(rev, &rgate, tc, qc, flags, m->scratch(), MatchOut{0.f, 0, rev_idx2, rev_d2, nullptr}, stream);
         HIPCHK(hipGetLastError());
     }
     return SIFT_HIP_OK;
@@ -566,10 +585,7 @@ int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int
     if (int rc = sift_hip_match_list_guided_device(m, q, nq, t, nt, gate, filter,
                                                    reinterpret_cast<sift_hip_dmatch*>(m->dList), m->dCount, nullptr))
         return rc;
-    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min(*count, cap);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
+    return read_list(m, out_host, cap, count);
 }
 
 int sift_hip_device_count(int* n) {

@@ -48,40 +48,54 @@ struct MatchPlan {
     int nw, S;
 };
 MatchPlan match_plan(int max_nq, int max_nt, int P);
-// codes / rowkeys: int8 code rows (128 B) and per row the key bias
-// -(256 |code|^2 + (row mod 256)); row `sentinel` of both is a zero code row with
-// the padding key (written once at allocation, never by a call); capacity for the
-// call's sets; flags: one word per set slot, == epoch when that set holds a
-// value that is not an integer 0..255 (matched by the general f16 path).
-// keys: 2 x u64 per (pair, query), all ones between calls; done: a counter per
-// (pair, kMatchQB-query block), zero between calls (the merging workgroup resets both).
-void launch_match(const MatchSets& sets, MatchBatch& batch, const MatchPlan& plan, int nq_stride, int8_t* codes,
-                  int* rowkeys, int sentinel,
-                  unsigned* flags, unsigned epoch, unsigned long long* keys, unsigned* done, float ratio,
-                  int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s);
+int match_direct_splits(int nq, int nt);  // splits of launch_match_pair
 
-// One pair of sets with matcher sidecars (detector-produced descriptor
-// buffers, sift_kernels.h Sidecar): codes qc/tc (128 B rows) and key biases
-// qk/tk; zc/zk the matcher's zero sentinel row and padding key.
-void launch_match_direct(const MatchPair& pr, const int8_t* qc, const int* qk, const int8_t* tc, const int* tk,
-                         const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
-                         int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s);
-int match_direct_splits(int nq, int nt);
-
-// Pairs of ready code sets (e.g. the sidecars of every rank all-gathered: C5):
-// k_match_batch on them with no prep launch and no flags (integers by
-// construction); pair p reads code rows qrow0.. / trow0.. of `codes` and key
-// biases qkrow0.. / tkrow0.. of `rowkeys`.  zc / zk: the zero code row and
-// padding key.
-void launch_match_codes(MatchBatch& batch, const MatchPlan& plan, int nq_stride, const int8_t* codes, const int* rowkeys,
-                        const int8_t* zc, const int* zk, unsigned long long* keys, unsigned* done, float ratio,
-                        int ratio_on_squared, int* idx2, float* d2, int* match, hipStream_t s);
-
-// --- Guided matching (sift_hip_match_guided_*): the top-2 of a query over the
-// train rows inside its search window (the rule is in include/sift_hip.h).
+// --- Launch records.  What travels together through the launchers travels as
+// one record; the launchers unpack them into the kernels' parameter lists.
 //
-// The gate as the kernel takes it (sift_hip_match_gate): row i of a set has its
-// position at xy[i * stride + {0, 1}].
+// A code set: int8 code rows (128 B) and per row the key bias
+// -(256 |code|^2 + (row mod 256)).  A detector buffer's sidecar (sift_kernels.h
+// Sidecar), rows of the matcher's prepared codes (k_match_prep), or a caller's
+// gathered code buffer.
+struct CodeSet {
+    const int8_t* codes;
+    const int* keys;
+};
+// The flags of prepared sets: one word per set slot of the call, == epoch when
+// that set holds a value that is not an integer 0..255 (its pairs take the
+// general f16 path on pr.q / pr.t).  flags == nullptr: ready code sets,
+// integers by construction.
+struct SetFlags {
+    unsigned* flags;
+    unsigned epoch;
+};
+// The matcher's scratch (filled from a sift_hip_matcher in one place,
+// matcher_api.hip).  keys: 2 x u64 per (pair, query), pair p at row p *
+// nq_stride, all ones between calls; done: a counter per (pair, kMatchQB-query
+// block), zero between calls (the merging workgroup resets both, so launches
+// ordered on a stream may share them).  zero: the sentinel row, a zero code row
+// with the padding key (written once at allocation, never by a call), read in
+// place of rows past a set's end.
+struct MatchScratch {
+    unsigned long long* keys;
+    unsigned* done;
+    int nq_stride;
+    CodeSet zero;
+};
+// What a call asks for: per query the top-2 indices (idx2) and squared
+// distances (d2), two entries each, and the ratio-tested match; a null pointer
+// skips that output.
+struct MatchOut {
+    float ratio;
+    int ratio_on_squared;
+    int* idx2;
+    float* d2;
+    int* match;
+};
+
+// The gate of guided matching as the kernel takes it (sift_hip_match_gate; the
+// window rule is in include/sift_hip.h): row i of a set has its position at
+// xy[i * stride + {0, 1}].
 struct MatchGate {
     const float* qxy;
     const float* txy;
@@ -89,19 +103,29 @@ struct MatchGate {
     float radius;
 };
 
-// k_match_prep alone: the call's distinct sets into codes / rowkeys / flags.
-void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, unsigned* flags, unsigned epoch,
-                       hipStream_t s);
+// One pair of fp16 sets, converted in the kernel (k_match_single), S =
+// match_plan(nq, nt, 1).S splits.
+void launch_match_single(const MatchPair& pr, int S, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
 
-// One pair of ready code sets -- sidecars, or what launch_match_prep wrote --
-// under a gate: k_match_guided, match_direct_splits(nq, nt) splits.  flags ==
-// nullptr: integer sets by construction (sidecars); otherwise a set whose flag
-// (flags[pr.qset], flags[pr.tset]) equals epoch sends the pair down the fp16
-// path on pr.q / pr.t.
-void launch_match_guided(const MatchPair& pr, const MatchGate& gate, const int8_t* qc, const int* qk, const int8_t* tc,
-                         const int* tk, const int8_t* zc, const int* zk, const unsigned* flags, unsigned epoch,
-                         unsigned long long* keys, unsigned* done, float ratio, int ratio_on_squared, int* idx2,
-                         float* d2, int* match, hipStream_t s);
+// k_match_prep: the call's distinct sets into codes / rowkeys (capacity for the
+// call's sets) and their flags.
+void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, const SetFlags& flags, hipStream_t s);
+
+// Pairs of code sets (k_match_batch, S = match_plan(.., P >= 2).S splits):
+// pair p reads code rows qrow0.. / trow0.. and key biases qkrow0.. / tkrow0..
+// of `set` -- what launch_match_prep wrote (with its flags), or ready codes
+// with no prep launch and no flags (e.g. the sidecars of every rank
+// all-gathered: C5).
+void launch_match_codes(const MatchBatch& batch, int S, const CodeSet& set, const SetFlags& flags,
+                        const MatchScratch& sc, const MatchOut& out, hipStream_t s);
+
+// One pair of ready code sets q / t, match_direct_splits(nq, nt) splits.
+// gate == nullptr: k_match_direct, for sets that are integers by construction
+// (sidecars; the kernel reads no flags).  Under a gate: k_match_guided, on
+// sidecars (no flags) or on what launch_match_prep wrote, where a flagged set
+// (flags[pr.qset], flags[pr.tset]) sends the pair down the gated fp16 path.
+void launch_match_pair(const MatchPair& pr, const MatchGate* gate, const CodeSet& q, const CodeSet& t,
+                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
 
 // --- Match lists (sift_hip_match_list_*): filter + ordered compaction of the
 // top-2 arrays the launchers above wrote (k_match_select).

@@ -92,6 +92,14 @@ def test_gate_off_is_match_device(sift, nq, nt):
     dq, dt, dqxy, dtxy = upload(sift, q), upload(sift, t), upload_xy(sift, q_xy), upload_xy(sift, t_xy)
     m = sift.Matcher(nq, nt)
     assert same(guided(sift, m, dq, nq, dt, nt, dqxy, dtxy, np.inf), ungated(sift, m, dq, nq, dt, nt))
+    if (nq, nt) == (257, 300):
+        # Both sets halved (as test_non_integer_sets: every product and sum stays exact in fp32): the gated and the
+        # ungated instantiation of the one fp16 block, two splits and a second 32-query block, byte for byte.
+        dq, dt = upload(sift, q * 0.5), upload(sift, t * 0.5)
+        assert sift.Matcher.guided_plan(nq, nt) == 2
+        ref = ungated(sift, m, dq, nq, dt, nt)
+        assert np.any(ref[1] != np.rint(ref[1]))  # fractional distances: not the integer path
+        assert same(guided(sift, m, dq, nq, dt, nt, dqxy, dtxy, np.inf), ref)
 
 
 def test_ties(sift):

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Compare the kernels of two device-assembly builds of one HIP source.
+
+    hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o a.s   (old tree)
+    hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o b.s   (new tree)
+    tools/kernel_isa_diff.py a.s b.s [--json out.json] [--count v_mfma ds_read ...]
+
+Per kernel (symbol .. function-end label) the text is compared after the local
+label numbers (.LBB<n>_, BB<n>_ in comments) are normalised; the resources are
+read from the compiler's own summary after the function.  Exit status 1 when a
+kernel's text differs.
+"""
+import argparse
+import json
+import re
+import sys
+
+RES = {"vgprs": r"; NumVgprs: (\d+)", "agprs": r"; NumAgprs: (\d+)", "sgprs": r"; TotalNumSgprs: (\d+)",
+       "scratch": r"; ScratchSize: (\d+)", "lds": r"; LDSByteSize: (\d+)", "code_bytes": r"; codeLenInByte = (\d+)"}
+
+
+def kernels(path):
+    out, name, body, tail = {}, None, [], None
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m and name is None and tail is None:
+            name, body = m.group(1), []
+            continue
+        if name is not None:
+            if line.startswith(".Lfunc_end"):
+                out[name] = {"text": body}
+                tail, name = out[name], None
+            else:
+                body.append(re.sub(r"BB\d+_", "BB_", line.split("; %bb.")[0]).rstrip())
+            continue
+        if tail is not None:
+            for k, pat in RES.items():
+                m = re.search(pat, line)
+                if m:
+                    tail[k] = int(m.group(1))
+            if line.startswith("; LDSByteSize"):
+                tail = None
+    return out
+
+
+def insns(text):
+    return [l.split()[0] for l in text if l.startswith("\t") and not l.lstrip().startswith((".", ";"))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--json")
+    ap.add_argument("--count", nargs="*", default=["v_mfma", "ds_read", "global_load_lds", "v_med3", "v_max3"],
+                    help="opcode prefixes counted for kernels whose text differs")
+    a = ap.parse_args()
+    old, new = kernels(a.old), kernels(a.new)
+    rep, same = {}, True
+    for k in sorted(set(old) | set(new)):
+        if k not in old or k not in new:
+            rep[k] = {"equal": False, "missing_in": "old" if k not in old else "new"}
+            same = False
+            continue
+        e = {"equal": old[k]["text"] == new[k]["text"]}
+        for side, d in (("old", old[k]), ("new", new[k])):
+            ops = insns(d["text"])
+            e[side] = {r: d.get(r) for r in RES}
+            e[side]["instructions"] = len(ops)
+            if not e["equal"]:
+                e[side]["counts"] = {p: sum(o.startswith(p) for o in ops) for p in a.count}
+        rep[k] = e
+        same &= e["equal"]
+        print(("equal   " if e["equal"] else "DIFFERS ") + k, e["old"], "->", e["new"])
+    if a.json:
+        json.dump({"kernels": rep}, open(a.json, "w"), indent=1)
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
