@@ -378,14 +378,21 @@ sift_hip_match_gate abi_gate(const MatchGate& g) {
     return sift_hip_match_gate{g.query_xy, g.query_stride, g.train_xy, g.train_stride, g.radius};
 }
 
+sift_hip_match_epipolar_gate abi_gate(const EpipolarGate& g) {
+    sift_hip_match_epipolar_gate a{g.query_xy, g.query_stride, g.train_xy, g.train_stride, g.radius, {}, g.max_error};
+    std::copy(g.F, g.F + 9, a.F);
+    return a;
+}
+
 struct DeviceFree {
     void operator()(void* p) const { sift_hip_free(p); }
 };
 
-}  // namespace
-
-std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
-                                    int num_src, const MatchGate& gate, const MatchFilter& filter) {
+// The bodies of the gated calls, for either gate: `call` is the C ABI's entry
+// point for the gate's type.  The thread-local matchers are per gate type.
+template <class AbiGate, class Call>
+std::vector<DMatch> gated_list(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                               const AbiGate& g, const MatchFilter& filter, Call call, const char* what) {
     thread_local std::unique_ptr<sift_hip_matcher, MatcherDeleter> matcher;
     thread_local int cap = 0;  // both limits: the reverse direction swaps the roles
     std::vector<DMatch> out;
@@ -393,24 +400,24 @@ std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, 
     if (!matcher || std::max(num_des, num_src) > cap) {
         cap = std::max(std::max(num_des, num_src), cap);
         sift_hip_matcher_t m = nullptr;
-        check(sift_hip_matcher_create(-1, cap, cap, 2, &m), "matchListGuided");
+        check(sift_hip_matcher_create(-1, cap, cap, 2, &m), what);
         matcher.reset(m);
     }
-    const sift_hip_match_gate g = abi_gate(gate);
     const sift_hip_match_filter f{filter.ratio, filter.ratio_on_squared, filter.ratio_both_ways, filter.max_distance,
                                   filter.cross_check};
     out.resize((size_t)num_des);
     int count = 0;
-    check_throw(sift_hip_match_list_guided_host(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
-                                                reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, &f,
-                                                reinterpret_cast<sift_hip_dmatch*>(out.data()), num_des, &count),
-                "matchListGuided");
+    check_throw(call(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                     reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, &f,
+                     reinterpret_cast<sift_hip_dmatch*>(out.data()), num_des, &count),
+                what);
     out.resize((size_t)count);
     return out;
 }
 
-std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
-                             const MatchGate& gate) {
+template <class AbiGate, class Call>
+std::vector<int> gated_match(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                             const AbiGate& g, Call call, const char* what) {
     thread_local std::unique_ptr<sift_hip_matcher, MatcherDeleter> matcher;
     thread_local std::unique_ptr<void, DeviceFree> dmatch;  // capQ ints
     thread_local int capQ = 0, capT = 0;
@@ -420,20 +427,43 @@ std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const D
         capQ = std::max(num_des, capQ);
         capT = std::max(std::max(num_src, 1), capT);
         sift_hip_matcher_t m = nullptr;
-        check(sift_hip_matcher_create(-1, capQ, capT, 1, &m), "matchGuided");
+        check(sift_hip_matcher_create(-1, capQ, capT, 1, &m), what);
         matcher.reset(m);
         void* p = nullptr;
-        check(sift_hip_malloc(&p, sizeof(int) * (size_t)capQ), "matchGuided");
+        check(sift_hip_malloc(&p, sizeof(int) * (size_t)capQ), what);
         dmatch.reset(p);
     }
-    const sift_hip_match_gate g = abi_gate(gate);
-    check_throw(sift_hip_match_guided_device(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
-                                             reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, 0.8f, 1, nullptr,
-                                             nullptr, static_cast<int*>(dmatch.get()), nullptr),
-                "matchGuided");
-    check(sift_hip_device_sync(), "matchGuided");
-    check(sift_hip_memcpy_d2h(out.data(), dmatch.get(), sizeof(int) * (size_t)num_des), "matchGuided");
+    check_throw(call(matcher.get(), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                     reinterpret_cast<const uint16_t*>(src.data()), num_src, &g, 0.8f, 1, nullptr, nullptr,
+                     static_cast<int*>(dmatch.get()), nullptr),
+                what);
+    check(sift_hip_device_sync(), what);
+    check(sift_hip_memcpy_d2h(out.data(), dmatch.get(), sizeof(int) * (size_t)num_des), what);
     return out;
+}
+
+}  // namespace
+
+std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                    int num_src, const MatchGate& gate, const MatchFilter& filter) {
+    return gated_list(des, num_des, src, num_src, abi_gate(gate), filter, sift_hip_match_list_guided_host,
+                      "matchListGuided");
+}
+
+std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                             const MatchGate& gate) {
+    return gated_match(des, num_des, src, num_src, abi_gate(gate), sift_hip_match_guided_device, "matchGuided");
+}
+
+std::vector<DMatch> matchListEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                      int num_src, const EpipolarGate& gate, const MatchFilter& filter) {
+    return gated_list(des, num_des, src, num_src, abi_gate(gate), filter, sift_hip_match_list_epipolar_host,
+                      "matchListEpipolar");
+}
+
+std::vector<int> matchEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                               const EpipolarGate& gate) {
+    return gated_match(des, num_des, src, num_src, abi_gate(gate), sift_hip_match_epipolar_device, "matchEpipolar");
 }
 
 }  // namespace sift_cuda

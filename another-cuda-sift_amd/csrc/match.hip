@@ -25,6 +25,10 @@
 //                  direct kernel with the train positions staged beside the
 //                  keys and a per-key gate in the top-2 fold.  Both are
 //                  wrappers around one body, match_pair.
+//  k_match_epipolar the same body under the gate of two-view geometry: a row is
+//                  a candidate when its Sampson distance to the pair's
+//                  fundamental matrix is within a bound (and it lies in the
+//                  window); a third plane holds the rows' side of that test.
 //  k_match_select  match lists: the top-2 arrays of both directions filtered
 //                  (ratio test, distance cap, cross check) and compacted in
 //                  query order into cv::DMatch records, one workgroup per pair.
@@ -47,8 +51,9 @@
 // sums), fp32 norms, a float top-2 in train order.
 //
 // Shared core: one integer fold (chunk_top2) and one fp16 block
-// (match_f16_block), both templates on a gate policy (NoGate, or the gate of
-// guided matching: in_gate is the window rule); one split rule for the kernels
+// (match_f16_block), both templates on a gate policy (NoGate, the window of
+// guided matching -- in_gate is its rule -- or the epipolar gate, epi_pass);
+// one split rule for the kernels
 // that split by whole key groups (GroupSplit, host and device); one merge
 // (merge_contribution).  The bit-exactness rules -- the tie order, INT_MIN
 // against kPadBias, rows past nt losing -- live there and nowhere else.
@@ -256,13 +261,76 @@ __device__ __forceinline__ bool in_gate(float tx, float ty, float qx, float qy, 
     return __builtin_fabsf(tx - qx) <= radius && __builtin_fabsf(ty - qy) <= radius;
 }
 
+// The epipolar gate (k_match_epipolar; the rule is in include/sift_hip.h):
+// train row t is a candidate of query i when its Sampson distance to the pair's
+// fundamental matrix is at most max_error and it lies in the query's window.
+// float32, round to nearest, the operations in the order written and never
+// fused: a query's side is its line (a, b, c) = F x_q and nq = a^2 + b^2, a
+// row's side nr = u^2 + v^2 of (u, v, .) = F^T x_t, and a pair costs
+// r = (a tx + b ty) + c, r r <= e2 (nq + nr).  Any NaN fails the compare.
+struct EpiQuery {
+    float a, b, c, nq, qx, qy;
+};
+__device__ __forceinline__ EpiQuery epi_query(const float (&F)[9], float qx, float qy) {
+#pragma clang fp contract(off)
+    EpiQuery e;
+    e.a = (F[0] * qx + F[1] * qy) + F[2];
+    e.b = (F[3] * qx + F[4] * qy) + F[5];
+    e.c = (F[6] * qx + F[7] * qy) + F[8];
+    e.nq = e.a * e.a + e.b * e.b;
+    e.qx = qx;
+    e.qy = qy;
+    return e;
+}
+__device__ __forceinline__ float epi_row(const float (&F)[9], float tx, float ty) {
+#pragma clang fp contract(off)
+    const float u = (F[0] * tx + F[3] * ty) + F[6];
+    const float v = (F[1] * tx + F[4] * ty) + F[7];
+    return u * u + v * v;
+}
+// The pair's side for V = float or two rows at once, V = f32x2 (the same
+// operations per component): r r and e2 (nq + nr) to compare, and the window's
+// two differences.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <class V>
+__device__ __forceinline__ void epi_terms(const EpiQuery& q, V tx, V ty, V nr, float e2, V& lhs, V& rhs, V& dx, V& dy) {
+#pragma clang fp contract(off)
+    const V r = (q.a * tx + q.b * ty) + q.c;
+    lhs = r * r;
+    rhs = e2 * (q.nq + nr);
+    dx = tx - q.qx;
+    dy = ty - q.qy;
+}
+__device__ __forceinline__ bool epi_in(float lhs, float rhs, float dx, float dy, float radius) {
+    return (lhs <= rhs) & (__builtin_fabsf(dx) <= radius) & (__builtin_fabsf(dy) <= radius);
+}
+__device__ __forceinline__ bool epi_pass(const EpiQuery& q, float tx, float ty, float nr, float e2, float radius) {
+    float lhs, rhs, dx, dy;
+    epi_terms(q, tx, ty, nr, e2, lhs, rhs, dx, dy);
+    return epi_in(lhs, rhs, dx, dy, radius);
+}
+// Two train rows at once: the integer fold takes keys in pairs of adjacent rows,
+// whose staged values sit in adjacent registers, so the packed fp32
+// instructions apply and a pair of keys costs what one did.
+__device__ __forceinline__ void epi_pass2(const EpiQuery& q, f32x2 tx, f32x2 ty, f32x2 nr, float e2, float radius,
+                                          bool& p0, bool& p1) {
+    f32x2 lhs, rhs, dx, dy;
+    epi_terms(q, tx, ty, nr, e2, lhs, rhs, dx, dy);
+    p0 = epi_in(lhs[0], rhs[0], dx[0], dy[0], radius);
+    p1 = epi_in(lhs[1], rhs[1], dx[1], dy[1], radius);
+}
+
+template <class Gate>
+constexpr bool kEpipolar = std::is_same<Gate, EpipolarGate>::value;
+
 // One wave's 32 queries (rows q0 + col of the pair) against train tiles
 // [tbeg, tend): f16 MFMA (train rows as A, queries as B, so the accumulator's
 // lane is the query and its 16 registers are train rows in increasing order),
 // float top-2 with a strict '<' insert.  Returns the full d^2.  Under a gate
 // (Gate = MatchGate) the insert also requires the row to lie in the query's
 // window; lane col carries the position of train row t0 + col, as it carries
-// its norm.
+// its norm -- and under the epipolar gate the row's nr, computed once per
+// tile row and shuffled with the position.
 template <class Gate>
 __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int tbeg, int tend, int col, int h) {
     const int qrow = q0 + col;
@@ -275,8 +343,15 @@ __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int 
         qx = qvalid ? g.qxy[(size_t)qrow * g.qstride] : NAN;
         qy = qvalid ? g.qxy[(size_t)qrow * g.qstride + 1] : NAN;
     }
-    float qn = sumsq8(bq);
-    qn += __shfl_xor(qn, 32);
+    // |q|^2: under the epipolar gate after the tile loop (bq lives across it
+    // anyway), one register less inside it -- the budget of k_match_epipolar.
+    float qn = 0.f;
+    if constexpr (!kEpipolar<Gate>) {
+        qn = sumsq8(bq);
+        qn += __shfl_xor(qn, 32);
+    }
+    EpiQuery eq{};
+    if constexpr (kEpipolar<Gate>) eq = epi_query(g.F, qx, qy);
     Top2 best{INFINITY, INFINITY, kNone, kNone};
     for (int tile = tbeg; tile < tend; tile++) {
         const int t0 = tile * kMatchTileRows, trow = t0 + col;
@@ -291,6 +366,8 @@ __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int 
         }
         float tn = sumsq8(a);
         tn += __shfl_xor(tn, 32);
+        float tv = 0.f;  // epipolar only
+        if constexpr (kEpipolar<Gate>) tv = epi_row(g.F, tx, ty);
         f32x16 acc = {}, acc2 = {};
 #pragma unroll
         for (int s = 0; s < 8; s += 2) {
@@ -303,7 +380,10 @@ __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int 
             const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
             const float d = __shfl(tn, row) - 2.f * acc[i];
             bool cand = true;
-            if constexpr (kGated<Gate>) cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
+            if constexpr (kEpipolar<Gate>)
+                cand = epi_pass(eq, __shfl(tx, row), __shfl(ty, row), __shfl(tv, row), g.e2, g.radius);
+            else if constexpr (kGated<Gate>)
+                cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
             if (t0 + row < pr.nt && cand && d < best.d2) {
                 if (d < best.d1) {
                     best.d2 = best.d1;
@@ -318,6 +398,10 @@ __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int 
         }
     }
     best = merge_top2(best, shfl_top2(best, 32));
+    if constexpr (kEpipolar<Gate>) {
+        qn = sumsq8(bq);
+        qn += __shfl_xor(qn, 32);
+    }
     best.d1 += qn;
     best.d2 += qn;
     return best;
@@ -454,6 +538,34 @@ __device__ __forceinline__ NoGate lane_gate(const NoGate&, int, int, int) {
     return {};
 }
 
+// A lane's side of the epipolar gate: the lines of its queries (and their
+// positions, for the window); e2 and the radius are wave-uniform.  sn is the
+// current chunk's third plane, the rows' nr beside their positions (match_pair
+// fills it from the staged px / py once the chunk has landed).
+template <int QBW>
+struct LaneEpipolar {
+    EpiQuery q[QBW];
+    float radius, e2;
+    const float* sn;
+};
+template <class Gate>
+constexpr bool kLaneEpipolar = false;
+template <int QBW>
+constexpr bool kLaneEpipolar<LaneEpipolar<QBW>> = true;
+template <int QBW>
+__device__ __forceinline__ LaneEpipolar<QBW> lane_gate(const EpipolarGate& g, int nq, int q0w, int col) {
+    LaneEpipolar<QBW> lg;
+    lg.radius = g.radius;
+    lg.e2 = g.e2;
+    lg.sn = nullptr;
+#pragma unroll
+    for (int qb = 0; qb < QBW; qb++) {
+        const float* p = g.qxy + (size_t)min(q0w + 32 * qb + col, nq - 1) * g.qstride;
+        lg.q[qb] = epi_query(g.F, p[0], p[1]);
+    }
+    return lg;
+}
+
 // One staged chunk of nc tiles (rows t0 ...) against a wave's two query
 // blocks: per tile 8 MFMAs from LDS fragments, then each lane folds its 32
 // keys into a per-block running key top-2 -- two at a time: for a pair (x, y)
@@ -462,10 +574,10 @@ __device__ __forceinline__ NoGate lane_gate(const NoGate&, int, int, int) {
 // block (accumulator registers 0-7 / 8-15).  The chunk lies in one key group
 // (r = row - t0 < 256), so its top-2 is decoded once into (e, train index) and
 // merged into the running pair (earlier groups win ties).
-// Under a gate (Gate = LaneGate, planes sx / sy) the key of a (query, row)
-// outside the window becomes INT_MIN before the fold -- below kInvalidKey, so
-// fold_group reads it as "none".  The positions are read as the keys are (the
-// same address across the lanes of a half: broadcast reads).
+// Under a gate (Gate = LaneGate or LaneEpipolar, planes sx / sy) the key of a
+// (query, row) that fails the gate becomes INT_MIN before the fold -- below
+// kInvalidKey, so fold_group reads it as "none".  The positions are read as
+// the keys are (the same address across the lanes of a half: broadcast reads).
 template <int QBW, class Gate>
 __device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, const float* sx, const float* sy, int nc,
                                            int t0, int col, int h, const i32x4 (&bq)[QBW][4], const Gate& g,
@@ -481,13 +593,14 @@ __device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, cons
     for (int j = 0; j < kChunkTiles; j++) {
         if (j < nc) {
             i32x4 a[4], tk[4];
-            f32x4 px[4], py[4];  // gated only
+            f32x4 px[4], py[4];  // the window gate only
 #pragma unroll
             for (int kb = 0; kb < 4; kb++)
                 a[kb] = *reinterpret_cast<const i32x4*>(ta0 + j * kTileBytes + 16 * ((4 * h + kb) ^ sw));
             // accumulator register i holds train row (i & 3) + 8 (i >> 2) + 4 h
 #pragma unroll
             for (int r = 0; r < 4; r++) {
+                if constexpr (kLaneEpipolar<Gate>) continue;  // loads its planes in the fold, below
                 tk[r] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * r);
                 if constexpr (kGated<Gate>) {
                     px[r] = *reinterpret_cast<const f32x4*>(sx + 4 * h + j * kMatchTileRows + 8 * r);
@@ -502,20 +615,48 @@ __device__ __forceinline__ void chunk_top2(const int8_t* sc, const int* sk, cons
                     acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kb], bq[qb][kb], acc[qb], 0, 0, 0);
 #pragma unroll
             for (int qb = 0; qb < QBW; qb++) {
-                auto key = [&](int i) {
-                    const int k = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
-                    if constexpr (kGated<Gate>)
-                        return in_gate(px[i >> 2][i & 3], py[i >> 2][i & 3], g.qx[qb], g.qy[qb], g.radius) ? k : INT_MIN;
-                    else
-                        return k;
-                };
+                if constexpr (kLaneEpipolar<Gate>) {
+                    // The epipolar gate reads four planes (keys, px, py, nr): one
+                    // row group at a time, loaded as the fold reaches it and not
+                    // all four up front (the register budget of two workgroups per
+                    // CU), its two pairs of adjacent rows into the two chains.  The
+                    // top-2 of the chunk does not depend on which chain a key enters.
 #pragma unroll
-                for (int i = 0; i < 8; i += 2) {
-                    const int x0 = key(i), y0 = key(i + 1), x1 = key(i + 8), y1 = key(i + 9);
-                    m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
-                    m1e[qb] = max3_i32(m1e[qb], x0, y0);
-                    m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
-                    m1o[qb] = max3_i32(m1o[qb], x1, y1);
+                    for (int r = 0; r < 4; r++) {
+                        const int o = 4 * h + j * kMatchTileRows + 8 * r;
+                        const i32x4 kr = *reinterpret_cast<const i32x4*>(sk + o);
+                        const f32x4 xr = *reinterpret_cast<const f32x4*>(sx + o);
+                        const f32x4 yr = *reinterpret_cast<const f32x4*>(sy + o);
+                        const f32x4 nr = *reinterpret_cast<const f32x4*>(g.sn + o);
+                        int x0 = (acc[qb][4 * r] << 9) + kr[0], y0 = (acc[qb][4 * r + 1] << 9) + kr[1];
+                        int x1 = (acc[qb][4 * r + 2] << 9) + kr[2], y1 = (acc[qb][4 * r + 3] << 9) + kr[3];
+                        bool p0, p1, p2, p3;
+                        epi_pass2(g.q[qb], f32x2{xr[0], xr[1]}, f32x2{yr[0], yr[1]}, f32x2{nr[0], nr[1]}, g.e2, g.radius,
+                                  p0, p1);
+                        epi_pass2(g.q[qb], f32x2{xr[2], xr[3]}, f32x2{yr[2], yr[3]}, f32x2{nr[2], nr[3]}, g.e2, g.radius,
+                                  p2, p3);
+                        x0 = p0 ? x0 : INT_MIN, y0 = p1 ? y0 : INT_MIN, x1 = p2 ? x1 : INT_MIN, y1 = p3 ? y1 : INT_MIN;
+                        m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
+                        m1e[qb] = max3_i32(m1e[qb], x0, y0);
+                        m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
+                        m1o[qb] = max3_i32(m1o[qb], x1, y1);
+                    }
+                } else {
+                    auto key = [&](int i) {
+                        const int k = (acc[qb][i] << 9) + tk[i >> 2][i & 3];
+                        if constexpr (kGated<Gate>)
+                            return in_gate(px[i >> 2][i & 3], py[i >> 2][i & 3], g.qx[qb], g.qy[qb], g.radius) ? k : INT_MIN;
+                        else
+                            return k;
+                    };
+#pragma unroll
+                    for (int i = 0; i < 8; i += 2) {
+                        const int x0 = key(i), y0 = key(i + 1), x1 = key(i + 8), y1 = key(i + 9);
+                        m2e[qb] = max(med3_i32(m1e[qb], x0, y0), m2e[qb]);
+                        m1e[qb] = max3_i32(m1e[qb], x0, y0);
+                        m2o[qb] = max(med3_i32(m1o[qb], x1, y1), m2o[qb]);
+                        m1o[qb] = max3_i32(m1o[qb], x1, y1);
+                    }
                 }
             }
         }
@@ -814,8 +955,9 @@ __global__ __launch_bounds__(64 * NW, (kMatchBatchWgPerCu * NW) / 4) void k_matc
 }
 
 // ---------------------------------------------------------------------------
-// match_pair: the body of the two kernels on one pair of ready code sets,
-// k_match_direct (Gate = NoGate) and k_match_guided (Gate = MatchGate).  The
+// match_pair: the body of the three kernels on one pair of ready code sets,
+// k_match_direct (Gate = NoGate), k_match_guided (Gate = MatchGate) and
+// k_match_epipolar (Gate = EpipolarGate; s_pn: its third plane).  The
 // integer path of k_match_batch with the codes and keys addressed directly:
 // query operands from the query set, the split's train key groups streamed
 // through the two LDS chunks by LDS-DMA -- under a gate with the train
@@ -825,14 +967,18 @@ __global__ __launch_bounds__(64 * NW, (kMatchBatchWgPerCu * NW) / 4) void k_matc
 // ---------------------------------------------------------------------------
 template <int NW, int QBW, class Gate>
 __device__ __forceinline__ void match_pair(int8_t (&s_codes)[2][kChunkTiles * kTileBytes], int (&s_key)[2][kChunkRows],
-                                           float (*s_px)[kChunkRows], float (*s_py)[kChunkRows], unsigned* s_last,
+                                           float (*s_px)[kChunkRows], float (*s_py)[kChunkRows],
+                                           float (*s_pn)[kChunkRows], unsigned* s_last,
                                            const MatchPair& pr, const Gate& g, const CodeSet& qs, const CodeSet& ts,
                                            const CodeSet& zero, const unsigned* flags, unsigned epoch, int S,
                                            unsigned long long* keys, unsigned* done, const MatchOut& out) {
     constexpr int QB = block_queries<NW, QBW>();
     const int q0 = blockIdx.x * QB;
     if (q0 >= pr.nq) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, h = lane >> 5;
+    // The wave's index: under the epipolar gate as a scalar, the one VGPR that
+    // keeps k_match_epipolar inside 128 registers without scratch.
+    const int w = kEpipolar<Gate> ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const GroupSplit split(match_tiles(pr.nt), S);
     const int tb = split.begin(blockIdx.y), te = split.end(blockIdx.y);
     const int q0w = q0 + 32 * QBW * w;
@@ -850,7 +996,7 @@ __device__ __forceinline__ void match_pair(int8_t (&s_codes)[2][kChunkTiles * kT
         i32x4 bq[QBW][4];
         int qn[QBW];
         load_queries<QBW>(qs.codes, qs.keys, pr.nq, q0w, col, h, bq, qn);
-        const auto lg = lane_gate<QBW>(g, pr.nq, q0w, col);
+        auto lg = lane_gate<QBW>(g, pr.nq, q0w, col);
         Best best[QBW];
 #pragma unroll
         for (int qb = 0; qb < QBW; qb++) best[qb] = Best{kNone, kNone, kNone, kNone};
@@ -861,6 +1007,13 @@ __device__ __forceinline__ void match_pair(int8_t (&s_codes)[2][kChunkTiles * kT
             if (c0 + kChunkTiles < te) stage(c0 + kChunkTiles, buf ^ 1);
             const float *sx = nullptr, *sy = nullptr;
             if constexpr (kGated<Gate>) sx = s_px[buf], sy = s_py[buf];
+            if constexpr (kEpipolar<Gate>) {
+                // The third plane: row r's nr from its landed position, once per
+                // chunk instead of once per lane that folds the row.
+                for (int r = tid; r < kChunkRows; r += 64 * NW) s_pn[buf][r] = epi_row(g.F, sx[r], sy[r]);
+                lg.sn = s_pn[buf];
+                __syncthreads();
+            }
             chunk_top2(s_codes[buf], s_key[buf], sx, sy, min(kChunkTiles, te - c0), c0 * kMatchTileRows, col, h, bq, lg,
                        best);
         }
@@ -901,7 +1054,7 @@ __global__ __launch_bounds__(64 * NW) void k_match_direct(
     __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
     __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
     __shared__ unsigned s_last;
-    match_pair<NW, QBW>(s_codes, s_key, nullptr, nullptr, &s_last, pr, NoGate{}, CodeSet{qc, qk},
+    match_pair<NW, QBW>(s_codes, s_key, nullptr, nullptr, nullptr, &s_last, pr, NoGate{}, CodeSet{qc, qk},
                         CodeSet{tc, tk}, CodeSet{zc, zk}, nullptr, 0u, S, keys, done,
                         MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
 }
@@ -924,7 +1077,27 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_guided(  // reg
     __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
     __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
     __shared__ unsigned s_last;
-    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, &s_last, pr, g, CodeSet{qc, qk}, CodeSet{tc, tk},
+    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, nullptr, &s_last, pr, g, CodeSet{qc, qk}, CodeSet{tc, tk},
+                        CodeSet{zc, zk}, flags, epoch, S, keys, done,
+                        MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
+}
+
+// k_match_epipolar: k_match_guided with the epipolar gate -- the same staging,
+// LDS and launch shape; the gate's extra work is VALU per key.
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_epipolar(  // registers for two workgroups per CU
+    MatchPair pr, EpipolarGate g, const int8_t* __restrict__ qc, const int* __restrict__ qk,
+    const int8_t* __restrict__ tc, const int* __restrict__ tk, const int8_t* __restrict__ zc,
+    const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch, int S,
+    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
+    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_pn[2][kChunkRows];
+    __shared__ unsigned s_last;
+    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, s_pn, &s_last, pr, g, CodeSet{qc, qk}, CodeSet{tc, tk},
                         CodeSet{zc, zk}, flags, epoch, S, keys, done,
                         MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
 }
@@ -957,6 +1130,15 @@ void launch_match_pair(const MatchPair& pr, const MatchGate* gate, const CodeSet
         hipLaunchKernelGGL((k_match_direct<kDirectNW, kDirectQBW>), g, b, 0, s, pr, q.codes, q.keys, t.codes, t.keys,
                            sc.zero.codes, sc.zero.keys, S, sc.keys, sc.done, out.ratio, out.ratio_on_squared, out.idx2,
                            out.d2, out.match);
+}
+
+void launch_match_pair(const MatchPair& pr, const EpipolarGate& gate, const CodeSet& q, const CodeSet& t,
+                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
+    const int S = match_direct_splits(pr.nq, pr.nt);
+    const dim3 g((max(pr.nq, 1) + kDirectQB - 1) / kDirectQB, S, 1), b(64 * kDirectNW);
+    hipLaunchKernelGGL((k_match_epipolar<kDirectNW, kDirectQBW>), g, b, 0, s, pr, gate, q.codes, q.keys, t.codes, t.keys,
+                       sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, S, sc.keys, sc.done, out.ratio,
+                       out.ratio_on_squared, out.idx2, out.d2, out.match);
 }
 
 void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, const SetFlags& flags, hipStream_t s) {

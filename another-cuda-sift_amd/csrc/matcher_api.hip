@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
+#include <string>
 
 #include "detector_state.h"
 #include "sift_match.h"
@@ -478,27 +480,82 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, co
 // --- Guided matching -----------------------------------------------------------
 namespace {
 
-// The gate's own rules first (they need no matcher), then the matcher's.  Nothing is launched on a failure.
-int check_guided_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                      const sift_hip_match_gate* g) {
-    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null match gate");
-    if (g->query_stride < 2 || g->train_stride < 2)
-        return fail(SIFT_HIP_ERR_INVALID, "match gate: a position stride below 2 floats");
-    if (!(g->radius > 0.f)) return fail(SIFT_HIP_ERR_INVALID, "match gate: the radius must be > 0");
+// The rules both gates share (`what` names the gate in the message): the position fields, which need no matcher ...
+int check_gate_positions(const char* what, int query_stride, int train_stride, float radius) {
+    if (query_stride < 2 || train_stride < 2)
+        return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": a position stride below 2 floats");
+    if (!(radius > 0.f)) return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": the radius must be > 0");
+    return SIFT_HIP_OK;
+}
+// ... then the matcher's and the sets'.
+int check_gated_sets(const char* what, const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                     const float* query_xy, const float* train_xy) {
     if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
     if (nq < 0 || nt < 0 || nq > m->maxQ || nt > m->maxT)
         return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
     if ((nq && !q) || (nt && !t)) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-    if ((nq && !g->query_xy) || (nt && !g->train_xy))
-        return fail(SIFT_HIP_ERR_INVALID, "match gate: null position pointer");
+    if ((nq && !query_xy) || (nt && !train_xy))
+        return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": null position pointer");
     return SIFT_HIP_OK;
 }
 
-// The guided top-2 of (q, t) into idx2 / d2 / match and, with rev_idx2, of (t, q) under the swapped gate into
-// rev_idx2 / rev_d2.  Arguments are checked by the caller; nq > 0.  Detector buffers with fresh sidecars: one launch
-// per direction on their codes.  Otherwise k_match_prep once for both sets, then one launch per direction.
-int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const sift_hip_match_gate& g,
-                float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, int* rev_idx2, float* rev_d2,
+// The gate's own rules first (they need no matcher), then the matcher's.  Nothing is launched on a failure.
+int check_guided_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                      const sift_hip_match_gate* g) {
+    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null match gate");
+    if (int rc = check_gate_positions("match gate", g->query_stride, g->train_stride, g->radius)) return rc;
+    return check_gated_sets("match gate", m, q, nq, t, nt, g->query_xy, g->train_xy);
+}
+
+int check_epipolar_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                        const sift_hip_match_epipolar_gate* g) {
+    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null epipolar gate");
+    if (int rc = check_gate_positions("epipolar gate", g->query_stride, g->train_stride, g->radius)) return rc;
+    if (!(g->max_error > 0.f) || !std::isfinite(g->max_error))
+        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: max_error must be > 0 and finite");
+    bool zero = true;
+    for (float f : g->F) {
+        if (!std::isfinite(f)) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: a non-finite entry of F");
+        zero = zero && f == 0.f;
+    }
+    if (zero) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: F is all zero");
+    return check_gated_sets("epipolar gate", m, q, nq, t, nt, g->query_xy, g->train_xy);
+}
+
+// The two directions of a pair under a gate, as the kernels take it: the forward gate, and the reverse direction's
+// with the roles swapped (the epipolar gate: and F transposed; e2 = max_error^2 is formed here, one float32 product).
+struct WindowGates {
+    MatchGate fwd, rev;
+    explicit WindowGates(const sift_hip_match_gate& g)
+        : fwd{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius},
+          rev{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius} {}
+};
+struct EpipolarGates {
+    EpipolarGate fwd, rev;
+    explicit EpipolarGates(const sift_hip_match_epipolar_gate& g) {
+        const float e2 = g.max_error * g.max_error;
+        fwd = EpipolarGate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius, e2, {}};
+        rev = EpipolarGate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius, e2, {}};
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) fwd.F[3 * r + c] = rev.F[3 * c + r] = g.F[3 * r + c];
+    }
+};
+void launch_gated_pair(const MatchPair& pr, const MatchGate& g, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
+                       const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
+    launch_match_pair(pr, &g, q, t, flags, sc, out, s);
+}
+void launch_gated_pair(const MatchPair& pr, const EpipolarGate& g, const CodeSet& q, const CodeSet& t,
+                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
+    launch_match_pair(pr, g, q, t, flags, sc, out, s);
+}
+
+// The guided top-2 of (q, t) into idx2 / d2 / match and, with rev_idx2, of (t, q) under the reverse gate into
+// rev_idx2 / rev_d2 (Gates: WindowGates or EpipolarGates).  Arguments are checked by the caller; nq > 0.  Detector
+// buffers with fresh sidecars: one launch per direction on their codes.  Otherwise k_match_prep once for both sets,
+// then one launch per direction.
+template <class Gates>
+int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g, float ratio,
+                int ratio_on_squared, int* idx2, float* d2, int* match, int* rev_idx2, float* rev_d2,
                 hipStream_t stream) {
     CodeSet qc, tc;
     SetFlags flags = kNoFlags;
@@ -524,18 +581,44 @@ int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* 
         qc = CodeSet{m->dCodes, m->dRowKeys}, tc = CodeSet{m->dCodes + (size_t)trow0 * 128, m->dRowKeys + trow0};
     }
     const MatchPair fwd{q, t, nq, nt, 0, qs, ts, 0, 0, 0, 0};
-    const MatchGate fgate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius};
-    launch_match_pair(fwd, &fgate, qc, tc, flags, m->scratch(), MatchOut{ratio, ratio_on_squared, idx2, d2, match},
+    launch_gated_pair(fwd, g.fwd, qc, tc, flags, m->scratch(), MatchOut{ratio, ratio_on_squared, idx2, d2, match},
                       stream);
     HIPCHK(hipGetLastError());
     if (rev_idx2 && nt > 0) {
         // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
         const MatchPair rev{t, q, nt, nq, 0, ts, qs, 0, 0, 0, 0};
-        const MatchGate rgate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius};
-        launch_match_pair(rev, &rgate, tc, qc, flags, m->scratch(), MatchOut{0.f, 0, rev_idx2, rev_d2, nullptr}, stream);
+        launch_gated_pair(rev, g.rev, tc, qc, flags, m->scratch(), MatchOut{0.f, 0, rev_idx2, rev_d2, nullptr}, stream);
         HIPCHK(hipGetLastError());
     }
     return SIFT_HIP_OK;
+}
+
+// The guided match list of a checked pair: the guided top-2 of the directions the filter needs into the select
+// scratch, then the filter and the compaction.
+template <class Gates>
+int guided_list(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g,
+                const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, hipStream_t stream) {
+    if (int rc = check_list_args(m, 1, &nq, &nt, filter, out, count)) return rc;
+    if (int rc = ensure_select_scratch(m)) return rc;
+    if (nq > 0 && nt > 0) {
+        const bool rev = needs_reverse(*filter);
+        if (int rc = guided_top2(m, q, nq, t, nt, g, 0.f, 0, m->dSelIdx, m->dSelD, nullptr,
+                                 rev ? m->dSelIdx + 2 * (size_t)nq : nullptr, m->dSelD + 2 * (size_t)nq, stream))
+            return rc;
+    }
+    HIPCHK(hipSetDevice(m->device));
+    return select_lists(m, 1, &nq, &nt, *filter, out, count, stream);
+}
+
+// The same into the matcher's own list, synchronously, and back to the host.
+template <class Gates>
+int guided_list_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g,
+                     const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count) {
+    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
+    if (int rc = ensure_select_scratch(m)) return rc;
+    if (int rc = guided_list(m, q, nq, t, nt, g, filter, reinterpret_cast<sift_hip_dmatch*>(m->dList), m->dCount, nullptr))
+        return rc;
+    return read_list(m, out_host, cap, count);
 }
 
 }  // namespace
@@ -547,7 +630,7 @@ int sift_hip_match_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq
                                  float* d2, int* match, void* stream) {
     if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
     if (nq == 0) return SIFT_HIP_OK;
-    return guided_top2(m, q, nq, t, nt, *gate, ratio, ratio_on_squared, idx2, d2, match, nullptr, nullptr,
+    return guided_top2(m, q, nq, t, nt, WindowGates(*gate), ratio, ratio_on_squared, idx2, d2, match, nullptr, nullptr,
                        (hipStream_t)stream);
 }
 
@@ -561,17 +644,7 @@ int sift_hip_match_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, i
                                       const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
                                       sift_hip_dmatch* out, int* count, void* stream) {
     if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
-    if (int rc = check_list_args(m, 1, &nq, &nt, filter, out, count)) return rc;
-    if (int rc = ensure_select_scratch(m)) return rc;
-    if (nq > 0 && nt > 0) {
-        const bool rev = needs_reverse(*filter);
-        if (int rc = guided_top2(m, q, nq, t, nt, *gate, 0.f, 0, m->dSelIdx, m->dSelD, nullptr,
-                                 rev ? m->dSelIdx + 2 * (size_t)nq : nullptr, m->dSelD + 2 * (size_t)nq,
-                                 (hipStream_t)stream))
-            return rc;
-    }
-    HIPCHK(hipSetDevice(m->device));
-    return select_lists(m, 1, &nq, &nt, *filter, out, count, (hipStream_t)stream);
+    return guided_list(m, q, nq, t, nt, WindowGates(*gate), filter, out, count, (hipStream_t)stream);
 }
 
 int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
@@ -580,12 +653,32 @@ int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int
     if (!filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
     *count = 0;
     if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
-    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
-    if (int rc = ensure_select_scratch(m)) return rc;
-    if (int rc = sift_hip_match_list_guided_device(m, q, nq, t, nt, gate, filter,
-                                                   reinterpret_cast<sift_hip_dmatch*>(m->dList), m->dCount, nullptr))
-        return rc;
-    return read_list(m, out_host, cap, count);
+    return guided_list_host(m, q, nq, t, nt, WindowGates(*gate), filter, out_host, cap, count);
+}
+
+int sift_hip_match_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                   const sift_hip_match_epipolar_gate* gate, float ratio, int ratio_on_squared,
+                                   int* idx2, float* d2, int* match, void* stream) {
+    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
+    if (nq == 0) return SIFT_HIP_OK;
+    return guided_top2(m, q, nq, t, nt, EpipolarGates(*gate), ratio, ratio_on_squared, idx2, d2, match, nullptr,
+                       nullptr, (hipStream_t)stream);
+}
+
+int sift_hip_match_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                        const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
+                                        sift_hip_dmatch* out, int* count, void* stream) {
+    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
+    return guided_list(m, q, nq, t, nt, EpipolarGates(*gate), filter, out, count, (hipStream_t)stream);
+}
+
+int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                      const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out_host, int cap, int* count) {
+    if (!filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
+    *count = 0;
+    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
+    return guided_list_host(m, q, nq, t, nt, EpipolarGates(*gate), filter, out_host, cap, count);
 }
 
 int sift_hip_device_count(int* n) {

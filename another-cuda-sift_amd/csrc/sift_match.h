@@ -103,6 +103,20 @@ struct MatchGate {
     float radius;
 };
 
+// The gate of guided matching under a fundamental matrix
+// (sift_hip_match_epipolar_gate; the rule is in include/sift_hip.h): the
+// positions as MatchGate's, F row-major with x_train^T F x_query = 0, and
+// e2 = max_error * max_error (one float32 product, formed on the host).  The
+// reverse direction of a pair takes the positions swapped and F transposed.
+struct EpipolarGate {
+    const float* qxy;
+    const float* txy;
+    int qstride, tstride;
+    float radius;
+    float e2;
+    float F[9];
+};
+
 // One pair of fp16 sets, converted in the kernel (k_match_single), S =
 // match_plan(nq, nt, 1).S splits.
 void launch_match_single(const MatchPair& pr, int S, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
@@ -125,6 +139,10 @@ void launch_match_codes(const MatchBatch& batch, int S, const CodeSet& set, cons
 // sidecars (no flags) or on what launch_match_prep wrote, where a flagged set
 // (flags[pr.qset], flags[pr.tset]) sends the pair down the gated fp16 path.
 void launch_match_pair(const MatchPair& pr, const MatchGate* gate, const CodeSet& q, const CodeSet& t,
+                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
+// The same pair under an epipolar gate: k_match_epipolar, the guided kernel's
+// launch shape and flag rule.
+void launch_match_pair(const MatchPair& pr, const EpipolarGate& gate, const CodeSet& q, const CodeSet& t,
                        const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
 
 // --- Match lists (sift_hip_match_list_*): filter + ordered compaction of the

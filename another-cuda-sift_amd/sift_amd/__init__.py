@@ -82,6 +82,29 @@ class _MatchGate(ctypes.Structure):
     ]
 
 
+class _MatchEpipolarGate(ctypes.Structure):
+    """sift_hip_match_epipolar_gate: the positions as _MatchGate, the pair's fundamental matrix (row-major,
+    x_train^T F x_query = 0) and the band's half-width (Sampson distance, pixels)."""
+    _fields_ = [
+        ("query_xy", ctypes.c_void_p),
+        ("query_stride", ctypes.c_int),
+        ("train_xy", ctypes.c_void_p),
+        ("train_stride", ctypes.c_int),
+        ("radius", ctypes.c_float),
+        ("F", ctypes.c_float * 9),
+        ("max_error", ctypes.c_float),
+    ]
+
+
+def _epipolar_gate(q_xy_ptr: int, q_stride: int, t_xy_ptr: int, t_stride: int, radius: float, F,
+                   max_error: float) -> _MatchEpipolarGate:
+    f = np.asarray(F, np.float32).reshape(-1)
+    if f.size != 9:
+        raise ValueError("F must have 9 entries (3 x 3, row-major)")
+    return _MatchEpipolarGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius,
+                              (ctypes.c_float * 9)(*f.tolist()), max_error)
+
+
 class _MatchFilter(ctypes.Structure):
     _fields_ = [
         ("ratio", ctypes.c_float),
@@ -192,6 +215,12 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.POINTER(_MatchFilter), vp, vp, vp]),
         "sift_hip_match_list_guided_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate),
                                                 ctypes.POINTER(_MatchFilter), vp, i, ip]),
+        "sift_hip_match_epipolar_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate), f, i, vp, vp, vp,
+                                               vp]),
+        "sift_hip_match_list_epipolar_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate),
+                                                    ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_epipolar_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate),
+                                                  ctypes.POINTER(_MatchFilter), vp, i, ip]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -829,6 +858,44 @@ class Matcher:
                                                      _ptr(out), len(out), ctypes.byref(n)), "match_list_guided_host")
         return out[: n.value]
 
+    # --- guided matching under a fundamental matrix: the same operations with the epipolar gate (the rule:
+    # include/sift_hip.h, and in numpy sift_amd.cv.epipolar_mask / epipolar_top2).  F: 9 floats, row-major, with
+    # x_train^T F x_query = 0; train row t is a candidate of query i when its Sampson distance is <= max_error and it
+    # lies in the window `radius` (inf: none).  The launch shape is guided_plan's.
+
+    def match_epipolar_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                              max_error: float, radius: float = float("inf"), q_stride: int = 3, t_stride: int = 3,
+                              ratio: float = 0.8, ratio_on_squared: bool = False, idx2_ptr: int = 0, d2_ptr: int = 0,
+                              match_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """match_device over each query's candidates only (sift_hip_match_epipolar_device)."""
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        _check(lib().sift_hip_match_epipolar_device(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ratio,
+                                                    int(ratio_on_squared), idx2_ptr or None, d2_ptr or None,
+                                                    match_ptr or None, stream), "match_epipolar_device")
+
+    def match_list_epipolar_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                   max_error: float, out_ptr: int, count_ptr: int, radius: float = float("inf"),
+                                   q_stride: int = 3, t_stride: int = 3, stream: Optional[int] = None,
+                                   **filter) -> None:
+        """match_list_device with the epipolar top-2 of both directions (sift_hip_match_list_epipolar_device)."""
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_epipolar_device(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ctypes.byref(f),
+                                                         out_ptr or None, count_ptr or None, stream),
+               "match_list_epipolar_device")
+
+    def match_list_epipolar_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                 max_error: float, radius: float = float("inf"), q_stride: int = 3, t_stride: int = 3,
+                                 **filter) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_list_epipolar_host)."""
+        out = np.zeros(max(nq, 0), DMATCH_DTYPE)
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        f = _match_filter(**filter)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_list_epipolar_host(self._m, q_ptr, nq, t_ptr, nt, ctypes.byref(g), ctypes.byref(f),
+                                                       _ptr(out), len(out), ctypes.byref(n)), "match_list_epipolar_host")
+        return out[: n.value]
+
 
 _default_matcher: Optional[Matcher] = None
 
@@ -869,6 +936,22 @@ def matchListGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffe
     qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
     return m.match_list_guided_host(des.data(), num_des, src.data(), num_src, qxy, txy, radius, des_stride, src_stride,
                                     **filter)
+
+
+def matchListEpipolar(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, F,
+                      max_error: float, radius: float = float("inf"), des_stride: int = 3, src_stride: int = 3,
+                      **filter) -> np.ndarray:
+    """matchList under a fundamental matrix: row t of src is a candidate of row i of des when it lies within
+    `max_error` pixels (Sampson distance) of i's epipolar line under F -- 9 floats, row-major, x_src^T F x_des = 0,
+    what cv.findFundamentalMat(des_points, src_points) returns -- and inside the window `radius` when that is finite
+    (the rule: sift_amd.cv.epipolar_mask).  The top-2 search of both directions, the ratio test and the cross check
+    see candidates only.  des_xy / src_xy and the `filter` keywords as matchListGuided."""
+    m = _list_matcher(num_des, num_src)
+    if num_des <= 0 or num_src <= 0:
+        return np.zeros(0, DMATCH_DTYPE)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    return m.match_list_epipolar_host(des.data(), num_des, src.data(), num_src, qxy, txy, F, max_error, radius,
+                                      des_stride, src_stride, **filter)
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

@@ -153,12 +153,42 @@ def gate_mask(q_xy, t_xy, radius) -> np.ndarray:
         return (dx <= r) & (dy <= r)
 
 
-def guided_top2(q, t, q_xy, t_xy, radius):
-    """Matcher.match_guided_device in numpy: (idx2, d2), (nq, 2) int32 / float32 laid out as match_device writes
-    them -- the two nearest candidates (gate_mask) of every query, ties to the lower train index, -1 / FLT_MAX where
-    there is none.  Squared distances come from an exact integer product when both sets hold integers, otherwise
-    from float64 (exact for the values the tests use), and are rounded to float32 once.  filter_matches consumes the
-    output unchanged."""
+def epipolar_mask(q_xy, t_xy, F, max_error, radius=np.inf) -> np.ndarray:
+    """The epipolar gate of include/sift_hip.h in numpy float32: an (nq, nt) bool array, True where train row t is a
+    candidate of query i.  F: 9 floats, row-major, x_train^T F x_query = 0.  Every operation is one float32 operation
+    rounded to nearest, in the header's order (numpy fuses nothing):
+        per query   a = (F00 qx + F01 qy) + F02, b = (F10 qx + F11 qy) + F12, c = (F20 qx + F21 qy) + F22, nq = a a + b b
+        per train   u = (F00 tx + F10 ty) + F20, v = (F01 tx + F11 ty) + F21, nr = u u + v v
+        per pair    r = (a tx + b ty) + c;  candidate when r r <= (max_error max_error) (nq + nr) and gate_mask(radius)
+    -- the Sampson distance <= max_error, inclusive.  A NaN anywhere is a candidate of nothing."""
+    q = np.asarray(q_xy, np.float32).reshape(len(q_xy), -1)[:, :2]
+    t = np.asarray(t_xy, np.float32).reshape(len(t_xy), -1)[:, :2]
+    f = np.asarray(F, np.float32).reshape(-1)
+    if f.size != 9:
+        raise ValueError("F must have 9 entries (3 x 3, row-major)")
+    e = np.float32(max_error)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        qx, qy, tx, ty = q[:, 0], q[:, 1], t[:, 0], t[:, 1]
+        a = (f[0] * qx + f[1] * qy) + f[2]
+        b = (f[3] * qx + f[4] * qy) + f[5]
+        c = (f[6] * qx + f[7] * qy) + f[8]
+        nq = a * a + b * b
+        u = (f[0] * tx + f[3] * ty) + f[6]
+        v = (f[1] * tx + f[4] * ty) + f[7]
+        nr = u * u + v * v
+        r = (a[:, None] * tx[None, :] + b[:, None] * ty[None, :]) + c[:, None]
+        e2 = e * e
+        band = r * r <= e2 * (nq[:, None] + nr[None, :])
+    assert r.dtype == np.float32 and nq.dtype == np.float32 and nr.dtype == np.float32
+    return band & gate_mask(q, t, radius)
+
+
+def mask_top2(q, t, cand):
+    """The top-2 of a candidate mask: (idx2, d2), (nq, 2) int32 / float32 laid out as match_device writes them -- the
+    two nearest rows of t among cand[i] for every row i of q, ties to the lower train index, -1 / FLT_MAX where there
+    is none.  Squared distances come from an exact integer product when both sets hold integers, otherwise from
+    float64 (exact for the values the tests use), and are rounded to float32 once.  cand: the (nq, nt) bool array, or
+    a function returning it, called only when neither set is empty."""
     q, t = np.asarray(q), np.asarray(t)
     nq, nt = len(q), len(t)
     idx2 = np.full((nq, 2), -1, np.int32)
@@ -168,7 +198,7 @@ def guided_top2(q, t, q_xy, t_xy, radius):
     exact = np.int64 if (np.all(q == np.rint(q)) and np.all(t == np.rint(t))) else np.float64
     a, b = q.astype(exact), t.astype(exact)
     dist = (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2 * (a @ b.T)
-    cand = gate_mask(q_xy, t_xy, radius)
+    cand = np.asarray(cand() if callable(cand) else cand, bool)
     if cand.shape != dist.shape:
         raise ValueError("positions and descriptor sets differ in length")
     order = np.argsort(np.where(cand, dist, np.inf), axis=1, kind="stable")[:, :2]  # stable: ties to the lower index
@@ -179,6 +209,18 @@ def guided_top2(q, t, q_xy, t_xy, radius):
         idx2[ok, k] = j[ok]
         d2[ok, k] = dist[rows, j][ok]
     return idx2, d2
+
+
+def guided_top2(q, t, q_xy, t_xy, radius):
+    """Matcher.match_guided_device in numpy: the top-2 (mask_top2) of every query among its candidates (gate_mask).
+    filter_matches consumes the output unchanged."""
+    return mask_top2(q, t, lambda: gate_mask(q_xy, t_xy, radius))
+
+
+def epipolar_top2(q, t, q_xy, t_xy, F, max_error, radius=np.inf):
+    """Matcher.match_epipolar_device in numpy: the top-2 (mask_top2) of every query among its candidates
+    (epipolar_mask).  The reverse direction of a cross check is epipolar_top2(t, q, t_xy, q_xy, F^T, ...)."""
+    return mask_top2(q, t, lambda: epipolar_mask(q_xy, t_xy, F, max_error, radius))
 
 
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):

@@ -190,4 +190,18 @@ std::vector<DMatch> matchListGuided(const DeviceBuffer<Half>& des, int num_des, 
 std::vector<int> matchGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
                              const MatchGate& gate);
 
+// Extra: matchListGuided / matchGuided under a fundamental matrix
+// (sift_hip_match_list_epipolar_host, sift_hip_match_epipolar_device): row t of
+// src is a candidate of row i of des when it lies within gate.max_error pixels
+// (Sampson distance) of i's epipolar line under gate.F, and inside the window
+// gate.radius when that is finite -- COLMAP's guided match, ORB-SLAM's
+// SearchForTriangulation.  F from the relative pose of two keyframes, a stereo
+// rig, or a RANSAC pass over matchList's output; the rule is spelled out in
+// include/sift_hip.h.  A bad gate (as above, or a max_error that is not > 0 and
+// finite, a non-finite or all-zero F) throws std::invalid_argument.
+std::vector<DMatch> matchListEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                      int num_src, const EpipolarGate& gate, const MatchFilter& filter = {});
+std::vector<int> matchEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                               const EpipolarGate& gate);
+
 }  // namespace sift_cuda

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 
 namespace sift_cuda {
 
@@ -83,6 +84,21 @@ struct MatchGate {
     const float* train_xy = nullptr;
     int train_stride = 3;
     float radius = 0.f;            // pixels, > 0; infinity: no gate
+};
+
+// The gate of matchListEpipolar / matchEpipolar (sift_hip_match_epipolar_gate,
+// include/sift_hip.h): the positions as MatchGate's, the fundamental matrix of
+// the pair and the width of the band round a query's epipolar line.  A train
+// row is a candidate of a query when its Sampson distance under F is at most
+// max_error pixels and it lies in the query's window (radius; infinity: none).
+struct EpipolarGate {
+    const float* query_xy = nullptr;
+    int query_stride = 3;
+    const float* train_xy = nullptr;
+    int train_stride = 3;
+    float radius = std::numeric_limits<float>::infinity();
+    float F[9] = {};               // row-major, x_train^T F x_query = 0 (cv::findFundamentalMat(query, train))
+    float max_error = 0.f;         // pixels, > 0 and finite
 };
 
 // Non-owning view of a device array owned by a Detector (stands in for the

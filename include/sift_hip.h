@@ -658,6 +658,78 @@ int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* query,
                                     const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
                                     sift_hip_dmatch* out_host, int cap, int* count);
 
+/* --- Guided matching under a fundamental matrix (the epipolar gate) -----------
+ *
+ * The gate of two-view geometry: COLMAP's and SiftGPU's guided match, ORB-SLAM's
+ * SearchForTriangulation.  The caller knows F -- from the relative pose of two
+ * keyframes, a calibrated stereo rig, or a first RANSAC pass over a match list
+ * -- but not where on its epipolar line a point lands, so no predicted position
+ * and no radius expresses it.  As with the window, the two nearest rows inside
+ * the band are not the global top-2.  (A homography needs nothing new: project
+ * the query positions and use the window above.)
+ *
+ * The rule.  F is 9 floats, row-major, with x_train^T F x_query = 0: the matrix
+ * cv::findFundamentalMat(query_points, train_points) returns.  Positions are
+ * read as for sift_hip_match_gate.  All arithmetic is float32, round to
+ * nearest, in exactly this order, and no multiply-add is fused:
+ *   per query (qx, qy):   a = (F[0]*qx + F[1]*qy) + F[2]
+ *                         b = (F[3]*qx + F[4]*qy) + F[5]
+ *                         c = (F[6]*qx + F[7]*qy) + F[8]
+ *                         nq = a*a + b*b
+ *   per train (tx, ty):   u = (F[0]*tx + F[3]*ty) + F[6]
+ *                         v = (F[1]*tx + F[4]*ty) + F[7]
+ *                         nr = u*u + v*v
+ *   per pair:             r = (a*tx + b*ty) + c
+ *                         e2 = max_error*max_error
+ * Train row t is a candidate of query i when
+ *   r*r <= e2 * (nq + nr)
+ *   && fabsf(tx - qx) <= radius && fabsf(ty - qy) <= radius
+ * -- the Sampson distance <= max_error, inclusive, inside the window (radius =
+ * +inf: no window; a stereo or SLAM caller bounds the search along the line
+ * with it).  A NaN anywhere makes a compare false, so its row is a candidate of
+ * nothing; in the overflow and degenerate cases the formula is the rule.
+ * sift_amd.cv.epipolar_mask is the same rule in numpy.
+ *
+ * The reverse direction of a cross check is the same formula with the roles
+ * swapped and F transposed (the library transposes).  In real arithmetic the
+ * predicate is symmetric; in float32 a pair within rounding of the threshold
+ * may be a candidate in one direction only.  The list rule is unchanged: the
+ * match-list filter on the two guided top-2 arrays.
+ *
+ * Everything else is as under sift_hip_match_gate: the same squared distances,
+ * ties to the lower train index, an absent neighbour -1 / FLT_MAX, a query with
+ * one candidate matches it, one pair per call, the same routes (sidecar codes,
+ * or converted first; non-integer sets on the general path).  The launch shape
+ * is the window gate's: sift_hip_match_guided_plan describes it. */
+typedef struct {
+    const float* query_xy; /* device; as sift_hip_match_gate */
+    int query_stride;      /* floats per row, >= 2 */
+    const float* train_xy;
+    int train_stride;
+    float radius;          /* pixels, > 0; +inf = no window */
+    float F[9];            /* row-major; x_train^T F x_query = 0 */
+    float max_error;       /* Sampson distance in pixels, > 0 and finite */
+} sift_hip_match_epipolar_gate;
+
+/* sift_hip_match_guided_device under the epipolar gate.  SIFT_HIP_ERR_INVALID,
+ * with nothing launched, for: a null matcher or gate, a stride < 2, a radius
+ * that is not > 0, a max_error that is not > 0 or not finite, a non-finite entry
+ * of F or F all zero, a size over the matcher's limits, a null descriptor or
+ * position pointer of a non-empty set.  Empty sets as in the guided calls. */
+int sift_hip_match_epipolar_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                   const sift_hip_match_epipolar_gate* gate, float ratio, int ratio_on_squared,
+                                   int* idx2, float* d2, int* match, void* stream);
+
+/* sift_hip_match_list_guided_device / _host under the epipolar gate. */
+int sift_hip_match_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                        int nt, const sift_hip_match_epipolar_gate* gate,
+                                        const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count,
+                                        void* stream);
+int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                      int nt, const sift_hip_match_epipolar_gate* gate,
+                                      const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap,
+                                      int* count);
+
 /* The launch plan a match call of this shape gets: train splits S per query
  * block (S > 1: split workgroups merge their top-2 through the scratch's
  * atomics) and waves per workgroup.  Host-only (no GPU call beyond reading the

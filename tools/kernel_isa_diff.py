@@ -7,8 +7,9 @@
 
 Per kernel (symbol .. function-end label) the text is compared after the local
 label numbers (.LBB<n>_, BB<n>_ in comments) are normalised; the resources are
-read from the compiler's own summary after the function.  Exit status 1 when a
-kernel's text differs.
+read from the compiler's own summary after the function.  A kernel of one build
+only is listed with its resources.  Exit status 1 when a kernel's text differs
+or a kernel is in one build only.
 """
 import argparse
 import json
@@ -59,7 +60,12 @@ def main():
     rep, same = {}, True
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
-            rep[k] = {"equal": False, "missing_in": "old" if k not in old else "new"}
+            # a kernel of one build only (added or removed): its resources, and no verdict on the others
+            side, d = ("new", new[k]) if k not in old else ("old", old[k])
+            rep[k] = {"equal": False, "missing_in": "old" if k not in old else "new",
+                      side: {**{r: d.get(r) for r in RES}, "instructions": len(insns(d["text"])),
+                             "counts": {p: sum(o.startswith(p) for o in insns(d["text"])) for p in a.count}}}
+            print(("added   " if k not in old else "removed ") + k, rep[k][side])
             same = False
             continue
         e = {"equal": old[k]["text"] == new[k]["text"]}
