@@ -48,7 +48,9 @@
 // A pair with a flagged set (non-integer or out-of-range fp16 values, e.g. the
 // reference's own unrounded x512 descriptors) runs the general path in the
 // same launch: v_mfma_f32_32x32x16_f16 dot products (exact products, fp32
-// sums), fp32 norms, a float top-2 in train order.
+// sums), fp32 norms, a float top-2 in train order; d^2 is clamped at 0 and a
+// query row holding NaN or an infinity has no neighbour (the contract: the
+// general-path paragraph of include/sift_hip.h).
 //
 // Shared core: one integer fold (chunk_top2) and one fp16 block
 // (match_f16_block), both templates on a gate policy (NoGate, the window of
@@ -404,6 +406,13 @@ __device__ Top2 match_f16_block(const MatchPair& pr, const Gate& g, int q0, int 
     }
     best.d1 += qn;
     best.d2 += qn;
+    // tn, qn and the dot product are three fp32 sums rounded apart, so a d^2 near 0 (a duplicate row) can come out
+    // below it: clamp (include/sift_hip.h, general path, item 1).  Every candidate of the query carries the same qn,
+    // so no selection changes, and match_key's bit order needs d^2 >= 0.  A query row holding NaN or an infinity
+    // (the only way to a qn that is not finite) has no neighbour: +Inf makes d = -Inf above, which would win.
+    if (!(qn < INFINITY)) best = Top2{INFINITY, INFINITY, kNone, kNone};
+    best.d1 = fmaxf(best.d1, 0.f);
+    best.d2 = fmaxf(best.d2, 0.f);
     return best;
 }
 

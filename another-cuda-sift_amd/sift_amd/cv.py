@@ -187,8 +187,11 @@ def mask_top2(q, t, cand):
     """The top-2 of a candidate mask: (idx2, d2), (nq, 2) int32 / float32 laid out as match_device writes them -- the
     two nearest rows of t among cand[i] for every row i of q, ties to the lower train index, -1 / FLT_MAX where there
     is none.  Squared distances come from an exact integer product when both sets hold integers, otherwise from
-    float64 (exact for the values the tests use), and are rounded to float32 once.  cand: the (nq, nt) bool array, or
-    a function returning it, called only when neither set is empty."""
+    float64 as |q|^2 + |t|^2 - 2 q.t, rounded to float32 once: exact (and compared byte for byte) where every product
+    and sum is representable, as for multiples of 0.5; for values where fp32 rounds it is the reference of a toleranced
+    comparison only (the bound of include/sift_hip.h; tests/general_cases.py sums (q_k - t_k)^2 instead, which is 0
+    for identical rows).  cand: the (nq, nt) bool array, or a function returning it, called only when neither set is
+    empty."""
     q, t = np.asarray(q), np.asarray(t)
     nq, nt = len(q), len(t)
     idx2 = np.full((nq, 2), -1, np.int32)

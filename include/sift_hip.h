@@ -446,7 +446,39 @@ int sift_hip_matcher_destroy(sift_hip_matcher_t m);
  * match[i] = idx2[2i] if d2[2i] < ratio^2 * d2[2i+1] (ratio on distances,
  * ratio_on_squared = 0) or d2[2i] < ratio * d2[2i+1] (ratio_on_squared = 1, the
  * reference's Match.cu:172 convention), else -1; a query with one train row
- * matches it.  Enqueued on `stream`. */
+ * matches it.  Enqueued on `stream`.
+ *
+ * The general path.  A set holding a value that is not an integer 0..255
+ * (unrounded x512 SIFT, RootSIFT, learned descriptors; -0.0, NaN and infinities
+ * count) is matched in fp16/fp32 instead of int8/int32: exact fp16 products,
+ * fp32 sums, d2 = |t|^2 - 2 q.t + |q|^2.  This holds for every match call of
+ * this header (single, batched, guided, epipolar, lists), for finite inputs:
+ *   1. Sign.  Every returned d2 is >= 0 and never NaN (three fp32 sums round
+ *      apart, so the raw value of a duplicate row can be below 0: it is clamped
+ *      to 0); its sqrt, and so every sift_hip_dmatch.distance, is finite.
+ *   2. Accuracy.  With D = sum_k (q_k - t_k)^2 in float64 on the fp16 values,
+ *      |d2 - D| <= B = 136 * 2^-23 * (|q|^2 + |t|^2 + 2 sum_k |q_k| |t_k|):
+ *      three sums of 128 exact products in any order ((n - 1) u sum |terms|),
+ *      9 combining operations, u = 2^-23 allowing for a truncating MFMA.
+ *   3. Indices.  With D1 <= D2 <= D3 the query's three smallest D among its
+ *      candidates and Bq its largest B: D[i1] <= D1 + 2 Bq, D[i2] <= D2 + 2 Bq,
+ *      i1 != i2; where D2 - D1 > 2 Bq and D3 - D2 > 2 Bq the indices are the
+ *      float64 order's exactly.
+ *   4. Duplicates.  Train rows of identical bytes get bit-identical d2 for any
+ *      query, and their tie goes to the lower index in every merge, across
+ *      splits too.
+ *   5. Routes.  idx2 and d2 of one pair are the same bytes through
+ *      sift_hip_match_device, sift_hip_match_batched (one pair or several),
+ *      sift_hip_match_guided_device with radius = inf and
+ *      sift_hip_match_epipolar_device with every row a candidate.
+ *   6. match, and every list, are the rules of this header applied to the
+ *      returned idx2 / d2 themselves (float32).
+ *   7. Special values.  A train row holding NaN or +-Inf is nobody's neighbour;
+ *      a query row holding one gets (-1, -1, FLT_MAX, FLT_MAX) and match -1;
+ *      every other query gets the bytes it would get with those train rows
+ *      deleted.  -0.0 selects the path but is the value 0.
+ * On integer sets 0..255 the general path returns the integer path's bytes
+ * (every sum is an integer below 2^24). */
 int sift_hip_match_device(sift_hip_matcher_t m, const uint16_t* query, int nq,
                           const uint16_t* train, int nt, float ratio, int ratio_on_squared,
                           int* idx2, float* d2, int* match, void* stream);

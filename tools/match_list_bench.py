@@ -17,9 +17,10 @@ usable (device sync for a-c -- the list stays on the device --, the finished hos
 such calls.  Passes of every leg alternate (a, b, c, d, a, ...), so clock and neighbour drift hit all alike; reported
 per leg: the median of the passes and their range.  Results are checked first: leg c's records must equal leg d's.
 
---parent-lib: a libsift_hip.so built from the parent commit.  match_device (leg a, both routes) is then timed in
-child processes alternating between this build and that one (SIFT_HIP_LIB), one interleaved pair per pass: its
-kernels are untouched, so the two should agree within the spread.  Written as measured."""
+--parent-lib: a libsift_hip.so built from the parent commit.  match_device (leg a, both routes, and
+`foreign_general`: the foreign rows halved, which takes the general fp16 path) is then timed in child processes
+alternating between this build and that one (SIFT_HIP_LIB), one interleaved pair per pass: where its kernels are
+untouched the two should agree within the spread.  Written as measured."""
 import argparse
 import json
 import os
@@ -153,8 +154,14 @@ def measure(legs, passes, calls):
 
 
 def child(calls):
-    """match_device alone on both routes (this process's library: SIFT_HIP_LIB or the default build)."""
+    """match_device alone on both routes (this process's library: SIFT_HIP_LIB or the default build), and on the
+    foreign rows halved (`foreign_general`: non-integer values, so the general fp16 path of k_match_single)."""
+    import torch
+
     _det, bufs, _keep = setup()
+    halved = [(rows.view(torch.float16) * 0.5).contiguous() for rows in _keep]
+    torch.cuda.synchronize()
+    bufs["foreign_general"] = (halved[0].data_ptr(), halved[1].data_ptr())
     out = {"library": sift.version()}
     for route, (q, t) in bufs.items():
         legs = Legs(q, t, 1)
@@ -182,7 +189,7 @@ def parent_pairs(parent_lib, passes, calls):
             pair[name] = json.loads(line[-1][6:])
         rows.append(pair)
     out = {"pairs": rows}
-    for route in ("detector", "foreign"):
+    for route in ("detector", "foreign", "foreign_general"):
         a, b = [p["this"][route] for p in rows], [p["parent"][route] for p in rows]
         out[route] = {"this_us": summary(a), "parent_us": summary(b),
                       "this_over_parent": round(float(np.median(a)) / float(np.median(b)), 3)}
