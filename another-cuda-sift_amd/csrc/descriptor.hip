@@ -10,9 +10,11 @@
 //   * k_bucket_rank already computed the keypoint's window (DescJob), read
 //     here with scalar loads;
 //   * only samples inside the rotated 4x4-cell square are enumerated: per row
-//     a conservative j-interval, a prefix sum over rows, and each lane takes a
-//     contiguous run of the enumerated samples (the oracle's exact per-sample
-//     test is still applied, so the set of samples is unchanged);
+//     the exact j-interval of the oracle's per-sample test (sift_desc_rows.h:
+//     a conservative interval, its ends moved inward while the test fails),
+//     a prefix sum over rows, and each lane takes a contiguous run of the
+//     enumerated samples; the set of samples is the oracle's, and the sample
+//     loop carries no test;
 //   * gradients are read straight from the Gaussian plane (L1/L2 resident:
 //     neighbouring keypoints share it) with bounds-checked buffer loads, four
 //     samples' loads in flight per lane;
@@ -36,13 +38,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
+#include "sift_desc_rows.h"
 #include "sift_kernels.h"
 #include "sift_math.h"
 
 namespace sift_amd {
 
 constexpr int kD = 4, kN = 8;
+static_assert(kD == kDescD, "sift_desc_rows.h tests the same d x d grid");
 constexpr int kCells = (kD + 2) * (kD + 2);  // 36 spatial cells incl. the border ring
 constexpr int kCellW = 10;                   // dwords per cell in each fixed-point histogram
 constexpr int kMaxRows = kDescMaxRows;       // enumerated windows: side = 2R+1 <= kMaxRows
@@ -126,28 +131,16 @@ __device__ __forceinline__ void trilinear(float mag, float rbf, float cbf, float
     v[0] = lo_b[1];
 }
 
-// Shrink [lo, hi] to a superset of the integers j with -1 < j*s + b < kD
-// (margin 1e-4 in bin units and one sample each side, so float rounding of the
-// exact per-sample test can never fall outside the enumerated range).
-// inv_s = 1 / s (computed once per keypoint).  Float: the bounds before
-// clamping to +-(R+2) carry a relative error of a few 1e-7, i.e. < 1e-4
-// samples for R <= 50, far inside the one-sample margin each side.
-__device__ __forceinline__ void clip_interval(int& lo, int& hi, float s, float inv_s, float b, int R) {
-    constexpr float lb = -1.f - 1e-4f, ub = kD + 1e-4f;
-    if (fabsf(s) < 1e-12f) {
-        if (b <= lb || b >= ub) hi = lo - 1;
-        return;
-    }
-    float x1 = (lb - b) * inv_s, x2 = (ub - b) * inv_s;
-    if (x1 > x2) {
-        const float t = x1;
-        x1 = x2;
-        x2 = t;
-    }
-    x1 = fmaxf(x1, (float)(-R - 2));
-    x2 = fminf(x2, (float)(R + 2));
-    lo = max(lo, (int)floorf(x1) - 1);
-    hi = min(hi, (int)ceilf(x2) + 1);
+// Samples j of window row t (i = t - radius) that the oracle's test accepts:
+// the image clipping (rows 1 .. rows-2, columns 1 .. cols-2), then the exact
+// interval of the bin test (sift_desc_rows.h).  Empty rows return hi < lo.
+__device__ __forceinline__ void desc_row(const DescGeom& G, int t, int side, int radius, float inv_cos, float inv_sin,
+                                         int& lo, int& hi) {
+    const int i = t - radius, r = G.pty + i;
+    lo = max(-radius, 1 - G.ptx);
+    hi = min(radius, G.cols - 2 - G.ptx);
+    if (r <= 0 || r >= G.rows - 1 || t >= side) hi = lo - 1;
+    desc_row_interval(lo, hi, i, G.cos_t, G.sin_t, inv_cos, inv_sin, radius);
 }
 
 // Sample math with native gfx950 instructions (v_rcp_f32, v_sqrt_f32,
@@ -285,11 +278,8 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
         if (enumerated) {
             const float inv_sin = __builtin_amdgcn_rcpf(G.sin_t), inv_cos = __builtin_amdgcn_rcpf(G.cos_t);
             for (int t = tid; t < side; t += kDT) {
-                const int i = t - radius, r = G.pty + i;
-                int lo = max(-radius, 1 - G.ptx), hi = min(radius, G.cols - 2 - G.ptx);
-                if (r <= 0 || r >= G.rows - 1) hi = lo - 1;
-                clip_interval(lo, hi, G.sin_t, inv_sin, (float)i * G.cos_t + (kD / 2 - 0.5f), radius);
-                clip_interval(lo, hi, G.cos_t, inv_cos, -(float)i * G.sin_t + (kD / 2 - 0.5f), radius);
+                int lo, hi;
+                desc_row(G, t, side, radius, inv_cos, inv_sin, lo, hi);
                 const int len = max(hi - lo + 1, 0);
                 rowlo[t] = lo;
                 rowln[t] = len;
@@ -324,16 +314,23 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
         const float fxs = ldexpf(1.f, S);
         lds_barrier();
 
-        // One sample from its four neighbours (l, r, u, d).  Branch-free so
-        // that the kGroup samples of a group interleave (ILP): a rejected
-        // sample keeps in-range bin indices and adds zeros.
-        auto accum_rot = [&](float c_rot, float r_rot, bool valid, float l, float r, float u, float d) {
+        // One sample from its gradient (dx, dy) = (r - l, u - d).  Branch-free so
+        // that the kGroup samples of a group interleave (ILP).  Two forms:
+        //   * tested (raster path): the oracle's bin test per sample; a
+        //     rejected sample keeps in-range bin indices (the clamps) and adds
+        //     zeros (the 0/1 factor);
+        //   * enumerated (tested = false_type): the caller hands in only
+        //     samples of the rows' exact intervals (desc_row), which pass the
+        //     test by construction, so rbin and cbin are in (-1, kD) and the
+        //     floors in [-1, kD - 1] without a compare or a clamp; `valid`
+        //     only zeroes the magnitude (the filler half of an odd item).
+        auto accum_rot = [&](auto tested, float c_rot, float r_rot, bool valid, float dx, float dy) {
+            constexpr bool kTested = decltype(tested)::value;
             // (cbin, rbin) and the squared radius as packed pairs (IEEE per half).
             const f32x2t rot = {c_rot, r_rot};
             const f32x2t bins = (rot + (f32x2t){(float)(kD / 2), (float)(kD / 2)}) - (f32x2t){0.5f, 0.5f};
             float cbin = bins[0], rbin = bins[1];
-            valid = valid && rbin > -1 && rbin < kD && cbin > -1 && cbin < kD;
-            const float dx = r - l, dy = u - d;
+            if (kTested) valid = valid && rbin > -1 && rbin < kD && cbin > -1 && cbin < kD;
             const f32x2t sq = rot * rot;
             // exp_scale = -1/8 is a power of two, so (r2 * -1/8) * log2(e)
             // = r2 * (-log2(e) / 8) with the same single rounding: one multiply.
@@ -344,11 +341,14 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
             // x 2^S (exact): the trilinear parts come out in fixed-point units.
             // A select, not a branch around the product (every operand is
             // finite: enumerated samples are in-image).
-            const float mag = (gmag * wgt * fxs) * (valid ? 1.f : 0.f);
+            // (Enumerated form: the select sits on the scale, a filler's
+            // magnitude is gmag * wgt * 0 -- one v_cndmask, and none where
+            // `valid` is a constant.)
+            const float mag = kTested ? (gmag * wgt * fxs) * (valid ? 1.f : 0.f) : gmag * wgt * (valid ? fxs : 0.f);
             // cvFloor in the float domain (the clamp only guards rejected
             // samples): r - floor(r) is the oracle's r - (float)cvFloor(r).
-            const float r0f = fminf(fmaxf(floorf(rbin), -1.f), (float)(kD - 1));
-            const float c0f = fminf(fmaxf(floorf(cbin), -1.f), (float)(kD - 1));
+            const float r0f = kTested ? fminf(fmaxf(floorf(rbin), -1.f), (float)(kD - 1)) : floorf(rbin);
+            const float c0f = kTested ? fminf(fmaxf(floorf(cbin), -1.f), (float)(kD - 1)) : floorf(cbin);
             const float o0f = floorf(obin);
             rbin -= r0f;
             cbin -= c0f;
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
         auto accumulate = [&](int i, int j, bool in, float l, float r, float u, float d) {
             float rbin, cbin, c_rot, r_rot;
             const bool valid = desc_sample(G, i, j, rbin, cbin, c_rot, r_rot) && in;
-            accum_rot(c_rot, r_rot, valid, l, r, u, d);
+            accum_rot(std::true_type{}, c_rot, r_rot, valid, r - l, u - d);
         };
         // Gradient loads of up to kGroup samples, then their accumulation.
         // Samples outside the plane read 0 (buffer range check) and are
@@ -404,13 +404,18 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
             // Work items of kItem (2) consecutive samples of one row: their
             // neighbours come in as one 16-byte and two 8-byte loads instead of
             // four dword loads per sample, and i * sin / i * cos are shared.  Each thread takes a contiguous run
-            // of items.  Rows hold only in-image samples (the intervals are
-            // clipped to 1 .. cols-2 / rows 1 .. rows-2), so validity is the
-            // oracle's bin-range test alone.
+            // of items.  Rows hold exactly the samples the oracle accepts
+            // (desc_row: in-image and inside the bin range), so the loop has
+            // no per-sample test; the one filler is the second half of an
+            // item at an odd row end, which takes the first half's
+            // coordinates (in-range bins) and magnitude 0.
+            // Balanced runs: N = kDT * q + rem items, the first rem threads
+            // take q + 1 and the rest q, so a wave whose threads all have q
+            // loops one step less than ceil(N / kDT).
             const int N = rowpre[side];
-            const int run = (N + kDT - 1) / kDT;
+            const int q = N / kDT, rem = N % kDT;
             const int tq = tid;  // this thread's run
-            const int k0 = min(N, tq * run), k1 = min(N, k0 + run);
+            const int k0 = tq * q + min(tq, rem), k1 = k0 + q + (tq < rem ? 1 : 0);
             if (k0 < k1) {
                 int lo = 0, hi = side - 1;  // last row with rowpre[row] <= k0 (non-empty)
                 while (lo < hi) {
@@ -429,24 +434,25 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
                     const int cnt = jend - jj;
                     const unsigned o = (unsigned)((G.pty + i) * jb.pitch + G.ptx + jj) * 4u;
                     // (x-1 .. x+kItem) of the row, (x .. x+kItem-1) of the rows above and below.
-                    float row6[kItem + 2], up[kItem], dn[kItem];
-                    {
-                        const f32x4d cm = __builtin_bit_cast(f32x4d, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o - 4u, 0, 0));
-                        static_assert(kItem == 2, "items of two samples");
-                        const f32x2d u2 = __builtin_bit_cast(f32x2d, __builtin_amdgcn_raw_buffer_load_b64(rsrc, o - pitch4, 0, 0));
-                        const f32x2d d2 = __builtin_bit_cast(f32x2d, __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + pitch4, 0, 0));
-                        for (int t = 0; t < 2; t++) up[t] = u2[t], dn[t] = d2[t];
-                        for (int t = 0; t < 4; t++) row6[t] = cm[t];
-                    }
+                    // Both samples' gradients as two packed subtracts on the
+                    // registers the loads fill (dx = (x+1, x+2) - (x-1, x):
+                    // the b128 load's upper minus its lower half; dy = up -
+                    // down), so no operand pair has to be assembled by moves.
+                    static_assert(kItem == 2, "items of two samples");
+                    const f32x4d cm = __builtin_bit_cast(f32x4d, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o - 4u, 0, 0));
+                    const f32x2d u2 = __builtin_bit_cast(f32x2d, __builtin_amdgcn_raw_buffer_load_b64(rsrc, o - pitch4, 0, 0));
+                    const f32x2d d2 = __builtin_bit_cast(f32x2d, __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + pitch4, 0, 0));
+                    const f32x2d dx2 = cm.zw - cm.xy, dy2 = u2 - d2;
                     const float fi = (float)i, is = fi * G.sin_t, ic = fi * G.cos_t;
 #pragma unroll
                     for (int t = 0; t < kItem; t++) {
-                        const float fj = (float)(jj + t);
+                        const bool real = t == 0 || t < cnt;  // cnt >= 1: the first half is a row sample
+                        const float fj = (float)(real ? jj + t : jj);
                         // desc_sample's rotation, operation for operation
                         // (c = j*cos - i*sin, r = j*sin + i*cos), packed.
                         const f32x2t pr = (f32x2t){fj, fj} * (f32x2t){G.cos_t, G.sin_t};
                         const f32x2t rot = pr + (f32x2t){-is, ic};
-                        accum_rot(rot[0], rot[1], t < cnt, row6[t], row6[t + 2], up[t], dn[t]);
+                        accum_rot(std::false_type{}, rot[0], rot[1], real, dx2[t], dy2[t]);
                         // One sample at a time: interleaving the four keeps
                         // ~90 VGPRs live (occupancy 5 instead of 8 waves/SIMD).
                         __builtin_amdgcn_sched_barrier(0);
@@ -686,11 +692,9 @@ __global__ __launch_bounds__(kExactWG, kExactMinWaves) void k_descriptor_exact(c
             int len2[2];
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                const int t = 2 * lane + h, i = t - radius, r = G.pty + i;
-                int lo = max(-radius, 1 - G.ptx), hi = min(radius, G.cols - 2 - G.ptx);
-                if (r <= 0 || r >= G.rows - 1 || t >= side) hi = lo - 1;
-                clip_interval(lo, hi, G.sin_t, inv_sin, (float)i * G.cos_t + (kD / 2 - 0.5f), radius);
-                clip_interval(lo, hi, G.cos_t, inv_cos, -(float)i * G.sin_t + (kD / 2 - 0.5f), radius);
+                const int t = 2 * lane + h;
+                int lo, hi;
+                desc_row(G, t, side, radius, inv_cos, inv_sin, lo, hi);
                 len2[h] = max(hi - lo + 1, 0);
                 if (t < side) rowlo[t] = lo;
             }
