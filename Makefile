@@ -21,12 +21,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CXXFLAGS := -O2 -std=c++17 -fPIC -Iinclude -Wall -Wextra
 
 HIP_SRCS := $(SRC)/detector.hip $(SRC)/lanes.hip $(SRC)/datagen.hip $(SRC)/matcher_api.hip $(SRC)/pyramid.hip $(SRC)/keypoints.hip $(SRC)/descriptor.hip $(SRC)/match.hip \
-            $(SRC)/multi.hip
+            $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/verify_api.hip
 HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OUT)/obj/%.o,$(HIP_SRCS)) $(OUT)/obj/synth_frame.o
 
 all: $(OUT)/libsift_hip.so $(OUT)/libsift_cuda.so tools
 
-$(OUT)/obj/%.o: $(SRC)/%.hip $(SRC)/detector_state.h $(SRC)/sift_kernels.h $(SRC)/sift_math.h $(SRC)/sift_match.h $(SRC)/sift_refine.h $(SRC)/sift_desc_rows.h include/sift_hip.h
+$(OUT)/obj/%.o: $(SRC)/%.hip $(SRC)/detector_state.h $(SRC)/sift_kernels.h $(SRC)/sift_math.h $(SRC)/sift_match.h $(SRC)/sift_refine.h $(SRC)/sift_desc_rows.h $(SRC)/sift_epipolar.h $(SRC)/sift_verify.h include/sift_hip.h
 	@mkdir -p $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -38,7 +38,7 @@ $(OUT)/libsift_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS) -ldl -L$(ROCM_LIB) -lrocprofiler-sdk-roctx \
 	    -Wl,-rpath,$(ROCM_LIB) -Wl,-soname,libsift_hip.so
 
-CXX_SRCS := $(SRC)/detector_cxx.cpp $(SRC)/multi_cxx.cpp
+CXX_SRCS := $(SRC)/detector_cxx.cpp $(SRC)/multi_cxx.cpp $(SRC)/verify_cxx.cpp
 
 $(OUT)/libsift_cuda.so: $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	$(CXX) $(CXXFLAGS) -pthread -shared -o $@ $(CXX_SRCS) -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN'
@@ -64,12 +64,18 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_multi.cpp $(CXX_SRCS) \
+	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
+
+# Argument validation of the verifier's C++ surface (verify_cxx.cpp), CPU only: tests/test_verify_asan.py.
+$(ASAN_DIR)/test_verify_args: tests/cpp/test_verify_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
+	@mkdir -p $(ASAN_DIR)
+	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_verify_args.cpp $(SRC)/verify_cxx.cpp \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
 clean:

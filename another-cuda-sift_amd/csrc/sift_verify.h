@@ -1,0 +1,58 @@
+// Two-view verifier launch interface (verify.hip) used by verify_api.hip's C
+// ABI (sift_hip_verify_*; the rule is in include/sift_hip.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sift_match.h"
+
+namespace sift_amd {
+
+constexpr int kVerifyMaxMatches = 65536;
+constexpr int kVerifyMaxHypotheses = 4096;
+
+// The match list as the kernels take it: `cap` records, of which
+// n = min(max(*count, 0), cap) count (count == nullptr: n = cap), and the
+// position rows the records index (row i of a set at xy[i * stride + {0, 1}],
+// rows [0, nq) / [0, nt) exist).
+struct VerifyInput {
+    const MatchRecord* matches;
+    const int* count;
+    int cap;
+    const float* qxy;
+    const float* txy;
+    int qstride, tstride;
+    int nq, nt;
+};
+
+// sift_hip_verify_result's layout.
+struct VerifyResult {
+    float F[9];
+    int inliers, hypothesis, matches, valid_hypotheses;
+};
+static_assert(sizeof(VerifyResult) == 52, "sift_hip_verify_result layout");
+
+// k_verify_gather: match j -> pts[j] = (qx, qy, tx, ty), NaN x 4 for a record
+// with an index outside its position array; j in [n, cap) is not written.
+void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s);
+
+// k_verify_hypotheses: hypothesis k in [0, K) draws its 8 matches
+// (samples[8 k ..], -1 when n < 8) and solves them: F[9 k ..] and valid[k]
+// (an invalid hypothesis has F all zero).
+void launch_verify_hypotheses(const VerifyInput& in, const float4* pts, int K, unsigned seed, int* samples, float* F,
+                              int* valid, hipStream_t s);
+
+// k_verify_score: counts[k] = the matches j < n that pass the epipolar
+// predicate under F[9 k ..] with e2 = max_error^2; 0 where valid (nullable)
+// says the hypothesis is invalid.
+void launch_verify_score(const VerifyInput& in, const float4* pts, const float* F, const int* valid, int K, float e2,
+                         int* counts, hipStream_t s);
+
+// k_verify_select: the winner (most inliers among the valid, ties to the lowest
+// k) into *result, its inlier mask (cap bytes, nullable), the inlier records in
+// input order (out, nullable) and their number (out_count, nullable).
+void launch_verify_select(const VerifyInput& in, const float4* pts, const float* F, const int* valid, const int* counts,
+                          int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count, uint8_t* mask,
+                          hipStream_t s);
+
+}  // namespace sift_amd

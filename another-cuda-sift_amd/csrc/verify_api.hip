@@ -1,0 +1,189 @@
+// Verifier handle (sift_hip_verifier_*, sift_hip_verify_*, sift_hip_score_*) of
+// libsift_hip.so; the kernels are verify.hip.  The handle owns every scratch
+// array from creation on, so a device call only launches kernels (capturable).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "detector_state.h"
+#include "sift_verify.h"
+
+struct sift_hip_verifier {
+    int device = 0;
+    int maxM = 0, maxK = 0;
+    float4* dPts = nullptr;      // the gathered matches (qx, qy, tx, ty)
+    int* dSamples = nullptr;     // 8 per hypothesis
+    float* dF = nullptr;         // 9 per hypothesis
+    int* dValid = nullptr;
+    int* dCounts = nullptr;
+    // the outputs of sift_hip_verify_fundamental_host
+    VerifyResult* dResult = nullptr;
+    MatchRecord* dOut = nullptr;
+    uint8_t* dMask = nullptr;
+    int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_hypotheses_host)
+    ~sift_hip_verifier() {
+        (void)hipSetDevice(device);
+        for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
+                        (void*)dOut, (void*)dMask})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static_assert(sizeof(sift_hip_verify_result) == sizeof(VerifyResult), "the result record is written by the kernel");
+
+namespace {
+
+// What can be judged without the handle first (nothing is dereferenced), then the handle's limits.  Nothing is
+// launched on a failure.
+int check_input(const sift_hip_verifier* v, const sift_hip_dmatch* matches, int cap, const float* query_xy,
+                int query_stride, int nq, const float* train_xy, int train_stride, int nt) {
+    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
+    if (cap < 0 || cap > kVerifyMaxMatches)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: cap must lie in 0.." + std::to_string(kVerifyMaxMatches));
+    if (query_stride < 2 || train_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "verify: a position stride below 2 floats");
+    if (nq < 0 || nt < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: a negative position row count");
+    if (cap > 0 && !matches) return fail(SIFT_HIP_ERR_INVALID, "verify: null matches");
+    if (cap > 0 && (!query_xy || !train_xy)) return fail(SIFT_HIP_ERR_INVALID, "verify: null position pointer");
+    return SIFT_HIP_OK;
+}
+int check_error(float max_error) {
+    if (!(max_error > 0.f) || !std::isfinite(max_error))
+        return fail(SIFT_HIP_ERR_INVALID, "verify: max_error must be > 0 and finite");
+    return SIFT_HIP_OK;
+}
+int check_limits(const sift_hip_verifier* v, int cap, int K) {
+    if (K < 1 || K > kVerifyMaxHypotheses || K > v->maxK)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: hypotheses outside 1..max_hypotheses");
+    if (cap > v->maxM) return fail(SIFT_HIP_ERR_INVALID, "verify: cap exceeds the verifier's max_matches");
+    return SIFT_HIP_OK;
+}
+
+int verify_device(sift_hip_verifier* v, const VerifyInput& in, const sift_hip_verify_params& p, VerifyResult* result,
+                  MatchRecord* out, int* out_count, uint8_t* mask, hipStream_t s) {
+    const float e2 = p.max_error * p.max_error;
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather(in, v->dPts, s);
+    launch_verify_hypotheses(in, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
+    launch_verify_score(in, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
+    launch_verify_select(in, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, result, out, out_count, mask, s);
+    HIPCHK(hipGetLastError());
+    v->lastK = p.hypotheses;
+    return SIFT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sift_hip_default_verify_params(sift_hip_verify_params* p) {
+    if (!p) return;
+    p->hypotheses = 1024;
+    p->seed = 0u;
+    p->max_error = 1.5f;
+}
+
+int sift_hip_verifier_create(int device, int max_matches, int max_hypotheses, sift_hip_verifier_t* out) {
+    if (!out || max_matches < 1 || max_matches > kVerifyMaxMatches || max_hypotheses < 1 ||
+        max_hypotheses > kVerifyMaxHypotheses)
+        return fail(SIFT_HIP_ERR_INVALID, "bad verifier limits");
+    *out = nullptr;
+    auto* v = new sift_hip_verifier();
+    if (device < 0) {
+        if (hipGetDevice(&v->device) != hipSuccess) v->device = 0;
+    } else {
+        v->device = device;
+    }
+    v->maxM = max_matches;
+    v->maxK = max_hypotheses;
+    const size_t M = (size_t)max_matches, K = (size_t)max_hypotheses;
+    if (hipSetDevice(v->device) != hipSuccess || hipMalloc((void**)&v->dPts, sizeof(float4) * M) != hipSuccess ||
+        hipMalloc((void**)&v->dSamples, sizeof(int) * 8 * K) != hipSuccess ||
+        hipMalloc((void**)&v->dF, sizeof(float) * 9 * K) != hipSuccess ||
+        hipMalloc((void**)&v->dValid, sizeof(int) * K) != hipSuccess ||
+        hipMalloc((void**)&v->dCounts, sizeof(int) * K) != hipSuccess ||
+        hipMalloc((void**)&v->dResult, sizeof(VerifyResult)) != hipSuccess ||
+        hipMalloc((void**)&v->dOut, sizeof(MatchRecord) * M) != hipSuccess ||
+        hipMalloc((void**)&v->dMask, M) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        delete v;
+        return fail(SIFT_HIP_ERR_NOMEM, "verifier allocation failed");
+    }
+    *out = v;
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
+    delete v;
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_verify_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                       const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                       int train_stride, int nt, const sift_hip_verify_params* params,
+                                       sift_hip_verify_result* result, sift_hip_dmatch* out, int* out_count,
+                                       uint8_t* mask, void* stream) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!params || !result) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
+    if (int rc = check_error(params->max_error)) return rc;
+    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
+    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
+    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    return verify_device(v, in, *params, reinterpret_cast<VerifyResult*>(result), reinterpret_cast<MatchRecord*>(out),
+                         out_count, mask, (hipStream_t)stream);
+}
+
+int sift_hip_verify_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, const sift_hip_verify_params* params,
+                                     sift_hip_verify_result* result_host, sift_hip_dmatch* out_host,
+                                     uint8_t* mask_host) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!params || !result_host) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
+    if (int rc = check_error(params->max_error)) return rc;
+    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    if (int rc = verify_device(v, in, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
+    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
+    const int n = std::min(result_host->inliers, cap);
+    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+    if (mask_host && cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                      int train_stride, int nt, const float* F, int K, float max_error, int* counts,
+                                      void* stream) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!F || !counts) return fail(SIFT_HIP_ERR_INVALID, "verify: null F or counts");
+    if (int rc = check_error(max_error)) return rc;
+    if (int rc = check_limits(v, cap, K)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather(in, v->dPts, (hipStream_t)stream);
+    launch_verify_score(in, v->dPts, F, nullptr, K, max_error * max_error, counts, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap) {
+    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
+    if (cap < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: negative cap");
+    if (v->lastK == 0) return fail(SIFT_HIP_ERR_STATE, "no verify call has run on this verifier");
+    const size_t K = (size_t)std::min(cap, v->lastK);
+    if (K == 0) return SIFT_HIP_OK;
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (samples) HIPCHK(hipMemcpy(samples, v->dSamples, sizeof(int) * 8 * K, hipMemcpyDeviceToHost));
+    if (F) HIPCHK(hipMemcpy(F, v->dF, sizeof(float) * 9 * K, hipMemcpyDeviceToHost));
+    if (counts) HIPCHK(hipMemcpy(counts, v->dCounts, sizeof(int) * K, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+}  // extern "C"

@@ -122,6 +122,33 @@ def _match_filter(ratio: float = 0.8, ratio_on_squared: bool = False, ratio_both
                         int(bool(cross_check)))
 
 
+class _VerifyParams(ctypes.Structure):
+    """sift_hip_verify_params: the hypothesis budget K, the sampler's seed and the inlier threshold (Sampson distance,
+    pixels)."""
+    _fields_ = [
+        ("hypotheses", ctypes.c_int),
+        ("seed", ctypes.c_uint),
+        ("max_error", ctypes.c_float),
+    ]
+
+
+class _VerifyResult(ctypes.Structure):
+    """sift_hip_verify_result: the winning hypothesis' F (row-major), its inlier count and index (-1: none), the number
+    of matches that counted and the number of hypotheses that were solved."""
+    _fields_ = [
+        ("F", ctypes.c_float * 9),
+        ("inliers", ctypes.c_int),
+        ("hypothesis", ctypes.c_int),
+        ("matches", ctypes.c_int),
+        ("valid_hypotheses", ctypes.c_int),
+    ]
+
+
+VERIFY_RESULT_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("matches", "<i4"),
+                                ("valid_hypotheses", "<i4")])
+assert VERIFY_RESULT_DTYPE.itemsize == ctypes.sizeof(_VerifyResult)
+
+
 def lib() -> ctypes.CDLL:
     """Load libsift_hip.so (once).  Fails loudly when the build is missing."""
     global _lib
@@ -221,6 +248,15 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.POINTER(_MatchFilter), vp, vp, vp]),
         "sift_hip_match_list_epipolar_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate),
                                                   ctypes.POINTER(_MatchFilter), vp, i, ip]),
+        "sift_hip_default_verify_params": (None, [ctypes.POINTER(_VerifyParams)]),
+        "sift_hip_verifier_create": (i, [i, i, i, ctypes.POINTER(vp)]),
+        "sift_hip_verifier_destroy": (i, [vp]),
+        "sift_hip_verify_fundamental_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams), vp,
+                                                   vp, vp, vp, vp]),
+        "sift_hip_verify_fundamental_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams),
+                                                 ctypes.POINTER(_VerifyResult), vp, vp]),
+        "sift_hip_score_fundamental_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, i, f, vp, vp]),
+        "sift_hip_verify_hypotheses_host": (i, [vp, vp, vp, vp, i]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -952,6 +988,92 @@ def matchListEpipolar(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuf
     qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
     return m.match_list_epipolar_host(des.data(), num_des, src.data(), num_src, qxy, txy, F, max_error, radius,
                                       des_stride, src_stride, **filter)
+
+
+class Verifier:
+    """Two-view verification of a match list on the device: a fixed-budget RANSAC for the fundamental matrix
+    (sift_hip_verifier_*; the rule: include/sift_hip.h, and in numpy sift_amd.cv.ransac_fundamental).  Owns all scratch
+    of its calls -- for lists of up to max_matches records and up to max_hypotheses hypotheses -- so a device call only
+    launches kernels.  Calls on one verifier must be ordered."""
+
+    def __init__(self, max_matches: int, max_hypotheses: int = 1024, device: int = -1):
+        self._v = ctypes.c_void_p()
+        _check(lib().sift_hip_verifier_create(device, max_matches, max_hypotheses, ctypes.byref(self._v)),
+               "verifier_create")
+        self.max_matches, self.max_hypotheses = max_matches, max_hypotheses
+        self._hypotheses = 0
+
+    def __del__(self):
+        v = getattr(self, "_v", None)
+        if v is not None and v.value and _lib is not None:
+            _lib.sift_hip_verifier_destroy(v)
+            self._v = None
+
+    def verify_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                      result_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0, mask_ptr: int = 0,
+                      max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                      t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """Enqueue the operation (sift_hip_verify_fundamental_device); every pointer is device memory.  count_ptr: the
+        device int holding the number of records (0: all `cap` count) -- e.g. match_list_device's count; result_ptr: a
+        VERIFY_RESULT_DTYPE record; out_ptr (room for cap records), out_count_ptr and mask_ptr (cap bytes) may be 0."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        _check(lib().sift_hip_verify_fundamental_device(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                        q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                        ctypes.byref(p), result_ptr or None, out_ptr or None,
+                                                        out_count_ptr or None, mask_ptr or None, stream),
+               "verify_fundamental_device")
+        self._hypotheses = hypotheses
+
+    def verify_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                    max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                    t_stride: int = 3, full: bool = False):
+        """Synchronous (sift_hip_verify_fundamental_host): (F 3 x 3 float32, the inlier records as a DMATCH_DTYPE array,
+        the winning hypothesis or -1).  full: (the VERIFY_RESULT_DTYPE record, the records, the mask of cap bytes)."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        r = _VerifyResult()
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        mask = np.zeros(max(cap, 0), np.uint8)
+        _check(lib().sift_hip_verify_fundamental_host(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                      q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                      ctypes.byref(p), ctypes.byref(r), _ptr(out), _ptr(mask)),
+               "verify_fundamental_host")
+        self._hypotheses = hypotheses
+        if full:
+            return np.frombuffer(bytes(r), VERIFY_RESULT_DTYPE)[0], out[: r.inliers], mask
+        return np.array(r.F, np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+
+    def score_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                     F_ptr: int, K: int, max_error: float, counts_ptr: int, q_stride: int = 3, t_stride: int = 3,
+                     stream: Optional[int] = None) -> None:
+        """The score alone on the caller's K hypotheses (device, K x 9 floats): counts (device, K ints)."""
+        _check(lib().sift_hip_score_fundamental_device(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                       q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                       F_ptr or None, K, max_error, counts_ptr or None, stream),
+               "score_fundamental_device")
+
+    def hypotheses(self):
+        """What the last verify call drew, solved and counted: (samples (K, 8) int32, F (K, 9) float32, valid (K,) bool
+        -- an invalid hypothesis has F all zero --, counts (K,) int32).  Synchronises the device."""
+        K = self._hypotheses
+        samples, F, counts = np.zeros((K, 8), np.int32), np.zeros((K, 9), np.float32), np.zeros(K, np.int32)
+        _check(lib().sift_hip_verify_hypotheses_host(self._v, _ptr(samples), _ptr(F), _ptr(counts), K),
+               "verify_hypotheses_host")
+        return samples, F, F.any(1), counts
+
+
+def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
+                      hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3):
+    """Geometric verification of a match list (matchList's output): (F 3 x 3 float32 with x_src^T F x_des = 0, the
+    inlier records in input order, the winning hypothesis or -1 when there are fewer than 8 matches or no sample could
+    be solved).  matches: a DMATCH_DTYPE array (uploaded here); des_xy / src_xy: DeviceBuffers or raw device pointers
+    of n_des / n_src float rows with x, y first, as for matchListEpipolar.  The returned F is what matchListEpipolar
+    takes; sift_amd.cv.fundamental_lstsq refits a rank-2 F on the inliers."""
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
+    v = Verifier(max(len(m), 1), hypotheses)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    return v.verify_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, max_error, hypotheses, seed,
+                         des_stride, src_stride)
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

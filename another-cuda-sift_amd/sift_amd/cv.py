@@ -226,6 +226,217 @@ def epipolar_top2(q, t, q_xy, t_xy, F, max_error, radius=np.inf):
     return mask_top2(q, t, lambda: epipolar_mask(q_xy, t_xy, F, max_error, radius))
 
 
+# --- Two-view verification: the rule of sift_hip_verify_* (include/sift_hip.h) in numpy float32.  Every function
+# below works on whole arrays of hypotheses at once; each array operation is one float32 operation per element, rounded
+# to nearest, in the header's order (numpy fuses nothing), so the device's bytes are the reference's.
+
+_F32 = np.float32
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(h):
+    """lowbias32 on uint32 values held in uint64 arrays (no overflow warnings)."""
+    h = np.asarray(h, np.uint64) & _M32
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x7FEB352D)) & _M32
+    h = h ^ (h >> np.uint64(15))
+    h = (h * np.uint64(0x846CA68B)) & _M32
+    return h ^ (h >> np.uint64(16))
+
+
+def ransac_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the verify rule: (K, 8) int32, row k the 8 distinct indices of [0, n) hypothesis k draws -- a
+    function of (seed, k, n) only.  n < 8: every entry -1 (nothing is drawn)."""
+    out = np.full((K, 8), -1, np.int64)
+    if n < 8:
+        return out.astype(np.int32)
+    base = _mix32(np.uint64(int(seed) & 0xFFFFFFFF) ^ _mix32(np.arange(K, dtype=np.uint64)))
+    for j in range(8):
+        h = _mix32((base + np.uint64((0x9E3779B9 * (j + 1)) & 0xFFFFFFFF)) & _M32)
+        r = ((h * np.uint64(n - j)) >> np.uint64(32)).astype(np.int64)
+        earlier = np.sort(out[:, :j], axis=1)
+        for i in range(j):
+            r = r + (r >= earlier[:, i])
+        out[:, j] = r
+    return out.astype(np.int32)
+
+
+def _normalise8(x, y):
+    """Hartley normalisation of (K, 8) coordinates: (x', y', s, ox, oy), sums in index order."""
+    sx, sy = x[:, 0].copy(), y[:, 0].copy()
+    for i in range(1, 8):
+        sx = sx + x[:, i]
+        sy = sy + y[:, i]
+    mx, my = sx / _F32(8), sy / _F32(8)
+    dx, dy = x - mx[:, None], y - my[:, None]
+    d = np.sqrt(dx * dx + dy * dy)
+    sd = d[:, 0].copy()
+    for i in range(1, 8):
+        sd = sd + d[:, i]
+    md = sd / _F32(8)
+    s = _F32(1.41421354) / md
+    return dx * s[:, None], dy * s[:, None], s, -(s * mx), -(s * my)
+
+
+def fundamental_from_8(q_xy8, t_xy8):
+    """The solver of the verify rule: the normalised 8-point F of 8 pairs (Gaussian elimination with full pivoting, no
+    rank-2 constraint, unit Frobenius norm).  q_xy8 / t_xy8: (8, 2) -> (F (9,) float32, valid bool), or (K, 8, 2) ->
+    (F (K, 9), valid (K,)).  An invalid hypothesis (a zero or non-finite pivot or result) has F all zero."""
+    q = np.asarray(q_xy8, np.float32)
+    t = np.asarray(t_xy8, np.float32)
+    single = q.ndim == 2
+    q, t = q.reshape(-1, 8, 2), t.reshape(-1, 8, 2)
+    K = len(q)
+    ar = np.arange(K)
+    with np.errstate(all="ignore"):
+        qx, qy, sq, oqx, oqy = _normalise8(q[:, :, 0], q[:, :, 1])
+        tx, ty, st, otx, oty = _normalise8(t[:, :, 0], t[:, :, 1])
+        A = np.stack([tx * qx, tx * qy, tx, ty * qx, ty * qy, ty, qx, qy, np.ones_like(qx)], axis=2)  # (K, 8, 9)
+        perm = np.tile(np.arange(9), (K, 1))
+        ok = np.ones(K, bool)
+        for c in range(8):
+            mag = np.abs(A[:, c:, c:]).reshape(K, -1)
+            flat = np.argmax(np.where(np.isnan(mag), _F32(-1), mag), axis=1)  # the first of the largest, row-major
+            flat = np.where(np.isnan(mag[:, 0]), 0, flat)  # nothing is larger than a NaN at (c, c)
+            pr, pc = c + flat // (9 - c), c + flat % (9 - c)
+            tmp = A[ar, c, :].copy()
+            A[ar, c, :] = A[ar, pr, :]
+            A[ar, pr, :] = tmp
+            tmp = A[ar, :, c].copy()
+            A[ar, :, c] = A[ar, :, pc]
+            A[ar, :, pc] = tmp
+            tmp = perm[ar, c].copy()
+            perm[ar, c] = perm[ar, pc]
+            perm[ar, pc] = tmp
+            p = A[:, c, c]
+            ok &= (p != 0) & np.isfinite(p)
+            m = A[:, c + 1:, c] / p[:, None]
+            A[:, c + 1:, c + 1:] = A[:, c + 1:, c + 1:] - m[:, :, None] * A[:, c:c + 1, c + 1:]
+        y = np.zeros((K, 9), np.float32)
+        y[:, 8] = 1
+        for i in range(7, -1, -1):
+            acc = A[:, i, i + 1] * y[:, i + 1]
+            for j in range(i + 2, 9):
+                acc = acc + A[:, i, j] * y[:, j]
+            y[:, i] = (-acc) / A[:, i, i]
+        g = np.zeros((K, 9), np.float32)
+        g[ar[:, None], perm] = y
+        G = g.reshape(K, 3, 3)
+        H = np.zeros((K, 3, 3), np.float32)
+        H[:, :, 0] = G[:, :, 0] * sq[:, None]
+        H[:, :, 1] = G[:, :, 1] * sq[:, None]
+        H[:, :, 2] = (G[:, :, 0] * oqx[:, None] + G[:, :, 1] * oqy[:, None]) + G[:, :, 2]
+        F = np.zeros((K, 3, 3), np.float32)
+        F[:, 0, :] = st[:, None] * H[:, 0, :]
+        F[:, 1, :] = st[:, None] * H[:, 1, :]
+        F[:, 2, :] = (otx[:, None] * H[:, 0, :] + oty[:, None] * H[:, 1, :]) + H[:, 2, :]
+        F = F.reshape(K, 9)
+        ss = F[:, 0] * F[:, 0]
+        for i in range(1, 9):
+            ss = ss + F[:, i] * F[:, i]
+        F = F / np.sqrt(ss)[:, None]
+        ok &= np.isfinite(F).all(1)
+    assert A.dtype == np.float32 and y.dtype == np.float32 and F.dtype == np.float32 and ss.dtype == np.float32
+    F[~ok] = 0
+    return (F[0], bool(ok[0])) if single else (F, ok)
+
+
+def _match_points(matches, q_xy, t_xy) -> np.ndarray:
+    """(n, 4) float32 (qx, qy, tx, ty) of a match list; NaN x 4 for a record with an index outside its array."""
+    q = np.asarray(q_xy, np.float32).reshape(len(q_xy), -1)[:, :2]
+    t = np.asarray(t_xy, np.float32).reshape(len(t_xy), -1)[:, :2]
+    qi = np.asarray(matches["queryIdx"], np.int64)
+    ti = np.asarray(matches["trainIdx"], np.int64)
+    ok = (qi >= 0) & (qi < len(q)) & (ti >= 0) & (ti < len(t))
+    pts = np.full((len(qi), 4), np.nan, np.float32)
+    pts[ok, :2] = q[qi[ok]]
+    pts[ok, 2:] = t[ti[ok]]
+    return pts
+
+
+def _sampson_pass(pts, F, max_error) -> np.ndarray:
+    """(K, n) bool: the epipolar predicate (epipolar_mask's operations, radius = inf) of every match's own pair under
+    each of the K rows of F (K, 9)."""
+    f = np.asarray(F, np.float32).reshape(-1, 9)[:, :, None]
+    e = np.float32(max_error)
+    qx, qy, tx, ty = (pts[None, :, i] for i in range(4))
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        a = (f[:, 0] * qx + f[:, 1] * qy) + f[:, 2]
+        b = (f[:, 3] * qx + f[:, 4] * qy) + f[:, 5]
+        c = (f[:, 6] * qx + f[:, 7] * qy) + f[:, 8]
+        nq = a * a + b * b
+        u = (f[:, 0] * tx + f[:, 3] * ty) + f[:, 6]
+        v = (f[:, 1] * tx + f[:, 4] * ty) + f[:, 7]
+        nr = u * u + v * v
+        r = (a * tx + b * ty) + c
+        band = r * r <= (e * e) * (nq + nr)
+        window = (np.abs(tx - qx) <= np.float32(np.inf)) & (np.abs(ty - qy) <= np.float32(np.inf))
+    assert r.dtype == np.float32 and nq.dtype == np.float32 and nr.dtype == np.float32
+    return band & window
+
+
+def sampson_inliers(matches, q_xy, t_xy, F, max_error) -> np.ndarray:
+    """The score of the verify rule: a bool per DMATCH_DTYPE record, True where the record's own pair passes the
+    epipolar predicate under F (Sampson distance <= max_error, inclusive) -- the diagonal of
+    epipolar_mask(q_xy[queryIdx], t_xy[trainIdx], F, max_error), computed per pair.  A record with an index outside
+    its position array, or a NaN position, is an inlier of nothing."""
+    f = np.asarray(F, np.float32).reshape(-1)
+    if f.size != 9:
+        raise ValueError("F must have 9 entries (3 x 3, row-major)")
+    return _sampson_pass(_match_points(matches, q_xy, t_xy), f, max_error)[0]
+
+
+def ransac_fundamental(matches, q_xy, t_xy, max_error=1.5, K: int = 1024, seed: int = 0) -> dict:
+    """The whole verify operation (sift_hip_verify_fundamental_*) in numpy.  matches: the n DMATCH_DTYPE records that
+    count.  Returns a dict: F (9,) float32, inliers, hypothesis (-1: none), matches (= n), valid_hypotheses, mask (n,)
+    uint8, list (the inlier records in input order), and what every hypothesis drew, solved and counted: samples
+    (K, 8), Fs (K, 9), valid (K,), counts (K,)."""
+    from . import DMATCH_DTYPE
+
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    pts = _match_points(matches, q_xy, t_xy)
+    samples = ransac_samples(n, K, seed)
+    if n >= 8:
+        Fs, valid = fundamental_from_8(pts[samples][:, :, :2], pts[samples][:, :, 2:])
+        passes = _sampson_pass(pts, Fs, max_error) & valid[:, None]
+    else:
+        Fs, valid, passes = np.zeros((K, 9), np.float32), np.zeros(K, bool), np.zeros((K, n), bool)
+    counts = passes.sum(1).astype(np.int32)
+    hyp = -1
+    if valid.any():
+        hyp = int(np.argmax(np.where(valid, counts, -1)))  # the first of the largest: ties to the lowest k
+    mask = passes[hyp].astype(np.uint8) if hyp >= 0 else np.zeros(n, np.uint8)
+    return dict(F=Fs[hyp].copy() if hyp >= 0 else np.zeros(9, np.float32), inliers=int(counts[hyp]) if hyp >= 0 else 0,
+                hypothesis=hyp, matches=n, valid_hypotheses=int(valid.sum()), mask=mask, list=matches[mask != 0],
+                samples=samples, Fs=Fs, valid=valid, counts=counts)
+
+
+def fundamental_lstsq(q_pts, t_pts, rank2: bool = True) -> np.ndarray:
+    """A convenience, not part of the device rule: the float64 normalised 8-point least-squares F (3 x 3, unit
+    Frobenius norm, x_t^T F x_q = 0) of n >= 8 pairs through np.linalg.svd, with the rank-2 projection -- a pose-grade
+    F from the inliers a verify call returns."""
+    q = np.asarray(q_pts, np.float64).reshape(len(q_pts), -1)[:, :2]
+    t = np.asarray(t_pts, np.float64).reshape(len(t_pts), -1)[:, :2]
+    if len(q) != len(t) or len(q) < 8:
+        raise ValueError("fundamental_lstsq needs the same number (>= 8) of points on both sides")
+
+    def norm(p):
+        m = p.mean(0)
+        s = np.sqrt(2.0) / np.sqrt(((p - m) ** 2).sum(1)).mean()
+        return (p - m) * s, np.array([[s, 0, -s * m[0]], [0, s, -s * m[1]], [0, 0, 1]])
+
+    (qn, Tq), (tn, Tt) = norm(q), norm(t)
+    A = np.stack([tn[:, 0] * qn[:, 0], tn[:, 0] * qn[:, 1], tn[:, 0], tn[:, 1] * qn[:, 0], tn[:, 1] * qn[:, 1],
+                  tn[:, 1], qn[:, 0], qn[:, 1], np.ones(len(q))], 1)
+    G = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    if rank2:
+        u, s, vt = np.linalg.svd(G)
+        G = u @ np.diag([s[0], s[1], 0.0]) @ vt
+    F = Tt.T @ G @ Tq
+    return F / np.linalg.norm(F)
+
+
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     import cv2
 

@@ -1,0 +1,69 @@
+// sift_cuda::Verifier / verifyFundamental: two-view verification of a match
+// list (a fixed-budget RANSAC for the fundamental matrix on the device) over
+// sift_hip_verify_* of include/sift_hip.h, where the rule is written out.
+// Plain C++: no HIP headers.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "sift_cuda/Types.hh"
+
+struct sift_hip_verifier;
+
+namespace sift_cuda {
+
+// sift_hip_verify_params with sift_hip_default_verify_params' defaults.
+struct VerifyParams {
+    int hypotheses = 1024;
+    unsigned seed = 0;
+    float max_error = 1.5f;  // Sampson distance in pixels, > 0 and finite
+};
+
+// The winning hypothesis: F row-major with x_train^T F x_query = 0 (zero when
+// hypothesis = -1: fewer than 8 matches or no solvable sample) and its inlier
+// records, the input's, in input order.
+struct TwoViewGeometry {
+    float F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int hypothesis = -1;
+    std::vector<DMatch> inliers;
+};
+
+// sift_hip_verify_result (device form: the record the kernels write).
+struct VerifyResult {
+    float F[9];
+    int inliers, hypothesis, matches, valid_hypotheses;
+};
+
+// A verifier owns the scratch of its calls; calls on one verifier must be
+// ordered.  What the ABI refuses (sift_hip_verify_fundamental_device) throws
+// std::invalid_argument; a failed allocation or HIP call std::runtime_error.
+class Verifier {
+public:
+    Verifier(int max_matches, int max_hypotheses = 1024, int device = -1);
+    ~Verifier();
+    Verifier(const Verifier&) = delete;
+    Verifier& operator=(const Verifier&) = delete;
+
+    // Enqueued on `stream` (a hipStream_t, nullptr: the default stream), not synchronised; every pointer is device
+    // memory.  count may be nullptr (n = cap); out, out_count and mask may be nullptr.
+    void verifyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                      const float* train_xy, int train_stride, int nt, const VerifyParams& params, VerifyResult* result,
+                      DMatch* out = nullptr, int* out_count = nullptr, uint8_t* mask = nullptr, void* stream = nullptr);
+    // Synchronous; matches, count and the positions on the device, the result on the host.
+    TwoViewGeometry verifyHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                               int nq, const float* train_xy, int train_stride, int nt, const VerifyParams& params = {});
+
+    sift_hip_verifier* handle() const { return m_handle; }
+
+private:
+    sift_hip_verifier* m_handle = nullptr;
+};
+
+// One shot: uploads the list and verifies it.  query_xy / train_xy: device position rows (x, y first; nq / nt rows of
+// query_stride / train_stride floats -- a Detector's device_kpts.data() with stride 3).
+TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
+                                  const float* train_xy, int nt, const VerifyParams& params = {}, int query_stride = 3,
+                                  int train_stride = 3);
+
+}  // namespace sift_cuda

@@ -695,7 +695,7 @@ int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* query,
  * The gate of two-view geometry: COLMAP's and SiftGPU's guided match, ORB-SLAM's
  * SearchForTriangulation.  The caller knows F -- from the relative pose of two
  * keyframes, a calibrated stereo rig, or a first RANSAC pass over a match list
- * -- but not where on its epipolar line a point lands, so no predicted position
+ * (sift_hip_verify_fundamental_device below) -- but not where on its epipolar line a point lands, so no predicted position
  * and no radius expresses it.  As with the window, the two nearest rows inside
  * the band are not the global top-2.  (A homography needs nothing new: project
  * the query positions and use the window above.)
@@ -767,6 +767,151 @@ int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* quer
  * atomics) and waves per workgroup.  Host-only (no GPU call beyond reading the
  * CU count; 256 without a device), for tests and tools. */
 int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, int* waves);
+
+/* --- Two-view verification: RANSAC for the fundamental matrix ------------------
+ *
+ * The step between a putative match list and guided matching under F (COLMAP's
+ * and SiftGPU's two-stage match; cv::findFundamentalMat(FM_RANSAC) plus its
+ * inlier mask): a fixed budget of K hypotheses, each the normalised 8-point
+ * solution of 8 sampled matches, each scored against every match by the
+ * epipolar predicate above; the best one's F, its inlier mask and its inlier
+ * records.  Everything runs on the caller's stream, the number of matches is
+ * read from device memory (a call can follow sift_hip_match_list_device with no
+ * host round trip), and the same bytes come out in every run.
+ *
+ * The rule.  All arithmetic is float32, every operation rounded to nearest, one
+ * at a time, in the written order; nothing is fused; sums run in index order
+ * ((x0 + x1) + x2 ...).  sift_amd.cv.ransac_fundamental is the same rule in
+ * numpy.
+ *
+ * Input.  n = min(max(*count, 0), cap), or cap when count is NULL.  Match j is
+ * (queryIdx, trainIdx) of record j; its positions (qx, qy), (tx, ty) are read
+ * as for sift_hip_match_gate (stride >= 2, x and y first).  nq and nt are the
+ * row counts of the position arrays: a record with queryIdx outside [0, nq) or
+ * trainIdx outside [0, nt) is never read through -- its four coordinates count
+ * as NaN, so it is an inlier of nothing and a hypothesis that samples it is
+ * invalid.
+ *
+ * Sampling.  mix(h), on uint32 (lowbias32):
+ *   h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ * Hypothesis k (0 <= k < K) has base = mix(seed ^ mix(k)).  Draw j = 0..7:
+ *   h = mix(base + 0x9e3779b9 * (j + 1))            (uint32, wrapping)
+ *   r = (uint64(h) * (n - j)) >> 32
+ *   for every earlier pick p, in ascending order of p: if r >= p: r++
+ *   sample[j] = r
+ * The 8 indices are distinct and the rule is total for every n >= 8; it is a
+ * function of (seed, k, n) only.
+ *
+ * Solver.  For each side of the sample (the 8 query positions; the 8 train
+ * positions), with (x_i, y_i) in sample order:
+ *   mx = (sum x_i) / 8, my = (sum y_i) / 8
+ *   dx_i = x_i - mx, dy_i = y_i - my, d_i = sqrtf(dx_i*dx_i + dy_i*dy_i)
+ *   md = (sum d_i) / 8, s = 1.41421354f / md
+ *   x'_i = dx_i * s, y'_i = dy_i * s, ox = -(s * mx), oy = -(s * my)
+ * (sq, oqx, oqy) for the query side and (st, otx, oty) for the train side.
+ * Row i of the 8 x 9 system A is, on the normalised coordinates,
+ *   [tx*qx, tx*qy, tx, ty*qx, ty*qy, ty, qx, qy, 1].
+ * Gaussian elimination with full pivoting, steps c = 0..7: the pivot is the
+ * entry of largest fabsf among rows c..7 and columns c..8, found by a scan that
+ * starts with (c, c), visits rows c..7 and inside a row columns c..8, and moves
+ * to an entry only when its fabsf is strictly larger (ties go to the first in
+ * row-major order; a NaN is never larger).  Rows c and the pivot's are swapped,
+ * then columns c and the pivot's (in all rows; perm records the columns).  The
+ * pivot p = A[c][c]; a zero or non-finite p makes the hypothesis invalid.  For
+ * rows r = c+1..7: m = A[r][c] / p, and for columns j = c+1..8:
+ *   A[r][j] = A[r][j] - m * A[c][j].
+ * Back-substitution with the free variable y[8] = 1, i = 7..0:
+ *   acc = A[i][i+1]*y[i+1]; for j = i+2..8: acc = acc + A[i][j]*y[j]
+ *   y[i] = (-acc) / A[i][i]
+ * The permutation is undone, g[perm[j]] = y[j] (perm[j]: the original column at
+ * position j), G = g as 3 x 3 row-major, and F = Tt^T G Tq written out:
+ *   H[r][0] = G[r][0]*sq, H[r][1] = G[r][1]*sq,
+ *   H[r][2] = (G[r][0]*oqx + G[r][1]*oqy) + G[r][2]                  (r = 0..2)
+ *   F[0][c] = st*H[0][c], F[1][c] = st*H[1][c],
+ *   F[2][c] = (otx*H[0][c] + oty*H[1][c]) + H[2][c]                  (c = 0..2)
+ * and scaled to unit Frobenius norm: ss = sum F[i]*F[i] over i = 0..8,
+ * F[i] = F[i] / sqrtf(ss).  A non-finite entry of the result makes the
+ * hypothesis invalid.  No rank-2 constraint is enforced (neither the Sampson
+ * formula nor the epipolar gate needs one).  An invalid hypothesis has inlier
+ * count 0 and F all zero.
+ *
+ * Score.  Match j is an inlier of a valid hypothesis when the epipolar
+ * predicate above holds for its own pair under the hypothesis' F, with
+ * e2 = max_error*max_error and radius = +inf (no window):
+ * r*r <= e2 * (nq + nr), inclusive.  A NaN is an inlier of nothing.
+ *
+ * Selection.  The valid hypothesis with the most inliers wins, ties to the
+ * lowest k.  With n < 8 (no hypothesis is drawn: every sample index is -1) or
+ * no valid hypothesis the result is hypothesis = -1, inliers = 0, F zero, an
+ * empty list and a zero mask -- a status of success, not an error.
+ *
+ * Output.  The result record; optionally (each may be NULL) the inlier records
+ * at out -- the input records, unchanged, in input order, room for cap --,
+ * their number at out_count, and a byte mask of cap entries (mask[j] = 1 for an
+ * inlier, 0 otherwise, also for j >= n).  out may not overlap the input. */
+typedef struct sift_hip_verifier* sift_hip_verifier_t;
+
+typedef struct {
+    int hypotheses;   /* K, 1 .. the verifier's max_hypotheses */
+    unsigned seed;
+    float max_error;  /* Sampson distance in pixels, > 0 and finite */
+} sift_hip_verify_params;
+
+typedef struct {
+    float F[9];            /* row-major; x_train^T F x_query = 0; zero when hypothesis = -1 */
+    int inliers;           /* inliers of the winning hypothesis */
+    int hypothesis;        /* its index k, -1: none */
+    int matches;           /* n */
+    int valid_hypotheses;  /* hypotheses that were solved */
+} sift_hip_verify_result;  /* 52 bytes */
+
+/* 1024 hypotheses, seed 0, max_error 1.5 px. */
+void sift_hip_default_verify_params(sift_hip_verify_params* params);
+
+/* A verifier owns all scratch of its calls (nothing is allocated later: every
+ * device call below only launches kernels and may run under stream capture).
+ * max_matches 1..65536, max_hypotheses 1..4096.  Calls on ONE verifier must be
+ * ordered (same stream, or synchronised). */
+int sift_hip_verifier_create(int device, int max_matches, int max_hypotheses, sift_hip_verifier_t* out);
+int sift_hip_verifier_destroy(sift_hip_verifier_t v);
+
+/* The operation, enqueued on `stream`, not synchronised.  matches, count,
+ * positions, result, out, out_count, mask: device memory.  SIFT_HIP_ERR_INVALID,
+ * with nothing launched, for: a null verifier, params or result; cap negative
+ * or over the verifier's max_matches; hypotheses outside 1..max_hypotheses; a
+ * max_error that is not > 0 and finite; a stride < 2; nq or nt negative; null
+ * matches or positions with cap > 0; out overlapping matches.  cap == 0
+ * succeeds with the empty result. */
+int sift_hip_verify_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                       const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                       int train_stride, int nt, const sift_hip_verify_params* params,
+                                       sift_hip_verify_result* result, sift_hip_dmatch* out, int* out_count,
+                                       uint8_t* mask, void* stream);
+
+/* Synchronous; matches, count and the positions still live on the device, the
+ * result record, the result->inliers records (out_host: room for cap, may be
+ * NULL) and the mask (mask_host: cap bytes, may be NULL) go to host memory. */
+int sift_hip_verify_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, const sift_hip_verify_params* params,
+                                     sift_hip_verify_result* result_host, sift_hip_dmatch* out_host,
+                                     uint8_t* mask_host);
+
+/* The score alone, on the caller's own hypotheses (a 5-point solver with known
+ * intrinsics, a pose prior): counts[k] (device, K ints) = the matches that are
+ * inliers of F[9 k .. 9 k + 8] (device, K x 9) by the Score rule -- the formula
+ * is the rule for every F (an all-NaN F counts nothing).  K and the other
+ * arguments as above. */
+int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                      int train_stride, int nt, const float* F, int K, float max_error, int* counts,
+                                      void* stream);
+
+/* For tests and tools: what the last verify call on v drew, solved and counted
+ * -- samples (K x 8), F (K x 9, zero rows: invalid hypotheses) and counts (K)
+ * of its first min(cap, K) hypotheses to host memory (each may be NULL).
+ * Synchronises the device.  SIFT_HIP_ERR_STATE before the first verify call. */
+int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap);
 
 /* --- Multi-GPU (the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
