@@ -30,11 +30,14 @@ int fail(int code, const std::string& msg) {
 
 namespace {
 
+// Tap count of OpenCV's GaussianBlur for a float image (ksize 0): cvRound(8 sigma + 1) | 1.
+int gaussian_ntaps(double sigma) { return (int)lrint(sigma * 4 * 2 + 1) | 1; }
+
 // OpenCV getGaussianKernelBitExact (same arithmetic as oracle gaussianTaps).
+// The caller has checked gaussian_ntaps(sigma) <= kMaxTaps (setup_taps).
 Taps gaussian_taps(double sigma) {
     Taps t{};
-    int n = (int)lrint(sigma * 4 * 2 + 1) | 1;
-    if (n > kMaxTaps) n = kMaxTaps;
+    const int n = gaussian_ntaps(sigma);
     const double scale2X = -0.125 / (sigma * sigma);
     const int n2 = (n - 1) / 2;
     std::vector<double> values(n2 + 1);
@@ -116,11 +119,10 @@ int setup_geometry(sift_hip_detector* d) {
     return SIFT_HIP_OK;
 }
 
-void setup_taps(sift_hip_detector* d) {
+int setup_taps(sift_hip_detector* d) {
     const float sigma = (float)d->cfg.sigma;
     const float sig_diff = d->firstOctave < 0 ? sqrtf(std::max(sigma * sigma - 0.5f * 0.5f * 4, 0.01f))
                                               : sqrtf(std::max(sigma * sigma - 0.5f * 0.5f, 0.01f));
-    d->initTaps = gaussian_taps((double)sig_diff);
     const int L = d->L;
     std::vector<double> sig(L + 3);
     sig[0] = d->cfg.sigma;
@@ -130,8 +132,34 @@ void setup_taps(sift_hip_detector* d) {
         const double sig_total = sig_prev * k;
         sig[i] = std::sqrt(sig_total * sig_total - sig_prev * sig_prev);
     }
-    d->layerTaps.resize(L + 3);
-    for (int i = 0; i < L + 3; i++) d->layerTaps[i] = gaussian_taps(sig[i]);
+    // The blur kernels are instantiated per radius up to kMaxTaps / 2 and OpenCV
+    // does not truncate its kernels: a configuration with a wider blur is
+    // refused, never computed with a clipped Gaussian.  (The first comparison
+    // keeps an infinite sigma away from lrint.)
+    auto too_wide = [](double s) { return !(s * 8 + 1 < kMaxTaps + 2) || gaussian_ntaps(s) > kMaxTaps; };
+    bool wide = too_wide((double)sig_diff);
+    for (int i = 1; i < L + 3; i++) wide = wide || too_wide(sig[i]);
+    if (wide) {
+        char msg[200];
+        snprintf(msg, sizeof msg,
+                 "sigma %g with numOctaveLayers %d needs a Gaussian kernel wider than the limit of %d taps (radius %d)",
+                 d->cfg.sigma, L, kMaxTaps, kMaxTaps / 2);
+        return fail(SIFT_HIP_ERR_INVALID, msg);
+    }
+    // Nor is there a radius-0 kernel: a layer blur below sigma 1/16 has one tap
+    // (the initial blur's sigma is at least 0.1: three taps).
+    for (int i = 1; i < L + 3; i++)
+        if (gaussian_ntaps(sig[i]) < 3) {
+            char msg[200];
+            snprintf(msg, sizeof msg,
+                     "sigma %g with numOctaveLayers %d gives a layer blur of one tap (its sigma %g < 0.0625); "
+                     "the smallest kernel has 3 taps",
+                     d->cfg.sigma, L, sig[i]);
+            return fail(SIFT_HIP_ERR_INVALID, msg);
+        }
+    d->initTaps = gaussian_taps((double)sig_diff);
+    d->layerTaps.assign(L + 3, Taps{});  // plane 0 is the initial blur's output: no layer taps
+    for (int i = 1; i < L + 3; i++) d->layerTaps[i] = gaussian_taps(sig[i]);
     // The pyramid tail for the small octaves.  (Measured alternative, round
     // 4: per-plane launches -- 752x480 sync 0.2177 vs 0.2094-0.2107 ms.)
     d->tailOct = L + 3 <= kTailMaxPlanes ? tail_first_octave(d->pyr, d->layerTaps.data(), L) : d->nOct;
@@ -167,6 +195,7 @@ void setup_taps(sift_hip_detector* d) {
     // Valid descriptor samples lie in a rotated square of side 5 * hist_width.
     const double hw = 3.0 * sclMax;
     d->kp.descNrec = std::min((int)std::ceil((5.0 * hw + 3.0) * (5.0 * hw + 3.0)), 8192);
+    return SIFT_HIP_OK;
 }
 
 void upload_exp_tab() {
@@ -962,11 +991,11 @@ int sift_hip_create(const sift_hip_config* cfg, int device, sift_hip_t* out) {
         d->device = device;
     }
     int rc = setup_geometry(d);
+    if (!rc) rc = setup_taps(d);
     if (rc) {
         delete d;
         return rc;
     }
-    setup_taps(d);
     *out = d;
     return SIFT_HIP_OK;
 }

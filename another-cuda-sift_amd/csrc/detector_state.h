@@ -497,7 +497,7 @@ namespace det {
 
 // ---- detector.hip ----
 int setup_geometry(sift_hip_detector* d);
-void setup_taps(sift_hip_detector* d);
+int setup_taps(sift_hip_detector* d);
 int allocate(sift_hip_detector* d);
 // Points the handle's buffer views at lane k (idx: the arena of a micro-batch frame).
 void bind_lane(sift_hip_detector* d, int k, int idx = 0);

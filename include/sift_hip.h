@@ -35,7 +35,16 @@ typedef struct sift_hip_detector* sift_hip_t;
 typedef struct sift_hip_matcher* sift_hip_matcher_t;
 
 /* Mirrors CudaSiftConfig (/root/reference/sift_cuda/types/CudaSiftConfig.hh:3-14),
- * field for field including the reference's spellings, plus defaulted extras. */
+ * field for field including the reference's spellings, plus defaulted extras.
+ *
+ * Limit: every Gaussian blur of the pyramid has at most 63 taps (radius 31),
+ * taps = cvRound(8 s + 1) | 1 as in OpenCV.  The blurs are the initial one, s =
+ * sqrt(sigma^2 - 0.25) (sqrt(sigma^2 - 1) with upscale), and per layer i =
+ * 1 .. numOctaveLayers + 2, s = sigma 2^((i-1)/L) sqrt(2^(2/L) - 1), L =
+ * numOctaveLayers.  sift_hip_create refuses a configuration beyond the limit
+ * with SIFT_HIP_ERR_INVALID (OpenCV does not truncate its kernels): e.g. sigma
+ * 1.6 needs numOctaveLayers >= 2, and numOctaveLayers 3 allows sigma <= 4.0.
+ * A layer blur of one tap (s < 0.0625) is refused in the same way. */
 typedef struct {
     int    col_width;           /* image width  (CudaSiftConfig.hh:4)            */
     int    row_width;           /* image height (CudaSiftConfig.hh:5)            */

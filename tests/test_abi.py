@@ -120,6 +120,48 @@ def test_invalid_arguments_fail_with_status(sift):
     assert L.sift_hip_results_host(None, ctypes.byref(k3), None, None, None) != 0  # null handle: a status, no crash
 
 
+def _create(sift, sigma, layers, upscale=False):
+    L = sift.lib()
+    h = ctypes.c_void_p()
+    c = sift._Config()
+    L.sift_hip_default_config(ctypes.byref(c), 64, 64)
+    c.sigma, c.numOctaveLayers, c.upscale = sigma, layers, int(upscale)
+    rc = L.sift_hip_create(ctypes.byref(c), 0, ctypes.byref(h))
+    msg = L.sift_hip_last_error().decode()
+    if h:
+        L.sift_hip_destroy(h)
+    return rc, msg, bool(h)
+
+
+@pytest.mark.parametrize("sigma,layers", [(1.6, 1), (3.0, 2), (8.0, 3), (float("inf"), 3)])
+def test_blur_wider_than_the_kernels_is_refused(sift, sigma, layers):
+    """The blurs are compiled for radii up to 31 (63 taps) and OpenCV does not
+    truncate its kernels: a configuration that needs a wider one (1.6 / one
+    layer: radii 11, 22, 45; 3.0 / two layers: 34; 8.0: the initial blur
+    already) fails at create time, it is never computed with a clipped
+    Gaussian."""
+    rc, msg, made = _create(sift, sigma, layers)
+    assert rc == -1 and not made  # SIFT_HIP_ERR_INVALID
+    assert f"sigma {sigma:g}" in msg and f"numOctaveLayers {layers}" in msg and "63 taps" in msg, msg
+
+
+def test_one_tap_layer_blur_is_refused(sift):
+    """The other end: there is no radius-0 kernel.  0.1 / nine layers asks for
+    a first layer blur of sigma 0.041, one tap; 0.16 / nine layers (0.065,
+    three taps) is the smallest that runs."""
+    rc, msg, made = _create(sift, 0.1, 9)
+    assert rc == -1 and not made and "one tap" in msg and "sigma 0.1" in msg and "numOctaveLayers 9" in msg, msg
+    rc, msg, made = _create(sift, 0.16, 9)
+    assert rc == 0 and made, msg
+
+
+@pytest.mark.parametrize("sigma,layers,upscale", [(4.0, 3, False), (1.0, 1, False), (1.6, 2, True), (5.0, 4, False)])
+def test_blur_at_the_limit_is_accepted(sift, sigma, layers, upscale):
+    """4.0 / three layers lands on radius 31 exactly; 1.0 / one layer needs 7, 14, 28."""
+    rc, msg, made = _create(sift, sigma, layers, upscale)
+    assert rc == 0 and made, msg
+
+
 def test_no_gpu_fails_loudly(sift):
     """Without a device the product path raises; there is no CPU fallback."""
     n = ctypes.c_int(-1)

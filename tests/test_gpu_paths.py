@@ -38,6 +38,16 @@ def test_many_layers_lds_extrema(sift, oracle, layers):
     ref = oracle.extrema(img, oracle.from_config(cfg))
     assert np.array_equal(cand[np.lexsort(cand.T[::-1])], ref[np.lexsort(ref.T[::-1])])
     check_vs_oracle(sift, oracle, cfg, det, img)
+    # The exact descriptor mode orders its jobs longest first only up to 8
+    # layers; beyond that it takes them in output order: the oracle's bytes
+    # either way.
+    _, dx = make_detector(sift, w, h, exact_descriptors=True, upscale=True, numOctaveLayers=layers, numFeatures=0)
+    dx.detectAndCompute(img)
+    assert dx.overflow_flags() == 0
+    xk, xd, _ = gpu_keypoints(dx)
+    ok, od = oracle.detect_and_compute(img, oracle.from_config(cfg))
+    assert_same_keypoints(xk, ok)
+    assert np.array_equal(xd[sort_keys(xk)], od[sort_keys(ok)])
 
 
 def test_many_buckets_four_kernel_order(sift, oracle):
