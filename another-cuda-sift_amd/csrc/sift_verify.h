@@ -1,5 +1,6 @@
 // Two-view verifier launch interface (verify.hip) used by verify_api.hip's C
-// ABI (sift_hip_verify_*; the rule is in include/sift_hip.h).
+// ABI (sift_hip_verify_*, sift_hip_project_homography_device; the rules are in
+// include/sift_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,23 +37,34 @@ static_assert(sizeof(VerifyResult) == 52, "sift_hip_verify_result layout");
 // with an index outside its position array; j in [n, cap) is not written.
 void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s);
 
-// k_verify_hypotheses: hypothesis k in [0, K) draws its 8 matches
-// (samples[8 k ..], -1 when n < 8) and solves them: F[9 k ..] and valid[k]
-// (an invalid hypothesis has F all zero).
-void launch_verify_hypotheses(const VerifyInput& in, const float4* pts, int K, unsigned seed, int* samples, float* F,
-                              int* valid, hipStream_t s);
+// The model a verify call fits: it selects the hypothesis kernel and the
+// predicate the score and select kernels are instantiated with.
+enum class VerifyModel { Fundamental = 1, Homography = 2 };
 
-// k_verify_score: counts[k] = the matches j < n that pass the epipolar
-// predicate under F[9 k ..] with e2 = max_error^2; 0 where valid (nullable)
-// says the hypothesis is invalid.
-void launch_verify_score(const VerifyInput& in, const float4* pts, const float* F, const int* valid, int K, float e2,
-                         int* counts, hipStream_t s);
+// k_verify_hypotheses / k_verify_hypotheses_h: hypothesis k in [0, K) draws its
+// m matches (m = 8 for the fundamental matrix, 4 for the homography;
+// samples[m k ..], -1 when n < m) and solves them: F[9 k ..] and valid[k] (an
+// invalid hypothesis has F all zero).
+void launch_verify_hypotheses(VerifyModel model, const VerifyInput& in, const float4* pts, int K, unsigned seed,
+                              int* samples, float* F, int* valid, hipStream_t s);
+
+// k_verify_score: counts[k] = the matches j < n that pass the model's predicate
+// (Sampson distance / forward transfer error) under F[9 k ..] with
+// e2 = max_error^2; 0 where valid (nullable) says the hypothesis is invalid.
+void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+                         int K, float e2, int* counts, hipStream_t s);
 
 // k_verify_select: the winner (most inliers among the valid, ties to the lowest
-// k) into *result, its inlier mask (cap bytes, nullable), the inlier records in
-// input order (out, nullable) and their number (out_count, nullable).
-void launch_verify_select(const VerifyInput& in, const float4* pts, const float* F, const int* valid, const int* counts,
-                          int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count, uint8_t* mask,
-                          hipStream_t s);
+// k) into *result (sift_hip_homography_result has the same layout), its inlier
+// mask (cap bytes, nullable), the inlier records in input order (out, nullable)
+// and their number (out_count, nullable).
+void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+                          const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
+                          uint8_t* mask, hipStream_t s);
+
+// k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
+// `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.
+void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,
+                               hipStream_t s);
 
 }  // namespace sift_amd

@@ -1,27 +1,35 @@
-// Two-view verification: a fixed-budget RANSAC for the fundamental matrix over
-// a match list, on the device (sift_hip_verify_*; the rule -- sampler, solver,
-// score, selection -- is written out in include/sift_hip.h and mirrored in
-// numpy by sift_amd.cv.ransac_fundamental).
+// Two-view verification: a fixed-budget RANSAC over a match list, on the device,
+// for the fundamental matrix (sift_hip_verify_fundamental_*) and the homography
+// (sift_hip_verify_homography_*), and the projection of positions through a
+// homography (sift_hip_project_homography_device).  The rules -- sampler,
+// solver, score, selection -- are written out in include/sift_hip.h and
+// mirrored in numpy by sift_amd.cv.ransac_fundamental / ransac_homography.
 //
-//  k_verify_gather      record j -> (qx, qy, tx, ty) in scratch, NaN for a
-//                       record whose index lies outside its position array:
-//                       the only kernel that reads positions through a record.
-//  k_verify_hypotheses  one thread per hypothesis: the counter-based draw of 8
-//                       distinct matches and the normalised 8-point solve.
-//                       Full pivoting indexes the 8 x 9 system by run-time
-//                       row and column, so it lives in LDS laid out
-//                       [entry][lane] (a lane's entries are 64 floats apart:
-//                       every access of a wave is one conflict-free row).
-//  k_verify_score       the hot path, K x n predicate evaluations: one wave
-//                       per hypothesis, the workgroup's waves share an
-//                       LDS-staged tile of the gathered matches, lanes stride
-//                       over it, ballot + popcount count, one store per
-//                       hypothesis.  The predicate is sift_epipolar.h's, the
-//                       matcher's own.
-//  k_verify_select      one 1024-thread workgroup: argmax with the tie rule,
-//                       the winner rescored into the mask, and the ordered
-//                       compaction of k_match_select (prefix sums, no atomics:
-//                       the same bytes in every run).
+//  k_verify_gather        record j -> (qx, qy, tx, ty) in scratch, NaN for a
+//                         record whose index lies outside its position array:
+//                         the only kernel that reads positions through a record.
+//  k_verify_hypotheses    one thread per hypothesis: the counter-based draw of 8
+//                         distinct matches and the normalised 8-point solve.
+//                         Full pivoting indexes the 8 x 9 system by run-time
+//                         row and column, so it lives in LDS laid out
+//                         [entry][lane] (a lane's entries are 64 floats apart:
+//                         every access of a wave is one conflict-free row).
+//  k_verify_hypotheses_h  the same for the homography: 4 matches, the
+//                         orientation test, the 8 x 9 DLT system through the
+//                         same elimination (solve_8x9), the sign of w.
+//  k_verify_score         the hot path, K x n predicate evaluations: one wave
+//                         per hypothesis, the workgroup's waves share an
+//                         LDS-staged tile of the gathered matches, lanes stride
+//                         over it, ballot + popcount count, one store per
+//                         hypothesis.  One body for both models: the predicate
+//                         is a template parameter (SampsonPass: sift_epipolar.h's,
+//                         the matcher's own; TransferPass: the forward transfer
+//                         error with the chirality test).
+//  k_verify_select        one 1024-thread workgroup: argmax with the tie rule,
+//                         the winner rescored into the mask, and the ordered
+//                         compaction of k_match_select (prefix sums, no atomics:
+//                         the same bytes in every run).  The same template.
+//  k_project_homography   one thread per position row.
 // Everything is float32 with -ffp-contract=off and correctly rounded division
 // and square root: the operation order written here is the one executed.
 #include <float.h>
@@ -52,29 +60,57 @@ __device__ __forceinline__ unsigned mix32(unsigned h) {
 
 __device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < INFINITY; }
 
-// Hartley normalisation of one side of a sample: x, y become the normalised
-// coordinates, (s, ox, oy) the similarity x' = s x + ox.
-__device__ __forceinline__ void normalise8(float (&x)[8], float (&y)[8], float& s, float& ox, float& oy) {
+// The draw of hypothesis k: M distinct indices of [0, n), n >= M, a function of (seed, k, n).
+template <int M>
+__device__ __forceinline__ void draw(unsigned seed, int k, int n, int (&pick)[M]) {
+    const unsigned base = mix32(seed ^ mix32((unsigned)k));
+    int sorted[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+        const unsigned h = mix32(base + 0x9e3779b9u * (unsigned)(j + 1));
+        int r = (int)(((unsigned long long)h * (unsigned long long)(unsigned)(n - j)) >> 32);
+#pragma unroll
+        for (int i = 0; i < j; i++)
+            if (r >= sorted[i]) r++;
+        pick[j] = r;
+        int v = r;
+#pragma unroll
+        for (int i = 0; i < j; i++)
+            if (sorted[i] > v) {
+                const int t = sorted[i];
+                sorted[i] = v;
+                v = t;
+            }
+        sorted[j] = v;
+    }
+}
+
+// Hartley normalisation of one side of a sample of M points: x, y become the
+// normalised coordinates, (s, ox, oy) the similarity x' = s x + ox, (mx, my) the
+// mean.
+template <int M>
+__device__ __forceinline__ void normalise(float (&x)[M], float (&y)[M], float& s, float& ox, float& oy, float& mx,
+                                          float& my) {
 #pragma clang fp contract(off)
     float sx = x[0], sy = y[0];
 #pragma unroll
-    for (int i = 1; i < 8; i++) {
+    for (int i = 1; i < M; i++) {
         sx = sx + x[i];
         sy = sy + y[i];
     }
-    const float mx = sx / 8.0f, my = sy / 8.0f;
+    mx = sx / (float)M, my = sy / (float)M;
     float sd = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
+    for (int i = 0; i < M; i++) {
         x[i] = x[i] - mx;
         y[i] = y[i] - my;
         const float d = __builtin_sqrtf(x[i] * x[i] + y[i] * y[i]);
         sd = i == 0 ? d : sd + d;
     }
-    const float md = sd / 8.0f;
+    const float md = sd / (float)M;
     s = 1.41421354f / md;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
+    for (int i = 0; i < M; i++) {
         x[i] = x[i] * s;
         y[i] = y[i] * s;
     }
@@ -83,6 +119,79 @@ __device__ __forceinline__ void normalise8(float (&x)[8], float (&y)[8], float& 
 }
 
 constexpr int kHypThreads = 64;
+
+// A lane's column of the [entry][lane] LDS arrays of the hypothesis kernels.
+#define VA(r, c) A[((r) * 9 + (c)) * kHypThreads]
+
+// The solver both models share, on one lane's 8 x 9 system A (entry e = 9 row + col at A[e * kHypThreads]), with Y
+// (9 entries) and P (9 entries) its scratch: Gaussian elimination with full pivoting, back-substitution with the free
+// variable 1, the column permutation undone into g.  False for a zero or non-finite pivot (g is then not written).
+__device__ __forceinline__ bool solve_8x9(float* const A, float* const Y, int* const P, float (&g)[9]) {
+#pragma clang fp contract(off)
+    for (int c = 0; c < 9; c++) P[c * kHypThreads] = c;
+    // The pivot: the largest |entry| of rows and columns >= c, the scan starting at (c, c) in row-major order and
+    // moving on a strictly larger value only.
+    for (int c = 0; c < 8; c++) {
+        float best = __builtin_fabsf(VA(c, c));
+        int pr = c, pc = c;
+        for (int r = c; r < 8; r++)
+            for (int j = c; j < 9; j++) {
+                const float a = __builtin_fabsf(VA(r, j));
+                if (a > best) best = a, pr = r, pc = j;
+            }
+        if (pr != c)
+            for (int j = c; j < 9; j++) {
+                const float t = VA(c, j);
+                VA(c, j) = VA(pr, j);
+                VA(pr, j) = t;
+            }
+        if (pc != c) {
+            for (int r = 0; r < 8; r++) {
+                const float t = VA(r, c);
+                VA(r, c) = VA(r, pc);
+                VA(r, pc) = t;
+            }
+            const int t = P[c * kHypThreads];
+            P[c * kHypThreads] = P[pc * kHypThreads];
+            P[pc * kHypThreads] = t;
+        }
+        const float p = VA(c, c);
+        if (!(p != 0.f && finite_f(p))) return false;
+        for (int r = c + 1; r < 8; r++) {
+            const float m = VA(r, c) / p;
+            for (int j = c + 1; j < 9; j++) VA(r, j) = VA(r, j) - m * VA(c, j);
+        }
+    }
+    // The free variable (position 8) is 1; back-substitution, sums in ascending column order.
+    Y[8 * kHypThreads] = 1.0f;
+    for (int i = 7; i >= 0; i--) {
+        float acc = VA(i, i + 1) * Y[(i + 1) * kHypThreads];
+        for (int j = i + 2; j < 9; j++) acc = acc + VA(i, j) * Y[j * kHypThreads];
+        Y[i * kHypThreads] = (-acc) / VA(i, i);
+    }
+    // Undo the column permutation (through the system's storage, no longer needed).
+    for (int j = 0; j < 9; j++) A[P[j * kHypThreads] * kHypThreads] = Y[j * kHypThreads];
+#pragma unroll
+    for (int i = 0; i < 9; i++) g[i] = A[i * kHypThreads];
+    return true;
+}
+
+// Scales m to unit Frobenius norm (ss summed in index order).
+__device__ __forceinline__ void unit_norm(float (&m)[9]) {
+#pragma clang fp contract(off)
+    float ss = m[0] * m[0];
+#pragma unroll
+    for (int i = 1; i < 9; i++) ss = ss + m[i] * m[i];
+    const float nrm = __builtin_sqrtf(ss);
+#pragma unroll
+    for (int i = 0; i < 9; i++) m[i] = m[i] / nrm;
+}
+
+// The signed area of the triangle (i, j, k) of a sample side, twice.
+__device__ __forceinline__ float area2(const float (&x)[4], const float (&y)[4], int i, int j, int k) {
+#pragma clang fp contract(off)
+    return (x[j] - x[i]) * (y[k] - y[i]) - (y[j] - y[i]) * (x[k] - x[i]);
+}
 
 }  // namespace
 
@@ -112,9 +221,6 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
     if (k >= K) return;  // no barrier below: a lane works on its own LDS column
     const int n = verify_n(in.count, in.cap);
     float* const A = s_a + lane;
-    float* const Y = s_y + lane;
-    int* const P = s_perm + lane;
-#define VA(r, c) A[((r) * 9 + (c)) * kHypThreads]
 
     bool ok = n >= 8;
     int pick[8];
@@ -125,35 +231,15 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
     for (int i = 0; i < 9; i++) g[i] = 0.f;
     float sq = 0.f, oqx = 0.f, oqy = 0.f, st = 0.f, otx = 0.f, oty = 0.f;
     if (ok) {
-        // The draw: 8 distinct indices of [0, n), a function of (seed, k, n).
-        const unsigned base = mix32(seed ^ mix32((unsigned)k));
-        int sorted[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const unsigned h = mix32(base + 0x9e3779b9u * (unsigned)(j + 1));
-            int r = (int)(((unsigned long long)h * (unsigned long long)(unsigned)(n - j)) >> 32);
-#pragma unroll
-            for (int i = 0; i < j; i++)
-                if (r >= sorted[i]) r++;
-            pick[j] = r;
-            int v = r;
-#pragma unroll
-            for (int i = 0; i < j; i++)
-                if (sorted[i] > v) {
-                    const int t = sorted[i];
-                    sorted[i] = v;
-                    v = t;
-                }
-            sorted[j] = v;
-        }
-        float qx[8], qy[8], tx[8], ty[8];
+        draw<8>(seed, k, n, pick);
+        float qx[8], qy[8], tx[8], ty[8], mx, my;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const float4 p = pts[pick[j]];
             qx[j] = p.x, qy[j] = p.y, tx[j] = p.z, ty[j] = p.w;
         }
-        normalise8(qx, qy, sq, oqx, oqy);
-        normalise8(tx, ty, st, otx, oty);
+        normalise<8>(qx, qy, sq, oqx, oqy, mx, my);
+        normalise<8>(tx, ty, st, otx, oty, mx, my);
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             VA(r, 0) = tx[r] * qx[r];
@@ -166,54 +252,9 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
             VA(r, 7) = qy[r];
             VA(r, 8) = 1.0f;
         }
-        for (int c = 0; c < 9; c++) P[c * kHypThreads] = c;
-        // Gaussian elimination with full pivoting: the largest |entry| of rows and columns >= c, the scan starting at
-        // (c, c) in row-major order and moving on a strictly larger value only.
-        for (int c = 0; c < 8 && ok; c++) {
-            float best = __builtin_fabsf(VA(c, c));
-            int pr = c, pc = c;
-            for (int r = c; r < 8; r++)
-                for (int j = c; j < 9; j++) {
-                    const float a = __builtin_fabsf(VA(r, j));
-                    if (a > best) best = a, pr = r, pc = j;
-                }
-            if (pr != c)
-                for (int j = c; j < 9; j++) {
-                    const float t = VA(c, j);
-                    VA(c, j) = VA(pr, j);
-                    VA(pr, j) = t;
-                }
-            if (pc != c) {
-                for (int r = 0; r < 8; r++) {
-                    const float t = VA(r, c);
-                    VA(r, c) = VA(r, pc);
-                    VA(r, pc) = t;
-                }
-                const int t = P[c * kHypThreads];
-                P[c * kHypThreads] = P[pc * kHypThreads];
-                P[pc * kHypThreads] = t;
-            }
-            const float p = VA(c, c);
-            ok = p != 0.f && finite_f(p);
-            if (!ok) break;
-            for (int r = c + 1; r < 8; r++) {
-                const float m = VA(r, c) / p;
-                for (int j = c + 1; j < 9; j++) VA(r, j) = VA(r, j) - m * VA(c, j);
-            }
-        }
+        ok = solve_8x9(A, s_y + lane, s_perm + lane, g);
     }
     if (ok) {
-        // The free variable (position 8) is 1; back-substitution, sums in ascending column order.
-        Y[8 * kHypThreads] = 1.0f;
-        for (int i = 7; i >= 0; i--) {
-            float acc = VA(i, i + 1) * Y[(i + 1) * kHypThreads];
-            for (int j = i + 2; j < 9; j++) acc = acc + VA(i, j) * Y[j * kHypThreads];
-            Y[i * kHypThreads] = (-acc) / VA(i, i);
-        }
-        // Undo the column permutation (through the system's storage, no longer needed).
-        for (int j = 0; j < 9; j++) A[P[j * kHypThreads] * kHypThreads] = Y[j * kHypThreads];
-#pragma unroll
-        for (int i = 0; i < 9; i++) g[i] = A[i * kHypThreads];
         // F = Tt^T G Tq: H = G Tq, then F = Tt^T H.
         float H[9], F[9];
 #pragma unroll
@@ -228,17 +269,13 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
             F[3 + c] = st * H[3 + c];
             F[6 + c] = (otx * H[c] + oty * H[3 + c]) + H[6 + c];
         }
-        float ss = F[0] * F[0];
-#pragma unroll
-        for (int i = 1; i < 9; i++) ss = ss + F[i] * F[i];
-        const float nrm = __builtin_sqrtf(ss);
+        unit_norm(F);
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            g[i] = F[i] / nrm;
+            g[i] = F[i];
             ok = ok && finite_f(g[i]);
         }
     }
-#undef VA
 #pragma unroll
     for (int j = 0; j < 8; j++) samples[8 * (size_t)k + j] = pick[j];
 #pragma unroll
@@ -246,17 +283,122 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
     valid[k] = ok ? 1 : 0;
 }
 
-// The predicate of match p under a hypothesis: the matcher's epipolar gate for
-// the match's own pair, no window (radius = +inf).
-__device__ __forceinline__ bool verify_pass(const float (&f)[9], const float4 p, float e2) {
-    const EpiQuery q = epi_query(f, p.x, p.y);
-    return epi_pass(q, p.z, p.w, epi_row(f, p.z, p.w), e2, INFINITY);
+__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(VerifyInput in, const float4* __restrict__ pts,
+                                                                    int K, unsigned seed, int* __restrict__ samples,
+                                                                    float* __restrict__ Hout, int* __restrict__ valid) {
+#pragma clang fp contract(off)
+    __shared__ float s_a[72 * kHypThreads];  // as in k_verify_hypotheses
+    __shared__ float s_y[9 * kHypThreads];
+    __shared__ int s_perm[9 * kHypThreads];
+    const int lane = threadIdx.x;
+    const int k = blockIdx.x * kHypThreads + lane;
+    if (k >= K) return;  // no barrier below: a lane works on its own LDS column
+    const int n = verify_n(in.count, in.cap);
+    float* const A = s_a + lane;
+
+    bool ok = n >= 4;
+    int pick[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) pick[j] = -1;
+    float g[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) g[i] = 0.f;
+    float qx[4], qy[4], tx[4], ty[4];
+    float qx0 = 0.f, qy0 = 0.f;
+    if (ok) {
+        draw<4>(seed, k, n, pick);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float4 p = pts[pick[j]];
+            qx[j] = p.x, qy[j] = p.y, tx[j] = p.z, ty[j] = p.w;
+        }
+        qx0 = qx[0], qy0 = qy[0];
+        // The orientation test on the raw coordinates: every triple keeps, or every triple flips, its orientation.
+        // A zero (three collinear points) or a NaN fails both.
+        bool keeps = true, flips = true;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int i = t < 3 ? 0 : 1, j = t < 2 ? 1 : 2, l = t == 0 ? 2 : 3;  // (0,1,2) (0,1,3) (0,2,3) (1,2,3)
+            const float p = area2(qx, qy, i, j, l) * area2(tx, ty, i, j, l);
+            keeps = keeps && p > 0.f;
+            flips = flips && p < 0.f;
+        }
+        ok = keeps || flips;
+    }
+    float sq = 0.f, oqx = 0.f, oqy = 0.f, st = 0.f, otx = 0.f, oty = 0.f, mqx, mqy, mtx = 0.f, mty = 0.f;
+    if (ok) {
+        normalise<4>(qx, qy, sq, oqx, oqy, mqx, mqy);
+        normalise<4>(tx, ty, st, otx, oty, mtx, mty);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {  // rows 2 i and 2 i + 1: pair i, (x, y) -> (u, v)
+            const float x = qx[i], y = qy[i], u = tx[i], v = ty[i];
+            VA(2 * i, 0) = x, VA(2 * i, 1) = y, VA(2 * i, 2) = 1.0f;
+            VA(2 * i, 3) = 0.f, VA(2 * i, 4) = 0.f, VA(2 * i, 5) = 0.f;
+            VA(2 * i, 6) = -(u * x), VA(2 * i, 7) = -(u * y), VA(2 * i, 8) = -u;
+            VA(2 * i + 1, 0) = 0.f, VA(2 * i + 1, 1) = 0.f, VA(2 * i + 1, 2) = 0.f;
+            VA(2 * i + 1, 3) = x, VA(2 * i + 1, 4) = y, VA(2 * i + 1, 5) = 1.0f;
+            VA(2 * i + 1, 6) = -(v * x), VA(2 * i + 1, 7) = -(v * y), VA(2 * i + 1, 8) = -v;
+        }
+        ok = solve_8x9(A, s_y + lane, s_perm + lane, g);
+    }
+    if (ok) {
+        // H = Tt^-1 G Tq: M = G Tq, then H = Tt^-1 M.
+        float M[9], H[9];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            M[3 * r + 0] = g[3 * r + 0] * sq;
+            M[3 * r + 1] = g[3 * r + 1] * sq;
+            M[3 * r + 2] = (g[3 * r + 0] * oqx + g[3 * r + 1] * oqy) + g[3 * r + 2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            H[c] = M[c] / st + mtx * M[6 + c];
+            H[3 + c] = M[3 + c] / st + mty * M[6 + c];
+            H[6 + c] = M[6 + c];
+        }
+        unit_norm(H);
+        // The sign that puts sample 0 in front (w > 0), so the score's chirality test means something.
+        const float w0 = (H[6] * qx0 + H[7] * qy0) + H[8];
+        ok = w0 != 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            g[i] = w0 < 0.f ? -H[i] : H[i];
+            ok = ok && finite_f(g[i]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) samples[4 * (size_t)k + j] = pick[j];
+#pragma unroll
+    for (int i = 0; i < 9; i++) Hout[9 * (size_t)k + i] = ok ? g[i] : 0.f;
+    valid[k] = ok ? 1 : 0;
 }
+#undef VA
+
+// The predicates of match p = (qx, qy, tx, ty) under a hypothesis, e2 = max_error^2.
+// Fundamental: the matcher's epipolar gate for the match's own pair, no window (radius = +inf).
+struct SampsonPass {
+    static __device__ __forceinline__ bool pass(const float (&f)[9], const float4 p, float e2) {
+        const EpiQuery q = epi_query(f, p.x, p.y);
+        return epi_pass(q, p.z, p.w, epi_row(f, p.z, p.w), e2, INFINITY);
+    }
+};
+// Homography: the forward transfer error, division-free, in front of the camera only.
+struct TransferPass {
+    static __device__ __forceinline__ bool pass(const float (&h)[9], const float4 p, float e2) {
+#pragma clang fp contract(off)
+        const float px = (h[0] * p.x + h[1] * p.y) + h[2];
+        const float py = (h[3] * p.x + h[4] * p.y) + h[5];
+        const float w = (h[6] * p.x + h[7] * p.y) + h[8];
+        const float dx = px - p.z * w, dy = py - p.w * w;
+        return (w > 0.f) & (dx * dx + dy * dy <= e2 * (w * w));
+    }
+};
 
 constexpr int kScoreWaves = 4;     // hypotheses per workgroup
 constexpr int kScoreUnroll = 4;    // matches per lane and loop iteration
 constexpr int kScoreTile = 2048;   // matches per LDS tile (32 KiB): 2000 matches are one tile
 
+template <class Pass>
 __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput in, const float4* __restrict__ pts,
                                                                    const float* __restrict__ F,
                                                                    const int* __restrict__ valid, int K, float e2,
@@ -265,7 +407,7 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput i
     const int n = verify_n(in.count, in.cap);
     const int tid = threadIdx.x, lane = tid & 63;
     const int k = blockIdx.x * kScoreWaves + __builtin_amdgcn_readfirstlane(tid >> 6);
-    // F and the flag are loaded side by side (an invalid hypothesis' row is zero, not garbage).
+    // The model and the flag are loaded side by side (an invalid hypothesis' row is zero, not garbage).
     float f[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) f[i] = k < K ? F[9 * (size_t)k + i] : 0.f;
@@ -282,7 +424,7 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput i
 #pragma unroll
                 for (int u = 0; u < kScoreUnroll; u++) {
                     const int i = i0 + 64 * u + lane;
-                    pass[u] = (i < m) & verify_pass(f, s_pts[i < m ? i : 0], e2);  // no branch: m >= 1 here
+                    pass[u] = (i < m) & Pass::pass(f, s_pts[i < m ? i : 0], e2);  // no branch: m >= 1 here
                 }
 #pragma unroll
                 for (int u = 0; u < kScoreUnroll; u++) cnt += __popcll(__ballot(pass[u]));
@@ -293,6 +435,7 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput i
 
 constexpr int kVSelThreads = 1024, kVSelWaves = kVSelThreads / 64;
 
+template <class Pass>
 __global__ __launch_bounds__(kVSelThreads) void k_verify_select(VerifyInput in, const float4* __restrict__ pts,
                                                                 const float* __restrict__ F,
                                                                 const int* __restrict__ valid,
@@ -343,7 +486,7 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(VerifyInput in, 
     int base = 0;
     for (int c0 = 0; c0 < in.cap; c0 += kVSelThreads) {  // workgroup-uniform
         const int j = c0 + tid;
-        const bool keep = hyp >= 0 && j < n && verify_pass(f, pts[j < n ? j : 0], e2);
+        const bool keep = hyp >= 0 && j < n && Pass::pass(f, pts[j < n ? j : 0], e2);
         if (mask && j < in.cap) mask[j] = keep ? 1 : 0;
         const unsigned long long bal = __ballot(keep);
         if (lane == 0) s_wave[w] = __popcll(bal);
@@ -362,27 +505,63 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(VerifyInput in, 
     if (tid == 0 && out_count) *out_count = base;
 }
 
+// Row i of xy through H: (px / w, py / w), NaN x 2 where w is not > 0.  out may be xy itself (equal strides): a
+// thread reads its row before it writes it.
+__global__ __launch_bounds__(256) void k_project_homography(const float* H, const float* xy, int stride, int n,
+                                                            float* out, int out_stride) {
+#pragma clang fp contract(off)
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    float h[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) h[e] = H[e];
+    const float x = xy[(size_t)i * stride], y = xy[(size_t)i * stride + 1];
+    const float px = (h[0] * x + h[1] * y) + h[2];
+    const float py = (h[3] * x + h[4] * y) + h[5];
+    const float w = (h[6] * x + h[7] * y) + h[8];
+    const bool front = w > 0.f;
+    out[(size_t)i * out_stride] = front ? px / w : NAN;
+    out[(size_t)i * out_stride + 1] = front ? py / w : NAN;
+}
+
 void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s) {
     if (in.cap > 0) hipLaunchKernelGGL(k_verify_gather, dim3((in.cap + 255) / 256), dim3(256), 0, s, in, pts);
 }
 
-void launch_verify_hypotheses(const VerifyInput& in, const float4* pts, int K, unsigned seed, int* samples, float* F,
-                              int* valid, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify_hypotheses, dim3((K + kHypThreads - 1) / kHypThreads), dim3(kHypThreads), 0, s, in, pts, K,
-                       seed, samples, F, valid);
+void launch_verify_hypotheses(VerifyModel model, const VerifyInput& in, const float4* pts, int K, unsigned seed,
+                              int* samples, float* F, int* valid, hipStream_t s) {
+    const dim3 grid((K + kHypThreads - 1) / kHypThreads), block(kHypThreads);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL(k_verify_hypotheses_h, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
+    else
+        hipLaunchKernelGGL(k_verify_hypotheses, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
 }
 
-void launch_verify_score(const VerifyInput& in, const float4* pts, const float* F, const int* valid, int K, float e2,
-                         int* counts, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify_score, dim3((K + kScoreWaves - 1) / kScoreWaves), dim3(64 * kScoreWaves), 0, s, in, pts, F,
-                       valid, K, e2, counts);
+void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+                         int K, float e2, int* counts, hipStream_t s) {
+    const dim3 grid((K + kScoreWaves - 1) / kScoreWaves), block(64 * kScoreWaves);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL(k_verify_score<TransferPass>, grid, block, 0, s, in, pts, F, valid, K, e2, counts);
+    else
+        hipLaunchKernelGGL(k_verify_score<SampsonPass>, grid, block, 0, s, in, pts, F, valid, K, e2, counts);
 }
 
-void launch_verify_select(const VerifyInput& in, const float4* pts, const float* F, const int* valid, const int* counts,
-                          int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count, uint8_t* mask,
-                          hipStream_t s) {
-    hipLaunchKernelGGL(k_verify_select, dim3(1), dim3(kVSelThreads), 0, s, in, pts, F, valid, counts, K, e2, result, out,
-                       out_count, mask);
+void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+                          const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
+                          uint8_t* mask, hipStream_t s) {
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL(k_verify_select<TransferPass>, dim3(1), dim3(kVSelThreads), 0, s, in, pts, F, valid, counts, K,
+                           e2, result, out, out_count, mask);
+    else
+        hipLaunchKernelGGL(k_verify_select<SampsonPass>, dim3(1), dim3(kVSelThreads), 0, s, in, pts, F, valid, counts, K,
+                           e2, result, out, out_count, mask);
+}
+
+void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,
+                               hipStream_t s) {
+    if (n > 0)
+        hipLaunchKernelGGL(k_project_homography, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, s, H, xy, stride,
+                           n, out, out_stride);
 }
 
 }  // namespace sift_amd

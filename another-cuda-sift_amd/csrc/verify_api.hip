@@ -1,10 +1,11 @@
-// Verifier handle (sift_hip_verifier_*, sift_hip_verify_*, sift_hip_score_*) of
-// libsift_hip.so; the kernels are verify.hip.  The handle owns every scratch
+// Verifier handle (sift_hip_verifier_*, sift_hip_verify_*, sift_hip_score_*) and
+// sift_hip_project_homography_device of libsift_hip.so; the kernels are verify.hip.  The handle owns every scratch
 // array from creation on, so a device call only launches kernels (capturable).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <string>
 
 #include "detector_state.h"
@@ -14,15 +15,16 @@ struct sift_hip_verifier {
     int device = 0;
     int maxM = 0, maxK = 0;
     float4* dPts = nullptr;      // the gathered matches (qx, qy, tx, ty)
-    int* dSamples = nullptr;     // 8 per hypothesis
-    float* dF = nullptr;         // 9 per hypothesis
+    int* dSamples = nullptr;     // 8 per hypothesis (the homography uses 4)
+    float* dF = nullptr;         // 9 per hypothesis (F, or H)
     int* dValid = nullptr;
     int* dCounts = nullptr;
-    // the outputs of sift_hip_verify_fundamental_host
+    // the outputs of sift_hip_verify_fundamental_host / _homography_host
     VerifyResult* dResult = nullptr;
     MatchRecord* dOut = nullptr;
     uint8_t* dMask = nullptr;
-    int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_hypotheses_host)
+    int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
+    int lastModel = 0;           // its VerifyModel, 0: none
     ~sift_hip_verifier() {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
@@ -32,6 +34,9 @@ struct sift_hip_verifier {
 };
 
 static_assert(sizeof(sift_hip_verify_result) == sizeof(VerifyResult), "the result record is written by the kernel");
+static_assert(sizeof(sift_hip_homography_result) == sizeof(VerifyResult) &&
+                  offsetof(sift_hip_homography_result, inliers) == offsetof(VerifyResult, inliers),
+              "both models' result records share the kernel's layout");
 
 namespace {
 
@@ -60,16 +65,89 @@ int check_limits(const sift_hip_verifier* v, int cap, int K) {
     return SIFT_HIP_OK;
 }
 
-int verify_device(sift_hip_verifier* v, const VerifyInput& in, const sift_hip_verify_params& p, VerifyResult* result,
-                  MatchRecord* out, int* out_count, uint8_t* mask, hipStream_t s) {
+int verify_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in, const sift_hip_verify_params& p,
+                  VerifyResult* result, MatchRecord* out, int* out_count, uint8_t* mask, hipStream_t s) {
     const float e2 = p.max_error * p.max_error;
     HIPCHK(hipSetDevice(v->device));
     launch_verify_gather(in, v->dPts, s);
-    launch_verify_hypotheses(in, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
-    launch_verify_score(in, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
-    launch_verify_select(in, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, result, out, out_count, mask, s);
+    launch_verify_hypotheses(model, in, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
+    launch_verify_score(model, in, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
+    launch_verify_select(model, in, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, result, out, out_count, mask,
+                         s);
     HIPCHK(hipGetLastError());
     v->lastK = p.hypotheses;
+    v->lastModel = (int)model;
+    return SIFT_HIP_OK;
+}
+
+// The entry points of both models (the record types share a layout): argument rules, then the launches.
+int verify_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
+                        const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                        const sift_hip_verify_params* params, void* result, sift_hip_dmatch* out, int* out_count,
+                        uint8_t* mask, void* stream) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!params || !result) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
+    if (int rc = check_error(params->max_error)) return rc;
+    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
+    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
+    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    return verify_device(v, model, in, *params, static_cast<VerifyResult*>(result), reinterpret_cast<MatchRecord*>(out),
+                         out_count, mask, (hipStream_t)stream);
+}
+
+int verify_model_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
+                      const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                      const sift_hip_verify_params* params, void* result_host, sift_hip_dmatch* out_host,
+                      uint8_t* mask_host) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!params || !result_host) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
+    if (int rc = check_error(params->max_error)) return rc;
+    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    if (int rc = verify_device(v, model, in, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
+    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
+    const int n = std::min(static_cast<const VerifyResult*>(result_host)->inliers, cap);
+    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+    if (mask_host && cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+int score_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
+                       const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                       const float* M, int K, float max_error, int* counts, void* stream) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (!M || !counts)
+        return fail(SIFT_HIP_ERR_INVALID, model == VerifyModel::Homography ? "verify: null H or counts"
+                                                                           : "verify: null F or counts");
+    if (int rc = check_error(max_error)) return rc;
+    if (int rc = check_limits(v, cap, K)) return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather(in, v->dPts, (hipStream_t)stream);
+    launch_verify_score(model, in, v->dPts, M, nullptr, K, max_error * max_error, counts, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// What the last verify call of `model` drew (m indices per hypothesis), solved and counted.
+int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples, float* M, int* counts, int cap) {
+    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
+    if (cap < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: negative cap");
+    if (v->lastK == 0) return fail(SIFT_HIP_ERR_STATE, "no verify call has run on this verifier");
+    if (v->lastModel != (int)model)
+        return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was of the other model");
+    const size_t K = (size_t)std::min(cap, v->lastK);
+    if (K == 0) return SIFT_HIP_OK;
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (samples) HIPCHK(hipMemcpy(samples, v->dSamples, sizeof(int) * (size_t)m * K, hipMemcpyDeviceToHost));
+    if (M) HIPCHK(hipMemcpy(M, v->dF, sizeof(float) * 9 * K, hipMemcpyDeviceToHost));
+    if (counts) HIPCHK(hipMemcpy(counts, v->dCounts, sizeof(int) * K, hipMemcpyDeviceToHost));
     return SIFT_HIP_OK;
 }
 
@@ -123,17 +201,8 @@ int sift_hip_verify_fundamental_device(sift_hip_verifier_t v, const sift_hip_dma
                                        int train_stride, int nt, const sift_hip_verify_params* params,
                                        sift_hip_verify_result* result, sift_hip_dmatch* out, int* out_count,
                                        uint8_t* mask, void* stream) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!params || !result) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
-    if (int rc = check_error(params->max_error)) return rc;
-    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
-    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
-    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    return verify_device(v, in, *params, reinterpret_cast<VerifyResult*>(result), reinterpret_cast<MatchRecord*>(out),
-                         out_count, mask, (hipStream_t)stream);
+    return verify_model_device(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                               train_stride, nt, params, result, out, out_count, mask, stream);
 }
 
 int sift_hip_verify_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
@@ -141,48 +210,68 @@ int sift_hip_verify_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatc
                                      int train_stride, int nt, const sift_hip_verify_params* params,
                                      sift_hip_verify_result* result_host, sift_hip_dmatch* out_host,
                                      uint8_t* mask_host) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!params || !result_host) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
-    if (int rc = check_error(params->max_error)) return rc;
-    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    if (int rc = verify_device(v, in, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
-    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
-    const int n = std::min(result_host->inliers, cap);
-    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
-    if (mask_host && cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
+    return verify_model_host(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                             train_stride, nt, params, result_host, out_host, mask_host);
 }
 
 int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
                                       const float* query_xy, int query_stride, int nq, const float* train_xy,
                                       int train_stride, int nt, const float* F, int K, float max_error, int* counts,
                                       void* stream) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!F || !counts) return fail(SIFT_HIP_ERR_INVALID, "verify: null F or counts");
-    if (int rc = check_error(max_error)) return rc;
-    if (int rc = check_limits(v, cap, K)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather(in, v->dPts, (hipStream_t)stream);
-    launch_verify_score(in, v->dPts, F, nullptr, K, max_error * max_error, counts, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
+    return score_model_device(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                              train_stride, nt, F, K, max_error, counts, stream);
 }
 
 int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap) {
-    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
-    if (cap < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: negative cap");
-    if (v->lastK == 0) return fail(SIFT_HIP_ERR_STATE, "no verify call has run on this verifier");
-    const size_t K = (size_t)std::min(cap, v->lastK);
-    if (K == 0) return SIFT_HIP_OK;
-    HIPCHK(hipSetDevice(v->device));
-    HIPCHK(hipDeviceSynchronize());
-    if (samples) HIPCHK(hipMemcpy(samples, v->dSamples, sizeof(int) * 8 * K, hipMemcpyDeviceToHost));
-    if (F) HIPCHK(hipMemcpy(F, v->dF, sizeof(float) * 9 * K, hipMemcpyDeviceToHost));
-    if (counts) HIPCHK(hipMemcpy(counts, v->dCounts, sizeof(int) * K, hipMemcpyDeviceToHost));
+    return hypotheses_host(v, VerifyModel::Fundamental, 8, samples, F, counts, cap);
+}
+
+int sift_hip_verify_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                      int train_stride, int nt, const sift_hip_verify_params* params,
+                                      sift_hip_homography_result* result, sift_hip_dmatch* out, int* out_count,
+                                      uint8_t* mask, void* stream) {
+    return verify_model_device(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                               train_stride, nt, params, result, out, out_count, mask, stream);
+}
+
+int sift_hip_verify_homography_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                    const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                    int train_stride, int nt, const sift_hip_verify_params* params,
+                                    sift_hip_homography_result* result_host, sift_hip_dmatch* out_host,
+                                    uint8_t* mask_host) {
+    return verify_model_host(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                             train_stride, nt, params, result_host, out_host, mask_host);
+}
+
+int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, const float* H, int K, float max_error, int* counts,
+                                     void* stream) {
+    return score_model_device(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
+                              train_stride, nt, H, K, max_error, counts, stream);
+}
+
+int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* samples, float* H, int* counts, int cap) {
+    return hypotheses_host(v, VerifyModel::Homography, 4, samples, H, counts, cap);
+}
+
+int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
+                                       void* stream) {
+    if (!H) return fail(SIFT_HIP_ERR_INVALID, "project: null H");
+    if (stride < 2 || out_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "project: a position stride below 2 floats");
+    if (n < 0) return fail(SIFT_HIP_ERR_INVALID, "project: a negative row count");
+    if (n == 0) return SIFT_HIP_OK;
+    if (!xy || !out_xy) return fail(SIFT_HIP_ERR_INVALID, "project: null position pointer");
+    // In place (the same rows: a thread reads its row before it writes it) or apart; anything between is refused.
+    const uintptr_t ib = (uintptr_t)xy, ob = (uintptr_t)out_xy;
+    const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
+    const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
+    // (differences, not sums: an extent may be as large as the address space)
+    if (!(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes))
+        return fail(SIFT_HIP_ERR_INVALID, "project: out_xy overlaps xy (only out_xy == xy with equal strides may)");
+    launch_project_homography(H, xy, stride, n, out_xy, out_stride, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return SIFT_HIP_OK;
 }
 

@@ -1,4 +1,5 @@
-// sift_cuda::Verifier / verifyFundamental (include/sift_cuda/Verify.hh) over the
+// sift_cuda::Verifier / verifyFundamental / verifyHomography / projectHomographyDevice
+// (include/sift_cuda/Verify.hh) over the
 // C ABI in include/sift_hip.h.  Plain C++ (g++): no HIP headers, no device code.
 #include "sift_cuda/Verify.hh"
 
@@ -15,6 +16,9 @@ namespace {
 static_assert(sizeof(VerifyResult) == sizeof(sift_hip_verify_result) &&
                   offsetof(VerifyResult, hypothesis) == offsetof(sift_hip_verify_result, hypothesis),
               "sift_cuda::VerifyResult is sift_hip_verify_result");
+static_assert(sizeof(HomographyResult) == sizeof(sift_hip_homography_result) &&
+                  offsetof(HomographyResult, hypothesis) == offsetof(sift_hip_homography_result, hypothesis),
+              "sift_cuda::HomographyResult is sift_hip_homography_result");
 
 void check_throw(int rc, const char* what) {
     if (rc == SIFT_HIP_OK) return;
@@ -28,7 +32,7 @@ sift_hip_verify_params toAbi(const VerifyParams& p) { return sift_hip_verify_par
 // A device allocation freed on every path out.
 struct DeviceBlock {
     void* p = nullptr;
-    explicit DeviceBlock(size_t bytes) { check_throw(sift_hip_malloc(&p, bytes ? bytes : 1), "verifyFundamental"); }
+    explicit DeviceBlock(size_t bytes) { check_throw(sift_hip_malloc(&p, bytes ? bytes : 1), "device allocation"); }
     ~DeviceBlock() { (void)sift_hip_free(p); }
     DeviceBlock(const DeviceBlock&) = delete;
     DeviceBlock& operator=(const DeviceBlock&) = delete;
@@ -71,6 +75,36 @@ TwoViewGeometry Verifier::verifyHost(const DMatch* matches, const int* count, in
     return g;
 }
 
+void Verifier::verifyHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                      int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                      const VerifyParams& params, HomographyResult* result, DMatch* out, int* out_count,
+                                      uint8_t* mask, void* stream) {
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(sift_hip_verify_homography_device(
+                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap, query_xy, query_stride, nq,
+                    train_xy, train_stride, nt, &p, reinterpret_cast<sift_hip_homography_result*>(result),
+                    reinterpret_cast<sift_hip_dmatch*>(out), out_count, mask, stream),
+                "Verifier::verifyHomographyDevice");
+}
+
+PlanarGeometry Verifier::verifyHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                              int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                              const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    sift_hip_homography_result r{};
+    std::vector<DMatch> list(cap > 0 ? (size_t)cap : 0);
+    check_throw(sift_hip_verify_homography_host(m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap,
+                                                query_xy, query_stride, nq, train_xy, train_stride, nt, &p, &r,
+                                                reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
+                "Verifier::verifyHomographyHost");
+    PlanarGeometry g;
+    for (int i = 0; i < 9; i++) g.H[i] = r.H[i];
+    g.hypothesis = r.hypothesis;
+    list.resize((size_t)r.inliers);
+    g.inliers = std::move(list);
+    return g;
+}
+
 TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
                                   const float* train_xy, int nt, const VerifyParams& params, int query_stride,
                                   int train_stride) {
@@ -81,6 +115,22 @@ TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const floa
     if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyFundamental");
     return v.verifyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
                         nt, params);
+}
+
+PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const VerifyParams& params, int query_stride, int train_stride) {
+    const int n = (int)matches.size();
+    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyHomography");
+    return v.verifyHomographyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy,
+                                  train_stride, nt, params);
+}
+
+void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
+                             void* stream) {
+    check_throw(sift_hip_project_homography_device(H, xy, stride, n, out_xy, out_stride, stream),
+                "projectHomographyDevice");
 }
 
 }  // namespace sift_cuda

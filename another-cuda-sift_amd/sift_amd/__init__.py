@@ -149,6 +149,23 @@ VERIFY_RESULT_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypoth
 assert VERIFY_RESULT_DTYPE.itemsize == ctypes.sizeof(_VerifyResult)
 
 
+class _HomographyResult(ctypes.Structure):
+    """sift_hip_homography_result: the winning hypothesis' H (row-major, x_train ~ H x_query), its inlier count and
+    index (-1: none), the number of matches that counted and the number of valid hypotheses."""
+    _fields_ = [
+        ("H", ctypes.c_float * 9),
+        ("inliers", ctypes.c_int),
+        ("hypothesis", ctypes.c_int),
+        ("matches", ctypes.c_int),
+        ("valid_hypotheses", ctypes.c_int),
+    ]
+
+
+HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("matches", "<i4"),
+                                    ("valid_hypotheses", "<i4")])
+assert HOMOGRAPHY_RESULT_DTYPE.itemsize == ctypes.sizeof(_HomographyResult)
+
+
 def lib() -> ctypes.CDLL:
     """Load libsift_hip.so (once).  Fails loudly when the build is missing."""
     global _lib
@@ -257,6 +274,13 @@ def lib() -> ctypes.CDLL:
                                                  ctypes.POINTER(_VerifyResult), vp, vp]),
         "sift_hip_score_fundamental_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, i, f, vp, vp]),
         "sift_hip_verify_hypotheses_host": (i, [vp, vp, vp, vp, i]),
+        "sift_hip_verify_homography_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams), vp,
+                                                  vp, vp, vp, vp]),
+        "sift_hip_verify_homography_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams),
+                                                ctypes.POINTER(_HomographyResult), vp, vp]),
+        "sift_hip_score_homography_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, i, f, vp, vp]),
+        "sift_hip_verify_homography_hypotheses_host": (i, [vp, vp, vp, vp, i]),
+        "sift_hip_project_homography_device": (i, [vp, vp, i, i, vp, i, vp]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -991,10 +1015,10 @@ def matchListEpipolar(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuf
 
 
 class Verifier:
-    """Two-view verification of a match list on the device: a fixed-budget RANSAC for the fundamental matrix
-    (sift_hip_verifier_*; the rule: include/sift_hip.h, and in numpy sift_amd.cv.ransac_fundamental).  Owns all scratch
-    of its calls -- for lists of up to max_matches records and up to max_hypotheses hypotheses -- so a device call only
-    launches kernels.  Calls on one verifier must be ordered."""
+    """Two-view verification of a match list on the device: a fixed-budget RANSAC for the fundamental matrix or the
+    homography (sift_hip_verifier_*; the rules: include/sift_hip.h, and in numpy sift_amd.cv.ransac_fundamental /
+    ransac_homography).  Owns all scratch of its calls -- for lists of up to max_matches records and up to
+    max_hypotheses hypotheses -- so a device call only launches kernels.  Calls on one verifier must be ordered."""
 
     def __init__(self, max_matches: int, max_hypotheses: int = 1024, device: int = -1):
         self._v = ctypes.c_void_p()
@@ -1002,6 +1026,7 @@ class Verifier:
                "verifier_create")
         self.max_matches, self.max_hypotheses = max_matches, max_hypotheses
         self._hypotheses = 0
+        self._h_hypotheses = 0
 
     def __del__(self):
         v = getattr(self, "_v", None)
@@ -1060,6 +1085,60 @@ class Verifier:
                "verify_hypotheses_host")
         return samples, F, F.any(1), counts
 
+    def verify_homography_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                                 nt: int, result_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0, mask_ptr: int = 0,
+                                 max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                                 t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """verify_device for the homography (sift_hip_verify_homography_device), argument for argument; result_ptr: a
+        HOMOGRAPHY_RESULT_DTYPE record, whose address is also the H project_homography_device takes; max_error: the
+        transfer error in pixels."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        _check(lib().sift_hip_verify_homography_device(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                       q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                       ctypes.byref(p), result_ptr or None, out_ptr or None,
+                                                       out_count_ptr or None, mask_ptr or None, stream),
+               "verify_homography_device")
+        self._h_hypotheses = hypotheses
+
+    def verify_homography_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                               nt: int, max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                               t_stride: int = 3, full: bool = False):
+        """Synchronous (sift_hip_verify_homography_host): (H 3 x 3 float32 of unit norm, the inlier records as a
+        DMATCH_DTYPE array, the winning hypothesis or -1).  full: (the HOMOGRAPHY_RESULT_DTYPE record, the records, the
+        mask of cap bytes)."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        r = _HomographyResult()
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        mask = np.zeros(max(cap, 0), np.uint8)
+        _check(lib().sift_hip_verify_homography_host(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                     q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                     ctypes.byref(p), ctypes.byref(r), _ptr(out), _ptr(mask)),
+               "verify_homography_host")
+        self._h_hypotheses = hypotheses
+        if full:
+            return np.frombuffer(bytes(r), HOMOGRAPHY_RESULT_DTYPE)[0], out[: r.inliers], mask
+        return np.array(r.H, np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+
+    def score_homography_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                                nt: int, H_ptr: int, K: int, max_error: float, counts_ptr: int, q_stride: int = 3,
+                                t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """The transfer-error score alone on the caller's K homographies (device, K x 9 floats): counts (device, K
+        ints)."""
+        _check(lib().sift_hip_score_homography_device(self._v, matches_ptr or None, count_ptr or None, cap,
+                                                      q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
+                                                      H_ptr or None, K, max_error, counts_ptr or None, stream),
+               "score_homography_device")
+
+    def homography_hypotheses(self):
+        """What the last verify call drew, solved and counted, when it was a homography call: (samples (K, 4) int32, H
+        (K, 9) float32, valid (K,) bool -- an invalid hypothesis has H all zero --, counts (K,) int32).  Synchronises
+        the device."""
+        K = self._h_hypotheses
+        samples, H, counts = np.zeros((K, 4), np.int32), np.zeros((K, 9), np.float32), np.zeros(K, np.int32)
+        _check(lib().sift_hip_verify_homography_hypotheses_host(self._v, _ptr(samples), _ptr(H), _ptr(counts), K),
+               "verify_homography_hypotheses_host")
+        return samples, H, H.any(1), counts
+
 
 def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
                       hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3):
@@ -1074,6 +1153,29 @@ def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: in
     qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
     return v.verify_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, max_error, hypotheses, seed,
                          des_stride, src_stride)
+
+
+def verifyHomography(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
+                     hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3):
+    """verifyFundamental for the homography: (H 3 x 3 float32 of unit norm with x_src ~ H x_des -- divide by H[2, 2]
+    for cv::findHomography's scale --, the inlier records in input order, the winning hypothesis or -1 when there are
+    fewer than 4 matches or no sample was valid).  sift_amd.cv.homography_lstsq refits on the inliers."""
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
+    v = Verifier(max(len(m), 1), hypotheses)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    return v.verify_homography_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, max_error, hypotheses,
+                                    seed, des_stride, src_stride)
+
+
+def project_homography_device(H_ptr: int, xy_ptr: int, n: int, out_ptr: int, stride: int = 3, out_stride: int = 2,
+                              stream: Optional[int] = None) -> None:
+    """Enqueue the projection (sift_hip_project_homography_device): row i of out = row i of xy (n device rows of
+    `stride` floats, x and y first) carried over by the 9 device floats at H_ptr -- normally the result record of
+    verify_homography_device --, (NaN, NaN) where the point lands behind the camera.  out_ptr may be xy_ptr with equal
+    strides."""
+    _check(lib().sift_hip_project_homography_device(H_ptr or None, xy_ptr or None, stride, n, out_ptr or None, out_stride,
+                                                    stream), "project_homography_device")
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

@@ -244,14 +244,14 @@ def _mix32(h):
     return h ^ (h >> np.uint64(16))
 
 
-def ransac_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
-    """The sampler of the verify rule: (K, 8) int32, row k the 8 distinct indices of [0, n) hypothesis k draws -- a
-    function of (seed, k, n) only.  n < 8: every entry -1 (nothing is drawn)."""
-    out = np.full((K, 8), -1, np.int64)
-    if n < 8:
+def _samples(n: int, K: int, seed: int, m: int) -> np.ndarray:
+    """The sampler of the verify rules: (K, m) int32, row k the m distinct indices of [0, n) hypothesis k draws -- a
+    function of (seed, k, n) only.  n < m: every entry -1 (nothing is drawn)."""
+    out = np.full((K, m), -1, np.int64)
+    if n < m:
         return out.astype(np.int32)
     base = _mix32(np.uint64(int(seed) & 0xFFFFFFFF) ^ _mix32(np.arange(K, dtype=np.uint64)))
-    for j in range(8):
+    for j in range(m):
         h = _mix32((base + np.uint64((0x9E3779B9 * (j + 1)) & 0xFFFFFFFF)) & _M32)
         r = ((h * np.uint64(n - j)) >> np.uint64(32)).astype(np.int64)
         earlier = np.sort(out[:, :j], axis=1)
@@ -261,21 +261,67 @@ def ransac_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
     return out.astype(np.int32)
 
 
-def _normalise8(x, y):
-    """Hartley normalisation of (K, 8) coordinates: (x', y', s, ox, oy), sums in index order."""
+def ransac_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the fundamental rule: (K, 8) int32, row k the 8 distinct indices of [0, n) hypothesis k draws --
+    a function of (seed, k, n) only.  n < 8: every entry -1 (nothing is drawn)."""
+    return _samples(n, K, seed, 8)
+
+
+def _normalise(x, y):
+    """Hartley normalisation of (K, m) coordinates: (x', y', s, ox, oy, mx, my), sums in index order."""
+    m = x.shape[1]
     sx, sy = x[:, 0].copy(), y[:, 0].copy()
-    for i in range(1, 8):
+    for i in range(1, m):
         sx = sx + x[:, i]
         sy = sy + y[:, i]
-    mx, my = sx / _F32(8), sy / _F32(8)
+    mx, my = sx / _F32(m), sy / _F32(m)
     dx, dy = x - mx[:, None], y - my[:, None]
     d = np.sqrt(dx * dx + dy * dy)
     sd = d[:, 0].copy()
-    for i in range(1, 8):
+    for i in range(1, m):
         sd = sd + d[:, i]
-    md = sd / _F32(8)
+    md = sd / _F32(m)
     s = _F32(1.41421354) / md
-    return dx * s[:, None], dy * s[:, None], s, -(s * mx), -(s * my)
+    return dx * s[:, None], dy * s[:, None], s, -(s * mx), -(s * my), mx, my
+
+
+def _solve_8x9(A):
+    """The shared solver of both rules on (K, 8, 9) systems (changed in place): Gaussian elimination with full
+    pivoting, back-substitution with the free variable y[8] = 1, the permutation undone.  (g (K, 9), ok (K,)): ok is
+    False where a pivot was zero or non-finite."""
+    K = len(A)
+    ar = np.arange(K)
+    perm = np.tile(np.arange(9), (K, 1))
+    ok = np.ones(K, bool)
+    for c in range(8):
+        mag = np.abs(A[:, c:, c:]).reshape(K, -1)
+        flat = np.argmax(np.where(np.isnan(mag), _F32(-1), mag), axis=1)  # the first of the largest, row-major
+        flat = np.where(np.isnan(mag[:, 0]), 0, flat)  # nothing is larger than a NaN at (c, c)
+        pr, pc = c + flat // (9 - c), c + flat % (9 - c)
+        tmp = A[ar, c, :].copy()
+        A[ar, c, :] = A[ar, pr, :]
+        A[ar, pr, :] = tmp
+        tmp = A[ar, :, c].copy()
+        A[ar, :, c] = A[ar, :, pc]
+        A[ar, :, pc] = tmp
+        tmp = perm[ar, c].copy()
+        perm[ar, c] = perm[ar, pc]
+        perm[ar, pc] = tmp
+        p = A[:, c, c]
+        ok &= (p != 0) & np.isfinite(p)
+        m = A[:, c + 1:, c] / p[:, None]
+        A[:, c + 1:, c + 1:] = A[:, c + 1:, c + 1:] - m[:, :, None] * A[:, c:c + 1, c + 1:]
+    y = np.zeros((K, 9), np.float32)
+    y[:, 8] = 1
+    for i in range(7, -1, -1):
+        acc = A[:, i, i + 1] * y[:, i + 1]
+        for j in range(i + 2, 9):
+            acc = acc + A[:, i, j] * y[:, j]
+        y[:, i] = (-acc) / A[:, i, i]
+    g = np.zeros((K, 9), np.float32)
+    g[ar[:, None], perm] = y
+    assert A.dtype == np.float32 and y.dtype == np.float32
+    return g, ok
 
 
 def fundamental_from_8(q_xy8, t_xy8):
@@ -287,40 +333,11 @@ def fundamental_from_8(q_xy8, t_xy8):
     single = q.ndim == 2
     q, t = q.reshape(-1, 8, 2), t.reshape(-1, 8, 2)
     K = len(q)
-    ar = np.arange(K)
     with np.errstate(all="ignore"):
-        qx, qy, sq, oqx, oqy = _normalise8(q[:, :, 0], q[:, :, 1])
-        tx, ty, st, otx, oty = _normalise8(t[:, :, 0], t[:, :, 1])
+        qx, qy, sq, oqx, oqy, _, _ = _normalise(q[:, :, 0], q[:, :, 1])
+        tx, ty, st, otx, oty, _, _ = _normalise(t[:, :, 0], t[:, :, 1])
         A = np.stack([tx * qx, tx * qy, tx, ty * qx, ty * qy, ty, qx, qy, np.ones_like(qx)], axis=2)  # (K, 8, 9)
-        perm = np.tile(np.arange(9), (K, 1))
-        ok = np.ones(K, bool)
-        for c in range(8):
-            mag = np.abs(A[:, c:, c:]).reshape(K, -1)
-            flat = np.argmax(np.where(np.isnan(mag), _F32(-1), mag), axis=1)  # the first of the largest, row-major
-            flat = np.where(np.isnan(mag[:, 0]), 0, flat)  # nothing is larger than a NaN at (c, c)
-            pr, pc = c + flat // (9 - c), c + flat % (9 - c)
-            tmp = A[ar, c, :].copy()
-            A[ar, c, :] = A[ar, pr, :]
-            A[ar, pr, :] = tmp
-            tmp = A[ar, :, c].copy()
-            A[ar, :, c] = A[ar, :, pc]
-            A[ar, :, pc] = tmp
-            tmp = perm[ar, c].copy()
-            perm[ar, c] = perm[ar, pc]
-            perm[ar, pc] = tmp
-            p = A[:, c, c]
-            ok &= (p != 0) & np.isfinite(p)
-            m = A[:, c + 1:, c] / p[:, None]
-            A[:, c + 1:, c + 1:] = A[:, c + 1:, c + 1:] - m[:, :, None] * A[:, c:c + 1, c + 1:]
-        y = np.zeros((K, 9), np.float32)
-        y[:, 8] = 1
-        for i in range(7, -1, -1):
-            acc = A[:, i, i + 1] * y[:, i + 1]
-            for j in range(i + 2, 9):
-                acc = acc + A[:, i, j] * y[:, j]
-            y[:, i] = (-acc) / A[:, i, i]
-        g = np.zeros((K, 9), np.float32)
-        g[ar[:, None], perm] = y
+        g, ok = _solve_8x9(A)
         G = g.reshape(K, 3, 3)
         H = np.zeros((K, 3, 3), np.float32)
         H[:, :, 0] = G[:, :, 0] * sq[:, None]
@@ -336,7 +353,7 @@ def fundamental_from_8(q_xy8, t_xy8):
             ss = ss + F[:, i] * F[:, i]
         F = F / np.sqrt(ss)[:, None]
         ok &= np.isfinite(F).all(1)
-    assert A.dtype == np.float32 and y.dtype == np.float32 and F.dtype == np.float32 and ss.dtype == np.float32
+    assert A.dtype == np.float32 and g.dtype == np.float32 and F.dtype == np.float32 and ss.dtype == np.float32
     F[~ok] = 0
     return (F[0], bool(ok[0])) if single else (F, ok)
 
@@ -435,6 +452,172 @@ def fundamental_lstsq(q_pts, t_pts, rank2: bool = True) -> np.ndarray:
         G = u @ np.diag([s[0], s[1], 0.0]) @ vt
     F = Tt.T @ G @ Tq
     return F / np.linalg.norm(F)
+
+
+# --- Homography verification: the rule of sift_hip_verify_homography_* and sift_hip_project_homography_device
+# (include/sift_hip.h) in numpy float32, on the conventions above.  The model is x_train ~ H x_query, H row-major: the
+# orientation of cv::findHomography(query_points, train_points).
+
+_TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
+
+
+def homography_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the homography rule: (K, 4) int32, ransac_samples' draw with 4 indices in place of 8.  n < 4:
+    every entry -1 (nothing is drawn)."""
+    return _samples(n, K, seed, 4)
+
+
+def _oriented(q, t):
+    """The orientation test on raw (K, 4, 2) samples: True where the signed areas of the four point triples have, on
+    both sides, products that are all > 0 or all < 0 (a collinear triple or a NaN fails both)."""
+    p = []
+    for i, j, k in _TRIPLES:
+        a = [(s[:, j, 0] - s[:, i, 0]) * (s[:, k, 1] - s[:, i, 1]) - (s[:, j, 1] - s[:, i, 1]) * (s[:, k, 0] - s[:, i, 0])
+             for s in (q, t)]
+        p.append(a[0] * a[1])
+    p = np.stack(p, 1)
+    assert p.dtype == np.float32
+    return (p > 0).all(1) | (p < 0).all(1)
+
+
+def homography_from_4(q_xy4, t_xy4):
+    """The solver of the homography rule: the normalised 4-point H of 4 pairs (the orientation test, the 8 x 9 system
+    through the fundamental rule's elimination, unit Frobenius norm, the sign that makes w positive at sample 0).
+    q_xy4 / t_xy4: (4, 2) -> (H (9,) float32, valid bool), or (K, 4, 2) -> (H (K, 9), valid (K,)).  An invalid
+    hypothesis (a failed orientation test, a zero or non-finite pivot or result, w0 = 0) has H all zero."""
+    q = np.asarray(q_xy4, np.float32)
+    t = np.asarray(t_xy4, np.float32)
+    single = q.ndim == 2
+    q, t = q.reshape(-1, 4, 2), t.reshape(-1, 4, 2)
+    K = len(q)
+    with np.errstate(all="ignore"):
+        ok = _oriented(q, t)
+        x, y, sq, oqx, oqy, _, _ = _normalise(q[:, :, 0], q[:, :, 1])
+        u, v, st, _, _, mtx, mty = _normalise(t[:, :, 0], t[:, :, 1])
+        one, zero = np.ones_like(x), np.zeros_like(x)
+        even = np.stack([x, y, one, zero, zero, zero, -(u * x), -(u * y), -u], axis=2)
+        odd = np.stack([zero, zero, zero, x, y, one, -(v * x), -(v * y), -v], axis=2)
+        A = np.stack([even, odd], axis=2).reshape(K, 8, 9)  # rows 2 i and 2 i + 1 belong to pair i
+        g, solved = _solve_8x9(A)
+        ok &= solved
+        G = g.reshape(K, 3, 3)
+        M = np.zeros((K, 3, 3), np.float32)
+        M[:, :, 0] = G[:, :, 0] * sq[:, None]
+        M[:, :, 1] = G[:, :, 1] * sq[:, None]
+        M[:, :, 2] = (G[:, :, 0] * oqx[:, None] + G[:, :, 1] * oqy[:, None]) + G[:, :, 2]
+        H = np.zeros((K, 3, 3), np.float32)
+        H[:, 0, :] = M[:, 0, :] / st[:, None] + mtx[:, None] * M[:, 2, :]
+        H[:, 1, :] = M[:, 1, :] / st[:, None] + mty[:, None] * M[:, 2, :]
+        H[:, 2, :] = M[:, 2, :]
+        H = H.reshape(K, 9)
+        ss = H[:, 0] * H[:, 0]
+        for i in range(1, 9):
+            ss = ss + H[:, i] * H[:, i]
+        H = H / np.sqrt(ss)[:, None]
+        w0 = (H[:, 6] * q[:, 0, 0] + H[:, 7] * q[:, 0, 1]) + H[:, 8]
+        H = np.where((w0 < 0)[:, None], -H, H)
+        ok &= np.isfinite(H).all(1) & (w0 != 0)
+    assert A.dtype == np.float32 and g.dtype == np.float32 and H.dtype == np.float32 and ss.dtype == np.float32
+    assert M.dtype == np.float32 and w0.dtype == np.float32
+    H[~ok] = 0
+    return (H[0], bool(ok[0])) if single else (H, ok)
+
+
+def _transfer_pass(pts, H, max_error) -> np.ndarray:
+    """(K, n) bool: the transfer predicate of every match (qx, qy, tx, ty) under each of the K rows of H (K, 9):
+    w > 0 and dx dx + dy dy <= (max_error max_error) (w w), inclusive, with dx = px - tx w, dy = py - ty w."""
+    h = np.asarray(H, np.float32).reshape(-1, 9)[:, :, None]
+    e = np.float32(max_error)
+    qx, qy, tx, ty = (pts[None, :, i] for i in range(4))
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        px = (h[:, 0] * qx + h[:, 1] * qy) + h[:, 2]
+        py = (h[:, 3] * qx + h[:, 4] * qy) + h[:, 5]
+        w = (h[:, 6] * qx + h[:, 7] * qy) + h[:, 8]
+        dx = px - tx * w
+        dy = py - ty * w
+        near = dx * dx + dy * dy <= (e * e) * (w * w)
+        front = w > 0
+    assert dx.dtype == np.float32 and dy.dtype == np.float32 and w.dtype == np.float32
+    return front & near
+
+
+def transfer_inliers(matches, q_xy, t_xy, H, max_error) -> np.ndarray:
+    """The score of the homography rule: a bool per DMATCH_DTYPE record, True where the record's query position,
+    carried over by H, lies in front (w > 0) and within max_error pixels of its train position (the forward transfer
+    error, inclusive, division-free).  A record with an index outside its position array, or a NaN position, is an
+    inlier of nothing."""
+    h = np.asarray(H, np.float32).reshape(-1)
+    if h.size != 9:
+        raise ValueError("H must have 9 entries (3 x 3, row-major)")
+    return _transfer_pass(_match_points(matches, q_xy, t_xy), h, max_error)[0]
+
+
+def ransac_homography(matches, q_xy, t_xy, max_error=1.5, K: int = 1024, seed: int = 0) -> dict:
+    """The whole operation (sift_hip_verify_homography_*) in numpy.  matches: the n DMATCH_DTYPE records that count.
+    Returns ransac_fundamental's dict with H (9,) and Hs (K, 9) in place of F and Fs; samples is (K, 4)."""
+    from . import DMATCH_DTYPE
+
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    pts = _match_points(matches, q_xy, t_xy)
+    samples = homography_samples(n, K, seed)
+    if n >= 4:
+        Hs, valid = homography_from_4(pts[samples][:, :, :2], pts[samples][:, :, 2:])
+        passes = _transfer_pass(pts, Hs, max_error) & valid[:, None]
+    else:
+        Hs, valid, passes = np.zeros((K, 9), np.float32), np.zeros(K, bool), np.zeros((K, n), bool)
+    counts = passes.sum(1).astype(np.int32)
+    hyp = -1
+    if valid.any():
+        hyp = int(np.argmax(np.where(valid, counts, -1)))  # the first of the largest: ties to the lowest k
+    mask = passes[hyp].astype(np.uint8) if hyp >= 0 else np.zeros(n, np.uint8)
+    return dict(H=Hs[hyp].copy() if hyp >= 0 else np.zeros(9, np.float32), inliers=int(counts[hyp]) if hyp >= 0 else 0,
+                hypothesis=hyp, matches=n, valid_hypotheses=int(valid.sum()), mask=mask, list=matches[mask != 0],
+                samples=samples, Hs=Hs, valid=valid, counts=counts)
+
+
+def project_homography(H, xy) -> np.ndarray:
+    """sift_hip_project_homography_device in numpy: (n, 2) float32, row i the position (px / w, py / w) that H carries
+    xy[i] to, (NaN, NaN) where w is not > 0 (a zero H -- the empty result -- gives NaN everywhere: candidates of
+    nothing under the window gate).  xy: (n, >= 2), x and y first."""
+    h = np.asarray(H, np.float32).reshape(-1)
+    if h.size != 9:
+        raise ValueError("H must have 9 entries (3 x 3, row-major)")
+    if len(xy) == 0:
+        return np.zeros((0, 2), np.float32)
+    p = np.asarray(xy, np.float32).reshape(len(xy), -1)[:, :2]
+    x, y = p[:, 0], p[:, 1]
+    with np.errstate(all="ignore"):
+        px = (h[0] * x + h[1] * y) + h[2]
+        py = (h[3] * x + h[4] * y) + h[5]
+        w = (h[6] * x + h[7] * y) + h[8]
+        out = np.stack([px / w, py / w], 1)
+    assert out.dtype == np.float32
+    out[~(w > 0)] = np.nan
+    return out
+
+
+def homography_lstsq(q_pts, t_pts) -> np.ndarray:
+    """A convenience, not part of the device rule: the float64 normalised DLT least-squares H (3 x 3, H[2][2] = 1,
+    x_t ~ H x_q) of n >= 4 pairs through np.linalg.svd -- a refit on the inliers a verify call returns."""
+    q = np.asarray(q_pts, np.float64).reshape(len(q_pts), -1)[:, :2]
+    t = np.asarray(t_pts, np.float64).reshape(len(t_pts), -1)[:, :2]
+    if len(q) != len(t) or len(q) < 4:
+        raise ValueError("homography_lstsq needs the same number (>= 4) of points on both sides")
+
+    def norm(p):
+        m = p.mean(0)
+        s = np.sqrt(2.0) / np.sqrt(((p - m) ** 2).sum(1)).mean()
+        return (p - m) * s, np.array([[s, 0, -s * m[0]], [0, s, -s * m[1]], [0, 0, 1]])
+
+    (qn, Tq), (tn, Tt) = norm(q), norm(t)
+    x, y, u, v = qn[:, 0], qn[:, 1], tn[:, 0], tn[:, 1]
+    one, zero = np.ones(len(q)), np.zeros(len(q))
+    A = np.r_[np.stack([x, y, one, zero, zero, zero, -u * x, -u * y, -u], 1),
+              np.stack([zero, zero, zero, x, y, one, -v * x, -v * y, -v], 1)]
+    G = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    H = np.linalg.inv(Tt) @ G @ Tq
+    return H / H[2, 2]
 
 
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):

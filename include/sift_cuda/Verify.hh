@@ -1,6 +1,8 @@
-// sift_cuda::Verifier / verifyFundamental: two-view verification of a match
-// list (a fixed-budget RANSAC for the fundamental matrix on the device) over
-// sift_hip_verify_* of include/sift_hip.h, where the rule is written out.
+// sift_cuda::Verifier / verifyFundamental / verifyHomography: two-view
+// verification of a match list (a fixed-budget RANSAC for the fundamental matrix
+// or the homography on the device) and projectHomographyDevice, over
+// sift_hip_verify_* and sift_hip_project_homography_device of
+// include/sift_hip.h, where the rules are written out.
 // Plain C++: no HIP headers.
 #pragma once
 
@@ -17,7 +19,7 @@ namespace sift_cuda {
 struct VerifyParams {
     int hypotheses = 1024;
     unsigned seed = 0;
-    float max_error = 1.5f;  // Sampson distance in pixels, > 0 and finite
+    float max_error = 1.5f;  // pixels, > 0 and finite: Sampson distance (homography: transfer error)
 };
 
 // The winning hypothesis: F row-major with x_train^T F x_query = 0 (zero when
@@ -32,6 +34,22 @@ struct TwoViewGeometry {
 // sift_hip_verify_result (device form: the record the kernels write).
 struct VerifyResult {
     float F[9];
+    int inliers, hypothesis, matches, valid_hypotheses;
+};
+
+// The homography's winning hypothesis: H row-major with x_train ~ H x_query,
+// unit Frobenius norm (zero when hypothesis = -1: fewer than 4 matches or no
+// valid sample), and its inlier records, the input's, in input order.
+struct PlanarGeometry {
+    float H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int hypothesis = -1;
+    std::vector<DMatch> inliers;
+};
+
+// sift_hip_homography_result (device form: the record the kernels write; H is
+// its first field, so its device address is what projectHomographyDevice takes).
+struct HomographyResult {
+    float H[9];
     int inliers, hypothesis, matches, valid_hypotheses;
 };
 
@@ -54,6 +72,15 @@ public:
     TwoViewGeometry verifyHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
                                int nq, const float* train_xy, int train_stride, int nt, const VerifyParams& params = {});
 
+    // The same two calls for the homography (sift_hip_verify_homography_device / _host).
+    void verifyHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                                int nq, const float* train_xy, int train_stride, int nt, const VerifyParams& params,
+                                HomographyResult* result, DMatch* out = nullptr, int* out_count = nullptr,
+                                uint8_t* mask = nullptr, void* stream = nullptr);
+    PlanarGeometry verifyHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                        int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                        const VerifyParams& params = {});
+
     sift_hip_verifier* handle() const { return m_handle; }
 
 private:
@@ -65,5 +92,15 @@ private:
 TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
                                   const float* train_xy, int nt, const VerifyParams& params = {}, int query_stride = 3,
                                   int train_stride = 3);
+
+// The same one shot for the homography.
+PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const VerifyParams& params = {}, int query_stride = 3, int train_stride = 3);
+
+// Enqueued on `stream`, not synchronised (sift_hip_project_homography_device): row i of out_xy = row i of xy carried
+// over by H, NaN where it lands behind the camera.  H: 9 floats of device memory (a HomographyResult's address); xy /
+// out_xy: n device rows of stride / out_stride floats, x and y first; out_xy may be xy with equal strides.
+void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride = 2,
+                             void* stream = nullptr);
 
 }  // namespace sift_cuda

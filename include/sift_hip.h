@@ -706,8 +706,9 @@ int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* query,
  * keyframes, a calibrated stereo rig, or a first RANSAC pass over a match list
  * (sift_hip_verify_fundamental_device below) -- but not where on its epipolar line a point lands, so no predicted position
  * and no radius expresses it.  As with the window, the two nearest rows inside
- * the band are not the global top-2.  (A homography needs nothing new: project
- * the query positions and use the window above.)
+ * the band are not the global top-2.  (Under a homography the gate is the
+ * window above on projected query positions: sift_hip_verify_homography_device
+ * finds H and sift_hip_project_homography_device projects, both below.)
  *
  * The rule.  F is 9 floats, row-major, with x_train^T F x_query = 0: the matrix
  * cv::findFundamentalMat(query_points, train_points) returns.  Positions are
@@ -863,7 +864,7 @@ typedef struct sift_hip_verifier* sift_hip_verifier_t;
 typedef struct {
     int hypotheses;   /* K, 1 .. the verifier's max_hypotheses */
     unsigned seed;
-    float max_error;  /* Sampson distance in pixels, > 0 and finite */
+    float max_error;  /* pixels, > 0 and finite: Sampson distance (the homography calls: transfer error) */
 } sift_hip_verify_params;
 
 typedef struct {
@@ -921,6 +922,128 @@ int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmat
  * of its first min(cap, K) hypotheses to host memory (each may be NULL).
  * Synchronises the device.  SIFT_HIP_ERR_STATE before the first verify call. */
 int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap);
+
+/* --- Homography verification: 4-point RANSAC and projection --------------------
+ *
+ * The model of planar targets, pure-rotation frames, panoramas and object
+ * instances (cv::findHomography(query_points, train_points, RANSAC) plus its
+ * inlier mask) -- the cases in which the fundamental matrix above is
+ * degenerate.  The same fixed budget of K hypotheses on the same verifier, each
+ * the normalised 4-point solution of 4 sampled matches, each scored against
+ * every match by the forward transfer error; the best one's H, its inlier mask
+ * and its inlier records.  sift_hip_project_homography_device then carries
+ * positions over by an H it reads from device memory -- the result record itself
+ * -- so match_list_device -> verify_homography_device ->
+ * project_homography_device -> match_list_guided_device runs on one stream with
+ * no read-back at all.
+ *
+ * The rule.  x_train ~ H x_query, H row-major h[0..8].  The conventions are the
+ * fundamental rule's: float32, every operation rounded to nearest, one at a
+ * time, in the written order; nothing fused; division and square root correctly
+ * rounded; sums in index order.  sift_amd.cv.ransac_homography is the same rule
+ * in numpy.
+ *
+ * Input.  As above: n, the positions of match j, and the four NaNs of a record
+ * with an index outside [0, nq) / [0, nt).
+ *
+ * Sampling.  The sampler above with 4 draws in place of 8: j = 0..3, the same
+ * base, h and r, the same skip of earlier picks.  Total for every n >= 4; with
+ * n < 4 nothing is drawn and every sample index is -1.
+ *
+ * Orientation test, on the raw sample coordinates (x_i, y_i), before any
+ * normalisation.  For the triples (i, j, k) = (0,1,2), (0,1,3), (0,2,3),
+ * (1,2,3) and each side:
+ *   a = (x_j - x_i) * (y_k - y_i) - (y_j - y_i) * (x_k - x_i)
+ * and p = a_query * a_train.  The sample is kept only when all four p > 0 or
+ * all four p < 0; a zero (three collinear points on either side) or a NaN fails
+ * both and makes the hypothesis invalid (OpenCV's sample check).
+ *
+ * Solver.  Each side is normalised as above with 8 replaced by 4 (mx, my, d_i,
+ * md, s = 1.41421354f / md, x' = dx * s, ox = -(s * mx), oy = -(s * my)):
+ * (sq, oqx, oqy) for the query side, (st, mtx, mty) -- the scale and the mean --
+ * for the train side.  With the normalised (x, y) / (u, v) of pair i, rows 2i
+ * and 2i+1 of the 8 x 9 system A are
+ *   [x, y, 1, 0, 0, 0, -(u*x), -(u*y), -u]
+ *   [0, 0, 0, x, y, 1, -(v*x), -(v*y), -v]
+ * Then word for word as above: Gaussian elimination with full pivoting (the same
+ * scan order, tie rule, NaN rule and invalid-pivot rule, on all 8 x 9 stored
+ * entries, the structural zeros included), back-substitution with the free
+ * variable y[8] = 1, the permutation undone: G.  H = Tt^-1 G Tq written out:
+ *   M[r][0] = G[r][0]*sq, M[r][1] = G[r][1]*sq,
+ *   M[r][2] = (G[r][0]*oqx + G[r][1]*oqy) + G[r][2]                  (r = 0..2)
+ *   H[0][c] = M[0][c] / st + mtx * M[2][c],
+ *   H[1][c] = M[1][c] / st + mty * M[2][c],  H[2][c] = M[2][c]       (c = 0..2)
+ * scaled to unit Frobenius norm (ss = sum H[i]*H[i] over i = 0..8 in index
+ * order, H[i] = H[i] / sqrtf(ss)).  Then w0 = (h6*qx0 + h7*qy0) + h8 for sample
+ * 0's raw query position; if w0 < 0 every entry of H is negated.  The hypothesis
+ * is invalid when any entry is non-finite or w0 == 0.  An invalid hypothesis has
+ * H all zero and inlier count 0.  There is no refit on the inliers and no
+ * h8 = 1 scaling: divide by H[8] for OpenCV's convention;
+ * sift_amd.cv.homography_lstsq refits on the host.
+ *
+ * Score.  Match (qx, qy, tx, ty) is an inlier of a valid hypothesis when
+ *   px = (h0*qx + h1*qy) + h2;  py = (h3*qx + h4*qy) + h5;  w = (h6*qx + h7*qy) + h8
+ *   dx = px - tx*w;  dy = py - ty*w
+ *   w > 0  &&  dx*dx + dy*dy <= (max_error*max_error) * (w*w)
+ * -- the forward transfer error (OpenCV's reprojection error) <= max_error,
+ * inclusive, division-free, with the chirality test the sign rule makes
+ * meaningful.  A NaN is an inlier of nothing.
+ *
+ * Selection and output.  As above: most inliers among the valid hypotheses,
+ * ties to the lowest k; with n < 4 or no valid hypothesis hypothesis = -1,
+ * inliers = 0, H zero, an empty list and a zero mask, status success; the
+ * 52-byte record, the records in input order, their count, the cap-byte mask;
+ * no atomics, the same bytes in every run.
+ *
+ * Projection.  Row i of xy (xy[i*stride + {0, 1}]) gives px, py, w as in the
+ * score; the output row is (px / w, py / w) when w > 0 and (NaN, NaN) otherwise
+ * (w <= 0 or NaN).  The window gate treats a NaN position as a candidate of
+ * nothing, so a zero H -- the empty result -- yields an empty guided list.  Only
+ * the first two floats of an output row are written. */
+typedef struct {
+    float H[9];            /* row-major; x_train ~ H x_query, unit norm; zero when hypothesis = -1 */
+    int inliers;           /* inliers of the winning hypothesis */
+    int hypothesis;        /* its index k, -1: none */
+    int matches;           /* n */
+    int valid_hypotheses;  /* hypotheses that passed the orientation test and were solved */
+} sift_hip_homography_result;  /* 52 bytes */
+
+/* sift_hip_verify_fundamental_device / _host / sift_hip_score_fundamental_device
+ * for the homography, argument for argument, on the same verifier (one model at
+ * a time: calls on one verifier are ordered); params->max_error is the transfer
+ * error in pixels.  The same arguments are refused, with nothing launched, and
+ * cap == 0 succeeds with the empty result. */
+int sift_hip_verify_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                      int train_stride, int nt, const sift_hip_verify_params* params,
+                                      sift_hip_homography_result* result, sift_hip_dmatch* out, int* out_count,
+                                      uint8_t* mask, void* stream);
+int sift_hip_verify_homography_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                    const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                    int train_stride, int nt, const sift_hip_verify_params* params,
+                                    sift_hip_homography_result* result_host, sift_hip_dmatch* out_host,
+                                    uint8_t* mask_host);
+int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, const float* H, int K, float max_error, int* counts,
+                                     void* stream);
+
+/* sift_hip_verify_hypotheses_host for the homography: samples (K x 4), H
+ * (K x 9, zero rows: invalid hypotheses) and counts (K).  A verifier remembers
+ * the model of its last verify call: each of the two getters returns
+ * SIFT_HIP_ERR_STATE unless that call was of its own model (and before any). */
+int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* samples, float* H, int* counts, int cap);
+
+/* The projection, enqueued on `stream` of the current device, not synchronised;
+ * needs no handle.  H: 9 floats in device memory, normally the result record of
+ * sift_hip_verify_homography_device on the same stream (H is its first field).
+ * xy: n device rows of `stride` floats, x and y first; out_xy: n device rows of
+ * out_stride floats.  out_xy may be xy itself with equal strides (in place);
+ * otherwise the two may not overlap.  SIFT_HIP_ERR_INVALID, with nothing
+ * launched, for: a null H, a stride below 2, a negative n, a null xy or out_xy
+ * with n > 0, a partial overlap.  n == 0 succeeds. */
+int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
+                                       void* stream);
 
 /* --- Multi-GPU (the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
