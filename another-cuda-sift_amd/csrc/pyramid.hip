@@ -1100,7 +1100,8 @@ constexpr int EX_SH = EX_TH + 2;
 constexpr int EX_LIST = 512;  // per-workgroup candidate list (LDS)
 
 // LT = compile-time layer count (1..6), or 0 for the generic runtime-L path.
-template <int LT>
+// FLAT: the launches with thr = 0 (extrema_block's test_row).
+template <int LT, bool FLAT>
 __global__ __launch_bounds__(256) void k_extrema(OctGeom g, int Lrt, int o, float thr, uint2* __restrict__ cand,
                                                  Counters* __restrict__ ctr, unsigned cap, long fs) {
     extern __shared__ float dog[];  // (L+2) planes of EX_SH x EX_SW
@@ -1178,6 +1179,13 @@ __global__ __launch_bounds__(256) void k_extrema(OctGeom g, int Lrt, int o, floa
                 const float val = cur[0];
                 if (fabsf(val) > thr) {
                     hit = true;
+                    if constexpr (FLAT) {  // a constant in-layer 3x3 block is no candidate
+                        hit = false;
+#pragma unroll
+                        for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+                            for (int dx = -1; dx <= 1; dx++) hit |= val != cur[dy * EX_SW + dx];
+                    }
                     if (val > 0) {
 #pragma unroll
                         for (int d = -1; d <= 1; d++)
@@ -1262,7 +1270,7 @@ constexpr int EX4_COLS = 64 * kExCpl;  // columns per wave
 // rows above and below are read once per NB * EX4_TR rows instead of once per
 // EX4_TR: strips of 6 rows read 8 (1.20x algorithmic HBM bytes measured at
 // 16 frames, round-3 verdict), 24-row streams read 26.
-template <int LT, int EX4_TR, int EX4_AHEAD, int NB = 1, int CPL = kExCpl>
+template <int LT, bool FLAT, int EX4_TR, int EX4_AHEAD, int NB = 1, int CPL = kExCpl>
 __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr, uint2* __restrict__ cand,
                                               Counters* __restrict__ ctr, unsigned cap, int tile, int strips,
                                               uint2* s_list, unsigned& s_cnt, unsigned& s_base) {
@@ -1385,7 +1393,19 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
                 const float m = fminf(fminf(hn[l - 1][c], hn[l][c]), hn[l + 1][c]);
                 // M >= v >= m always (v is one of the 27), so "v >= all" is v == M;
                 // |v| > thr >= 0 excludes v == 0, and the sign picks the test.
-                const bool h = rowOK && colOK[c] && fabsf(v) > thr && v == (v > 0 ? M : m);
+                bool h = rowOK && colOK[c] && fabsf(v) > thr && v == (v > 0 ? M : m);
+                // FLAT (the launches with thr = 0): a hit whose in-layer 3x3 block
+                // is constant (hx == hn) is dropped.  At thr = 0 every sample of a
+                // flat non-zero region is such a plateau of rounding residue
+                // (OpenCV makes them candidates), and adjustLocalExtrema can keep
+                // none -- dxx = dyy = dxy = 0 and dx = dy = 0, so the 3x3 system is
+                // singular (solve returns 0, the iteration stays in place) and the
+                // 2-D det = 0 fails det > 0.  They only filled the candidate list
+                // (overflow bit 0).  One compare per sample: 242 -> 250-254 us per
+                // 16-frame C2 launch when always on, so launches with thr >= 1,
+                // where such a block would have to be constant at |v| > 1, run
+                // without it.
+                if constexpr (FLAT) h = h && hx[l][c] != hn[l][c];
                 hits |= (unsigned)h << ((l - 1) * CPL + c);
             }
         return hits;
@@ -1464,7 +1484,7 @@ struct ExtremaPlan {
     int tall[kMaxOctaves];
 };
 
-template <int LT>
+template <int LT, bool FLAT>
 __global__ __launch_bounds__(256) void k_extrema_all(PyrDesc pyr, ExtremaPlan plan, float thr,
                                                      uint2* __restrict__ cand, Counters* __restrict__ ctr,
                                                      unsigned cap, long fs) {
@@ -1484,9 +1504,9 @@ __global__ __launch_bounds__(256) void k_extrema_all(PyrDesc pyr, ExtremaPlan pl
     ctr = fptr(ctr, f * fs);
     const int blk = b - plan.start[o];
     if (plan.tall[o])
-        extrema_block<LT, 6, 2, kExStream>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
+        extrema_block<LT, FLAT, 6, 2, kExStream>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
     else
-        extrema_block<LT, 2, 2>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
+        extrema_block<LT, FLAT, 2, 2>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
 }
 
 // Octave o alone, for L > 6 (LDS-staged k_extrema).
@@ -1495,7 +1515,12 @@ void launch_extrema(const PyrDesc& pyr, int o, float threshold, uint2* cand, Cou
     const OctGeom& g = pyr.oct[o];
     dim3 grid((g.W + EX_TW - 1) / EX_TW, (g.H + EX_TH - 1) / EX_TH, fr.nf);
     const size_t lds = sizeof(float) * (size_t)(pyr.L + 2) * EX_SH * EX_SW;
-    hipLaunchKernelGGL(k_extrema<0>, grid, dim3(256), lds, s, g, pyr.L, o, threshold, cand, ctr, cap, fr.stride);
+    if (threshold == 0.f)
+        hipLaunchKernelGGL((k_extrema<0, true>), grid, dim3(256), lds, s, g, pyr.L, o, threshold, cand, ctr, cap,
+                           fr.stride);
+    else
+        hipLaunchKernelGGL((k_extrema<0, false>), grid, dim3(256), lds, s, g, pyr.L, o, threshold, cand, ctr, cap,
+                           fr.stride);
 }
 
 bool launch_extrema_all(const PyrDesc& pyr, float threshold, uint2* cand, Counters* ctr, unsigned cap,
@@ -1516,12 +1541,18 @@ bool launch_extrema_all(const PyrDesc& pyr, float threshold, uint2* cand, Counte
         total += strips * ((g.H + 4 * tr - 1) / (4 * tr));
     }
     plan.start[pyr.nOct] = total;
+    const bool flat = threshold == 0.f;  // drop in-layer-flat hits (extrema_block's test_row)
     switch (pyr.L) {
 #define SIFT_EX_CASE(LV) \
-    case LV:                                                                                                    \
-        hipLaunchKernelGGL(k_extrema_all<LV>, dim3(total * fr.nf), dim3(256), 0, s, pyr, plan, threshold, cand, ctr, \
-                           cap, fr.stride);                                                                         \
-        break;
+    case LV: {                                                                                                      \
+        if (flat)                                                                                                   \
+            hipLaunchKernelGGL((k_extrema_all<LV, true>), dim3(total * fr.nf), dim3(256), 0, s, pyr, plan, threshold, \
+                               cand, ctr, cap, fr.stride);                                                          \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_extrema_all<LV, false>), dim3(total * fr.nf), dim3(256), 0, s, pyr, plan,         \
+                               threshold, cand, ctr, cap, fr.stride);                                               \
+        break;                                                                                                      \
+    }
         SIFT_EX_CASE(1)
         SIFT_EX_CASE(2)
         SIFT_EX_CASE(3)

@@ -728,11 +728,15 @@ class Detector:
         _check(lib().sift_hip_debug_gaussian(self._h, octave, layer, _ptr(out)), "debug_gaussian")
         return out
 
-    def debug_candidates(self, cap: int = 1 << 20) -> np.ndarray:
+    def debug_candidates(self, cap: int = 1 << 20, return_count: bool = False):
+        """The stored candidate rows (octave, layer, r, c): min(hits, candidate capacity, cap) of them.
+        return_count=True: (rows, hits), hits counting every extremum met, stored or not (more than
+        the capacity on overflow flag 1)."""
         q = np.zeros((cap, 4), np.int32)
         cnt = ctypes.c_int()
         _check(lib().sift_hip_debug_candidates(self._h, _ptr(q), cap, ctypes.byref(cnt)), "debug_candidates")
-        return q[: min(cnt.value, cap)]
+        rows = q[: min(cnt.value, cap, self.capacities()["candidates"])]
+        return (rows, cnt.value) if return_count else rows
 
     def setDataGen(self, path: str) -> None:
         """Detector.hh:48-51: from now on every single-frame detect writes its stage

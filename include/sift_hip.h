@@ -350,7 +350,10 @@ int sift_hip_capacities(sift_hip_t h, int* candidates, int* refined, int* orient
 
 /* Non-zero when a capacity overflowed (1 candidates, 2 refined, 4 oriented,
  * 8 results) or sift_hip_compute_device met an invalid keypoint
- * (SIFT_HIP_FLAG_BAD_KEYPOINT, 16). */
+ * (SIFT_HIP_FLAG_BAD_KEYPOINT, 16).  With bit 1 (value 1) set the frame's
+ * candidate list was full: an arbitrary subset of the candidates (atomic
+ * order) went on, so the results are a subset of the full result and can
+ * differ between runs; every keypoint returned is still a correct one. */
 int sift_hip_overflow_flags(sift_hip_t h, int* flags);
 
 /* Device result arrays (Detector.hh:54-57): kpts = float3 {x, y, layer}
@@ -434,7 +437,13 @@ int sift_hip_timing_entry(sift_hip_t h, int i, const char** name, double* total_
 int sift_hip_timing_reset(sift_hip_t h);
 
 /* Debug/parity accessors (tests): Gaussian plane (octave, layer) as w*h floats;
- * pre-refinement candidates as (octave, layer, r, c) int quadruples. */
+ * pre-refinement candidates as (octave, layer, r, c) int quadruples: OpenCV's
+ * 3x3x3 extrema (|v| > thr, thr = floor(0.5 * contrastThreshould /
+ * numOctaveLayers * 255)), at thr = 0 minus those whose 3x3 block in their own
+ * DoG layer is constant (rounding residue of flat regions), which
+ * adjustLocalExtrema can never keep.  *count is the number
+ * of hits, stored or not: above the candidate capacity min(*count, capacity)
+ * rows exist (overflow flag 1). */
 int sift_hip_debug_gaussian(sift_hip_t h, int octave, int layer, float* out);
 int sift_hip_debug_candidates(sift_hip_t h, int* quads, int cap, int* count);
 

@@ -11,7 +11,12 @@ replays it three ways:
 
   * against the CPU oracle (test infrastructure): every Gaussian plane
     bit-exact, the 3x3x3 candidate set exact, keypoints bit-exact, descriptors
-    within the parity bar (parity_bar.py);
+    within the parity bar (parity_bar.py).  Where the extrema threshold
+    floor(0.5 * contrastThreshould / numOctaveLayers * 255) is 0, the library's
+    candidates are the oracle's minus those whose 3x3 block in their own DoG
+    layer is constant (plateaus of rounding residue in flat regions, which no
+    refinement keeps): the comparison removes them from the oracle's set
+    (threshold_cases.library_candidates);
   * against this library, whole frame (--gpu): the dumped input through a
     fresh detector gives the dumped planes, keypoints and descriptors bit for
     bit (a kernel regression check across builds or boxes);
@@ -113,6 +118,7 @@ def check_oracle(d):
     sys.path.insert(0, HERE)
     import oracle_binding as oracle
     from parity_bar import DESC_EXACT_MIN, DESC_MAX_ABS_DIFF
+    from threshold_cases import library_candidates
 
     c = d["meta"]["config"]
     p = oracle.params(c["numFeatures"], c["numOctaveLayers"], c["contrastThreshould"], c["edgeThreshould"], c["sigma"],
@@ -124,7 +130,7 @@ def check_oracle(d):
     out["gaussian_planes_bitexact"] = out["octaves"] and all(
         np.array_equal(g.view(np.uint32), o.view(np.uint32))
         for planes, ops in zip(d["gauss"], pyr) for g, o in zip(planes, ops))
-    oc = oracle.extrema(img, p)
+    oc = library_candidates(img, p, oracle.extrema(img, p))  # thr = 0: minus the in-layer-flat ones (header)
     gc = d["candidates"]
     out["candidates_exact"] = gc.shape == oc.shape and np.array_equal(gc[np.lexsort(gc.T[::-1])],
                                                                       oc[np.lexsort(oc.T[::-1])])
