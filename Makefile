@@ -64,7 +64,7 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
@@ -82,6 +82,12 @@ $(ASAN_DIR)/test_verify_args: tests/cpp/test_verify_args.cpp $(SRC)/verify_cxx.c
 $(ASAN_DIR)/test_homography_args: tests/cpp/test_homography_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_homography_args.cpp $(SRC)/verify_cxx.cpp \
+	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
+
+# The same for the batched calls: tests/test_verify_batched_asan.py.
+$(ASAN_DIR)/test_verify_batched_args: tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
+	@mkdir -p $(ASAN_DIR)
+	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
 clean:

@@ -26,6 +26,26 @@ struct VerifyInput {
     int nq, nt;
 };
 
+// A batch of lists as the batched kernels take it, by value (as MatchBatch is):
+// pair p's `cap` rows of matches, out, mask and of the gathered points start at
+// row0 = sum of the caps before it; its n comes from counts[p] (counts ==
+// nullptr: n = cap); its positions are its own, the strides the call's.
+constexpr int kVerifyMaxPairs = kMaxMatchPairs;
+struct VerifyBatchPair {
+    const float* qxy;
+    const float* txy;
+    int row0, cap;
+    int nq, nt;
+};
+struct VerifyBatch {
+    VerifyBatchPair pair[kVerifyMaxPairs];
+    const MatchRecord* matches;
+    const int* counts;
+    int qstride, tstride;
+    int P;
+    int rows, max_cap;  // the sum and the largest of the caps
+};
+
 // sift_hip_verify_result's layout.
 struct VerifyResult {
     float F[9];
@@ -61,6 +81,21 @@ void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4*
 void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s);
+
+// The batched twins: the same four steps for all P pairs of a batch in one
+// launch each, pair p = blockIdx.y running the single-pair body on its own
+// slices -- points at row0[p], samples at m K p (m = 8 / 4), models at 9 K p,
+// valid flags and counts at K p -- with the seed `seed + p` (wrapping).
+// results, out_counts: P entries; out, mask: batch.rows rows (each nullable as
+// above).  A workgroup serves one pair.
+void launch_verify_gather_batched(const VerifyBatch& batch, float4* pts, hipStream_t s);
+void launch_verify_hypotheses_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, int K,
+                                      unsigned seed, int* samples, float* F, int* valid, hipStream_t s);
+void launch_verify_score_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
+                                 const int* valid, int K, float e2, int* counts, hipStream_t s);
+void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
+                                  const int* valid, const int* counts, int K, float e2, VerifyResult* results,
+                                  MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s);
 
 // k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
 // `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.

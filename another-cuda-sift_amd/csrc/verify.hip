@@ -30,6 +30,12 @@
 //                         compaction of k_match_select (prefix sums, no atomics:
 //                         the same bytes in every run).  The same template.
 //  k_project_homography   one thread per position row.
+// The four verify kernels are templates over the list they take.  VerifyInput:
+// the single-pair call's list.  VerifyBatch (sift_hip_verify_*_batched_*): all P
+// pairs of a batch in one launch, the pair is blockIdx.y, its list and
+// positions come from a table passed by value, and it works on its own slices
+// of the scratch with the seed `seed + p` -- the same code on the same values,
+// so pair p's bytes are the single call's.  A workgroup serves one pair.
 // Everything is float32 with -ffp-contract=off and correctly rounded division
 // and square root: the operation order written here is the one executed.
 #include <float.h>
@@ -193,9 +199,44 @@ __device__ __forceinline__ float area2(const float (&x)[4], const float (&y)[4],
     return (x[j] - x[i]) * (y[k] - y[i]) - (y[j] - y[i]) * (x[k] - x[i]);
 }
 
+// The LDS of a hypothesis workgroup.  Declared here, in a plain function, not in the kernel templates: the compiler
+// allocates 20,736 B per workgroup for it as declared here (one 9-entry array is optimised away, as before the
+// kernels became templates) and all 23,040 B when the arrays are a template's own.
+struct HypLds {
+    float* a;   // the 8 x 9 system, entry e = 9 row + col of lane l at [e][l]
+    float* y;   // the solution in pivot order, then in column order
+    int* perm;  // the original column at each position
+};
+__device__ __forceinline__ HypLds hyp_lds() {
+    __shared__ float s_a[72 * kHypThreads];
+    __shared__ float s_y[9 * kHypThreads];
+    __shared__ int s_perm[9 * kHypThreads];
+    return HypLds{s_a, s_y, s_perm};
+}
+
+// The list a workgroup works on: the call's own, or pair blockIdx.y's rows of the batch's match buffer, its counter
+// and its positions.
+__device__ __forceinline__ const VerifyInput& list_of(const VerifyInput& in) { return in; }
+__device__ __forceinline__ VerifyInput list_of(const VerifyBatch& b) {
+    const int p = blockIdx.y;
+    const VerifyBatchPair& e = b.pair[p];
+    return VerifyInput{b.matches + e.row0, b.counts ? b.counts + p : nullptr, e.cap, e.qxy, e.txy, b.qstride, b.tstride,
+                       e.nq, e.nt};
+}
+// A batch's workgroup: its pair, and the pair's first row of the per-match arrays.
+__device__ __forceinline__ int pair_of(const VerifyBatch&) { return blockIdx.y; }
+__device__ __forceinline__ int row0_of(const VerifyBatch& b) { return b.pair[blockIdx.y].row0; }
+template <class List>
+constexpr bool kBatched = false;
+template <>
+constexpr bool kBatched<VerifyBatch> = true;
+
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_verify_gather(VerifyInput in, float4* __restrict__ pts) {
+template <class List>
+__global__ __launch_bounds__(256) void k_verify_gather(List list, float4* __restrict__ pts) {
+    if constexpr (kBatched<List>) pts += row0_of(list);
+    const VerifyInput in = list_of(list);
     const int n = verify_n(in.count, in.cap);
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
@@ -209,13 +250,20 @@ __global__ __launch_bounds__(256) void k_verify_gather(VerifyInput in, float4* _
     pts[j] = p;
 }
 
-__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput in, const float4* __restrict__ pts, int K,
+template <class List>
+__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(List list, const float4* __restrict__ pts, int K,
                                                                   unsigned seed, int* __restrict__ samples,
                                                                   float* __restrict__ Fout, int* __restrict__ valid) {
 #pragma clang fp contract(off)
-    __shared__ float s_a[72 * kHypThreads];  // the 8 x 9 system, entry e = 9 row + col of lane l at [e][l]
-    __shared__ float s_y[9 * kHypThreads];   // the solution in pivot order, then in column order
-    __shared__ int s_perm[9 * kHypThreads];  // the original column at each position
+    if constexpr (kBatched<List>) {
+        const size_t k0 = (size_t)K * pair_of(list);
+        pts += row0_of(list), seed += (unsigned)pair_of(list), samples += 8 * k0, Fout += 9 * k0, valid += k0;
+    }
+    const VerifyInput in = list_of(list);
+    const HypLds lds = hyp_lds();
+    float* const s_a = lds.a;
+    float* const s_y = lds.y;
+    int* const s_perm = lds.perm;
     const int lane = threadIdx.x;
     const int k = blockIdx.x * kHypThreads + lane;
     if (k >= K) return;  // no barrier below: a lane works on its own LDS column
@@ -283,13 +331,20 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(VerifyInput i
     valid[k] = ok ? 1 : 0;
 }
 
-__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(VerifyInput in, const float4* __restrict__ pts,
-                                                                    int K, unsigned seed, int* __restrict__ samples,
+template <class List>
+__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, const float4* __restrict__ pts, int K,
+                                                                    unsigned seed, int* __restrict__ samples,
                                                                     float* __restrict__ Hout, int* __restrict__ valid) {
 #pragma clang fp contract(off)
-    __shared__ float s_a[72 * kHypThreads];  // as in k_verify_hypotheses
-    __shared__ float s_y[9 * kHypThreads];
-    __shared__ int s_perm[9 * kHypThreads];
+    if constexpr (kBatched<List>) {
+        const size_t k0 = (size_t)K * pair_of(list);
+        pts += row0_of(list), seed += (unsigned)pair_of(list), samples += 4 * k0, Hout += 9 * k0, valid += k0;
+    }
+    const VerifyInput in = list_of(list);
+    const HypLds lds = hyp_lds();  // as in k_verify_hypotheses
+    float* const s_a = lds.a;
+    float* const s_y = lds.y;
+    int* const s_perm = lds.perm;
     const int lane = threadIdx.x;
     const int k = blockIdx.x * kHypThreads + lane;
     if (k >= K) return;  // no barrier below: a lane works on its own LDS column
@@ -398,11 +453,16 @@ constexpr int kScoreWaves = 4;     // hypotheses per workgroup
 constexpr int kScoreUnroll = 4;    // matches per lane and loop iteration
 constexpr int kScoreTile = 2048;   // matches per LDS tile (32 KiB): 2000 matches are one tile
 
-template <class Pass>
-__global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput in, const float4* __restrict__ pts,
+template <class Pass, class List>
+__global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(List list, const float4* __restrict__ pts,
                                                                    const float* __restrict__ F,
                                                                    const int* __restrict__ valid, int K, float e2,
                                                                    int* __restrict__ counts) {
+    if constexpr (kBatched<List>) {
+        const size_t k0 = (size_t)K * pair_of(list);
+        pts += row0_of(list), F += 9 * k0, valid += k0, counts += k0;  // a batch always has valid flags
+    }
+    const VerifyInput in = list_of(list);
     __shared__ float4 s_pts[kScoreTile];
     const int n = verify_n(in.count, in.cap);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -435,8 +495,9 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(VerifyInput i
 
 constexpr int kVSelThreads = 1024, kVSelWaves = kVSelThreads / 64;
 
-template <class Pass>
-__global__ __launch_bounds__(kVSelThreads) void k_verify_select(VerifyInput in, const float4* __restrict__ pts,
+// A batch: one workgroup per pair, result and out_count its entries, out and mask (each nullable) its rows.
+template <class Pass, class List>
+__global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const float4* __restrict__ pts,
                                                                 const float* __restrict__ F,
                                                                 const int* __restrict__ valid,
                                                                 const int* __restrict__ counts, int K, float e2,
@@ -444,6 +505,15 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(VerifyInput in, 
                                                                 MatchRecord* __restrict__ out, int* __restrict__ out_count,
                                                                 uint8_t* __restrict__ mask) {
     __shared__ int s_key[kVSelWaves], s_nv[kVSelWaves], s_wave[kVSelWaves];
+    if constexpr (kBatched<List>) {
+        const int p = pair_of(list), row0 = row0_of(list);
+        const size_t k0 = (size_t)K * p;
+        pts += row0, F += 9 * k0, valid += k0, counts += k0, result += p;
+        if (out) out += row0;
+        if (out_count) out_count += p;
+        if (mask) mask += row0;
+    }
+    const VerifyInput in = list_of(list);
     const int n = verify_n(in.count, in.cap);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // The winner: most inliers among the valid hypotheses, ties to the lowest k, as the largest key
@@ -525,36 +595,77 @@ __global__ __launch_bounds__(256) void k_project_homography(const float* H, cons
 }
 
 void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s) {
-    if (in.cap > 0) hipLaunchKernelGGL(k_verify_gather, dim3((in.cap + 255) / 256), dim3(256), 0, s, in, pts);
+    if (in.cap > 0)
+        hipLaunchKernelGGL(k_verify_gather<VerifyInput>, dim3((in.cap + 255) / 256), dim3(256), 0, s, in, pts);
 }
 
 void launch_verify_hypotheses(VerifyModel model, const VerifyInput& in, const float4* pts, int K, unsigned seed,
                               int* samples, float* F, int* valid, hipStream_t s) {
     const dim3 grid((K + kHypThreads - 1) / kHypThreads), block(kHypThreads);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_hypotheses_h, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
+        hipLaunchKernelGGL(k_verify_hypotheses_h<VerifyInput>, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
     else
-        hipLaunchKernelGGL(k_verify_hypotheses, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
+        hipLaunchKernelGGL(k_verify_hypotheses<VerifyInput>, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
 }
 
 void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
                          int K, float e2, int* counts, hipStream_t s) {
     const dim3 grid((K + kScoreWaves - 1) / kScoreWaves), block(64 * kScoreWaves);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_score<TransferPass>, grid, block, 0, s, in, pts, F, valid, K, e2, counts);
+        hipLaunchKernelGGL((k_verify_score<TransferPass, VerifyInput>), grid, block, 0, s, in, pts, F, valid, K, e2,
+                           counts);
     else
-        hipLaunchKernelGGL(k_verify_score<SampsonPass>, grid, block, 0, s, in, pts, F, valid, K, e2, counts);
+        hipLaunchKernelGGL((k_verify_score<SampsonPass, VerifyInput>), grid, block, 0, s, in, pts, F, valid, K, e2,
+                           counts);
 }
 
 void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s) {
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_select<TransferPass>, dim3(1), dim3(kVSelThreads), 0, s, in, pts, F, valid, counts, K,
-                           e2, result, out, out_count, mask);
+        hipLaunchKernelGGL((k_verify_select<TransferPass, VerifyInput>), dim3(1), dim3(kVSelThreads), 0, s, in, pts, F,
+                           valid, counts, K, e2, result, out, out_count, mask);
     else
-        hipLaunchKernelGGL(k_verify_select<SampsonPass>, dim3(1), dim3(kVSelThreads), 0, s, in, pts, F, valid, counts, K,
-                           e2, result, out, out_count, mask);
+        hipLaunchKernelGGL((k_verify_select<SampsonPass, VerifyInput>), dim3(1), dim3(kVSelThreads), 0, s, in, pts, F,
+                           valid, counts, K, e2, result, out, out_count, mask);
+}
+
+void launch_verify_gather_batched(const VerifyBatch& batch, float4* pts, hipStream_t s) {
+    if (batch.max_cap > 0)
+        hipLaunchKernelGGL(k_verify_gather<VerifyBatch>, dim3((batch.max_cap + 255) / 256, batch.P), dim3(256), 0, s,
+                           batch, pts);
+}
+
+void launch_verify_hypotheses_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, int K,
+                                      unsigned seed, int* samples, float* F, int* valid, hipStream_t s) {
+    const dim3 grid((K + kHypThreads - 1) / kHypThreads, batch.P), block(kHypThreads);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL(k_verify_hypotheses_h<VerifyBatch>, grid, block, 0, s, batch, pts, K, seed, samples, F, valid);
+    else
+        hipLaunchKernelGGL(k_verify_hypotheses<VerifyBatch>, grid, block, 0, s, batch, pts, K, seed, samples, F, valid);
+}
+
+void launch_verify_score_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
+                                 const int* valid, int K, float e2, int* counts, hipStream_t s) {
+    const dim3 grid((K + kScoreWaves - 1) / kScoreWaves, batch.P), block(64 * kScoreWaves);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL((k_verify_score<TransferPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, K, e2,
+                           counts);
+    else
+        hipLaunchKernelGGL((k_verify_score<SampsonPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, K, e2,
+                           counts);
+}
+
+void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
+                                  const int* valid, const int* counts, int K, float e2, VerifyResult* results,
+                                  MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s) {
+    const dim3 grid(1, batch.P), block(kVSelThreads);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL((k_verify_select<TransferPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, counts,
+                           K, e2, results, out, out_counts, mask);
+    else
+        hipLaunchKernelGGL((k_verify_select<SampsonPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, counts,
+                           K, e2, results, out, out_counts, mask);
 }
 
 void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,

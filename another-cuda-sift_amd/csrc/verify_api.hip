@@ -1,6 +1,8 @@
 // Verifier handle (sift_hip_verifier_*, sift_hip_verify_*, sift_hip_score_*) and
 // sift_hip_project_homography_device of libsift_hip.so; the kernels are verify.hip.  The handle owns every scratch
-// array from creation on, so a device call only launches kernels (capturable).
+// array from creation on, so a device call only launches kernels (capturable).  A handle from
+// sift_hip_verifier_create_batched holds the scratch of up to maxP pairs per call (sift_hip_verify_*_batched_*): maxM
+// then bounds a call's rows over all its pairs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,18 +15,19 @@
 
 struct sift_hip_verifier {
     int device = 0;
-    int maxM = 0, maxK = 0;
-    float4* dPts = nullptr;      // the gathered matches (qx, qy, tx, ty)
-    int* dSamples = nullptr;     // 8 per hypothesis (the homography uses 4)
+    int maxM = 0, maxK = 0, maxP = 0;
+    float4* dPts = nullptr;      // the gathered matches (qx, qy, tx, ty), maxM rows
+    int* dSamples = nullptr;     // 8 per hypothesis (the homography uses 4), maxP x maxK hypotheses as are dF .. dCounts
     float* dF = nullptr;         // 9 per hypothesis (F, or H)
     int* dValid = nullptr;
     int* dCounts = nullptr;
-    // the outputs of sift_hip_verify_fundamental_host / _homography_host
-    VerifyResult* dResult = nullptr;
+    // the outputs of sift_hip_verify_fundamental_host / _homography_host and their batched forms
+    VerifyResult* dResult = nullptr;  // maxP records
     MatchRecord* dOut = nullptr;
     uint8_t* dMask = nullptr;
     int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
     int lastModel = 0;           // its VerifyModel, 0: none
+    bool lastBatch = false;      // it was a batched call (the getters read one pair's scratch layout)
     ~sift_hip_verifier() {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
@@ -77,6 +80,94 @@ int verify_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in
     HIPCHK(hipGetLastError());
     v->lastK = p.hypotheses;
     v->lastModel = (int)model;
+    v->lastBatch = false;
+    return SIFT_HIP_OK;
+}
+
+// The batched call's argument rules: what can be judged without the handle first, then its limits; `b` is the pair
+// table the kernels take.  out: the device form's output rows (may not overlap matches), null otherwise.
+int check_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, const int* counts, int P,
+                const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                const sift_hip_verify_params* params, const void* results, const sift_hip_dmatch* out, VerifyBatch& b) {
+    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
+    if (!pairs) return fail(SIFT_HIP_ERR_INVALID, "verify: null pairs");
+    if (!params || !results) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
+    if (P < 1 || P > kVerifyMaxPairs)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: pairs outside 1.." + std::to_string(kVerifyMaxPairs));
+    if (query_stride < 2 || train_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "verify: a position stride below 2 floats");
+    int rows = 0, max_cap = 0;  // P x 65536 fits
+    for (int p = 0; p < P; p++) {
+        const sift_hip_verify_pair& e = pairs[p];
+        const std::string at = " (pair " + std::to_string(p) + ")";
+        if (e.cap < 0 || e.cap > kVerifyMaxMatches)
+            return fail(SIFT_HIP_ERR_INVALID, "verify: cap must lie in 0.." + std::to_string(kVerifyMaxMatches) + at);
+        if (e.nq < 0 || e.nt < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: a negative position row count" + at);
+        if (e.cap > 0 && (!e.query_xy || !e.train_xy))
+            return fail(SIFT_HIP_ERR_INVALID, "verify: null position pointer" + at);
+        b.pair[p] = VerifyBatchPair{e.query_xy, e.train_xy, rows, e.cap, e.nq, e.nt};
+        rows += e.cap;
+        max_cap = std::max(max_cap, e.cap);
+    }
+    if (rows > 0 && !matches) return fail(SIFT_HIP_ERR_INVALID, "verify: null matches");
+    if (int rc = check_error(params->max_error)) return rc;
+    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)rows;
+    if (out && rows > 0 && ob < mb + bytes && mb < ob + bytes)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
+    if (params->hypotheses < 1 || params->hypotheses > kVerifyMaxHypotheses || params->hypotheses > v->maxK)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: hypotheses outside 1..max_hypotheses");
+    if (P > v->maxP) return fail(SIFT_HIP_ERR_INVALID, "verify: more pairs than the verifier's max_pairs");
+    if (rows > v->maxM) return fail(SIFT_HIP_ERR_INVALID, "verify: the caps' sum exceeds the verifier's max_matches");
+    b.matches = reinterpret_cast<const MatchRecord*>(matches);
+    b.counts = counts;
+    b.qstride = query_stride, b.tstride = train_stride;
+    b.P = P, b.rows = rows, b.max_cap = max_cap;
+    return SIFT_HIP_OK;
+}
+
+// One launch per step for the whole batch.  Every index stays inside the handle's scratch: rows <= maxM,
+// P <= maxP and K <= maxK were checked.
+int verify_batched_device(sift_hip_verifier* v, VerifyModel model, const VerifyBatch& b, const sift_hip_verify_params& p,
+                          VerifyResult* results, MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s) {
+    const float e2 = p.max_error * p.max_error;
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather_batched(b, v->dPts, s);
+    launch_verify_hypotheses_batched(model, b, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
+    launch_verify_score_batched(model, b, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
+    launch_verify_select_batched(model, b, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, results, out,
+                                 out_counts, mask, s);
+    HIPCHK(hipGetLastError());
+    v->lastK = p.hypotheses;
+    v->lastModel = (int)model;
+    v->lastBatch = true;
+    return SIFT_HIP_OK;
+}
+
+int verify_model_batched_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches,
+                                const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                int train_stride, const sift_hip_verify_params* params, void* results,
+                                sift_hip_dmatch* out, int* out_counts, uint8_t* mask, void* stream) {
+    VerifyBatch b{};
+    if (int rc = check_batch(v, matches, counts, P, pairs, query_stride, train_stride, params, results, out, b)) return rc;
+    return verify_batched_device(v, model, b, *params, static_cast<VerifyResult*>(results),
+                                 reinterpret_cast<MatchRecord*>(out), out_counts, mask, (hipStream_t)stream);
+}
+
+int verify_model_batched_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
+                              int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                              const sift_hip_verify_params* params, void* results_host, sift_hip_dmatch* out_host,
+                              uint8_t* mask_host) {
+    VerifyBatch b{};
+    if (int rc = check_batch(v, matches, counts, P, pairs, query_stride, train_stride, params, results_host, nullptr, b))
+        return rc;
+    if (int rc = verify_batched_device(v, model, b, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
+    HIPCHK(hipMemcpy(results_host, v->dResult, sizeof(VerifyResult) * (size_t)P, hipMemcpyDeviceToHost));
+    const VerifyResult* r = static_cast<const VerifyResult*>(results_host);
+    for (int p = 0; out_host && p < P; p++) {  // a pair's rows past its inliers stay as they are, as on the device
+        const int n = std::min(r[p].inliers, b.pair[p].cap), row0 = b.pair[p].row0;
+        if (n > 0)
+            HIPCHK(hipMemcpy(out_host + row0, v->dOut + row0, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    if (mask_host && b.rows > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
     return SIFT_HIP_OK;
 }
 
@@ -139,6 +230,7 @@ int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples
     if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
     if (cap < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: negative cap");
     if (v->lastK == 0) return fail(SIFT_HIP_ERR_STATE, "no verify call has run on this verifier");
+    if (v->lastBatch) return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was a batch");
     if (v->lastModel != (int)model)
         return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was of the other model");
     const size_t K = (size_t)std::min(cap, v->lastK);
@@ -163,8 +255,14 @@ void sift_hip_default_verify_params(sift_hip_verify_params* p) {
 }
 
 int sift_hip_verifier_create(int device, int max_matches, int max_hypotheses, sift_hip_verifier_t* out) {
-    if (!out || max_matches < 1 || max_matches > kVerifyMaxMatches || max_hypotheses < 1 ||
-        max_hypotheses > kVerifyMaxHypotheses)
+    if (max_matches > kVerifyMaxMatches) return fail(SIFT_HIP_ERR_INVALID, "bad verifier limits");
+    return sift_hip_verifier_create_batched(device, max_matches, max_hypotheses, 1, out);
+}
+
+int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypotheses, int max_pairs,
+                                     sift_hip_verifier_t* out) {
+    if (!out || max_matches < 1 || max_matches > kVerifyMaxPairs * kVerifyMaxMatches || max_hypotheses < 1 ||
+        max_hypotheses > kVerifyMaxHypotheses || max_pairs < 1 || max_pairs > kVerifyMaxPairs)
         return fail(SIFT_HIP_ERR_INVALID, "bad verifier limits");
     *out = nullptr;
     auto* v = new sift_hip_verifier();
@@ -175,13 +273,14 @@ int sift_hip_verifier_create(int device, int max_matches, int max_hypotheses, si
     }
     v->maxM = max_matches;
     v->maxK = max_hypotheses;
-    const size_t M = (size_t)max_matches, K = (size_t)max_hypotheses;
+    v->maxP = max_pairs;
+    const size_t M = (size_t)max_matches, K = (size_t)max_hypotheses * (size_t)max_pairs;
     if (hipSetDevice(v->device) != hipSuccess || hipMalloc((void**)&v->dPts, sizeof(float4) * M) != hipSuccess ||
         hipMalloc((void**)&v->dSamples, sizeof(int) * 8 * K) != hipSuccess ||
         hipMalloc((void**)&v->dF, sizeof(float) * 9 * K) != hipSuccess ||
         hipMalloc((void**)&v->dValid, sizeof(int) * K) != hipSuccess ||
         hipMalloc((void**)&v->dCounts, sizeof(int) * K) != hipSuccess ||
-        hipMalloc((void**)&v->dResult, sizeof(VerifyResult)) != hipSuccess ||
+        hipMalloc((void**)&v->dResult, sizeof(VerifyResult) * (size_t)max_pairs) != hipSuccess ||
         hipMalloc((void**)&v->dOut, sizeof(MatchRecord) * M) != hipSuccess ||
         hipMalloc((void**)&v->dMask, M) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         delete v;
@@ -254,6 +353,41 @@ int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatc
 
 int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* samples, float* H, int* counts, int cap) {
     return hypotheses_host(v, VerifyModel::Homography, 4, samples, H, counts, cap);
+}
+
+int sift_hip_verify_fundamental_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                               int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                               int train_stride, const sift_hip_verify_params* params,
+                                               sift_hip_verify_result* results, sift_hip_dmatch* out, int* out_counts,
+                                               uint8_t* mask, void* stream) {
+    return verify_model_batched_device(v, VerifyModel::Fundamental, matches, counts, P, pairs, query_stride, train_stride,
+                                       params, results, out, out_counts, mask, stream);
+}
+
+int sift_hip_verify_fundamental_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                             int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                             const sift_hip_verify_params* params, sift_hip_verify_result* results_host,
+                                             sift_hip_dmatch* out_host, uint8_t* mask_host) {
+    return verify_model_batched_host(v, VerifyModel::Fundamental, matches, counts, P, pairs, query_stride, train_stride,
+                                     params, results_host, out_host, mask_host);
+}
+
+int sift_hip_verify_homography_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                              int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                              int train_stride, const sift_hip_verify_params* params,
+                                              sift_hip_homography_result* results, sift_hip_dmatch* out, int* out_counts,
+                                              uint8_t* mask, void* stream) {
+    return verify_model_batched_device(v, VerifyModel::Homography, matches, counts, P, pairs, query_stride, train_stride,
+                                       params, results, out, out_counts, mask, stream);
+}
+
+int sift_hip_verify_homography_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                            int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                            const sift_hip_verify_params* params,
+                                            sift_hip_homography_result* results_host, sift_hip_dmatch* out_host,
+                                            uint8_t* mask_host) {
+    return verify_model_batched_host(v, VerifyModel::Homography, matches, counts, P, pairs, query_stride, train_stride,
+                                     params, results_host, out_host, mask_host);
 }
 
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

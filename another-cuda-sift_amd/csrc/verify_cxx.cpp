@@ -20,6 +20,13 @@ static_assert(sizeof(HomographyResult) == sizeof(sift_hip_homography_result) &&
                   offsetof(HomographyResult, hypothesis) == offsetof(sift_hip_homography_result, hypothesis),
               "sift_cuda::HomographyResult is sift_hip_homography_result");
 
+static_assert(sizeof(VerifyPair) == sizeof(sift_hip_verify_pair) &&
+                  offsetof(VerifyPair, train_xy) == offsetof(sift_hip_verify_pair, train_xy) &&
+                  offsetof(VerifyPair, nq) == offsetof(sift_hip_verify_pair, nq) &&
+                  offsetof(VerifyPair, nt) == offsetof(sift_hip_verify_pair, nt) &&
+                  offsetof(VerifyPair, cap) == offsetof(sift_hip_verify_pair, cap),
+              "sift_cuda::VerifyPair is sift_hip_verify_pair");
+
 void check_throw(int rc, const char* what) {
     if (rc == SIFT_HIP_OK) return;
     const std::string msg = std::string(what) + ": " + sift_hip_last_error() + " (status " + std::to_string(rc) + ")";
@@ -38,7 +45,90 @@ struct DeviceBlock {
     DeviceBlock& operator=(const DeviceBlock&) = delete;
 };
 
+const sift_hip_verify_pair* toAbi(const std::vector<VerifyPair>& pairs) {
+    return reinterpret_cast<const sift_hip_verify_pair*>(pairs.data());
+}
+
+// The rows of a batch (0 for caps the ABI refuses: the call throws before anything is read).
+size_t batchRows(const std::vector<VerifyPair>& pairs) {
+    size_t rows = 0;
+    for (const VerifyPair& p : pairs)
+        if (p.cap < 0 || p.cap > 65536) return 0;
+        else rows += (size_t)p.cap;
+    return rows;
+}
+
+// One geometry per pair from the host forms' outputs: pair p's records are the first r[p].inliers of its rows.
+template <class Geometry, class Record>
+std::vector<Geometry> geometries(const std::vector<VerifyPair>& pairs, const std::vector<Record>& r,
+                                 const std::vector<DMatch>& list, float (Geometry::*model)[9],
+                                 float (Record::*from)[9]) {
+    std::vector<Geometry> out(pairs.size());
+    size_t row0 = 0;
+    for (size_t p = 0; p < pairs.size(); p++) {
+        for (int i = 0; i < 9; i++) (out[p].*model)[i] = (r[p].*from)[i];
+        out[p].hypothesis = r[p].hypothesis;
+        out[p].inliers.assign(list.begin() + row0, list.begin() + row0 + (size_t)r[p].inliers);
+        row0 += (size_t)pairs[p].cap;
+    }
+    return out;
+}
+
 }  // namespace
+
+Verifier::Verifier(int max_matches, int max_hypotheses, int device, int max_pairs) {
+    check_throw(sift_hip_verifier_create_batched(device, max_matches, max_hypotheses, max_pairs, &m_handle),
+                "Verifier::Verifier");
+}
+
+void Verifier::verifyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                   int query_stride, int train_stride, const VerifyParams& params, VerifyResult* results,
+                                   DMatch* out, int* out_counts, uint8_t* mask, void* stream) {
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(sift_hip_verify_fundamental_batched_device(
+                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
+                    query_stride, train_stride, &p, reinterpret_cast<sift_hip_verify_result*>(results),
+                    reinterpret_cast<sift_hip_dmatch*>(out), out_counts, mask, stream),
+                "Verifier::verifyBatchedDevice");
+}
+
+void Verifier::verifyHomographyBatchedDevice(const DMatch* matches, const int* counts,
+                                             const std::vector<VerifyPair>& pairs, int query_stride, int train_stride,
+                                             const VerifyParams& params, HomographyResult* results, DMatch* out,
+                                             int* out_counts, uint8_t* mask, void* stream) {
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(sift_hip_verify_homography_batched_device(
+                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
+                    query_stride, train_stride, &p, reinterpret_cast<sift_hip_homography_result*>(results),
+                    reinterpret_cast<sift_hip_dmatch*>(out), out_counts, mask, stream),
+                "Verifier::verifyHomographyBatchedDevice");
+}
+
+std::vector<TwoViewGeometry> Verifier::verifyBatchedHost(const DMatch* matches, const int* counts,
+                                                         const std::vector<VerifyPair>& pairs, int query_stride,
+                                                         int train_stride, const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    std::vector<sift_hip_verify_result> r(pairs.size());
+    std::vector<DMatch> list(batchRows(pairs));
+    check_throw(sift_hip_verify_fundamental_batched_host(
+                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
+                    query_stride, train_stride, &p, r.data(), reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
+                "Verifier::verifyBatchedHost");
+    return geometries<TwoViewGeometry>(pairs, r, list, &TwoViewGeometry::F, &sift_hip_verify_result::F);
+}
+
+std::vector<PlanarGeometry> Verifier::verifyHomographyBatchedHost(const DMatch* matches, const int* counts,
+                                                                  const std::vector<VerifyPair>& pairs, int query_stride,
+                                                                  int train_stride, const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    std::vector<sift_hip_homography_result> r(pairs.size());
+    std::vector<DMatch> list(batchRows(pairs));
+    check_throw(sift_hip_verify_homography_batched_host(
+                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
+                    query_stride, train_stride, &p, r.data(), reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
+                "Verifier::verifyHomographyBatchedHost");
+    return geometries<PlanarGeometry>(pairs, r, list, &PlanarGeometry::H, &sift_hip_homography_result::H);
+}
 
 Verifier::Verifier(int max_matches, int max_hypotheses, int device) {
     check_throw(sift_hip_verifier_create(device, max_matches, max_hypotheses, &m_handle), "Verifier::Verifier");

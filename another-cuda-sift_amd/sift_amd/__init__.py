@@ -149,6 +149,21 @@ VERIFY_RESULT_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypoth
 assert VERIFY_RESULT_DTYPE.itemsize == ctypes.sizeof(_VerifyResult)
 
 
+class _VerifyPair(ctypes.Structure):
+    """sift_hip_verify_pair: one pair of a batched verify call -- its device position rows and their counts, and cap,
+    its number of rows in the call's matches, out and mask arrays (its rows start at the sum of the caps before it)."""
+    _fields_ = [
+        ("query_xy", ctypes.c_void_p),
+        ("train_xy", ctypes.c_void_p),
+        ("nq", ctypes.c_int),
+        ("nt", ctypes.c_int),
+        ("cap", ctypes.c_int),
+    ]
+
+
+assert ctypes.sizeof(_VerifyPair) == 32
+
+
 class _HomographyResult(ctypes.Structure):
     """sift_hip_homography_result: the winning hypothesis' H (row-major, x_train ~ H x_query), its inlier count and
     index (-1: none), the number of matches that counted and the number of valid hypotheses."""
@@ -281,6 +296,15 @@ def lib() -> ctypes.CDLL:
         "sift_hip_score_homography_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, i, f, vp, vp]),
         "sift_hip_verify_homography_hypotheses_host": (i, [vp, vp, vp, vp, i]),
         "sift_hip_project_homography_device": (i, [vp, vp, i, i, vp, i, vp]),
+        "sift_hip_verifier_create_batched": (i, [i, i, i, i, ctypes.POINTER(vp)]),
+        "sift_hip_verify_fundamental_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                           ctypes.POINTER(_VerifyParams), vp, vp, vp, vp, vp]),
+        "sift_hip_verify_fundamental_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                         ctypes.POINTER(_VerifyParams), vp, vp, vp]),
+        "sift_hip_verify_homography_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                          ctypes.POINTER(_VerifyParams), vp, vp, vp, vp, vp]),
+        "sift_hip_verify_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                        ctypes.POINTER(_VerifyParams), vp, vp, vp]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -1024,11 +1048,17 @@ class Verifier:
     ransac_homography).  Owns all scratch of its calls -- for lists of up to max_matches records and up to
     max_hypotheses hypotheses -- so a device call only launches kernels.  Calls on one verifier must be ordered."""
 
-    def __init__(self, max_matches: int, max_hypotheses: int = 1024, device: int = -1):
+    def __init__(self, max_matches: int, max_hypotheses: int = 1024, max_pairs: int = 1, device: int = -1):
+        """max_pairs > 1: a verifier for the batched calls (sift_hip_verifier_create_batched) of up to max_pairs pairs
+        whose caps sum to at most max_matches (up to 64 x 65536)."""
         self._v = ctypes.c_void_p()
-        _check(lib().sift_hip_verifier_create(device, max_matches, max_hypotheses, ctypes.byref(self._v)),
-               "verifier_create")
-        self.max_matches, self.max_hypotheses = max_matches, max_hypotheses
+        if max_pairs == 1:
+            _check(lib().sift_hip_verifier_create(device, max_matches, max_hypotheses, ctypes.byref(self._v)),
+                   "verifier_create")
+        else:
+            _check(lib().sift_hip_verifier_create_batched(device, max_matches, max_hypotheses, max_pairs,
+                                                          ctypes.byref(self._v)), "verifier_create_batched")
+        self.max_matches, self.max_hypotheses, self.max_pairs = max_matches, max_hypotheses, max_pairs
         self._hypotheses = 0
         self._h_hypotheses = 0
 
@@ -1142,6 +1172,111 @@ class Verifier:
         _check(lib().sift_hip_verify_homography_hypotheses_host(self._v, _ptr(samples), _ptr(H), _ptr(counts), K),
                "verify_homography_hypotheses_host")
         return samples, H, H.any(1), counts
+
+    # --- all pairs of a batch in one pass (sift_hip_verify_*_batched_*).  pairs: (q_xy_ptr, nq, t_xy_ptr, nt) -- as
+    # sift_amd.multi.position_pairs returns them -- or (q_xy_ptr, nq, t_xy_ptr, nt, cap); cap, the pair's rows in the
+    # matches, out and mask arrays, defaults to nq, which is Matcher.match_list_batched's layout.  Pair p's rows
+    # start at the sum of the caps before it, and its outputs are the single call's with seed + p.
+
+    @staticmethod
+    def _pairs(pairs: Sequence):
+        rec = [(p[0] or None, p[2] or None, p[1], p[3], p[4] if len(p) > 4 else p[1]) for p in pairs]
+        return (_VerifyPair * max(len(rec), 1))(*[_VerifyPair(*r) for r in rec]), [r[4] for r in rec]
+
+    def _batched_device(self, fn, what, matches_ptr, counts_ptr, pairs, results_ptr, out_ptr, out_counts_ptr, mask_ptr,
+                        max_error, hypotheses, seed, q_stride, t_stride, stream):
+        p = _VerifyParams(hypotheses, seed & 0xFFFFFFFF, max_error)
+        table, _ = self._pairs(pairs)
+        _check(fn(self._v, matches_ptr or None, counts_ptr or None, len(pairs), table, q_stride, t_stride, ctypes.byref(p),
+                  results_ptr or None, out_ptr or None, out_counts_ptr or None, mask_ptr or None, stream), what)
+
+    def verify_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                              out_ptr: int = 0, out_counts_ptr: int = 0, mask_ptr: int = 0, max_error: float = 1.5,
+                              hypotheses: int = 1024, seed: int = 0, q_stride: int = 3, t_stride: int = 3,
+                              stream: Optional[int] = None) -> None:
+        """Enqueue the fundamental-matrix verification of every pair (sift_hip_verify_fundamental_batched_device);
+        every pointer is device memory.  counts_ptr: len(pairs) device ints (0: every pair counts its cap) -- e.g.
+        match_list_batched's counts; results_ptr: len(pairs) VERIFY_RESULT_DTYPE records; out_ptr and mask_ptr (the
+        caps' sum rows / bytes) and out_counts_ptr (len(pairs) ints) may be 0."""
+        self._batched_device(lib().sift_hip_verify_fundamental_batched_device, "verify_fundamental_batched_device",
+                             matches_ptr, counts_ptr, pairs, results_ptr, out_ptr, out_counts_ptr, mask_ptr, max_error,
+                             hypotheses, seed, q_stride, t_stride, stream)
+
+    def verify_homography_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                         out_ptr: int = 0, out_counts_ptr: int = 0, mask_ptr: int = 0,
+                                         max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0,
+                                         q_stride: int = 3, t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """verify_batched_device for the homography (sift_hip_verify_homography_batched_device); results_ptr:
+        HOMOGRAPHY_RESULT_DTYPE records."""
+        self._batched_device(lib().sift_hip_verify_homography_batched_device, "verify_homography_batched_device",
+                             matches_ptr, counts_ptr, pairs, results_ptr, out_ptr, out_counts_ptr, mask_ptr, max_error,
+                             hypotheses, seed, q_stride, t_stride, stream)
+
+    def _batched_host(self, fn, what, dtype, matches_ptr, counts_ptr, pairs, max_error, hypotheses, seed, q_stride,
+                      t_stride, full):
+        p = _VerifyParams(hypotheses, seed & 0xFFFFFFFF, max_error)
+        table, caps = self._pairs(pairs)
+        rows = sum(c for c in caps if 0 <= c <= 65536)
+        res = np.zeros(max(len(pairs), 1), dtype)
+        out, mask = np.zeros(rows, DMATCH_DTYPE), np.zeros(rows, np.uint8)
+        _check(fn(self._v, matches_ptr or None, counts_ptr or None, len(pairs), table, q_stride, t_stride, ctypes.byref(p),
+                  _ptr(res), _ptr(out), _ptr(mask)), what)
+        row0 = np.concatenate([[0], np.cumsum(caps)]).astype(int)
+        model = dtype.names[0]
+        got = []
+        for i, r in enumerate(res[:len(pairs)]):
+            recs = out[row0[i]: row0[i] + r["inliers"]].copy()
+            if full:
+                got.append((r.copy(), recs, mask[row0[i]: row0[i + 1]].copy()))
+            else:
+                got.append((r[model].reshape(3, 3).copy(), recs, int(r["hypothesis"])))
+        return got
+
+    def verify_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, max_error: float = 1.5,
+                            hypotheses: int = 1024, seed: int = 0, q_stride: int = 3, t_stride: int = 3,
+                            full: bool = False) -> list:
+        """Synchronous (sift_hip_verify_fundamental_batched_host): per pair what verify_host returns -- (F, the inlier
+        records, the winning hypothesis or -1), or with full (the VERIFY_RESULT_DTYPE record, the records, the pair's
+        mask of cap bytes)."""
+        return self._batched_host(lib().sift_hip_verify_fundamental_batched_host, "verify_fundamental_batched_host",
+                                  VERIFY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, max_error, hypotheses, seed,
+                                  q_stride, t_stride, full)
+
+    def verify_homography_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, max_error: float = 1.5,
+                                       hypotheses: int = 1024, seed: int = 0, q_stride: int = 3, t_stride: int = 3,
+                                       full: bool = False) -> list:
+        """verify_batched_host for the homography (sift_hip_verify_homography_batched_host)."""
+        return self._batched_host(lib().sift_hip_verify_homography_batched_host, "verify_homography_batched_host",
+                                  HOMOGRAPHY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, max_error, hypotheses, seed,
+                                  q_stride, t_stride, full)
+
+
+def _verify_batched(host, matches_per_pair, xy_per_pair, max_error, hypotheses, seed):
+    if len(matches_per_pair) != len(xy_per_pair):
+        raise ValueError("one (des_xy, src_xy) per match list")
+    lists = [np.ascontiguousarray(np.asarray(m, DMATCH_DTYPE)).reshape(-1) for m in matches_per_pair]
+    xy = [[np.ascontiguousarray(np.asarray(a, np.float32)[:, :2]) for a in qt] for qt in xy_per_pair]
+    rows = sum(len(m) for m in lists)
+    v = Verifier(max(rows, 1), hypotheses, max(len(lists), 1))
+    d = DeviceArray.from_numpy(np.concatenate(lists) if lists else np.zeros(0, DMATCH_DTYPE))
+    dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
+    pairs = [(dq.value, len(q), dt.value, len(t), len(m)) for m, (q, t), (dq, dt) in zip(lists, xy, dxy)]
+    return host(v, d.value if rows else 0, 0, pairs, max_error, hypotheses, seed, 2, 2)
+
+
+def verifyFundamentalBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, max_error: float = 1.5,
+                             hypotheses: int = 1024, seed: int = 0) -> list:
+    """verifyFundamental for P lists in one pass: matches_per_pair[p] a DMATCH_DTYPE array, xy_per_pair[p] =
+    (des_xy, src_xy) host float arrays of rows with x, y first.  A list of what verifyFundamental returns per pair --
+    (F, the inlier records, the winning hypothesis or -1) --, pair p verified with the seed `seed + p`."""
+    return _verify_batched(Verifier.verify_batched_host, matches_per_pair, xy_per_pair, max_error, hypotheses, seed)
+
+
+def verifyHomographyBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, max_error: float = 1.5,
+                            hypotheses: int = 1024, seed: int = 0) -> list:
+    """verifyFundamentalBatched for the homography: per pair what verifyHomography returns."""
+    return _verify_batched(Verifier.verify_homography_batched_host, matches_per_pair, xy_per_pair, max_error,
+                           hypotheses, seed)
 
 
 def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,

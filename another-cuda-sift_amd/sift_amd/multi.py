@@ -144,6 +144,22 @@ def code_pairs(counts: Sequence[int], rank: int, world: int, n_pad: int) -> List
     return out
 
 
+def position_pairs(gathered_xy: torch.Tensor, counts: Sequence[int], rank: int,
+                   world: int) -> List[Tuple[int, int, int, int]]:
+    """The position rows of this rank's C5 pairs, in code_pairs' order, as
+    Verifier.verify_batched_device takes them: (q_ptr, nq, t_ptr, nt) over a
+    (world, n, c) float32 tensor of all-gathered position rows (x, y first;
+    all_gather_rows carries them), with c the position stride of the call.  With
+    cap = nq per pair the rows of Matcher.match_list_codes_batched's output are
+    the verifier's input as they lie."""
+    if gathered_xy.dim() != 3 or gathered_xy.shape[0] != world or gathered_xy.dtype != torch.float32:
+        raise ValueError("position_pairs takes a (world, n, c) float32 tensor")
+    if not gathered_xy.is_contiguous():
+        raise ValueError("position_pairs takes a contiguous tensor (rows of c floats)")
+    return [(gathered_xy[rank].data_ptr(), counts[rank], gathered_xy[j].data_ptr(), counts[j])
+            for _, j in peer_pairs(rank, world)]
+
+
 MatchFn = Callable[[Sequence[torch.Tensor], Sequence[int], Sequence[torch.Tensor], Sequence[int]], List[torch.Tensor]]
 
 

@@ -53,12 +53,24 @@ struct HomographyResult {
     int inliers, hypothesis, matches, valid_hypotheses;
 };
 
+// sift_hip_verify_pair: one pair of a batched call -- its device position rows (nq / nt rows) and cap, its number of
+// rows in the call's matches, out and mask arrays, where its rows start at the sum of the caps before it.
+struct VerifyPair {
+    const float* query_xy = nullptr;
+    const float* train_xy = nullptr;
+    int nq = 0, nt = 0;
+    int cap = 0;
+};
+
 // A verifier owns the scratch of its calls; calls on one verifier must be
 // ordered.  What the ABI refuses (sift_hip_verify_fundamental_device) throws
 // std::invalid_argument; a failed allocation or HIP call std::runtime_error.
 class Verifier {
 public:
     Verifier(int max_matches, int max_hypotheses = 1024, int device = -1);
+    // For the batched calls below (sift_hip_verifier_create_batched): up to max_pairs (1..64) pairs per call, whose
+    // caps sum to at most max_matches (1..64 x 65536).
+    Verifier(int max_matches, int max_hypotheses, int device, int max_pairs);
     ~Verifier();
     Verifier(const Verifier&) = delete;
     Verifier& operator=(const Verifier&) = delete;
@@ -80,6 +92,26 @@ public:
     PlanarGeometry verifyHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
                                         int query_stride, int nq, const float* train_xy, int train_stride, int nt,
                                         const VerifyParams& params = {});
+
+    // All pairs of a batch in one pass (sift_hip_verify_fundamental_batched_device / _homography_batched_device):
+    // pair p's result, out rows, out_count and mask are those of the single call on its list with the seed
+    // params.seed + p.  counts (pairs.size() device ints, nullptr: every pair counts its cap), results (pairs.size()
+    // device records); out, out_counts and mask may be nullptr.  Enqueued on `stream`, not synchronised.
+    void verifyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                             int query_stride, int train_stride, const VerifyParams& params, VerifyResult* results,
+                             DMatch* out = nullptr, int* out_counts = nullptr, uint8_t* mask = nullptr,
+                             void* stream = nullptr);
+    void verifyHomographyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                       int query_stride, int train_stride, const VerifyParams& params,
+                                       HomographyResult* results, DMatch* out = nullptr, int* out_counts = nullptr,
+                                       uint8_t* mask = nullptr, void* stream = nullptr);
+    // Synchronous; one geometry per pair, in the pairs' order.
+    std::vector<TwoViewGeometry> verifyBatchedHost(const DMatch* matches, const int* counts,
+                                                   const std::vector<VerifyPair>& pairs, int query_stride,
+                                                   int train_stride, const VerifyParams& params = {});
+    std::vector<PlanarGeometry> verifyHomographyBatchedHost(const DMatch* matches, const int* counts,
+                                                            const std::vector<VerifyPair>& pairs, int query_stride,
+                                                            int train_stride, const VerifyParams& params = {});
 
     sift_hip_verifier* handle() const { return m_handle; }
 

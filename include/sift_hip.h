@@ -1054,6 +1054,85 @@ int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* sampl
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
                                        void* stream);
 
+/* --- Batched verification: every pair of a match batch in one pass --------------
+ *
+ * What sift_hip_match_list_batched is to sift_hip_match_list_device: P lists
+ * verified by one gather, one hypotheses, one score and one select launch, on
+ * the caller's stream, so the chain match_list_batched -> verify_*_batched_device
+ * runs with no read-back for the whole batch.
+ *
+ * The rule.  Pair p of a batched call gives, byte for byte, the result record,
+ * mask, out records and out_count of the single-pair call above on that pair's
+ * list and positions with the same hypotheses and max_error and the seed
+ * params->seed + p (uint32, wrapping): sift_amd.cv.ransac_fundamental /
+ * ransac_homography (matches_p, q_xy_p, t_xy_p, max_error, K, seed + p).
+ *
+ * Layout.  A host array of P pair records.  query_xy / train_xy: the pair's
+ * device position rows, nq / nt their row counts; cap: the pair's number of
+ * rows in matches, out and mask.  Pair p's rows start at row0[p] = the sum of
+ * cap[r] over r < p in all three arrays -- with cap[p] = nq[p] exactly what
+ * sift_hip_match_list_batched wrote.  counts: P device ints, pair p counts
+ * n = min(max(counts[p], 0), cap[p]) records (NULL: all cap[p]).  results: P
+ * device records of 52 bytes; out_counts: P device ints.  query_stride and
+ * train_stride hold for every pair.  A pair with cap = 0, or with fewer than 8
+ * (homography: 4) matches, gives the empty result (hypothesis = -1, matches = n,
+ * out_count = 0), as the single call does. */
+typedef struct {
+    const float* query_xy;
+    const float* train_xy;
+    int nq, nt;
+    int cap;
+} sift_hip_verify_pair;
+
+/* A verifier for batched calls (and for the single-pair calls above, which it
+ * serves as any other): max_pairs 1..64 pairs per call, max_matches
+ * 1..64 x 65536 rows over all the pairs of a call (a single-pair call's cap is
+ * bounded by it and by 65536), max_hypotheses 1..4096 per pair.  It owns, from
+ * creation on, the gathered points of max_matches rows and the samples, models,
+ * valid flags and counts of max_pairs x max_hypotheses hypotheses.
+ * sift_hip_verifier_create gives max_pairs = 1. */
+int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypotheses, int max_pairs,
+                                     sift_hip_verifier_t* out);
+
+/* Enqueued on `stream`, not synchronised; matches, counts, positions, results,
+ * out, out_counts, mask: device memory; pairs: host memory, read before the
+ * call returns.  out, out_counts and mask may each be NULL.  All cap[p] mask
+ * bytes of every pair are written; out rows past a pair's inlier count are not
+ * touched.  SIFT_HIP_ERR_INVALID, with nothing launched, for: a null verifier,
+ * pairs, params or results; P < 1 or over the verifier's max_pairs; a cap[p]
+ * outside 0..65536; the caps' sum over the verifier's max_matches; a negative
+ * nq or nt; a stride < 2; a null position pointer on a pair with cap > 0; null
+ * matches with a caps' sum > 0; hypotheses outside 1..max_hypotheses; a
+ * max_error that is not > 0 and finite; out overlapping matches. */
+int sift_hip_verify_fundamental_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                               int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                               int train_stride, const sift_hip_verify_params* params,
+                                               sift_hip_verify_result* results, sift_hip_dmatch* out, int* out_counts,
+                                               uint8_t* mask, void* stream);
+int sift_hip_verify_homography_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                              int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                              int train_stride, const sift_hip_verify_params* params,
+                                              sift_hip_homography_result* results, sift_hip_dmatch* out, int* out_counts,
+                                              uint8_t* mask, void* stream);
+
+/* Synchronous; matches, counts and the positions still live on the device.  P
+ * result records, pair p's results[p].inliers records at row0[p] of out_host
+ * (room for the caps' sum, may be NULL; rows past a pair's inliers are not
+ * written) and the masks (mask_host: the caps' sum bytes, may be NULL) go to
+ * host memory. */
+int sift_hip_verify_fundamental_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                             int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                             const sift_hip_verify_params* params, sift_hip_verify_result* results_host,
+                                             sift_hip_dmatch* out_host, uint8_t* mask_host);
+int sift_hip_verify_homography_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                            int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                            const sift_hip_verify_params* params,
+                                            sift_hip_homography_result* results_host, sift_hip_dmatch* out_host,
+                                            uint8_t* mask_host);
+/* After a batched call sift_hip_verify_hypotheses_host and
+ * sift_hip_verify_homography_hypotheses_host return SIFT_HIP_ERR_STATE (the
+ * scratch holds P pairs' hypotheses) until a single-pair verify call has run. */
+
 /* --- Multi-GPU (the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
 
