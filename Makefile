@@ -38,7 +38,7 @@ $(OUT)/libsift_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS) -ldl -L$(ROCM_LIB) -lrocprofiler-sdk-roctx \
 	    -Wl,-rpath,$(ROCM_LIB) -Wl,-soname,libsift_hip.so
 
-CXX_SRCS := $(SRC)/detector_cxx.cpp $(SRC)/multi_cxx.cpp $(SRC)/verify_cxx.cpp
+CXX_SRCS := $(SRC)/detector_cxx.cpp $(SRC)/multi_cxx.cpp $(SRC)/verify_cxx.cpp $(SRC)/match_batched_cxx.cpp
 
 $(OUT)/libsift_cuda.so: $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	$(CXX) $(CXXFLAGS) -pthread -shared -o $@ $(CXX_SRCS) -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN'

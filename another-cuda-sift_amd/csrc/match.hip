@@ -29,6 +29,9 @@
 //                  a candidate when its Sampson distance to the pair's
 //                  fundamental matrix is within a bound (and it lies in the
 //                  window); a third plane holds the rows' side of that test.
+//  k_match_guided_batch / k_match_epipolar_batch  the two gated kernels with a
+//                  pair dimension: P pairs of one code set per launch, the
+//                  epipolar geometry read from device memory per pair.
 //  k_match_select  match lists: the top-2 arrays of both directions filtered
 //                  (ratio test, distance cap, cross check) and compacted in
 //                  query order into cv::DMatch records, one workgroup per pair.
@@ -1056,6 +1059,80 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_epipolar(  // r
                         MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
 }
 
+// k_match_guided_batch / k_match_epipolar_batch: the two gated kernels with a
+// pair dimension.  grid = (query blocks of 32 QBW NW, splits S of whole key
+// groups, pairs); pair p = blockIdx.z runs match_pair on its rows of the
+// launch's code set, with its own slice of the scratch keys (p * nq_stride) and
+// of the done counters, as k_match_batch does.  The pair's record (kernarg) and
+// everything derived from it are wave-uniform: the strides of a reverse pair
+// are the launch's swapped.  LDS and registers are the single-pair kernels'.
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_guided_batch(  // registers for two workgroups per CU
+    GatedBatch batch, int qstride, int tstride, float radius, int S, int nq_stride, const int8_t* __restrict__ codes,
+    const int* __restrict__ rowkeys, const int8_t* __restrict__ zc, const int* __restrict__ zk,
+    const unsigned* __restrict__ flags, unsigned epoch, unsigned long long* __restrict__ keys,
+    unsigned* __restrict__ done, float ratio, int ratio_on_squared, int* __restrict__ idx2, float* __restrict__ d2out,
+    int* __restrict__ match) {
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ unsigned s_last;
+    const int p = blockIdx.z;
+    const GatedPair& gp = batch.pair[p];
+    const MatchGate g{gp.qxy, gp.txy, gp.swapped ? tstride : qstride, gp.swapped ? qstride : tstride, radius};
+    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, nullptr, &s_last, gp.pr, g,
+                        CodeSet{codes + (size_t)gp.pr.qrow0 * 128, rowkeys + gp.pr.qkrow0},
+                        CodeSet{codes + (size_t)gp.pr.trow0 * 128, rowkeys + gp.pr.tkrow0}, CodeSet{zc, zk}, flags, epoch,
+                        S, keys + 2 * (size_t)p * nq_stride, done + (size_t)p * gridDim.x,
+                        MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
+}
+
+// The epipolar twin reads pair p's nine floats from device memory (geometry +
+// geom * geometry_stride bytes: one wave-uniform load per workgroup, kept in
+// scalar registers), transposed for a reverse pair.  A record that holds a
+// value that is not finite, or nine zeros (the empty verify result), has no
+// candidates: its e2 becomes NaN, which fails every compare of the gate (the
+// device-side rule of include/sift_hip.h; a zero F would otherwise pass every
+// row, 0 <= e2 * 0).
+template <int NW, int QBW>
+__global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void k_match_epipolar_batch(  // registers for two workgroups per CU
+    GatedBatch batch, int qstride, int tstride, float radius, float e2, const char* __restrict__ geometry,
+    int geometry_stride, int S, int nq_stride, const int8_t* __restrict__ codes, const int* __restrict__ rowkeys,
+    const int8_t* __restrict__ zc, const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch,
+    unsigned long long* __restrict__ keys, unsigned* __restrict__ done, float ratio, int ratio_on_squared,
+    int* __restrict__ idx2, float* __restrict__ d2out, int* __restrict__ match) {
+    __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
+    __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_pn[2][kChunkRows];
+    __shared__ unsigned s_last;
+    const int p = blockIdx.z;
+    const GatedPair& gp = batch.pair[p];
+    const unsigned* const G = reinterpret_cast<const unsigned*>(geometry + (size_t)gp.geom * geometry_stride);
+    float f[9];
+    bool usable = true, zero = true;
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+        f[e] = __uint_as_float(__builtin_amdgcn_readfirstlane(G[e]));
+        usable = usable && __builtin_fabsf(f[e]) < INFINITY;
+        zero = zero && f[e] == 0.f;
+    }
+    usable = usable && !zero;
+    EpipolarGate g{gp.qxy, gp.txy, gp.swapped ? tstride : qstride, gp.swapped ? qstride : tstride, radius,
+                   usable ? e2 : NAN, {}};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) g.F[3 * r + c] = gp.swapped ? f[3 * c + r] : f[3 * r + c];
+    match_pair<NW, QBW>(s_codes, s_key, s_px, s_py, s_pn, &s_last, gp.pr, g,
+                        CodeSet{codes + (size_t)gp.pr.qrow0 * 128, rowkeys + gp.pr.qkrow0},
+                        CodeSet{codes + (size_t)gp.pr.trow0 * 128, rowkeys + gp.pr.tkrow0}, CodeSet{zc, zk}, flags, epoch,
+                        S, keys + 2 * (size_t)p * nq_stride, done + (size_t)p * gridDim.x,
+                        MatchOut{ratio, ratio_on_squared, idx2, d2out, match});
+}
+
 // Direct single pairs: 8 waves x 1 query block (256 queries per workgroup),
 // one key group (256 train rows) per split up to kDirectWgTarget workgroups.
 // 2000 x 2000 on detector buffers (tools/match_direct_time.py, two passes):
@@ -1093,6 +1170,38 @@ void launch_match_pair(const MatchPair& pr, const EpipolarGate& gate, const Code
     hipLaunchKernelGGL((k_match_epipolar<kDirectNW, kDirectQBW>), g, b, 0, s, pr, gate, q.codes, q.keys, t.codes, t.keys,
                        sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, S, sc.keys, sc.done, out.ratio,
                        out.ratio_on_squared, out.idx2, out.d2, out.match);
+}
+
+// Gated batches take the direct shape per pair (8 waves x 1 query block: the
+// epipolar body has no registers for a second block) and split each pair's
+// train rows into whole key groups until the launch fills two workgroups per CU
+// of a 256-CU device once.  One pair gets the single-pair kernels' split.
+constexpr int kGatedBatchWgTarget = 512;
+
+int match_gated_splits(int max_nq, int max_nt, int P) {
+    const int ntiles = match_tiles(max_nt), groups = (ntiles + kGroupTiles - 1) / kGroupTiles;
+    const int units = (max(max_nq, 1) + kDirectQB - 1) / kDirectQB * max(P, 1);
+    return GroupSplit(ntiles, max(1, min(groups, kGatedBatchWgTarget / units))).count();
+}
+
+void launch_match_gated(const GatedBatch& batch, const GatedCall& call, const CodeSet& set, const SetFlags& flags,
+                        const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
+    int max_nq = 1, max_nt = 1;
+    for (int p = 0; p < batch.P; p++) {
+        max_nq = max(max_nq, batch.pair[p].pr.nq);
+        max_nt = max(max_nt, batch.pair[p].pr.nt);
+    }
+    const int S = match_gated_splits(max_nq, max_nt, batch.P);
+    const dim3 g((max_nq + kDirectQB - 1) / kDirectQB, S, batch.P), b(64 * kDirectNW);
+    if (call.geometry)
+        hipLaunchKernelGGL((k_match_epipolar_batch<kDirectNW, kDirectQBW>), g, b, 0, s, batch, call.qstride, call.tstride,
+                           call.radius, call.e2, reinterpret_cast<const char*>(call.geometry), call.geometry_stride, S,
+                           sc.nq_stride, set.codes, set.keys, sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch,
+                           sc.keys, sc.done, out.ratio, out.ratio_on_squared, out.idx2, out.d2, out.match);
+    else
+        hipLaunchKernelGGL((k_match_guided_batch<kDirectNW, kDirectQBW>), g, b, 0, s, batch, call.qstride, call.tstride,
+                           call.radius, S, sc.nq_stride, set.codes, set.keys, sc.zero.codes, sc.zero.keys, flags.flags,
+                           flags.epoch, sc.keys, sc.done, out.ratio, out.ratio_on_squared, out.idx2, out.d2, out.match);
 }
 
 void launch_match_prep(const MatchSets& sets, int8_t* codes, int* rowkeys, const SetFlags& flags, hipStream_t s) {

@@ -681,6 +681,273 @@ int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, i
     return guided_list_host(m, q, nq, t, nt, EpipolarGates(*gate), filter, out_host, cap, count);
 }
 
+}  // extern "C"
+
+// --- Batched guided matching ------------------------------------------------------
+static_assert(sizeof(sift_hip_match_positions) == 2 * sizeof(void*), "two device pointers per pair");
+
+namespace {
+
+// The call-wide rules of a gated batch, which need no matcher: the position fields, then under the epipolar gate
+// (epipolar: geometry, its stride and max_error are looked at) the geometry's.  The nine floats themselves are on the
+// device: the kernel applies the usable-geometry rule to them.
+int check_gated_call(bool epipolar, int query_stride, int train_stride, float radius, const void* geometry,
+                     int geometry_stride, float max_error) {
+    const char* what = epipolar ? "epipolar gate" : "match gate";
+    if (int rc = check_gate_positions(what, query_stride, train_stride, radius)) return rc;
+    if (!epipolar) return SIFT_HIP_OK;
+    if (!(max_error > 0.f) || !std::isfinite(max_error))
+        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: max_error must be > 0 and finite");
+    if (!geometry) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: null geometry");
+    if (geometry_stride < 36 || geometry_stride % 4)
+        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: geometry_stride_bytes must be >= 36 and a multiple of 4");
+    return SIFT_HIP_OK;
+}
+
+// ... then the matcher's and the pairs'.
+int check_gated_pairs(bool epipolar, const sift_hip_matcher* m, int P, const int* nq, const int* nt,
+                      const sift_hip_match_positions* positions) {
+    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
+    if (P <= 0 || P > m->maxP || !nq || !nt || !positions) return fail(SIFT_HIP_ERR_INVALID, "bad gated batch");
+    for (int p = 0; p < P; p++) {
+        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
+            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
+        if ((nq[p] && !positions[p].query_xy) || (nt[p] && !positions[p].train_xy))
+            return fail(SIFT_HIP_ERR_INVALID,
+                        std::string(epipolar ? "epipolar gate" : "match gate") + ": null position pointer");
+    }
+    return SIFT_HIP_OK;
+}
+
+// A gated call as the launcher takes it; e2 = max_error^2 is formed here, one float32 product.
+GatedCall gated_call(bool epipolar, int query_stride, int train_stride, float radius, const void* geometry,
+                     int geometry_stride, float max_error) {
+    return GatedCall{query_stride, train_stride, radius, epipolar ? max_error * max_error : 0.f,
+                     epipolar ? geometry : nullptr, epipolar ? geometry_stride : 0};
+}
+
+// The pairs of a call: the forward pairs [0, P) with their rows at sum_{r<p} nq[r], and -- when a filter needs them --
+// the reverse pairs [P, 2P) with the roles swapped, rows at sum nq + sum_{r<p} nt[r] (select_lists' layout).
+struct GatedPairs {
+    GatedPair pair[2 * kMaxMatchPairs];
+    void fill(int P, bool rev, const sift_hip_match_positions* pos) {
+        int totq = 0;
+        for (int p = 0; p < P; p++) totq += pair[p].pr.nq;
+        int fwd = 0, roff = totq;
+        for (int p = 0; p < P; p++) {
+            GatedPair& f = pair[p];
+            f.pr.out_off = fwd;
+            f.qxy = pos[p].query_xy, f.txy = pos[p].train_xy, f.geom = p, f.swapped = 0;
+            fwd += f.pr.nq;
+            if (!rev) continue;
+            const MatchPair& a = f.pr;
+            pair[P + p] = GatedPair{MatchPair{a.t, a.q, a.nt, a.nq, roff, a.tset, a.qset, a.trow0, a.qrow0, a.tkrow0,
+                                              a.qkrow0},
+                                    f.txy, f.qxy, p, 1};
+            roff += a.nt;
+        }
+    }
+};
+
+// Whether a call has an output row to write at all (a query without train rows still gets its -1 / FLT_MAX row).
+bool any_rows(int P, const int* nq, const int* nt, bool rev) {
+    for (int p = 0; p < P; p++)
+        if (nq[p] > 0 || (rev && nt[p] > 0)) return true;
+    return false;
+}
+
+// n pairs in launches of at most kMaxGatedPairs, ordered on the stream (the scratch is restored when each ends).
+int launch_gated(sift_hip_matcher* m, const GatedPair* pairs, int n, const GatedCall& call, const CodeSet& set,
+                 const SetFlags& flags, const MatchOut& out, hipStream_t stream) {
+    for (int p0 = 0; p0 < n; p0 += kMaxGatedPairs) {
+        GatedBatch b{};
+        b.P = std::min(kMaxGatedPairs, n - p0);
+        std::copy(pairs + p0, pairs + p0 + b.P, b.pair);
+        launch_match_gated(b, call, set, flags, m->scratch(), out, stream);
+        HIPCHK(hipGetLastError());
+    }
+    return SIFT_HIP_OK;
+}
+
+// Forward pairs, and with `rev` the reverse pairs: in one pass over 2P pairs when the matcher holds that many,
+// else in two of P.  The bytes are the same either way.
+int launch_gated_directions(sift_hip_matcher* m, const GatedPairs& g, int P, bool rev, const GatedCall& call,
+                            const CodeSet& set, const SetFlags& flags, const MatchOut& out, hipStream_t stream) {
+    if (rev && 2 * P <= m->maxP) return launch_gated(m, g.pair, 2 * P, call, set, flags, out, stream);
+    if (int rc = launch_gated(m, g.pair, P, call, set, flags, out, stream)) return rc;
+    return rev ? launch_gated(m, g.pair + P, P, call, set, flags, out, stream) : SIFT_HIP_OK;
+}
+
+// fp16 sets: always converted (k_match_prep, distinct sets once, as sift_hip_match_batched does for P > 1), then the
+// gated launches on the prepared codes with their flags.  Arguments are checked by the caller.
+int gated_batch_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
+                     const int* nt, const sift_hip_match_positions* pos, bool rev, const GatedCall& call,
+                     const MatchOut& out, hipStream_t stream) {
+    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "bad gated batch");
+    for (int p = 0; p < P; p++)
+        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
+    if (!any_rows(P, nq, nt, rev)) return SIFT_HIP_OK;
+    MatchSets sets{};
+    auto set_of = [&](const uint16_t* ptr, int n) {
+        for (int k = 0; k < sets.nsets; k++)
+            if (sets.set[k].src == ptr) {
+                sets.set[k].n = std::max(sets.set[k].n, n);
+                return k;
+            }
+        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
+        return sets.nsets++;
+    };
+    GatedPairs g{};
+    for (int p = 0; p < P; p++) {
+        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
+        g.pair[p].pr = MatchPair{q[p], t[p], nq[p], nt[p], 0, qs, ts, 0, 0, 0, 0};
+    }
+    long row = 0;
+    for (int k = 0; k < sets.nsets; k++) {
+        sets.set[k].row0 = (int)row;
+        row += sets.set[k].n;
+        sets.maxn = std::max(sets.maxn, sets.set[k].n);
+    }
+    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
+    for (int p = 0; p < P; p++) {
+        MatchPair& pr = g.pair[p].pr;
+        pr.qrow0 = pr.qkrow0 = sets.set[pr.qset].row0;
+        pr.trow0 = pr.tkrow0 = sets.set[pr.tset].row0;
+    }
+    g.fill(P, rev, pos);
+    const SetFlags flags = m->next_epoch();
+    HIPCHK(hipSetDevice(m->device));
+    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
+    HIPCHK(hipGetLastError());
+    return launch_gated_directions(m, g, P, rev, call, CodeSet{m->dCodes, m->dRowKeys}, flags, out, stream);
+}
+
+// Ready code sets (sift_hip_match_list_codes_batched's arguments): no conversion, no flags.
+int gated_batch_codes(sift_hip_matcher* m, const int8_t* codes, const int* keys, int P, const int* qrow0,
+                      const int* qkey0, const int* nq, const int* trow0, const int* tkey0, const int* nt,
+                      const sift_hip_match_positions* pos, bool rev, const GatedCall& call, const MatchOut& out,
+                      hipStream_t stream) {
+    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
+    for (int p = 0; p < P; p++)
+        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
+            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
+    if (!any_rows(P, nq, nt, rev)) return SIFT_HIP_OK;
+    GatedPairs g{};
+    for (int p = 0; p < P; p++)
+        g.pair[p].pr = MatchPair{nullptr, nullptr, nq[p], nt[p], 0, 0, 0, qrow0[p], trow0[p], qkey0[p], tkey0[p]};
+    g.fill(P, rev, pos);
+    HIPCHK(hipSetDevice(m->device));
+    return launch_gated_directions(m, g, P, rev, call, CodeSet{codes, keys}, kNoFlags, out, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_hip_match_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                  const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
+                                  int query_stride, int train_stride, float radius, float ratio, int ratio_on_squared,
+                                  int* idx2, float* d2, int* match, void* stream) {
+    if (int rc = check_gated_call(false, query_stride, train_stride, radius, nullptr, 0, 0.f)) return rc;
+    if (int rc = check_gated_pairs(false, m, P, nq, nt, positions)) return rc;
+    return gated_batch_fp16(m, P, q, nq, t, nt, positions, false,
+                            gated_call(false, query_stride, train_stride, radius, nullptr, 0, 0.f),
+                            MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
+}
+
+int sift_hip_match_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                    const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
+                                    int query_stride, int train_stride, float radius, const void* geometry,
+                                    int geometry_stride_bytes, float max_error, float ratio, int ratio_on_squared,
+                                    int* idx2, float* d2, int* match, void* stream) {
+    if (int rc = check_gated_call(true, query_stride, train_stride, radius, geometry, geometry_stride_bytes, max_error))
+        return rc;
+    if (int rc = check_gated_pairs(true, m, P, nq, nt, positions)) return rc;
+    return gated_batch_fp16(m, P, q, nq, t, nt, positions, false,
+                            gated_call(true, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
+                                       max_error),
+                            MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The four list forms: the gated top-2 of the directions the filter needs into the select scratch, then the filter
+// and the compaction (select_lists: sift_hip_match_list_batched's layout, imgIdx = p, counts on the device).
+template <class Top2>
+int gated_list(bool epipolar, sift_hip_matcher* m, int P, const int* nq, const int* nt,
+               const sift_hip_match_positions* positions, int query_stride, int train_stride, float radius,
+               const void* geometry, int geometry_stride, float max_error, const sift_hip_match_filter* filter,
+               sift_hip_dmatch* out, int* counts, hipStream_t stream, Top2 top2) {
+    if (int rc = check_gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error))
+        return rc;
+    if (int rc = check_gated_pairs(epipolar, m, P, nq, nt, positions)) return rc;
+    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
+    if (int rc = ensure_select_scratch(m)) return rc;
+    const GatedCall call = gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error);
+    if (int rc = top2(needs_reverse(*filter), call, MatchOut{0.f, 0, m->dSelIdx, m->dSelD, nullptr})) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    return select_lists(m, P, nq, nt, *filter, out, counts, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_hip_match_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                       const uint16_t* const* t, const int* nt,
+                                       const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                       float radius, const sift_hip_match_filter* filter, sift_hip_dmatch* out,
+                                       int* counts, void* stream) {
+    return gated_list(false, m, P, nq, nt, positions, query_stride, train_stride, radius, nullptr, 0, 0.f, filter, out,
+                      counts, (hipStream_t)stream, [&](bool rev, const GatedCall& call, const MatchOut& o) {
+                          return gated_batch_fp16(m, P, q, nq, t, nt, positions, rev, call, o, (hipStream_t)stream);
+                      });
+}
+
+int sift_hip_match_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                         const uint16_t* const* t, const int* nt,
+                                         const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                         float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                         const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
+                                         void* stream) {
+    return gated_list(true, m, P, nq, nt, positions, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
+                      max_error, filter, out, counts, (hipStream_t)stream,
+                      [&](bool rev, const GatedCall& call, const MatchOut& o) {
+                          return gated_batch_fp16(m, P, q, nq, t, nt, positions, rev, call, o, (hipStream_t)stream);
+                      });
+}
+
+int sift_hip_match_list_guided_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                             const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                             const int* tkey0, const int* nt,
+                                             const sift_hip_match_positions* positions, int query_stride,
+                                             int train_stride, float radius, const sift_hip_match_filter* filter,
+                                             sift_hip_dmatch* out, int* counts, void* stream) {
+    return gated_list(false, m, P, nq, nt, positions, query_stride, train_stride, radius, nullptr, 0, 0.f, filter, out,
+                      counts, (hipStream_t)stream, [&](bool rev, const GatedCall& call, const MatchOut& o) {
+                          return gated_batch_codes(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, positions, rev,
+                                                   call, o, (hipStream_t)stream);
+                      });
+}
+
+int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                               const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                               const int* tkey0, const int* nt,
+                                               const sift_hip_match_positions* positions, int query_stride,
+                                               int train_stride, float radius, const void* geometry,
+                                               int geometry_stride_bytes, float max_error,
+                                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
+                                               void* stream) {
+    return gated_list(true, m, P, nq, nt, positions, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
+                      max_error, filter, out, counts, (hipStream_t)stream,
+                      [&](bool rev, const GatedCall& call, const MatchOut& o) {
+                          return gated_batch_codes(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, positions, rev,
+                                                   call, o, (hipStream_t)stream);
+                      });
+}
+
 int sift_hip_device_count(int* n) {
     if (!n) return fail(SIFT_HIP_ERR_INVALID, "null argument");
     if (hipGetDeviceCount(n) != hipSuccess) *n = 0;

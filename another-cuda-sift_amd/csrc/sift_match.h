@@ -145,6 +145,47 @@ void launch_match_pair(const MatchPair& pr, const MatchGate* gate, const CodeSet
 void launch_match_pair(const MatchPair& pr, const EpipolarGate& gate, const CodeSet& q, const CodeSet& t,
                        const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s);
 
+// --- Gated batches (sift_hip_match_*_guided_batched / *_epipolar_batched): pairs of code sets under a gate in one
+// launch (k_match_guided_batch, k_match_epipolar_batch).
+//
+// Pair p of a gated launch: the pair as k_match_batch takes it (rows of the launch's code set, its fp16 rows for the
+// general path) and the two position arrays of its direction.  swapped marks the reverse direction of a cross check:
+// the pair reads the launch's strides swapped and, under the epipolar gate, its geometry transposed; geom is the
+// index of its geometry record (a reverse pair shares its forward pair's).
+struct GatedPair {
+    MatchPair pr;
+    const float* qxy;
+    const float* txy;
+    int geom, swapped;
+};
+static_assert(sizeof(GatedPair) == 80, "kernarg layout");
+
+// Passed by value, like MatchBatch, so a launch holds at most kMaxGatedPairs pairs (32 x 80 B = 2.5 KiB of kernarg
+// beside the other arguments; 64 would not fit the 4 KiB segment).  A call of more pairs is several launches ordered
+// on the stream: the scratch is restored when each ends, and the bytes do not depend on the cut.
+constexpr int kMaxGatedPairs = 32;
+struct GatedBatch {
+    GatedPair pair[kMaxGatedPairs];
+    int P;
+};
+
+// What is uniform over a gated call: the strides of the forward direction, the radius, and under the epipolar gate
+// e2 = max_error * max_error (formed on the host) and the geometry records in device memory -- pair p's nine floats
+// at geometry + geom * geometry_stride bytes, read by the kernel and never by the host.  geometry == nullptr: the
+// window gate.
+struct GatedCall {
+    int qstride, tstride;
+    float radius, e2;
+    const void* geometry;
+    int geometry_stride;
+};
+
+// The pairs of `batch` on rows of `set` (what launch_match_prep wrote, with its flags, or ready codes without), S =
+// match_gated_splits(max nq, max nt, batch.P) splits.
+int match_gated_splits(int max_nq, int max_nt, int P);
+void launch_match_gated(const GatedBatch& batch, const GatedCall& call, const CodeSet& set, const SetFlags& flags,
+                        const MatchScratch& sc, const MatchOut& out, hipStream_t s);
+
 // --- Match lists (sift_hip_match_list_*): filter + ordered compaction of the
 // top-2 arrays the launchers above wrote (k_match_select).
 //

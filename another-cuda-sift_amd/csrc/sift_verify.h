@@ -102,4 +102,19 @@ void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, c
 void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,
                                hipStream_t s);
 
+// k_project_homography_batch: the same for P sets in one launch, pair p =
+// blockIdx.y with the matrix at geometry + p * geometry_stride bytes (device)
+// and its own rows; the strides are the call's.  By value, as VerifyBatch is.
+struct ProjectPair {
+    const float* xy;
+    float* out;
+    int n;
+};
+struct ProjectBatch {
+    ProjectPair pair[kVerifyMaxPairs];
+    int P, max_n;
+};
+void launch_project_homography_batched(const void* geometry, int geometry_stride, const ProjectBatch& batch, int stride,
+                                       int out_stride, hipStream_t s);
+
 }  // namespace sift_amd

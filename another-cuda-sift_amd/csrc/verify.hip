@@ -594,6 +594,27 @@ __global__ __launch_bounds__(256) void k_project_homography(const float* H, cons
     out[(size_t)i * out_stride + 1] = front ? py / w : NAN;
 }
 
+// The same rows rule for pair blockIdx.y of a batch: its matrix from its geometry record, its own rows.
+__global__ __launch_bounds__(256) void k_project_homography_batch(const char* geometry, int geometry_stride,
+                                                                  ProjectBatch batch, int stride, int out_stride) {
+#pragma clang fp contract(off)
+    const int p = blockIdx.y;
+    const ProjectPair pr = batch.pair[p];
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)pr.n) return;
+    const float* H = reinterpret_cast<const float*>(geometry + (size_t)p * geometry_stride);
+    float h[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) h[e] = H[e];
+    const float x = pr.xy[(size_t)i * stride], y = pr.xy[(size_t)i * stride + 1];
+    const float px = (h[0] * x + h[1] * y) + h[2];
+    const float py = (h[3] * x + h[4] * y) + h[5];
+    const float w = (h[6] * x + h[7] * y) + h[8];
+    const bool front = w > 0.f;
+    pr.out[(size_t)i * out_stride] = front ? px / w : NAN;
+    pr.out[(size_t)i * out_stride + 1] = front ? py / w : NAN;
+}
+
 void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s) {
     if (in.cap > 0)
         hipLaunchKernelGGL(k_verify_gather<VerifyInput>, dim3((in.cap + 255) / 256), dim3(256), 0, s, in, pts);
@@ -673,6 +694,14 @@ void launch_project_homography(const float* H, const float* xy, int stride, int 
     if (n > 0)
         hipLaunchKernelGGL(k_project_homography, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, s, H, xy, stride,
                            n, out, out_stride);
+}
+
+void launch_project_homography_batched(const void* geometry, int geometry_stride, const ProjectBatch& batch, int stride,
+                                       int out_stride, hipStream_t s) {
+    if (batch.max_n > 0)
+        hipLaunchKernelGGL(k_project_homography_batch, dim3((unsigned)(((size_t)batch.max_n + 255) / 256), batch.P),
+                           dim3(256), 0, s, reinterpret_cast<const char*>(geometry), geometry_stride, batch, stride,
+                           out_stride);
 }
 
 }  // namespace sift_amd

@@ -409,4 +409,34 @@ int sift_hip_project_homography_device(const float* H, const float* xy, int stri
     return SIFT_HIP_OK;
 }
 
+int sift_hip_project_homography_batched_device(const void* geometry, int geometry_stride_bytes, int P,
+                                               const sift_hip_project_set* sets, int stride, int out_stride,
+                                               void* stream) {
+    if (!geometry) return fail(SIFT_HIP_ERR_INVALID, "project: null geometry");
+    if (geometry_stride_bytes < 36 || geometry_stride_bytes % 4)
+        return fail(SIFT_HIP_ERR_INVALID, "project: geometry_stride_bytes must be >= 36 and a multiple of 4");
+    if (P <= 0 || P > kVerifyMaxPairs || !sets) return fail(SIFT_HIP_ERR_INVALID, "project: bad batch");
+    if (stride < 2 || out_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "project: a position stride below 2 floats");
+    ProjectBatch b{};
+    b.P = P;
+    for (int p = 0; p < P; p++) {
+        const int n = sets[p].n;
+        if (n < 0) return fail(SIFT_HIP_ERR_INVALID, "project: a negative row count");
+        b.pair[p] = ProjectPair{sets[p].xy, sets[p].out_xy, n};
+        b.max_n = std::max(b.max_n, n);
+        if (n == 0) continue;
+        if (!sets[p].xy || !sets[p].out_xy) return fail(SIFT_HIP_ERR_INVALID, "project: null position pointer");
+        // Per pair as in the single call: in place (the same rows) or apart.
+        const uintptr_t ib = (uintptr_t)sets[p].xy, ob = (uintptr_t)sets[p].out_xy;
+        const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
+        const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
+        if (!(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes))
+            return fail(SIFT_HIP_ERR_INVALID, "project: out_xy overlaps xy (only out_xy == xy with equal strides may)");
+    }
+    if (b.max_n == 0) return SIFT_HIP_OK;
+    launch_project_homography_batched(geometry, geometry_stride_bytes, b, stride, out_stride, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
 }  // extern "C"

@@ -223,4 +223,17 @@ void projectHomographyDevice(const float* H, const float* xy, int stride, int n,
                 "projectHomographyDevice");
 }
 
+static_assert(sizeof(ProjectSet) == sizeof(sift_hip_project_set) &&
+                  offsetof(ProjectSet, n) == offsetof(sift_hip_project_set, n) &&
+                  offsetof(ProjectSet, out_xy) == offsetof(sift_hip_project_set, out_xy),
+              "sift_cuda::ProjectSet is sift_hip_project_set");
+
+void projectHomographyBatchedDevice(const void* geometry, int geometry_stride_bytes, const std::vector<ProjectSet>& sets,
+                                    int stride, int out_stride, void* stream) {
+    check_throw(sift_hip_project_homography_batched_device(geometry, geometry_stride_bytes, (int)sets.size(),
+                                                           reinterpret_cast<const sift_hip_project_set*>(sets.data()),
+                                                           stride, out_stride, stream),
+                "projectHomographyBatchedDevice");
+}
+
 }  // namespace sift_cuda

@@ -105,6 +105,16 @@ def _epipolar_gate(q_xy_ptr: int, q_stride: int, t_xy_ptr: int, t_stride: int, r
                               (ctypes.c_float * 9)(*f.tolist()), max_error)
 
 
+class _MatchPositions(ctypes.Structure):
+    """sift_hip_match_positions: pair p's device position rows in a batched gated call."""
+    _fields_ = [("query_xy", ctypes.c_void_p), ("train_xy", ctypes.c_void_p)]
+
+
+class _ProjectSet(ctypes.Structure):
+    """sift_hip_project_set: one set of sift_hip_project_homography_batched_device."""
+    _fields_ = [("xy", ctypes.c_void_p), ("n", ctypes.c_int), ("out_xy", ctypes.c_void_p)]
+
+
 class _MatchFilter(ctypes.Structure):
     _fields_ = [
         ("ratio", ctypes.c_float),
@@ -280,6 +290,21 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.POINTER(_MatchFilter), vp, vp, vp]),
         "sift_hip_match_list_epipolar_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate),
                                                   ctypes.POINTER(_MatchFilter), vp, i, ip]),
+        "sift_hip_match_guided_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f, f, i, vp,
+                                              vp, vp, vp]),
+        "sift_hip_match_epipolar_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f, vp, i, f,
+                                                f, i, vp, vp, vp, vp]),
+        "sift_hip_match_list_guided_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f,
+                                                   ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_epipolar_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f, vp,
+                                                     i, f, ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_guided_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp,
+                                                         ctypes.POINTER(_MatchPositions), i, i, f,
+                                                         ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_list_epipolar_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp,
+                                                           ctypes.POINTER(_MatchPositions), i, i, f, vp, i, f,
+                                                           ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_project_homography_batched_device": (i, [vp, i, i, ctypes.POINTER(_ProjectSet), i, i, vp]),
         "sift_hip_default_verify_params": (None, [ctypes.POINTER(_VerifyParams)]),
         "sift_hip_verifier_create": (i, [i, i, i, ctypes.POINTER(vp)]),
         "sift_hip_verifier_destroy": (i, [vp]),
@@ -984,6 +1009,100 @@ class Matcher:
                                                        _ptr(out), len(out), ctypes.byref(n)), "match_list_epipolar_host")
         return out[: n.value]
 
+    # --- batched guided matching: both gates for all pairs of a batch in one pass (the rule: include/sift_hip.h).
+    # positions: per pair (q_xy_ptr, nq, t_xy_ptr, nt) as multi.position_pairs returns them, or (q_xy_ptr, t_xy_ptr);
+    # the strides and the radius are the call's.  Under the epipolar gate geometry_ptr is DEVICE memory: pair p's nine
+    # floats at geometry_ptr + p * geometry_stride bytes -- with the default stride, 52, the VERIFY_RESULT_DTYPE
+    # records of Verifier.verify_batched_device as they lie.  A pair whose record is not usable
+    # (sift_amd.cv.geometry_usable: a non-finite entry, or all zero) has no candidates.  Outputs are laid out as
+    # match_batched's / match_list_batched's.
+
+    @staticmethod
+    def _positions(positions: Sequence, P: int):
+        if len(positions) != P:
+            raise ValueError("one position pair per pair of sets")
+        rec = [(p[0], p[2]) if len(p) == 4 else (p[0], p[1]) for p in positions]
+        return (_MatchPositions * max(P, 1))(*[_MatchPositions(a or None, b or None) for a, b in rec])
+
+    @staticmethod
+    def _sets(q_ptrs, nqs, t_ptrs, nts):
+        P = len(q_ptrs)
+        return (P, (ctypes.c_void_p * P)(*q_ptrs), (ctypes.c_int * P)(*nqs), (ctypes.c_void_p * P)(*t_ptrs),
+                (ctypes.c_int * P)(*nts))
+
+    def match_guided_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int], nts: Sequence[int],
+                             positions: Sequence, radius: float, q_stride: int = 3, t_stride: int = 3,
+                             ratio: float = 0.8, ratio_on_squared: bool = False, idx2_ptr: int = 0, d2_ptr: int = 0,
+                             match_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """match_batched under the window gate (sift_hip_match_guided_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_guided_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P), q_stride,
+                                                   t_stride, radius, ratio, int(ratio_on_squared), idx2_ptr or None,
+                                                   d2_ptr or None, match_ptr or None, stream), "match_guided_batched")
+
+    def match_epipolar_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                               nts: Sequence[int], positions: Sequence, geometry_ptr: int, max_error: float,
+                               radius: float = float("inf"), geometry_stride: int = 52, q_stride: int = 3,
+                               t_stride: int = 3, ratio: float = 0.8, ratio_on_squared: bool = False, idx2_ptr: int = 0,
+                               d2_ptr: int = 0, match_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """match_batched under the epipolar gate, F read on the device (sift_hip_match_epipolar_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_epipolar_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P), q_stride,
+                                                     t_stride, radius, geometry_ptr or None, geometry_stride, max_error,
+                                                     ratio, int(ratio_on_squared), idx2_ptr or None, d2_ptr or None,
+                                                     match_ptr or None, stream), "match_epipolar_batched")
+
+    def match_list_guided_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                  nts: Sequence[int], positions: Sequence, radius: float, out_ptr: int, counts_ptr: int,
+                                  q_stride: int = 3, t_stride: int = 3, stream: Optional[int] = None, **filter) -> None:
+        """match_list_batched under the window gate (sift_hip_match_list_guided_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_guided_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                        q_stride, t_stride, radius, ctypes.byref(f), out_ptr or None,
+                                                        counts_ptr or None, stream), "match_list_guided_batched")
+
+    def match_list_epipolar_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                    nts: Sequence[int], positions: Sequence, geometry_ptr: int, max_error: float,
+                                    out_ptr: int, counts_ptr: int, radius: float = float("inf"),
+                                    geometry_stride: int = 52, q_stride: int = 3, t_stride: int = 3,
+                                    stream: Optional[int] = None, **filter) -> None:
+        """match_list_batched under the epipolar gate (sift_hip_match_list_epipolar_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_epipolar_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                          q_stride, t_stride, radius, geometry_ptr or None,
+                                                          geometry_stride, max_error, ctypes.byref(f), out_ptr or None,
+                                                          counts_ptr or None, stream), "match_list_epipolar_batched")
+
+    def match_list_guided_codes_batched(self, codes_ptr: int, keys_ptr: int, pairs: Sequence, positions: Sequence,
+                                        radius: float, out_ptr: int, counts_ptr: int, q_stride: int = 3,
+                                        t_stride: int = 3, stream: Optional[int] = None, **filter) -> None:
+        """match_list_codes_batched under the window gate: pairs as multi.code_pairs, positions as
+        multi.position_pairs return them (sift_hip_match_list_guided_codes_batched)."""
+        P = len(pairs)
+        qr, qk, nq, tr, tk, nt = ((ctypes.c_int * P)(*[p[k] for p in pairs]) for k in range(6))
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_guided_codes_batched(self._m, codes_ptr, keys_ptr, P, qr, qk, nq, tr, tk, nt,
+                                                              self._positions(positions, P), q_stride, t_stride, radius,
+                                                              ctypes.byref(f), out_ptr or None, counts_ptr or None,
+                                                              stream), "match_list_guided_codes_batched")
+
+    def match_list_epipolar_codes_batched(self, codes_ptr: int, keys_ptr: int, pairs: Sequence, positions: Sequence,
+                                          geometry_ptr: int, max_error: float, out_ptr: int, counts_ptr: int,
+                                          radius: float = float("inf"), geometry_stride: int = 52, q_stride: int = 3,
+                                          t_stride: int = 3, stream: Optional[int] = None, **filter) -> None:
+        """match_list_codes_batched under the epipolar gate (sift_hip_match_list_epipolar_codes_batched)."""
+        P = len(pairs)
+        qr, qk, nq, tr, tk, nt = ((ctypes.c_int * P)(*[p[k] for p in pairs]) for k in range(6))
+        f = _match_filter(**filter)
+        _check(lib().sift_hip_match_list_epipolar_codes_batched(self._m, codes_ptr, keys_ptr, P, qr, qk, nq, tr, tk, nt,
+                                                                self._positions(positions, P), q_stride, t_stride,
+                                                                radius, geometry_ptr or None, geometry_stride,
+                                                                max_error, ctypes.byref(f), out_ptr or None,
+                                                                counts_ptr or None, stream),
+               "match_list_epipolar_codes_batched")
+
 
 _default_matcher: Optional[Matcher] = None
 
@@ -1315,6 +1434,62 @@ def project_homography_device(H_ptr: int, xy_ptr: int, n: int, out_ptr: int, str
     strides."""
     _check(lib().sift_hip_project_homography_device(H_ptr or None, xy_ptr or None, stride, n, out_ptr or None, out_stride,
                                                     stream), "project_homography_device")
+
+
+def project_homography_batched_device(geometry_ptr: int, sets: Sequence, stride: int = 3, out_stride: int = 2,
+                                      geometry_stride: int = 52, stream: Optional[int] = None) -> None:
+    """project_homography_device for len(sets) sets in one launch (sift_hip_project_homography_batched_device): set p
+    = (xy_ptr, n, out_ptr) goes through the 9 device floats at geometry_ptr + p * geometry_stride bytes -- with the
+    default stride the HOMOGRAPHY_RESULT_DTYPE records of Verifier.verify_homography_batched_device as they lie."""
+    P = len(sets)
+    table = (_ProjectSet * max(P, 1))(*[_ProjectSet(s[0] or None, s[1], s[2] or None) for s in sets])
+    _check(lib().sift_hip_project_homography_batched_device(geometry_ptr or None, geometry_stride, P, table, stride,
+                                                            out_stride, stream), "project_homography_batched_device")
+
+
+def _match_list_gated_batched(desc_per_pair, xy_per_pair, run):
+    if len(desc_per_pair) != len(xy_per_pair):
+        raise ValueError("one (des_xy, src_xy) per (des, src)")
+    P = len(desc_per_pair)
+    if P == 0:
+        return []
+    des = [[np.ascontiguousarray(np.asarray(a, np.float16).reshape(-1, 128)) for a in qt] for qt in desc_per_pair]
+    xy = [[np.ascontiguousarray(np.asarray(a, np.float32)[:, :2]) for a in qt] for qt in xy_per_pair]
+    cap = max(max(len(a) for ds in des for a in ds), 1)
+    m = Matcher(cap, cap, max_pairs=2 * P if 2 * P <= 64 else P)
+    dd = [[DeviceArray.from_numpy(a) for a in ds] for ds in des]
+    dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
+    nqs, nts = [len(ds[0]) for ds in des], [len(ds[1]) for ds in des]
+    out, counts = DeviceArray(DMATCH_DTYPE.itemsize * max(sum(nqs), 1)), DeviceArray(4 * P)
+    run(m, [d[0].value if n else 0 for d, n in zip(dd, nqs)], nqs, [d[1].value if n else 0 for d, n in zip(dd, nts)], nts,
+        [(a.value, b.value) for a, b in dxy], out.value, counts.value)
+    _check(lib().sift_hip_device_sync(), "device_sync")
+    rec, cnt = out.to_numpy(DMATCH_DTYPE, max(sum(nqs), 1)), counts.to_numpy(np.int32, P)
+    row0 = np.concatenate([[0], np.cumsum(nqs)]).astype(int)
+    return [rec[row0[p]: row0[p] + cnt[p]].copy() for p in range(P)]
+
+
+def matchListGuidedBatched(desc_per_pair: Sequence, xy_per_pair: Sequence, radius: float, **filter) -> list:
+    """matchListGuided for P pairs in one pass, on host arrays: desc_per_pair[p] = (des, src) descriptor rows (n x 128,
+    converted to float16), xy_per_pair[p] = (des_xy, src_xy) float rows with x, y first.  A list of DMATCH_DTYPE arrays
+    (imgIdx = p), pair p what matchListGuided gives on it.  `filter` keywords as matchList."""
+    return _match_list_gated_batched(
+        desc_per_pair, xy_per_pair,
+        lambda m, q, nq, t, nt, pos, out, counts: m.match_list_guided_batched(q, nq, t, nt, pos, radius, out, counts, 2, 2,
+                                                                              **filter))
+
+
+def matchListEpipolarBatched(desc_per_pair: Sequence, xy_per_pair: Sequence, F_per_pair: Sequence, max_error: float,
+                             radius: float = float("inf"), **filter) -> list:
+    """matchListEpipolar for P pairs in one pass, on host arrays as matchListGuidedBatched takes them; F_per_pair[p]:
+    pair p's 9 floats (uploaded here; a pair whose F is not cv.geometry_usable gets an empty list)."""
+    F = np.ascontiguousarray(np.asarray(F_per_pair, np.float32).reshape(len(desc_per_pair), 9))
+    dF = DeviceArray.from_numpy(F)
+    return _match_list_gated_batched(
+        desc_per_pair, xy_per_pair,
+        lambda m, q, nq, t, nt, pos, out, counts: m.match_list_epipolar_batched(q, nq, t, nt, pos, dF.value, max_error,
+                                                                                out, counts, radius, 36, 2, 2,
+                                                                                **filter))
 
 
 def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src: int) -> np.ndarray:

@@ -183,6 +183,18 @@ def epipolar_mask(q_xy, t_xy, F, max_error, radius=np.inf) -> np.ndarray:
     return band & gate_mask(q, t, radius)
 
 
+def geometry_usable(F) -> bool:
+    """The device-side rule of the batched epipolar calls (include/sift_hip.h): a pair's nine floats are usable when
+    every one is finite and not all are zero (-0 counts as zero).  The single-pair calls refuse an F that fails this
+    on the host; a batched call reads F on the device, where a pair that fails it has no candidates at all -- every
+    query -1 / FLT_MAX, an empty list -- instead of epipolar_mask's formula (under which a zero F passes every row).
+    The empty verify result (hypothesis = -1, F all zero) is the case it exists for."""
+    f = np.asarray(F, np.float32).reshape(-1)
+    if f.size != 9:
+        raise ValueError("F must have 9 entries (3 x 3, row-major)")
+    return bool(np.isfinite(f).all() and (f != 0).any())
+
+
 def mask_top2(q, t, cand):
     """The top-2 of a candidate mask: (idx2, d2), (nq, 2) int32 / float32 laid out as match_device writes them -- the
     two nearest rows of t among cand[i] for every row i of q, ties to the lower train index, -1 / FLT_MAX where there

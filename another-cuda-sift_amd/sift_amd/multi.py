@@ -151,7 +151,9 @@ def position_pairs(gathered_xy: torch.Tensor, counts: Sequence[int], rank: int,
     (world, n, c) float32 tensor of all-gathered position rows (x, y first;
     all_gather_rows carries them), with c the position stride of the call.  With
     cap = nq per pair the rows of Matcher.match_list_codes_batched's output are
-    the verifier's input as they lie."""
+    the verifier's input as they lie.  The same list feeds the batched guided
+    calls (Matcher.match_list_guided_codes_batched and its kin) as their
+    position pairs."""
     if gathered_xy.dim() != 3 or gathered_xy.shape[0] != world or gathered_xy.dtype != torch.float32:
         raise ValueError("position_pairs takes a (world, n, c) float32 tensor")
     if not gathered_xy.is_contiguous():

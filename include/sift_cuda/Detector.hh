@@ -11,6 +11,7 @@
 #include "sift_cuda/Types.hh"
 
 struct sift_hip_detector;
+struct sift_hip_matcher;
 
 namespace sift_cuda {
 
@@ -203,5 +204,50 @@ std::vector<DMatch> matchListEpipolar(const DeviceBuffer<Half>& des, int num_des
                                       int num_src, const EpipolarGate& gate, const MatchFilter& filter = {});
 std::vector<int> matchEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
                                const EpipolarGate& gate);
+
+// Extra: the guided match lists of P pairs in one pass, over raw device
+// pointers and enqueued on a stream (sift_hip_match_list_guided_batched /
+// sift_hip_match_list_epipolar_batched), so that the chain batched match ->
+// Verifier::verify*BatchedDevice -> (projectHomographyBatchedDevice ->) guided
+// rematch never returns to the host.  A BatchMatcher owns the scratch of its
+// calls (sift_hip_matcher_create); calls on one must be ordered.  With a filter
+// that needs the reverse direction max_query and max_train both bound both sets,
+// and max_pairs >= 2 P puts both directions into one pass.
+class BatchMatcher {
+public:
+    BatchMatcher(int max_query, int max_train, int max_pairs, int device = -1);
+    ~BatchMatcher();
+    BatchMatcher(const BatchMatcher&) = delete;
+    BatchMatcher& operator=(const BatchMatcher&) = delete;
+    sift_hip_matcher* handle() const { return m_handle; }
+
+private:
+    sift_hip_matcher* m_handle = nullptr;
+};
+
+// One pair of a batched guided call: its fp16 descriptor rows and position rows, all device memory.
+struct GuidedPair {
+    const Half* des = nullptr;
+    int num_des = 0;
+    const Half* src = nullptr;
+    int num_src = 0;
+    const float* des_xy = nullptr;
+    const float* src_xy = nullptr;
+};
+
+// Pair p's records (imgIdx = p) start at row sum_{r<p} num_des[r] of `out`, its
+// count is counts[p] (device ints); both are what matchListGuided /
+// matchListEpipolar give on the pair.  The strides, the radius and max_error are
+// the call's.  geometry: device memory, pair p's nine floats at geometry +
+// p * geometry_stride_bytes (sizeof(VerifyResult) for verifyBatchedDevice's
+// results as they lie); a record with a non-finite entry or all zero gives its
+// pair an empty list.  What the ABI refuses throws std::invalid_argument.
+void matchListGuidedBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                  int src_stride, float radius, const MatchFilter& filter, DMatch* out, int* counts,
+                                  void* stream = nullptr);
+void matchListEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                    int src_stride, float radius, const void* geometry, int geometry_stride_bytes,
+                                    float max_error, const MatchFilter& filter, DMatch* out, int* counts,
+                                    void* stream = nullptr);
 
 }  // namespace sift_cuda

@@ -135,4 +135,17 @@ PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float*
 void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride = 2,
                              void* stream = nullptr);
 
+// sift_hip_project_set: one set of a batched projection.
+struct ProjectSet {
+    const float* xy = nullptr;
+    int n = 0;
+    float* out_xy = nullptr;
+};
+
+// All sets in one launch (sift_hip_project_homography_batched_device): set p goes through the 9 device floats at
+// geometry + p * geometry_stride_bytes -- sizeof(HomographyResult) for verifyHomographyBatchedDevice's results as they
+// lie -- and gives what projectHomographyDevice gives on it.  Enqueued on `stream`, not synchronised.
+void projectHomographyBatchedDevice(const void* geometry, int geometry_stride_bytes, const std::vector<ProjectSet>& sets,
+                                    int stride, int out_stride = 2, void* stream = nullptr);
+
 }  // namespace sift_cuda

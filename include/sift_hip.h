@@ -672,8 +672,9 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq
  * One pair per call.  Two detector descriptor buffers with fresh sidecars are
  * matched on their codes in one launch; any other pair is converted first (two
  * launches); a set with non-integer fp16 values takes the general path, as in
- * sift_hip_match_device.  Batched, code-set (sift_hip_match_codes_batched) and
- * multi-GPU guided forms do not exist. */
+ * sift_hip_match_device.  P pairs in one call, on fp16 sets or on ready code
+ * sets (the all-gathered buffers of a multi-GPU run), are the batched gated
+ * calls below (sift_hip_match_guided_batched and its kin). */
 typedef struct {
     const float* query_xy; /* device; query i's predicted position is query_xy[i*query_stride + {0,1}] */
     int query_stride;      /* floats per row, >= 2 (3 passes a detector's kpts3 buffer as it is) */
@@ -780,6 +781,99 @@ int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* quer
                                       int nt, const sift_hip_match_epipolar_gate* gate,
                                       const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap,
                                       int* count);
+
+/* --- Batched guided matching: both gates for all pairs of a batch -------------
+ *
+ * What sift_hip_match_batched / sift_hip_match_list_batched are to the
+ * single-pair calls: P pairs under a gate in one pass on one stream, so that
+ * match_list_batched -> verify_*_batched_device -> (project_homography_batched_
+ * device ->) the guided rematch never returns to the host.  Per pair: its sets
+ * and a position record; per call: both strides, the radius, and under the
+ * epipolar gate max_error and the geometry -- P records of nine floats in
+ * DEVICE memory, pair p's at geometry + p * geometry_stride_bytes (>= 36, a
+ * multiple of 4).  geometry = the results of
+ * sift_hip_verify_fundamental_batched_device with stride 52 takes those records
+ * as they lie; the host never reads them.  P = 1 is the single-pair epipolar
+ * call without the read-back of F.
+ *
+ * The rule.  Pair p of a batched gated call gives, byte for byte, the idx2 /
+ * d2 / match rows, or the list records and count, of the single-pair call on
+ * that pair under the gate {pair p's positions, the call's strides and radius,
+ * F = pair p's nine floats, the call's max_error}.  Rows and records lie in
+ * sift_hip_match_batched's / sift_hip_match_list_batched's layout: pair p's
+ * start at sum_{r<p} nq[r], records carry imgIdx = p, counts[p] is a device
+ * int, rows of `out` past a pair's count are not written.
+ * The single-pair epipolar call refuses an unusable F on the host; a batched
+ * call cannot see it, so on the device: a pair whose nine floats hold a value
+ * that is not finite, or are all zero (the empty verify result, hypothesis =
+ * -1), has no candidates -- every query of it gets -1 / -1, FLT_MAX / FLT_MAX
+ * and match = -1, and its list count is 0.  (Without this rule a zero F would
+ * make every row a candidate: 0 <= e2 * 0.)  sift_amd.cv.geometry_usable is the
+ * same test in numpy.
+ *
+ * The fp16 forms always convert their sets first (distinct sets once, as
+ * sift_hip_match_batched does for P > 1; sidecars are not used); a set with
+ * non-integer values sends its pairs down the gated general path.  A launch
+ * holds at most 32 pairs (kernel-argument space), so a call is
+ * ceil(pairs / 32) match launches per pass: the forward and reverse pairs of a
+ * list in one pass of 2P pairs when 2P <= max_pairs, otherwise in two of P.
+ * The bytes do not depend on it.  The matcher's scratch is restored when a
+ * call ends.
+ *
+ * SIFT_HIP_ERR_INVALID, with nothing launched, for: a stride < 2, a radius that
+ * is not > 0, a max_error that is not > 0 or not finite, a null geometry, a
+ * geometry stride below 36 or not a multiple of 4 (these need no matcher and
+ * are looked at first); a null matcher; P outside 1..max_pairs or a null pair
+ * array; a size over the matcher's limits (with a filter that needs the reverse
+ * direction also nt <= max_query and nq <= max_train); a null descriptor or
+ * position pointer of a non-empty set; the list calls' rules for filter, out
+ * and counts. */
+typedef struct {
+    const float* query_xy; /* device; pair p's query positions, rows of query_stride floats */
+    const float* train_xy; /* device; its train positions, rows of train_stride floats */
+} sift_hip_match_positions;
+
+/* sift_hip_match_batched under the window gate / the epipolar gate. */
+int sift_hip_match_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                  const uint16_t* const* train, const int* nt,
+                                  const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                  float radius, float ratio, int ratio_on_squared, int* idx2, float* d2, int* match,
+                                  void* stream);
+int sift_hip_match_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                    const uint16_t* const* train, const int* nt,
+                                    const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                    float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                    float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, void* stream);
+
+/* sift_hip_match_list_batched under the two gates. */
+int sift_hip_match_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                       const uint16_t* const* train, const int* nt,
+                                       const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                       float radius, const sift_hip_match_filter* filter, sift_hip_dmatch* out,
+                                       int* counts, void* stream);
+int sift_hip_match_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                         const uint16_t* const* train, const int* nt,
+                                         const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                         float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                         const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
+                                         void* stream);
+
+/* sift_hip_match_list_codes_batched under the two gates: pairs of ready code
+ * sets (e.g. every rank's sidecars all-gathered), no conversion. */
+int sift_hip_match_list_guided_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                             const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                             const int* tkey0, const int* nt,
+                                             const sift_hip_match_positions* positions, int query_stride,
+                                             int train_stride, float radius, const sift_hip_match_filter* filter,
+                                             sift_hip_dmatch* out, int* counts, void* stream);
+int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                               const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                               const int* tkey0, const int* nt,
+                                               const sift_hip_match_positions* positions, int query_stride,
+                                               int train_stride, float radius, const void* geometry,
+                                               int geometry_stride_bytes, float max_error,
+                                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
+                                               void* stream);
 
 /* The launch plan a match call of this shape gets: train splits S per query
  * block (S > 1: split workgroups merge their top-2 through the scratch's
@@ -1053,6 +1147,23 @@ int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* sampl
  * with n > 0, a partial overlap.  n == 0 succeeds. */
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
                                        void* stream);
+
+/* P projections in one launch: set p goes through the 9 floats at
+ * geometry + p * geometry_stride_bytes (device memory; stride 52 takes the
+ * records of sift_hip_verify_homography_batched_device as they lie) and gives,
+ * byte for byte, what the single call gives on {that H, sets[p]}.  `sets` is a
+ * host array of P records; the strides are the call's.  SIFT_HIP_ERR_INVALID,
+ * with nothing launched, for: a null geometry or sets, a geometry stride below
+ * 36 or not a multiple of 4, P outside 1..64, a stride below 2, and per set
+ * the single call's rules (n == 0 is an empty set). */
+typedef struct {
+    const float* xy; /* device; n rows of `stride` floats */
+    int n;
+    float* out_xy;   /* device; n rows of `out_stride` floats; may be xy with equal strides */
+} sift_hip_project_set;
+int sift_hip_project_homography_batched_device(const void* geometry, int geometry_stride_bytes, int P,
+                                               const sift_hip_project_set* sets, int stride, int out_stride,
+                                               void* stream);
 
 /* --- Batched verification: every pair of a match batch in one pass --------------
  *
