@@ -21,12 +21,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CXXFLAGS := -O2 -std=c++17 -fPIC -Iinclude -Wall -Wextra
 
 HIP_SRCS := $(SRC)/detector.hip $(SRC)/lanes.hip $(SRC)/datagen.hip $(SRC)/matcher_api.hip $(SRC)/pyramid.hip $(SRC)/keypoints.hip $(SRC)/descriptor.hip $(SRC)/match.hip \
-            $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/verify_api.hip
+            $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/refit.hip $(SRC)/verify_api.hip
 HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OUT)/obj/%.o,$(HIP_SRCS)) $(OUT)/obj/synth_frame.o
 
 all: $(OUT)/libsift_hip.so $(OUT)/libsift_cuda.so tools
 
-$(OUT)/obj/%.o: $(SRC)/%.hip $(SRC)/detector_state.h $(SRC)/sift_kernels.h $(SRC)/sift_math.h $(SRC)/sift_match.h $(SRC)/sift_refine.h $(SRC)/sift_desc_rows.h $(SRC)/sift_epipolar.h $(SRC)/sift_verify.h include/sift_hip.h
+$(OUT)/obj/%.o: $(SRC)/%.hip $(SRC)/detector_state.h $(SRC)/sift_kernels.h $(SRC)/sift_math.h $(SRC)/sift_match.h $(SRC)/sift_refine.h $(SRC)/sift_desc_rows.h $(SRC)/sift_epipolar.h $(SRC)/sift_verify.h $(SRC)/sift_verify_dev.h include/sift_hip.h
 	@mkdir -p $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -64,7 +64,7 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
@@ -88,6 +88,12 @@ $(ASAN_DIR)/test_homography_args: tests/cpp/test_homography_args.cpp $(SRC)/veri
 $(ASAN_DIR)/test_verify_batched_args: tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp \
+	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
+
+# The same for the refit calls: tests/test_refit_asan.py.
+$(ASAN_DIR)/test_refit_args: tests/cpp/test_refit_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
+	@mkdir -p $(ASAN_DIR)
+	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_refit_args.cpp $(SRC)/verify_cxx.cpp \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
 clean:

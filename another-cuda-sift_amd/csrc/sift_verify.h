@@ -97,6 +97,30 @@ void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, c
                                   const int* valid, const int* counts, int K, float e2, VerifyResult* results,
                                   MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s);
 
+// The refit of a verified model on its inliers (refit.hip; sift_hip_refine_*, the rule is in include/sift_hip.h).
+// One round is two launches, both with one workgroup per pair (blockIdx.y in a batch):
+// k_refit_fit: the least-squares model of the records j < n with mask[j] != 0 and finite gathered points, under the
+//   current record *result, into the verifier's scratch record *cand (valid = 0: no refit, the model all zero).
+// k_refit_accept: the candidate rescored over the n records with the model's predicate; when it is valid and counts
+//   at least result->inliers records, result's model and inliers and mask[0, n) become the candidate's.  out
+//   (nullable) then receives the records of the mask as it stands, in input order, and out_count (nullable) their
+//   number; *accepted (nullable) is set to (first_round ? 0 : *accepted) + 1 on an accepted round.
+struct RefitCandidate {
+    float m[9];
+    int valid;
+};
+void launch_refit_fit(VerifyModel model, const VerifyInput& in, const float4* pts, const uint8_t* mask,
+                      const VerifyResult* result, RefitCandidate* cand, hipStream_t s);
+void launch_refit_accept(VerifyModel model, const VerifyInput& in, const float4* pts, const RefitCandidate* cand,
+                         float e2, VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
+                         bool first_round, hipStream_t s);
+// The batched twins: pair p's points, mask and out rows at row0[p], its result, candidate, out_count and accepted at p.
+void launch_refit_fit_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const uint8_t* mask,
+                              const VerifyResult* results, RefitCandidate* cand, hipStream_t s);
+void launch_refit_accept_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts,
+                                 const RefitCandidate* cand, float e2, VerifyResult* results, uint8_t* mask,
+                                 MatchRecord* out, int* out_counts, int* accepted, bool first_round, hipStream_t s);
+
 // k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
 // `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.
 void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,

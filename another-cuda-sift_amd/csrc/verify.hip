@@ -43,16 +43,11 @@
 
 #include "sift_epipolar.h"
 #include "sift_verify.h"
+#include "sift_verify_dev.h"
 
 namespace sift_amd {
 
 namespace {
-
-__device__ __forceinline__ int verify_n(const int* count, int cap) {
-    if (!count) return cap;
-    const int c = *count;
-    return c < 0 ? 0 : (c < cap ? c : cap);
-}
 
 // lowbias32 (the header writes it out).
 __device__ __forceinline__ unsigned mix32(unsigned h) {
@@ -63,8 +58,6 @@ __device__ __forceinline__ unsigned mix32(unsigned h) {
     h ^= h >> 16;
     return h;
 }
-
-__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < INFINITY; }
 
 // The draw of hypothesis k: M distinct indices of [0, n), n >= M, a function of (seed, k, n).
 template <int M>
@@ -213,23 +206,6 @@ __device__ __forceinline__ HypLds hyp_lds() {
     __shared__ int s_perm[9 * kHypThreads];
     return HypLds{s_a, s_y, s_perm};
 }
-
-// The list a workgroup works on: the call's own, or pair blockIdx.y's rows of the batch's match buffer, its counter
-// and its positions.
-__device__ __forceinline__ const VerifyInput& list_of(const VerifyInput& in) { return in; }
-__device__ __forceinline__ VerifyInput list_of(const VerifyBatch& b) {
-    const int p = blockIdx.y;
-    const VerifyBatchPair& e = b.pair[p];
-    return VerifyInput{b.matches + e.row0, b.counts ? b.counts + p : nullptr, e.cap, e.qxy, e.txy, b.qstride, b.tstride,
-                       e.nq, e.nt};
-}
-// A batch's workgroup: its pair, and the pair's first row of the per-match arrays.
-__device__ __forceinline__ int pair_of(const VerifyBatch&) { return blockIdx.y; }
-__device__ __forceinline__ int row0_of(const VerifyBatch& b) { return b.pair[blockIdx.y].row0; }
-template <class List>
-constexpr bool kBatched = false;
-template <>
-constexpr bool kBatched<VerifyBatch> = true;
 
 }  // namespace
 
@@ -428,26 +404,6 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, 
     valid[k] = ok ? 1 : 0;
 }
 #undef VA
-
-// The predicates of match p = (qx, qy, tx, ty) under a hypothesis, e2 = max_error^2.
-// Fundamental: the matcher's epipolar gate for the match's own pair, no window (radius = +inf).
-struct SampsonPass {
-    static __device__ __forceinline__ bool pass(const float (&f)[9], const float4 p, float e2) {
-        const EpiQuery q = epi_query(f, p.x, p.y);
-        return epi_pass(q, p.z, p.w, epi_row(f, p.z, p.w), e2, INFINITY);
-    }
-};
-// Homography: the forward transfer error, division-free, in front of the camera only.
-struct TransferPass {
-    static __device__ __forceinline__ bool pass(const float (&h)[9], const float4 p, float e2) {
-#pragma clang fp contract(off)
-        const float px = (h[0] * p.x + h[1] * p.y) + h[2];
-        const float py = (h[3] * p.x + h[4] * p.y) + h[5];
-        const float w = (h[6] * p.x + h[7] * p.y) + h[8];
-        const float dx = px - p.z * w, dy = py - p.w * w;
-        return (w > 0.f) & (dx * dx + dy * dy <= e2 * (w * w));
-    }
-};
 
 constexpr int kScoreWaves = 4;     // hypotheses per workgroup
 constexpr int kScoreUnroll = 4;    // matches per lane and loop iteration

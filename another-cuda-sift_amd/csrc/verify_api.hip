@@ -25,13 +25,15 @@ struct sift_hip_verifier {
     VerifyResult* dResult = nullptr;  // maxP records
     MatchRecord* dOut = nullptr;
     uint8_t* dMask = nullptr;
+    RefitCandidate* dCand = nullptr;  // the refit's candidate model per pair (sift_hip_refine_*), maxP records
+    int* dRefineInts = nullptr;       // sift_hip_refine_*_host: maxP out counts, then maxP accepted rounds
     int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
     int lastModel = 0;           // its VerifyModel, 0: none
     bool lastBatch = false;      // it was a batched call (the getters read one pair's scratch layout)
     ~sift_hip_verifier() {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
-                        (void*)dOut, (void*)dMask})
+                        (void*)dOut, (void*)dMask, (void*)dCand, (void*)dRefineInts})
             if (p) (void)hipFree(p);
     }
 };
@@ -84,11 +86,28 @@ int verify_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in
     return SIFT_HIP_OK;
 }
 
+// The refit's own argument rules (sift_hip_refine_*), judged without the handle.
+struct RefineArgs {
+    int rounds;
+    const uint8_t* mask;
+};
+constexpr int kRefineMaxRounds = 8;
+
+int check_refine(int rounds, const void* result, const uint8_t* mask, int rows) {
+    if (!result) return fail(SIFT_HIP_ERR_INVALID, "refine: null result");
+    if (rows > 0 && !mask) return fail(SIFT_HIP_ERR_INVALID, "refine: null mask (the mask is the fit set)");
+    if (rounds < 1 || rounds > kRefineMaxRounds)
+        return fail(SIFT_HIP_ERR_INVALID, "refine: rounds must lie in 1.." + std::to_string(kRefineMaxRounds));
+    return SIFT_HIP_OK;
+}
+
 // The batched call's argument rules: what can be judged without the handle first, then its limits; `b` is the pair
-// table the kernels take.  out: the device form's output rows (may not overlap matches), null otherwise.
+// table the kernels take.  out: the device form's output rows (may not overlap matches), null otherwise.  refine: a
+// refine call's further arguments, judged before the limits.
 int check_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, const int* counts, int P,
                 const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                const sift_hip_verify_params* params, const void* results, const sift_hip_dmatch* out, VerifyBatch& b) {
+                const sift_hip_verify_params* params, const void* results, const sift_hip_dmatch* out, VerifyBatch& b,
+                const RefineArgs* refine = nullptr) {
     if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
     if (!pairs) return fail(SIFT_HIP_ERR_INVALID, "verify: null pairs");
     if (!params || !results) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
@@ -113,6 +132,8 @@ int check_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, cons
     const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)rows;
     if (out && rows > 0 && ob < mb + bytes && mb < ob + bytes)
         return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
+    if (refine)
+        if (int rc = check_refine(refine->rounds, results, refine->mask, rows)) return rc;
     if (params->hypotheses < 1 || params->hypotheses > kVerifyMaxHypotheses || params->hypotheses > v->maxK)
         return fail(SIFT_HIP_ERR_INVALID, "verify: hypotheses outside 1..max_hypotheses");
     if (P > v->maxP) return fail(SIFT_HIP_ERR_INVALID, "verify: more pairs than the verifier's max_pairs");
@@ -243,6 +264,143 @@ int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples
     return SIFT_HIP_OK;
 }
 
+// --- The refit (sift_hip_refine_*): `rounds` rounds of fit -> rescore -> accept on the gathered list; out is written
+// by the last round only.  The verifier's hypothesis scratch is not touched.
+
+int refine_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in, float max_error, int rounds,
+                  VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted, hipStream_t s) {
+    const float e2 = max_error * max_error;
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather(in, v->dPts, s);
+    for (int r = 0; r < rounds; r++) {
+        const bool last = r == rounds - 1;
+        launch_refit_fit(model, in, v->dPts, mask, result, v->dCand, s);
+        launch_refit_accept(model, in, v->dPts, v->dCand, e2, result, mask, last ? out : nullptr,
+                            last ? out_count : nullptr, accepted, r == 0, s);
+    }
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+int refine_batched_device(sift_hip_verifier* v, VerifyModel model, const VerifyBatch& b, float max_error, int rounds,
+                          VerifyResult* results, uint8_t* mask, MatchRecord* out, int* out_counts, int* accepted,
+                          hipStream_t s) {
+    const float e2 = max_error * max_error;
+    HIPCHK(hipSetDevice(v->device));
+    launch_verify_gather_batched(b, v->dPts, s);
+    for (int r = 0; r < rounds; r++) {
+        const bool last = r == rounds - 1;
+        launch_refit_fit_batched(model, b, v->dPts, mask, results, v->dCand, s);
+        launch_refit_accept_batched(model, b, v->dPts, v->dCand, e2, results, mask, last ? out : nullptr,
+                                    last ? out_counts : nullptr, accepted, r == 0, s);
+    }
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// The single-pair argument rules: the verify call's, then the refit's own.
+int check_refine_single(const sift_hip_verifier* v, const sift_hip_dmatch* matches, int cap, const float* query_xy,
+                        int query_stride, int nq, const float* train_xy, int train_stride, int nt, float max_error,
+                        int rounds, const void* result, const uint8_t* mask, const sift_hip_dmatch* out) {
+    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
+    if (int rc = check_refine(rounds, result, mask, cap)) return rc;
+    if (int rc = check_error(max_error)) return rc;
+    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
+    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
+    return check_limits(v, cap, 1);
+}
+
+int refine_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
+                        const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                        float max_error, int rounds, void* result, uint8_t* mask, sift_hip_dmatch* out, int* out_count,
+                        int* accepted, void* stream) {
+    if (int rc = check_refine_single(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, max_error,
+                                     rounds, result, mask, out))
+        return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    return refine_device(v, model, in, max_error, rounds, static_cast<VerifyResult*>(result), mask,
+                         reinterpret_cast<MatchRecord*>(out), out_count, accepted, (hipStream_t)stream);
+}
+
+int refine_model_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
+                      const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                      float max_error, int rounds, void* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,
+                      int* out_count_host, int* accepted_host) {
+    if (int rc = check_refine_single(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, max_error,
+                                     rounds, result_host, mask_host, nullptr))
+        return rc;
+    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
+                         train_stride, nq, nt};
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipMemcpy(v->dResult, result_host, sizeof(VerifyResult), hipMemcpyHostToDevice));
+    if (cap > 0) HIPCHK(hipMemcpy(v->dMask, mask_host, (size_t)cap, hipMemcpyHostToDevice));
+    if (int rc = refine_device(v, model, in, max_error, rounds, v->dResult, v->dMask, v->dOut, v->dRefineInts,
+                               v->dRefineInts + v->maxP, nullptr))
+        return rc;
+    int ints[2] = {0, 0};
+    HIPCHK(hipMemcpy(&ints[0], v->dRefineInts, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ints[1], v->dRefineInts + v->maxP, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
+    if (cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
+    const int n = std::min(ints[0], cap);
+    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+    if (out_count_host) *out_count_host = ints[0];
+    if (accepted_host) *accepted_host = ints[1];
+    return SIFT_HIP_OK;
+}
+
+// The batched argument rules: check_batch's (with the one-hypothesis budget every verifier has), then the refit's own.
+int check_refine_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, const int* counts, int P,
+                       const sift_hip_verify_pair* pairs, int query_stride, int train_stride, float max_error, int rounds,
+                       const void* results, const uint8_t* mask, const sift_hip_dmatch* out, VerifyBatch& b) {
+    const sift_hip_verify_params params{1, 0u, max_error};
+    const RefineArgs refine{rounds, mask};
+    return check_batch(v, matches, counts, P, pairs, query_stride, train_stride, &params, results, out, b, &refine);
+}
+
+int refine_model_batched_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
+                                int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                float max_error, int rounds, void* results, uint8_t* mask, sift_hip_dmatch* out,
+                                int* out_counts, int* accepted, void* stream) {
+    VerifyBatch b{};
+    if (int rc = check_refine_batch(v, matches, counts, P, pairs, query_stride, train_stride, max_error, rounds, results,
+                                    mask, out, b))
+        return rc;
+    return refine_batched_device(v, model, b, max_error, rounds, static_cast<VerifyResult*>(results), mask,
+                                 reinterpret_cast<MatchRecord*>(out), out_counts, accepted, (hipStream_t)stream);
+}
+
+int refine_model_batched_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
+                              int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                              float max_error, int rounds, void* results_host, uint8_t* mask_host,
+                              sift_hip_dmatch* out_host, int* out_counts_host, int* accepted_host) {
+    VerifyBatch b{};
+    if (int rc = check_refine_batch(v, matches, counts, P, pairs, query_stride, train_stride, max_error, rounds,
+                                    results_host, mask_host, nullptr, b))
+        return rc;
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipMemcpy(v->dResult, results_host, sizeof(VerifyResult) * (size_t)P, hipMemcpyHostToDevice));
+    if (b.rows > 0) HIPCHK(hipMemcpy(v->dMask, mask_host, (size_t)b.rows, hipMemcpyHostToDevice));
+    if (int rc = refine_batched_device(v, model, b, max_error, rounds, v->dResult, v->dMask, v->dOut, v->dRefineInts,
+                                       v->dRefineInts + v->maxP, nullptr))
+        return rc;
+    int ints[2 * kVerifyMaxPairs];
+    HIPCHK(hipMemcpy(ints, v->dRefineInts, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ints + kVerifyMaxPairs, v->dRefineInts + v->maxP, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(results_host, v->dResult, sizeof(VerifyResult) * (size_t)P, hipMemcpyDeviceToHost));
+    if (b.rows > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
+    for (int p = 0; p < P; p++) {  // a pair's rows past its records stay as they are, as on the device
+        const int n = std::min(ints[p], b.pair[p].cap), row0 = b.pair[p].row0;
+        if (out_host && n > 0)
+            HIPCHK(hipMemcpy(out_host + row0, v->dOut + row0, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+        if (out_counts_host) out_counts_host[p] = ints[p];
+        if (accepted_host) accepted_host[p] = ints[kVerifyMaxPairs + p];
+    }
+    return SIFT_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -282,7 +440,10 @@ int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypoth
         hipMalloc((void**)&v->dCounts, sizeof(int) * K) != hipSuccess ||
         hipMalloc((void**)&v->dResult, sizeof(VerifyResult) * (size_t)max_pairs) != hipSuccess ||
         hipMalloc((void**)&v->dOut, sizeof(MatchRecord) * M) != hipSuccess ||
-        hipMalloc((void**)&v->dMask, M) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        hipMalloc((void**)&v->dMask, M) != hipSuccess ||
+        hipMalloc((void**)&v->dCand, sizeof(RefitCandidate) * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dRefineInts, sizeof(int) * 2 * (size_t)max_pairs) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
         delete v;
         return fail(SIFT_HIP_ERR_NOMEM, "verifier allocation failed");
     }
@@ -389,6 +550,43 @@ int sift_hip_verify_homography_batched_host(sift_hip_verifier_t v, const sift_hi
     return verify_model_batched_host(v, VerifyModel::Homography, matches, counts, P, pairs, query_stride, train_stride,
                                      params, results_host, out_host, mask_host);
 }
+
+#define SIFT_REFINE_ENTRIES(name, MODEL, RESULT)                                                                          \
+    int sift_hip_refine_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap, \
+                                        const float* query_xy, int query_stride, int nq, const float* train_xy,          \
+                                        int train_stride, int nt, float max_error, int rounds, RESULT* result,           \
+                                        uint8_t* mask, sift_hip_dmatch* out, int* out_count, int* accepted,              \
+                                        void* stream) {                                                                  \
+        return refine_model_device(v, MODEL, matches, count, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, \
+                                   max_error, rounds, result, mask, out, out_count, accepted, stream);                   \
+    }                                                                                                                    \
+    int sift_hip_refine_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,  \
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,            \
+                                      int train_stride, int nt, float max_error, int rounds, RESULT* result_host,        \
+                                      uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_count_host,                \
+                                      int* accepted_host) {                                                              \
+        return refine_model_host(v, MODEL, matches, count, cap, query_xy, query_stride, nq, train_xy, train_stride, nt,   \
+                                 max_error, rounds, result_host, mask_host, out_host, out_count_host, accepted_host);    \
+    }                                                                                                                    \
+    int sift_hip_refine_##name##_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts, \
+                                                int P, const sift_hip_verify_pair* pairs, int query_stride,              \
+                                                int train_stride, float max_error, int rounds, RESULT* results,          \
+                                                uint8_t* mask, sift_hip_dmatch* out, int* out_counts, int* accepted,     \
+                                                void* stream) {                                                          \
+        return refine_model_batched_device(v, MODEL, matches, counts, P, pairs, query_stride, train_stride, max_error,   \
+                                           rounds, results, mask, out, out_counts, accepted, stream);                    \
+    }                                                                                                                    \
+    int sift_hip_refine_##name##_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,  \
+                                              int P, const sift_hip_verify_pair* pairs, int query_stride,                \
+                                              int train_stride, float max_error, int rounds, RESULT* results_host,       \
+                                              uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,       \
+                                              int* accepted_host) {                                                      \
+        return refine_model_batched_host(v, MODEL, matches, counts, P, pairs, query_stride, train_stride, max_error,     \
+                                         rounds, results_host, mask_host, out_host, out_counts_host, accepted_host);     \
+    }
+SIFT_REFINE_ENTRIES(fundamental, VerifyModel::Fundamental, sift_hip_verify_result)
+SIFT_REFINE_ENTRIES(homography, VerifyModel::Homography, sift_hip_homography_result)
+#undef SIFT_REFINE_ENTRIES
 
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
                                        void* stream) {

@@ -217,6 +217,190 @@ PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float*
                                   train_stride, nt, params);
 }
 
+// --- The refit (sift_hip_refine_*).
+
+namespace {
+
+sift_hip_dmatch* abi(DMatch* p) { return reinterpret_cast<sift_hip_dmatch*>(p); }
+const sift_hip_dmatch* abi(const DMatch* p) { return reinterpret_cast<const sift_hip_dmatch*>(p); }
+
+// The host forms' mask: one byte per row, or the ABI's refusal of the rows themselves (nothing is read then).
+void check_mask(const std::vector<uint8_t>& mask, size_t rows, const char* what) {
+    if (mask.size() != rows) throw std::invalid_argument(std::string(what) + ": mask must hold one byte per row");
+}
+
+}  // namespace
+
+void Verifier::refineDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                            int nq, const float* train_xy, int train_stride, int nt, float max_error, int rounds,
+                            VerifyResult* result, uint8_t* mask, DMatch* out, int* out_count, int* accepted,
+                            void* stream) {
+    check_throw(sift_hip_refine_fundamental_device(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
+                                                   train_stride, nt, max_error, rounds,
+                                                   reinterpret_cast<sift_hip_verify_result*>(result), mask, abi(out),
+                                                   out_count, accepted, stream),
+                "Verifier::refineDevice");
+}
+
+void Verifier::refineHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                      int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                      float max_error, int rounds, HomographyResult* result, uint8_t* mask, DMatch* out,
+                                      int* out_count, int* accepted, void* stream) {
+    check_throw(sift_hip_refine_homography_device(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
+                                                  train_stride, nt, max_error, rounds,
+                                                  reinterpret_cast<sift_hip_homography_result*>(result), mask, abi(out),
+                                                  out_count, accepted, stream),
+                "Verifier::refineHomographyDevice");
+}
+
+int Verifier::refineHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                         const float* train_xy, int train_stride, int nt, float max_error, int rounds,
+                         VerifyResult& result, std::vector<uint8_t>& mask, std::vector<DMatch>* inliers) {
+    if (cap >= 0 && cap <= 65536) check_mask(mask, (size_t)cap, "Verifier::refineHost");
+    std::vector<DMatch> list(inliers && cap > 0 && cap <= 65536 ? (size_t)cap : 0);
+    int n = 0, accepted = 0;
+    check_throw(sift_hip_refine_fundamental_host(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
+                                                 train_stride, nt, max_error, rounds,
+                                                 reinterpret_cast<sift_hip_verify_result*>(&result),
+                                                 mask.empty() ? nullptr : mask.data(),
+                                                 inliers ? abi(list.data()) : nullptr, &n, &accepted),
+                "Verifier::refineHost");
+    if (inliers) {
+        list.resize((size_t)n);
+        *inliers = std::move(list);
+    }
+    return accepted;
+}
+
+int Verifier::refineHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                   int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                   float max_error, int rounds, HomographyResult& result, std::vector<uint8_t>& mask,
+                                   std::vector<DMatch>* inliers) {
+    if (cap >= 0 && cap <= 65536) check_mask(mask, (size_t)cap, "Verifier::refineHomographyHost");
+    std::vector<DMatch> list(inliers && cap > 0 && cap <= 65536 ? (size_t)cap : 0);
+    int n = 0, accepted = 0;
+    check_throw(sift_hip_refine_homography_host(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
+                                                train_stride, nt, max_error, rounds,
+                                                reinterpret_cast<sift_hip_homography_result*>(&result),
+                                                mask.empty() ? nullptr : mask.data(),
+                                                inliers ? abi(list.data()) : nullptr, &n, &accepted),
+                "Verifier::refineHomographyHost");
+    if (inliers) {
+        list.resize((size_t)n);
+        *inliers = std::move(list);
+    }
+    return accepted;
+}
+
+void Verifier::refineBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                   int query_stride, int train_stride, float max_error, int rounds, VerifyResult* results,
+                                   uint8_t* mask, DMatch* out, int* out_counts, int* accepted, void* stream) {
+    check_throw(sift_hip_refine_fundamental_batched_device(m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs),
+                                                           query_stride, train_stride, max_error, rounds,
+                                                           reinterpret_cast<sift_hip_verify_result*>(results), mask,
+                                                           abi(out), out_counts, accepted, stream),
+                "Verifier::refineBatchedDevice");
+}
+
+void Verifier::refineHomographyBatchedDevice(const DMatch* matches, const int* counts,
+                                             const std::vector<VerifyPair>& pairs, int query_stride, int train_stride,
+                                             float max_error, int rounds, HomographyResult* results, uint8_t* mask,
+                                             DMatch* out, int* out_counts, int* accepted, void* stream) {
+    check_throw(sift_hip_refine_homography_batched_device(m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs),
+                                                          query_stride, train_stride, max_error, rounds,
+                                                          reinterpret_cast<sift_hip_homography_result*>(results), mask,
+                                                          abi(out), out_counts, accepted, stream),
+                "Verifier::refineHomographyBatchedDevice");
+}
+
+std::vector<int> Verifier::refineBatchedHost(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                             int query_stride, int train_stride, float max_error, int rounds,
+                                             std::vector<VerifyResult>& results, std::vector<uint8_t>& mask,
+                                             std::vector<DMatch>* out, std::vector<int>* out_counts) {
+    if (results.size() != pairs.size())
+        throw std::invalid_argument("Verifier::refineBatchedHost: one result record per pair");
+    const size_t rows = batchRows(pairs);
+    if (rows > 0) check_mask(mask, rows, "Verifier::refineBatchedHost");
+    std::vector<DMatch> list(out ? rows : 0);
+    std::vector<int> n(pairs.size()), accepted(pairs.size());
+    check_throw(sift_hip_refine_fundamental_batched_host(
+                    m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs), query_stride, train_stride, max_error,
+                    rounds, reinterpret_cast<sift_hip_verify_result*>(results.data()), mask.empty() ? nullptr : mask.data(),
+                    out ? abi(list.data()) : nullptr, n.data(), accepted.data()),
+                "Verifier::refineBatchedHost");
+    if (out) *out = std::move(list);
+    if (out_counts) *out_counts = n;
+    return accepted;
+}
+
+std::vector<int> Verifier::refineHomographyBatchedHost(const DMatch* matches, const int* counts,
+                                                       const std::vector<VerifyPair>& pairs, int query_stride,
+                                                       int train_stride, float max_error, int rounds,
+                                                       std::vector<HomographyResult>& results, std::vector<uint8_t>& mask,
+                                                       std::vector<DMatch>* out, std::vector<int>* out_counts) {
+    if (results.size() != pairs.size())
+        throw std::invalid_argument("Verifier::refineHomographyBatchedHost: one result record per pair");
+    const size_t rows = batchRows(pairs);
+    if (rows > 0) check_mask(mask, rows, "Verifier::refineHomographyBatchedHost");
+    std::vector<DMatch> list(out ? rows : 0);
+    std::vector<int> n(pairs.size()), accepted(pairs.size());
+    check_throw(sift_hip_refine_homography_batched_host(
+                    m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs), query_stride, train_stride, max_error,
+                    rounds, reinterpret_cast<sift_hip_homography_result*>(results.data()),
+                    mask.empty() ? nullptr : mask.data(), out ? abi(list.data()) : nullptr, n.data(), accepted.data()),
+                "Verifier::refineHomographyBatchedHost");
+    if (out) *out = std::move(list);
+    if (out_counts) *out_counts = n;
+    return accepted;
+}
+
+TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
+                                  const float* train_xy, int nt, const VerifyParams& params, int query_stride,
+                                  int train_stride, int refit) {
+    if (refit == 0) return verifyFundamental(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride);
+    const int n = (int)matches.size();
+    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyFundamental");
+    const sift_hip_verify_params p = toAbi(params);
+    VerifyResult r{};
+    std::vector<uint8_t> mask(matches.size());
+    check_throw(sift_hip_verify_fundamental_host(v.handle(), abi(static_cast<const DMatch*>(d.p)), nullptr, n, query_xy,
+                                                 query_stride, nq, train_xy, train_stride, nt, &p,
+                                                 reinterpret_cast<sift_hip_verify_result*>(&r), nullptr,
+                                                 mask.empty() ? nullptr : mask.data()),
+                "verifyFundamental");
+    TwoViewGeometry g;
+    v.refineHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride, nt,
+                 params.max_error, refit, r, mask, &g.inliers);
+    for (int i = 0; i < 9; i++) g.F[i] = r.F[i];
+    g.hypothesis = r.hypothesis;
+    return g;
+}
+
+PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const VerifyParams& params, int query_stride, int train_stride, int refit) {
+    if (refit == 0) return verifyHomography(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride);
+    const int n = (int)matches.size();
+    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyHomography");
+    const sift_hip_verify_params p = toAbi(params);
+    HomographyResult r{};
+    std::vector<uint8_t> mask(matches.size());
+    check_throw(sift_hip_verify_homography_host(v.handle(), abi(static_cast<const DMatch*>(d.p)), nullptr, n, query_xy,
+                                                query_stride, nq, train_xy, train_stride, nt, &p,
+                                                reinterpret_cast<sift_hip_homography_result*>(&r), nullptr,
+                                                mask.empty() ? nullptr : mask.data()),
+                "verifyHomography");
+    PlanarGeometry g;
+    v.refineHomographyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
+                           nt, params.max_error, refit, r, mask, &g.inliers);
+    for (int i = 0; i < 9; i++) g.H[i] = r.H[i];
+    g.hypothesis = r.hypothesis;
+    return g;
+}
+
 void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
                              void* stream) {
     check_throw(sift_hip_project_homography_device(H, xy, stride, n, out_xy, out_stride, stream),

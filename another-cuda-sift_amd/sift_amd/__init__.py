@@ -330,6 +330,18 @@ def lib() -> ctypes.CDLL:
                                                           ctypes.POINTER(_VerifyParams), vp, vp, vp, vp, vp]),
         "sift_hip_verify_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
                                                         ctypes.POINTER(_VerifyParams), vp, vp, vp]),
+        "sift_hip_refine_fundamental_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, vp, vp, vp]),
+        "sift_hip_refine_fundamental_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, ip, ip]),
+        "sift_hip_refine_homography_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, vp, vp, vp]),
+        "sift_hip_refine_homography_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, ip, ip]),
+        "sift_hip_refine_fundamental_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                           vp, vp, vp, vp]),
+        "sift_hip_refine_fundamental_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                         vp, vp, vp]),
+        "sift_hip_refine_homography_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                          vp, vp, vp, vp]),
+        "sift_hip_refine_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                        vp, vp, vp]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -1369,8 +1381,129 @@ class Verifier:
                                   HOMOGRAPHY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, max_error, hypotheses, seed,
                                   q_stride, t_stride, full)
 
+    # --- the refit of a verified model on its inliers (sift_hip_refine_*; the rule: include/sift_hip.h, in numpy
+    # sift_amd.cv.refine_fundamental / refine_homography).  The list, count, cap and positions are the verify call's;
+    # result(s) and mask are what it wrote, updated in place.
 
-def _verify_batched(host, matches_per_pair, xy_per_pair, max_error, hypotheses, seed):
+    def _refine_device(self, fn, what, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, mask_ptr,
+                       out_ptr, out_count_ptr, accepted_ptr, max_error, rounds, q_stride, t_stride, stream):
+        _check(fn(self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+                  t_stride, nt, max_error, rounds, result_ptr or None, mask_ptr or None, out_ptr or None,
+                  out_count_ptr or None, accepted_ptr or None, stream), what)
+
+    def refine_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                      result_ptr: int, mask_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0, accepted_ptr: int = 0,
+                      max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3,
+                      stream: Optional[int] = None) -> None:
+        """Enqueue `rounds` (1..8) refit rounds of the fundamental matrix (sift_hip_refine_fundamental_device); every
+        pointer is device memory.  result_ptr and mask_ptr: the record and the mask of verify_device on the same list,
+        updated in place; out_ptr (room for cap records), out_count_ptr and accepted_ptr (an int: the number of
+        accepted rounds) may be 0."""
+        self._refine_device(lib().sift_hip_refine_fundamental_device, "refine_fundamental_device", matches_ptr,
+                            count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, mask_ptr, out_ptr, out_count_ptr,
+                            accepted_ptr, max_error, rounds, q_stride, t_stride, stream)
+
+    def refine_homography_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                                 nt: int, result_ptr: int, mask_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0,
+                                 accepted_ptr: int = 0, max_error: float = 1.5, rounds: int = 1, q_stride: int = 3,
+                                 t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """refine_device for the homography (sift_hip_refine_homography_device)."""
+        self._refine_device(lib().sift_hip_refine_homography_device, "refine_homography_device", matches_ptr, count_ptr,
+                            cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, mask_ptr, out_ptr, out_count_ptr, accepted_ptr,
+                            max_error, rounds, q_stride, t_stride, stream)
+
+    def _refine_host(self, fn, what, dtype, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result, mask,
+                     max_error, rounds, q_stride, t_stride):
+        res = np.array([result], dtype)  # copies: the caller's record and mask are not changed
+        mask = np.array(np.asarray(mask, np.uint8).reshape(-1), np.uint8)
+        if len(mask) != max(cap, 0):
+            raise ValueError("one mask byte per row of the list (cap)")
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        n_out, accepted = ctypes.c_int(0), ctypes.c_int(0)
+        _check(fn(self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+                  t_stride, nt, max_error, rounds, _ptr(res), _ptr(mask) if cap > 0 else None, _ptr(out),
+                  ctypes.byref(n_out), ctypes.byref(accepted)), what)
+        return res[0], out[: n_out.value], mask, accepted.value
+
+    def refine_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                    result, mask, max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3):
+        """Synchronous (sift_hip_refine_fundamental_host): result (a VERIFY_RESULT_DTYPE record) and mask (cap bytes)
+        are host values as verify_host(full=True) returns them; the list and positions are device memory.  Returns
+        (the updated record, the inlier records, the updated mask, the number of accepted rounds)."""
+        return self._refine_host(lib().sift_hip_refine_fundamental_host, "refine_fundamental_host", VERIFY_RESULT_DTYPE,
+                                 matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result, mask, max_error, rounds,
+                                 q_stride, t_stride)
+
+    def refine_homography_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                               nt: int, result, mask, max_error: float = 1.5, rounds: int = 1, q_stride: int = 3,
+                               t_stride: int = 3):
+        """refine_host for the homography (sift_hip_refine_homography_host; a HOMOGRAPHY_RESULT_DTYPE record)."""
+        return self._refine_host(lib().sift_hip_refine_homography_host, "refine_homography_host",
+                                 HOMOGRAPHY_RESULT_DTYPE, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result,
+                                 mask, max_error, rounds, q_stride, t_stride)
+
+    def _refine_batched_device(self, fn, what, matches_ptr, counts_ptr, pairs, results_ptr, mask_ptr, out_ptr,
+                               out_counts_ptr, accepted_ptr, max_error, rounds, q_stride, t_stride, stream):
+        table, _ = self._pairs(pairs)
+        _check(fn(self._v, matches_ptr or None, counts_ptr or None, len(pairs), table, q_stride, t_stride, max_error,
+                  rounds, results_ptr or None, mask_ptr or None, out_ptr or None, out_counts_ptr or None,
+                  accepted_ptr or None, stream), what)
+
+    def refine_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int, mask_ptr: int,
+                              out_ptr: int = 0, out_counts_ptr: int = 0, accepted_ptr: int = 0, max_error: float = 1.5,
+                              rounds: int = 1, q_stride: int = 3, t_stride: int = 3,
+                              stream: Optional[int] = None) -> None:
+        """Enqueue the refit of every pair (sift_hip_refine_fundamental_batched_device) on what verify_batched_device
+        wrote: results_ptr (len(pairs) records) and mask_ptr (the caps' sum bytes) are updated in place; out_ptr,
+        out_counts_ptr and accepted_ptr (len(pairs) ints each) may be 0.  Pair p's bytes are the single call's."""
+        self._refine_batched_device(lib().sift_hip_refine_fundamental_batched_device, "refine_fundamental_batched_device",
+                                    matches_ptr, counts_ptr, pairs, results_ptr, mask_ptr, out_ptr, out_counts_ptr,
+                                    accepted_ptr, max_error, rounds, q_stride, t_stride, stream)
+
+    def refine_homography_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                         mask_ptr: int, out_ptr: int = 0, out_counts_ptr: int = 0, accepted_ptr: int = 0,
+                                         max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3,
+                                         stream: Optional[int] = None) -> None:
+        """refine_batched_device for the homography (sift_hip_refine_homography_batched_device)."""
+        self._refine_batched_device(lib().sift_hip_refine_homography_batched_device, "refine_homography_batched_device",
+                                    matches_ptr, counts_ptr, pairs, results_ptr, mask_ptr, out_ptr, out_counts_ptr,
+                                    accepted_ptr, max_error, rounds, q_stride, t_stride, stream)
+
+    def _refine_batched_host(self, fn, what, dtype, matches_ptr, counts_ptr, pairs, verified, max_error, rounds, q_stride,
+                             t_stride):
+        table, caps = self._pairs(pairs)
+        if len(verified) != len(pairs):
+            raise ValueError("one verified (record, records, mask) per pair")
+        row0 = np.concatenate([[0], np.cumsum([c if 0 <= c <= 65536 else 0 for c in caps])]).astype(int)
+        res = np.array([v[0] for v in verified], dtype) if len(pairs) else np.zeros(1, dtype)
+        mask = np.zeros(row0[-1], np.uint8)
+        for i, v in enumerate(verified):
+            mask[row0[i]: row0[i + 1]] = np.asarray(v[2], np.uint8).reshape(-1)
+        out = np.zeros(row0[-1], DMATCH_DTYPE)
+        n_out, accepted = np.zeros(max(len(pairs), 1), np.int32), np.zeros(max(len(pairs), 1), np.int32)
+        _check(fn(self._v, matches_ptr or None, counts_ptr or None, len(pairs), table, q_stride, t_stride, max_error,
+                  rounds, _ptr(res), _ptr(mask) if len(mask) else None, _ptr(out), _ptr(n_out), _ptr(accepted)), what)
+        return [(res[i].copy(), out[row0[i]: row0[i] + n_out[i]].copy(), mask[row0[i]: row0[i + 1]].copy(),
+                 int(accepted[i])) for i in range(len(pairs))]
+
+    def refine_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, verified: Sequence,
+                            max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3) -> list:
+        """Synchronous (sift_hip_refine_fundamental_batched_host): verified is verify_batched_host(full=True)'s list of
+        (record, records, mask); per pair what refine_host returns."""
+        return self._refine_batched_host(lib().sift_hip_refine_fundamental_batched_host, "refine_fundamental_batched_host",
+                                         VERIFY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, verified, max_error, rounds,
+                                         q_stride, t_stride)
+
+    def refine_homography_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, verified: Sequence,
+                                       max_error: float = 1.5, rounds: int = 1, q_stride: int = 3,
+                                       t_stride: int = 3) -> list:
+        """refine_batched_host for the homography (sift_hip_refine_homography_batched_host)."""
+        return self._refine_batched_host(lib().sift_hip_refine_homography_batched_host, "refine_homography_batched_host",
+                                         HOMOGRAPHY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, verified, max_error,
+                                         rounds, q_stride, t_stride)
+
+
+def _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit):
     if len(matches_per_pair) != len(xy_per_pair):
         raise ValueError("one (des_xy, src_xy) per match list")
     lists = [np.ascontiguousarray(np.asarray(m, DMATCH_DTYPE)).reshape(-1) for m in matches_per_pair]
@@ -1380,50 +1513,64 @@ def _verify_batched(host, matches_per_pair, xy_per_pair, max_error, hypotheses, 
     d = DeviceArray.from_numpy(np.concatenate(lists) if lists else np.zeros(0, DMATCH_DTYPE))
     dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
     pairs = [(dq.value, len(q), dt.value, len(t), len(m)) for m, (q, t), (dq, dt) in zip(lists, xy, dxy)]
-    return host(v, d.value if rows else 0, 0, pairs, max_error, hypotheses, seed, 2, 2)
+    if not refit:
+        return host(v, d.value if rows else 0, 0, pairs, max_error, hypotheses, seed, 2, 2)
+    verified = host(v, d.value if rows else 0, 0, pairs, max_error, hypotheses, seed, 2, 2, True)
+    refined = refine(v, d.value if rows else 0, 0, pairs, verified, max_error, refit, 2, 2)
+    return [(r[r.dtype.names[0]].reshape(3, 3).copy(), recs, int(r["hypothesis"])) for r, recs, _, _ in refined]
 
 
 def verifyFundamentalBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, max_error: float = 1.5,
-                             hypotheses: int = 1024, seed: int = 0) -> list:
+                             hypotheses: int = 1024, seed: int = 0, refit: int = 0) -> list:
     """verifyFundamental for P lists in one pass: matches_per_pair[p] a DMATCH_DTYPE array, xy_per_pair[p] =
     (des_xy, src_xy) host float arrays of rows with x, y first.  A list of what verifyFundamental returns per pair --
-    (F, the inlier records, the winning hypothesis or -1) --, pair p verified with the seed `seed + p`."""
-    return _verify_batched(Verifier.verify_batched_host, matches_per_pair, xy_per_pair, max_error, hypotheses, seed)
+    (F, the inlier records, the winning hypothesis or -1) --, pair p verified with the seed `seed + p`.  refit: as for verifyFundamental."""
+    return _verify_batched(Verifier.verify_batched_host, Verifier.refine_batched_host, matches_per_pair, xy_per_pair,
+                           max_error, hypotheses, seed, refit)
 
 
 def verifyHomographyBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, max_error: float = 1.5,
-                            hypotheses: int = 1024, seed: int = 0) -> list:
+                            hypotheses: int = 1024, seed: int = 0, refit: int = 0) -> list:
     """verifyFundamentalBatched for the homography: per pair what verifyHomography returns."""
-    return _verify_batched(Verifier.verify_homography_batched_host, matches_per_pair, xy_per_pair, max_error,
-                           hypotheses, seed)
+    return _verify_batched(Verifier.verify_homography_batched_host, Verifier.refine_homography_batched_host,
+                           matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit)
 
 
 def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
-                      hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3):
+                      hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3, refit: int = 0):
     """Geometric verification of a match list (matchList's output): (F 3 x 3 float32 with x_src^T F x_des = 0, the
     inlier records in input order, the winning hypothesis or -1 when there are fewer than 8 matches or no sample could
     be solved).  matches: a DMATCH_DTYPE array (uploaded here); des_xy / src_xy: DeviceBuffers or raw device pointers
     of n_des / n_src float rows with x, y first, as for matchListEpipolar.  The returned F is what matchListEpipolar
-    takes; sift_amd.cv.fundamental_lstsq refits a rank-2 F on the inliers."""
+    takes.  refit = 1..8: that many refit rounds on the device (Verifier.refine_host) follow -- F is then the rank-2
+    least-squares fit of its inliers whenever that fit counts at least as many; 0: the minimal-sample winner."""
     m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
     v = Verifier(max(len(m), 1), hypotheses)
     d = DeviceArray.from_numpy(m)
     qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
-    return v.verify_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, max_error, hypotheses, seed,
-                         des_stride, src_stride)
+    args = (d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src)
+    if not refit:
+        return v.verify_host(*args, max_error, hypotheses, seed, des_stride, src_stride)
+    r, _, mask = v.verify_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True)
+    r, recs, _, _ = v.refine_host(*args, r, mask, max_error, refit, des_stride, src_stride)
+    return r["F"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
 
 
 def verifyHomography(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
-                     hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3):
+                     hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3, refit: int = 0):
     """verifyFundamental for the homography: (H 3 x 3 float32 of unit norm with x_src ~ H x_des -- divide by H[2, 2]
     for cv::findHomography's scale --, the inlier records in input order, the winning hypothesis or -1 when there are
-    fewer than 4 matches or no sample was valid).  sift_amd.cv.homography_lstsq refits on the inliers."""
+    fewer than 4 matches or no sample was valid).  refit: as for verifyFundamental (Verifier.refine_homography_host)."""
     m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
     v = Verifier(max(len(m), 1), hypotheses)
     d = DeviceArray.from_numpy(m)
     qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
-    return v.verify_homography_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, max_error, hypotheses,
-                                    seed, des_stride, src_stride)
+    args = (d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src)
+    if not refit:
+        return v.verify_homography_host(*args, max_error, hypotheses, seed, des_stride, src_stride)
+    r, _, mask = v.verify_homography_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True)
+    r, recs, _, _ = v.refine_homography_host(*args, r, mask, max_error, refit, des_stride, src_stride)
+    return r["H"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
 
 
 def project_homography_device(H_ptr: int, xy_ptr: int, n: int, out_ptr: int, stride: int = 3, out_stride: int = 2,

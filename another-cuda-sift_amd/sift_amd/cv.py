@@ -632,6 +632,258 @@ def homography_lstsq(q_pts, t_pts) -> np.ndarray:
     return H / H[2, 2]
 
 
+# --- The refit of a verified model on its inliers: the rule of sift_hip_refine_* (include/sift_hip.h, "Refit of the
+# verified model") in numpy float64.  Every operation below is one IEEE float64 operation, rounded to nearest, in the
+# header's order; the nine results are rounded to float32 once.  The device performs the same operations in the same
+# order, so its bytes are this code's.
+
+REFIT_SLOTS = 256   # slot of record j: j mod 256
+REFIT_SWEEPS = 8    # Jacobi sweeps, for the 9 x 9 and the 3 x 3 problem alike
+REFIT_MAX_ROUNDS = 8
+_SQRT2 = np.float64(1.4142135623730951)
+
+
+def _slot_sum(v, fit):
+    """The one summation order of the refit rule, for the columns of v (n, c) float64 over the records fit marks:
+    record j belongs to slot j mod 256; a slot adds its fit records to +0 in ascending j; the 64 slots of each of the
+    four groups [64 g, 64 g + 64) combine by a halving tree (slot i += slot i + d, d = 32, 16 .. 1, i mod 64 < d);
+    the total is (g0 + g1) + (g2 + g3).  A record that is not fit adds nothing (as +0 it changes no sum)."""
+    return _slot_sum_rows([np.asarray(v, np.float64)], fit)
+
+
+def _jacobi_pivots(m: int):
+    """The pivot order of one sweep for odd m: round r = 0 .. m - 1 holds the pivots ((r + i) mod m, (r - i) mod m),
+    i = 1 .. (m - 1) / 2, each written (p, q) with p < q.  Every index pair occurs once per sweep; the pairs of a round
+    are disjoint, and index r rests."""
+    return [[tuple(sorted(((r + i) % m, (r - i) % m))) for i in range(1, (m - 1) // 2 + 1)] for r in range(m)]
+
+
+def _jacobi(A, sweeps: int = REFIT_SWEEPS):
+    """Cyclic Jacobi on a symmetric (m, m) float64 matrix, m odd: `sweeps` sweeps over the pivots in round-robin order
+    (_jacobi_pivots: m rounds of (m - 1) / 2 pivots on disjoint index pairs, which a device applies side by side -- a
+    rotation reads nothing an earlier rotation of its round wrote but the entries it shares with it, and those in
+    this order); a pivot whose entry is exactly 0 is skipped.  The rotation, with a = A[p][q]:
+        theta = (A[q][q] - A[p][p]) / (2 a);  t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0;
+        c = 1 / sqrt(t t + 1);  s = t c;
+        k != p, q:  A[k][p] = A[p][k] = c A[k][p] - s A[k][q],  A[k][q] = A[q][k] = s A[k][p] + c A[k][q] (old values);
+        A[p][p] -= t a;  A[q][q] += t a;  A[p][q] = A[q][p] = 0;
+        every k:  V[k][p] = c V[k][p] - s V[k][q],  V[k][q] = s V[k][p] + c V[k][q] (old values), V = I at the start.
+    Returns the column of V whose diagonal entry of A is the smallest (ties to the lowest index) -- the eigenvector of
+    the smallest eigenvalue -- and the diagonal."""
+    m = len(A)
+    A = [[float(A[r][c]) for c in range(m)] for r in range(m)]
+    V = [[1.0 if r == c else 0.0 for c in range(m)] for r in range(m)]
+    for _ in range(sweeps):
+        for rnd in _jacobi_pivots(m):
+            for p, q in rnd:
+                a = A[p][q]
+                if a == 0.0:
+                    continue
+                theta = np.float64(A[q][q] - A[p][p]) / np.float64(2.0 * a)  # numpy: x / 0 and inf pass silently
+                theta = float(theta)
+                root = float(np.sqrt(np.float64(theta * theta + 1.0)))
+                t = 1.0 / (abs(theta) + root)
+                if theta < 0.0:
+                    t = -t
+                c = 1.0 / float(np.sqrt(np.float64(t * t + 1.0)))
+                s = t * c
+                for k in range(m):
+                    if k != p and k != q:
+                        akp, akq = A[k][p], A[k][q]
+                        A[k][p] = A[p][k] = c * akp - s * akq
+                        A[k][q] = A[q][k] = s * akp + c * akq
+                A[p][p] = A[p][p] - t * a
+                A[q][q] = A[q][q] + t * a
+                A[p][q] = A[q][p] = 0.0
+                for k in range(m):
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = c * vkp - s * vkq
+                    V[k][q] = s * vkp + c * vkq
+    best = 0
+    for i in range(1, m):
+        if A[i][i] < A[best][best]:
+            best = i
+    return np.array([V[k][best] for k in range(m)], np.float64), np.array([A[i][i] for i in range(m)], np.float64)
+
+
+def _refit_points(pts_or_matches, q_xy, t_xy):
+    a = np.asarray(pts_or_matches)
+    if a.dtype.names:
+        return _match_points(a, q_xy, t_xy)
+    a = np.asarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("points must be (n, 4): qx, qy, tx, ty")
+    return a
+
+
+def _refit(model: str, pts, mask, sweeps: int = REFIT_SWEEPS, detail: bool = False):
+    """One fit of the refit rule on gathered points (n, 4) float32 and their mask: (model (9,) float32, valid)."""
+    assert pts.dtype == np.float32
+    n = len(pts)
+    mask = np.asarray(mask).reshape(-1)[:n]
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    need = 8 if model == "F" else 4
+    zero = np.zeros(9, np.float32)
+    fit = (mask != 0) & np.isfinite(pts).all(1)
+    m = int(fit.sum())
+    if m < need:
+        return (zero, False, None) if detail else (zero, False)
+    p = pts.astype(np.float64)
+    with np.errstate(all="ignore"):
+        mean = _slot_sum(p, fit) / np.float64(m)                       # (mqx, mqy, mtx, mty)
+        d = p - mean
+        dist = np.stack([np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]), np.sqrt(d[:, 2] * d[:, 2] + d[:, 3] * d[:, 3])], 1)
+        md = _slot_sum(dist, fit) / np.float64(m)
+        sq, st = _SQRT2 / md[0], _SQRT2 / md[1]
+        if not (np.isfinite(sq) and np.isfinite(st)):
+            return (zero, False, None) if detail else (zero, False)
+        x, y, u, v = d[:, 0] * sq, d[:, 1] * sq, d[:, 2] * st, d[:, 3] * st
+        one, nil = np.ones(n), np.zeros(n)
+        if model == "F":
+            rows = [np.stack([u * x, u * y, u, v * x, v * y, v, x, y, one], 1)]
+        else:
+            rows = [np.stack([x, y, one, nil, nil, nil, -(u * x), -(u * y), -u], 1),
+                    np.stack([nil, nil, nil, x, y, one, -(v * x), -(v * y), -v], 1)]
+        iu = [(r, c) for r in range(9) for c in range(r, 9)]
+        # a record adds its rows' products one row after the other; a product of a structural zero adds nothing
+        if len(rows) == 1:
+            terms = np.stack([rows[0][:, r] * rows[0][:, c] for r, c in iu], 1)
+            sums = _slot_sum(terms, fit)
+        else:
+            sums = _slot_sum_rows([np.stack([a[:, r] * a[:, c] for r, c in iu], 1) for a in rows], fit)
+        M = np.zeros((9, 9), np.float64)
+        for (r, c), s in zip(iu, sums):
+            M[r, c] = M[c, r] = s
+        g, _ = _jacobi(M, sweeps)
+        G = g.reshape(3, 3).copy()
+        if model == "F":
+            GtG = np.zeros((3, 3), np.float64)
+            for r in range(3):
+                for c in range(r, 3):
+                    GtG[r, c] = GtG[c, r] = (G[0, r] * G[0, c] + G[1, r] * G[1, c]) + G[2, r] * G[2, c]
+            v3, _ = _jacobi(GtG, sweeps)
+            Gv = [(G[r, 0] * v3[0] + G[r, 1] * v3[1]) + G[r, 2] * v3[2] for r in range(3)]
+            for r in range(3):
+                for c in range(3):
+                    G[r, c] = G[r, c] - Gv[r] * v3[c]
+        oqx, oqy = -(sq * mean[0]), -(sq * mean[1])
+        T = np.zeros((3, 3), np.float64)
+        T[:, 0] = G[:, 0] * sq
+        T[:, 1] = G[:, 1] * sq
+        T[:, 2] = (G[:, 0] * oqx + G[:, 1] * oqy) + G[:, 2]
+        R = np.zeros((3, 3), np.float64)
+        if model == "F":
+            otx, oty = -(st * mean[2]), -(st * mean[3])
+            R[0] = st * T[0]
+            R[1] = st * T[1]
+            R[2] = (otx * T[0] + oty * T[1]) + T[2]
+        else:
+            R[0] = T[0] / st + mean[2] * T[2]
+            R[1] = T[1] / st + mean[3] * T[2]
+            R[2] = T[2]
+        R = R.reshape(9)
+        ss = R[0] * R[0]
+        for i in range(1, 9):
+            ss = ss + R[i] * R[i]
+        R = R / np.sqrt(ss)
+        ok = True
+        if model == "H":
+            j0 = int(np.flatnonzero(fit)[0])
+            w0 = (R[6] * p[j0, 0] + R[7] * p[j0, 1]) + R[8]
+            if w0 < 0:
+                R = -R
+            ok = bool(w0 != 0)
+        out = R.astype(np.float32)
+        ok = ok and bool(np.isfinite(out).all())
+    assert M.dtype == np.float64 and R.dtype == np.float64 and out.dtype == np.float32
+    if not ok:
+        out = zero
+    return (out, ok, G) if detail else (out, ok)
+
+
+def _slot_sum_rows(terms, fit):
+    """_slot_sum where a record adds several terms to its slot one after the other (the homography's two rows): the
+    slot's order is record by record in ascending j, and within a record term by term."""
+    n, c = terms[0].shape
+    k = len(terms)
+    inter = np.stack(terms, 1)  # (n, k, c): record j's terms in order
+    rows = -(-max(n, 1) // REFIT_SLOTS)
+    pad = np.zeros((rows * REFIT_SLOTS, k, c), np.float64)
+    pad[:n] = np.where(np.asarray(fit, bool)[:, None, None], inter, 0.0)
+    pad = pad.reshape(rows, REFIT_SLOTS, k, c)
+    slots = np.zeros((REFIT_SLOTS, c), np.float64)
+    for r in range(rows):
+        for i in range(k):
+            slots = slots + pad[r, :, i]
+    g = slots.reshape(4, 64, c)
+    d = 32
+    while d >= 1:
+        g = g[:, :d] + g[:, d:2 * d]
+        d //= 2
+    g = g[:, 0]
+    return (g[0] + g[1]) + (g[2] + g[3])
+
+
+def refit_fundamental(pts_or_matches, q_xy=None, t_xy=None, mask=None):
+    """One fit of the refit rule (include/sift_hip.h) for the fundamental matrix: the least-squares, rank-2 F of the
+    records mask marks, (F (9,) float32 of unit norm, valid).  pts_or_matches: gathered points (n, 4) float32 (qx, qy,
+    tx, ty; q_xy and t_xy are then ignored), or DMATCH_DTYPE records with their position arrays.  An invalid fit
+    (fewer than 8 fit records, a degenerate normalisation, a non-finite result) has F all zero."""
+    pts = _refit_points(pts_or_matches, q_xy, t_xy)
+    return _refit("F", pts, np.ones(len(pts), np.uint8) if mask is None else mask)
+
+
+def refit_homography(pts_or_matches, q_xy=None, t_xy=None, mask=None):
+    """refit_fundamental for the homography: the least-squares H of the records mask marks (at least 4), of unit norm
+    and with w > 0 at the first fit record; w = 0 there is invalid."""
+    pts = _refit_points(pts_or_matches, q_xy, t_xy)
+    return _refit("H", pts, np.ones(len(pts), np.uint8) if mask is None else mask)
+
+
+def _refine(model, passes, matches, q_xy, t_xy, result, max_error, rounds):
+    from . import DMATCH_DTYPE
+
+    if not 1 <= int(rounds) <= REFIT_MAX_ROUNDS:
+        raise ValueError("rounds must lie in 1..8")
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    out = dict(result)
+    cur = np.asarray(result[model], np.float32).reshape(9).copy()
+    mask = np.asarray(result["mask"], np.uint8).reshape(-1)[:n].copy()
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    inliers = int(result["inliers"])
+    accepted = 0
+    pts = _match_points(matches, q_xy, t_xy)
+    if int(result["hypothesis"]) >= 0 and geometry_usable(cur):
+        for _ in range(int(rounds)):
+            cand, ok = _refit(model, pts, mask)
+            if not ok:
+                break  # the state is unchanged, so every later round fails the same way
+            keep = passes(pts, cand, max_error)[0]
+            if int(keep.sum()) < inliers:
+                break
+            cur, mask, inliers = cand, keep.astype(np.uint8), int(keep.sum())
+            accepted += 1
+    assert cur.dtype == np.float32 and mask.dtype == np.uint8
+    out[model], out["mask"], out["inliers"], out["list"] = cur, mask, inliers, matches[mask != 0]
+    out["accepted"] = accepted
+    return out
+
+
+def refine_fundamental(matches, q_xy, t_xy, result, max_error=1.5, rounds: int = 1) -> dict:
+    """The whole refit operation (sift_hip_refine_fundamental_*) in numpy, on a ransac_fundamental dict (read: F,
+    inliers, hypothesis, mask): `rounds` rounds of fit -> rescore -> accept.  Returns the dict with F, inliers, mask
+    and list updated and `accepted`, the number of accepted rounds; every other entry is the input's."""
+    return _refine("F", _sampson_pass, matches, q_xy, t_xy, result, max_error, rounds)
+
+
+def refine_homography(matches, q_xy, t_xy, result, max_error=1.5, rounds: int = 1) -> dict:
+    """refine_fundamental for a ransac_homography dict (sift_hip_refine_homography_*)."""
+    return _refine("H", _transfer_pass, matches, q_xy, t_xy, result, max_error, rounds)
+
+
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     import cv2
 

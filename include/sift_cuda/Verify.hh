@@ -113,6 +113,49 @@ public:
                                                             const std::vector<VerifyPair>& pairs, int query_stride,
                                                             int train_stride, const VerifyParams& params = {});
 
+    // The refit of a verified model on its inliers (sift_hip_refine_*; the rule: include/sift_hip.h, "Refit of the
+    // verified model"): `rounds` (1..8) rounds of least-squares fit -> rescore -> accept on the list, count and
+    // positions of the verify call that wrote *result and mask, both updated in place (device memory).  out,
+    // out_count and accepted (the number of accepted rounds) may be nullptr.  Enqueued on `stream`, not synchronised.
+    void refineDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                      const float* train_xy, int train_stride, int nt, float max_error, int rounds, VerifyResult* result,
+                      uint8_t* mask, DMatch* out = nullptr, int* out_count = nullptr, int* accepted = nullptr,
+                      void* stream = nullptr);
+    void refineHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                                int nq, const float* train_xy, int train_stride, int nt, float max_error, int rounds,
+                                HomographyResult* result, uint8_t* mask, DMatch* out = nullptr, int* out_count = nullptr,
+                                int* accepted = nullptr, void* stream = nullptr);
+    // Synchronous; the list and positions on the device, `result` and `mask` (cap bytes) on the host, both updated in
+    // place; inliers (nullable) receives the records of the updated mask.  Returns the number of accepted rounds.
+    int refineHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                   const float* train_xy, int train_stride, int nt, float max_error, int rounds, VerifyResult& result,
+                   std::vector<uint8_t>& mask, std::vector<DMatch>* inliers = nullptr);
+    int refineHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                             int nq, const float* train_xy, int train_stride, int nt, float max_error, int rounds,
+                             HomographyResult& result, std::vector<uint8_t>& mask, std::vector<DMatch>* inliers = nullptr);
+    // All pairs of a batch (sift_hip_refine_*_batched_*): results, out_counts and accepted hold pairs.size() entries,
+    // mask and out the caps' sum rows; pair p's bytes are the single call's.
+    void refineBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                             int query_stride, int train_stride, float max_error, int rounds, VerifyResult* results,
+                             uint8_t* mask, DMatch* out = nullptr, int* out_counts = nullptr, int* accepted = nullptr,
+                             void* stream = nullptr);
+    void refineHomographyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                       int query_stride, int train_stride, float max_error, int rounds,
+                                       HomographyResult* results, uint8_t* mask, DMatch* out = nullptr,
+                                       int* out_counts = nullptr, int* accepted = nullptr, void* stream = nullptr);
+    // Synchronous; results (one per pair) and mask (the caps' sum bytes) on the host, updated in place; out (nullable)
+    // is resized to the caps' sum rows and out_counts (nullable) to one count per pair.  Returns the accepted rounds
+    // per pair.
+    std::vector<int> refineBatchedHost(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                       int query_stride, int train_stride, float max_error, int rounds,
+                                       std::vector<VerifyResult>& results, std::vector<uint8_t>& mask,
+                                       std::vector<DMatch>* out = nullptr, std::vector<int>* out_counts = nullptr);
+    std::vector<int> refineHomographyBatchedHost(const DMatch* matches, const int* counts,
+                                                 const std::vector<VerifyPair>& pairs, int query_stride, int train_stride,
+                                                 float max_error, int rounds, std::vector<HomographyResult>& results,
+                                                 std::vector<uint8_t>& mask, std::vector<DMatch>* out = nullptr,
+                                                 std::vector<int>* out_counts = nullptr);
+
     sift_hip_verifier* handle() const { return m_handle; }
 
 private:
@@ -128,6 +171,15 @@ TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const floa
 // The same one shot for the homography.
 PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                                 int nt, const VerifyParams& params = {}, int query_stride = 3, int train_stride = 3);
+
+// The one shots followed by `refit` refit rounds on the device (Verifier::refineHost): the geometry is then the
+// least-squares model of its inliers (F of rank 2) whenever that model counts at least as many.  refit = 0: the calls
+// above, byte for byte.
+TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
+                                  const float* train_xy, int nt, const VerifyParams& params, int query_stride,
+                                  int train_stride, int refit);
+PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const VerifyParams& params, int query_stride, int train_stride, int refit);
 
 // Enqueued on `stream`, not synchronised (sift_hip_project_homography_device): row i of out_xy = row i of xy carried
 // over by H, NaN where it lands behind the camera.  H: 9 floats of device memory (a HomographyResult's address); xy /

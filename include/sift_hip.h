@@ -1244,6 +1244,148 @@ int sift_hip_verify_homography_batched_host(sift_hip_verifier_t v, const sift_hi
  * sift_hip_verify_homography_hypotheses_host return SIFT_HIP_ERR_STATE (the
  * scratch holds P pairs' hypotheses) until a single-pair verify call has run. */
 
+/* --- Refit of the verified model: least-squares F and H on the inliers ----------
+ *
+ * A verify call returns the winning minimal-sample model (8 points for F, 4 for
+ * H).  A refine call refits that model on its inliers, on the device, rescores
+ * it with the verifier's own predicate and keeps it when it counts at least as
+ * many records: the local-optimisation step of LO-RANSAC, and the algebraic
+ * least-squares fit cv::findFundamentalMat / cv::findHomography end with (no
+ * Levenberg-Marquardt polish).  Its result records, mask and out lists have the
+ * layouts the guided matchers and the projection read.  The numpy mirror
+ * sift_amd.cv.refit_fundamental / refit_homography (one fit) and
+ * refine_fundamental / refine_homography (the operation) is the specification:
+ * the device equals it byte for byte.
+ *
+ * The rule.  One round, for a list of n records, the current result record and
+ * its mask:
+ *   1. Fit set: the records j < n with mask[j] != 0 whose four gathered
+ *      coordinates (qx, qy, tx, ty; NaN for an index outside its position
+ *      array) are finite; m their number, j0 the first.  A masked record with a
+ *      NaN coordinate is skipped.  m < 8 (H: 4): the refit is invalid.
+ *   2. Arithmetic: IEEE float64 throughout, nothing fused, correctly rounded
+ *      division and square root.  Coordinates convert float32 -> float64
+ *      exactly; the nine results are rounded to float32 once, at the end.
+ *   3. Summation order, for every sum below: record j belongs to slot j mod 256;
+ *      a slot adds its fit records to +0 in ascending j (a record with two rows
+ *      adds the even row's term, then the odd row's); the 64 slots of each group
+ *      [64 g, 64 g + 64), g = 0..3, combine by a halving tree (slot i += slot
+ *      i + d for d = 32, 16, .. 1, i mod 64 < d); the total is
+ *      (g0 + g1) + (g2 + g3).  It depends on j alone, not on a launch shape.
+ *   4. Hartley normalisation of each side: mean = sum / m per coordinate;
+ *      md = (sum of sqrt(dx dx + dy dy)) / m with dx = x - mean_x;
+ *      s = 1.4142135623730951 / md; x' = dx s.  s not finite on either side
+ *      (all points equal): invalid.
+ *   5. Normal matrix M = A^T A, its 45 upper-triangle sums of a_r a_c, over the
+ *      rows the minimal solvers use, in normalised coordinates (q' = (x, y),
+ *      t' = (u, v)).  F, one row per record: (u x, u y, u, v x, v y, v, x, y, 1).
+ *      H, two rows: (x, y, 1, 0, 0, 0, -(u x), -(u y), -u) and
+ *      (0, 0, 0, x, y, 1, -(v x), -(v y), -v); a product with a structural zero
+ *      adds nothing.
+ *   6. Smallest eigenvector of M by cyclic Jacobi: V = I; 8 sweeps.  A sweep
+ *      of an m x m matrix (m = 9, and 3 in step 7) visits the pivots in
+ *      round-robin order: round r = 0 .. m - 1 holds the pivots
+ *      ((r + i) mod m, (r - i) mod m), i = 1 .. (m - 1) / 2, each taken as
+ *      (p, q) with p < q.  Every index pair occurs once per sweep, and the
+ *      pivots of a round are disjoint (index r rests), so a device may apply a
+ *      round's rotations side by side: the only entries two of them share are
+ *      updated by the earlier pivot first, which is this sequential order.  A
+ *      pivot with M[p][q] exactly 0 is skipped.  With a = M[p][q]:
+ *        theta = (M[q][q] - M[p][p]) / (2 a);
+ *        t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0;
+ *        c = 1 / sqrt(t t + 1);  s = t c;
+ *        k != p, q: M[k][p] = M[p][k] = c M[k][p] - s M[k][q] and
+ *                   M[k][q] = M[q][k] = s M[k][p] + c M[k][q] (old values);
+ *        M[p][p] -= t a;  M[q][q] += t a;  M[p][q] = M[q][p] = 0;
+ *        every k:   V[k][p] = c V[k][p] - s V[k][q] and
+ *                   V[k][q] = s V[k][p] + c V[k][q] (old values).
+ *      g = the column of V whose diagonal entry of M is the smallest (ties to
+ *      the lowest index), G = g as 3 x 3 row-major.  The sweep count: on every
+ *      test case 6 sweeps already give the float32 output of 8, and a 9th
+ *      changes none (tests/test_refit_cases.py checks 8 against 9).
+ *   7. F only, rank 2, in normalised coordinates: N = G^T G with
+ *      N[r][c] = (G[0][r] G[0][c] + G[1][r] G[1][c]) + G[2][r] G[2][c]; v its
+ *      eigenvector of the smallest eigenvalue by the same routine (3 x 3, 8
+ *      sweeps); w[r] = (G[r][0] v[0] + G[r][1] v[1]) + G[r][2] v[2];
+ *      G[r][c] -= w[r] v[c].
+ *   8. Denormalise with the minimal solvers' formulas in float64 (ox = -(s mean_x)):
+ *      T = G Tq, then F = Tt^T T, or H = Tt^-1 T.  Scale to unit Frobenius norm
+ *      (squares summed in index order, each entry divided by the root).  H only:
+ *      w0 = (H[6] qx + H[7] qy) + H[8] at record j0's raw coordinates; w0 < 0
+ *      negates H; w0 = 0 is invalid.  Round to float32; a non-finite entry is
+ *      invalid.  An invalid refit is all zero.
+ *   9. Rescore the refit over all n records with the model's predicate (the
+ *      Sampson / transfer test of the verify rule, float32, same max_error).
+ *      Accept when the refit is valid and passes at least result.inliers
+ *      records: the record's model and inliers, and mask[0, n), become the
+ *      refit's.  Otherwise everything stays as it was.  hypothesis, matches and
+ *      valid_hypotheses never change.
+ * `rounds` (1..8) repeats this; each round fits on the mask the one before left.
+ * A rejected round leaves the state unchanged, so every later round rejects too.
+ * A current record that is empty (hypothesis < 0) or whose nine floats are not
+ * all finite and not all zero stays as it is.  After the last round `out` holds
+ * the records j < n with mask[j] != 0 in input order and out_count their number
+ * (rows past them are not written); `accepted` receives the number of accepted
+ * rounds.
+ *
+ * Consequences.  The inlier count never decreases.  The output is a function of
+ * the inputs alone: the same bytes in every run, and in the single and batched
+ * forms (pair p of a batched call equals the single call on that pair).
+ *
+ * Device forms: enqueued on `stream`, not synchronised, no allocation (all
+ * scratch is the verifier's), capturable.  The list, count(s), cap(s) and
+ * positions are the matching verify call's; result(s) and mask are in-out device
+ * memory (mask: cap bytes, the caps' sum for a batch; bytes at and past n are
+ * neither read nor written); out, out_count(s) and accepted may each be NULL.
+ * SIFT_HIP_ERR_INVALID, with nothing launched, for what the matching verify call
+ * refuses on the same arguments (hypotheses aside) and for: a null result; a
+ * null mask with cap (a batch: the caps' sum) > 0; rounds outside 1..8.
+ * Host forms: synchronous; the list and positions still live on the device,
+ * result(s) and mask are in-out host memory, out_host / out_count(s)_host /
+ * accepted_host (each nullable) receive host copies. */
+int sift_hip_refine_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                       const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                       int train_stride, int nt, float max_error, int rounds,
+                                       sift_hip_verify_result* result, uint8_t* mask, sift_hip_dmatch* out,
+                                       int* out_count, int* accepted, void* stream);
+int sift_hip_refine_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, float max_error, int rounds,
+                                     sift_hip_verify_result* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,
+                                     int* out_count_host, int* accepted_host);
+int sift_hip_refine_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                      int train_stride, int nt, float max_error, int rounds,
+                                      sift_hip_homography_result* result, uint8_t* mask, sift_hip_dmatch* out,
+                                      int* out_count, int* accepted, void* stream);
+int sift_hip_refine_homography_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                    const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                    int train_stride, int nt, float max_error, int rounds,
+                                    sift_hip_homography_result* result_host, uint8_t* mask_host,
+                                    sift_hip_dmatch* out_host, int* out_count_host, int* accepted_host);
+/* The batched forms: results, out_counts and accepted hold P entries, mask and
+ * out the caps' sum rows, laid out as in the batched verify calls. */
+int sift_hip_refine_fundamental_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                               int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                               int train_stride, float max_error, int rounds,
+                                               sift_hip_verify_result* results, uint8_t* mask, sift_hip_dmatch* out,
+                                               int* out_counts, int* accepted, void* stream);
+int sift_hip_refine_fundamental_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                             int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                             float max_error, int rounds, sift_hip_verify_result* results_host,
+                                             uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,
+                                             int* accepted_host);
+int sift_hip_refine_homography_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                              int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                              int train_stride, float max_error, int rounds,
+                                              sift_hip_homography_result* results, uint8_t* mask, sift_hip_dmatch* out,
+                                              int* out_counts, int* accepted, void* stream);
+int sift_hip_refine_homography_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                            int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                            float max_error, int rounds, sift_hip_homography_result* results_host,
+                                            uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,
+                                            int* accepted_host);
+
 /* --- Multi-GPU (the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
 
