@@ -72,28 +72,12 @@ $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_multi.cpp $(CXX_SRCS) \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
-# Argument validation of the verifier's C++ surface (verify_cxx.cpp), CPU only: tests/test_verify_asan.py.
-$(ASAN_DIR)/test_verify_args: tests/cpp/test_verify_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
+# Argument validation of the verifier's C++ surface (verify_cxx.cpp), CPU only: test_verify_args (run by
+# tests/test_verify_asan.py), test_homography_args for the homography calls and the projection, test_verify_batched_args
+# for the batched calls and test_refit_args for the refit calls, each with its tests/test_*_asan.py.
+$(ASAN_DIR)/test_%_args: tests/cpp/test_%_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
-	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_verify_args.cpp $(SRC)/verify_cxx.cpp \
-	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
-
-# The same for the homography calls and the projection: tests/test_homography_asan.py.
-$(ASAN_DIR)/test_homography_args: tests/cpp/test_homography_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
-	@mkdir -p $(ASAN_DIR)
-	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_homography_args.cpp $(SRC)/verify_cxx.cpp \
-	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
-
-# The same for the batched calls: tests/test_verify_batched_asan.py.
-$(ASAN_DIR)/test_verify_batched_args: tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
-	@mkdir -p $(ASAN_DIR)
-	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_verify_batched_args.cpp $(SRC)/verify_cxx.cpp \
-	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
-
-# The same for the refit calls: tests/test_refit_asan.py.
-$(ASAN_DIR)/test_refit_args: tests/cpp/test_refit_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
-	@mkdir -p $(ASAN_DIR)
-	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ tests/cpp/test_refit_args.cpp $(SRC)/verify_cxx.cpp \
+	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ $< $(SRC)/verify_cxx.cpp \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
 clean:

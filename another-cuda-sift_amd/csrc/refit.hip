@@ -449,49 +449,37 @@ __global__ __launch_bounds__(kAcceptThreads) void k_refit_accept(List list, cons
     if (tid == 0 && out_count) *out_count = base;
 }
 
+// The launchers: one workgroup per pair (list_pairs), the model picks the instantiation.
 template <class List>
-static void fit(VerifyModel model, const List& list, dim3 grid, const float4* pts, const uint8_t* mask,
-                const VerifyResult* result, RefitCandidate* cand, hipStream_t s) {
-    if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_refit_fit<VerifyModel::Homography, List>), grid, dim3(kRefitThreads), 0, s, list, pts, mask,
-                           result, cand);
-    else
-        hipLaunchKernelGGL((k_refit_fit<VerifyModel::Fundamental, List>), grid, dim3(kRefitThreads), 0, s, list, pts, mask,
-                           result, cand);
-}
-
-template <class List>
-static void accept(VerifyModel model, const List& list, dim3 grid, const float4* pts, const RefitCandidate* cand, float e2,
-                   VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted, bool first_round,
-                   hipStream_t s) {
-    if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_refit_accept<TransferPass, List>), grid, dim3(kAcceptThreads), 0, s, list, pts, cand, e2,
-                           result, mask, out, out_count, accepted, first_round ? 1 : 0);
-    else
-        hipLaunchKernelGGL((k_refit_accept<SampsonPass, List>), grid, dim3(kAcceptThreads), 0, s, list, pts, cand, e2,
-                           result, mask, out, out_count, accepted, first_round ? 1 : 0);
-}
-
-void launch_refit_fit(VerifyModel model, const VerifyInput& in, const float4* pts, const uint8_t* mask,
+void launch_refit_fit(VerifyModel model, const List& list, const float4* pts, const uint8_t* mask,
                       const VerifyResult* result, RefitCandidate* cand, hipStream_t s) {
-    fit(model, in, dim3(1), pts, mask, result, cand, s);
+    const dim3 grid(1, list_pairs(list)), block(kRefitThreads);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL((k_refit_fit<VerifyModel::Homography, List>), grid, block, 0, s, list, pts, mask, result, cand);
+    else
+        hipLaunchKernelGGL((k_refit_fit<VerifyModel::Fundamental, List>), grid, block, 0, s, list, pts, mask, result, cand);
 }
 
-void launch_refit_accept(VerifyModel model, const VerifyInput& in, const float4* pts, const RefitCandidate* cand,
-                         float e2, VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
+template <class List>
+void launch_refit_accept(VerifyModel model, const List& list, const float4* pts, const RefitCandidate* cand, float e2,
+                         VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
                          bool first_round, hipStream_t s) {
-    accept(model, in, dim3(1), pts, cand, e2, result, mask, out, out_count, accepted, first_round, s);
+    const dim3 grid(1, list_pairs(list)), block(kAcceptThreads);
+    if (model == VerifyModel::Homography)
+        hipLaunchKernelGGL((k_refit_accept<TransferPass, List>), grid, block, 0, s, list, pts, cand, e2, result, mask, out,
+                           out_count, accepted, first_round ? 1 : 0);
+    else
+        hipLaunchKernelGGL((k_refit_accept<SampsonPass, List>), grid, block, 0, s, list, pts, cand, e2, result, mask, out,
+                           out_count, accepted, first_round ? 1 : 0);
 }
 
-void launch_refit_fit_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const uint8_t* mask,
-                              const VerifyResult* results, RefitCandidate* cand, hipStream_t s) {
-    fit(model, batch, dim3(1, batch.P), pts, mask, results, cand, s);
-}
-
-void launch_refit_accept_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts,
-                                 const RefitCandidate* cand, float e2, VerifyResult* results, uint8_t* mask,
-                                 MatchRecord* out, int* out_counts, int* accepted, bool first_round, hipStream_t s) {
-    accept(model, batch, dim3(1, batch.P), pts, cand, e2, results, mask, out, out_counts, accepted, first_round, s);
-}
+#define SIFT_REFIT_LAUNCHERS(List)                                                                                  \
+    template void launch_refit_fit<List>(VerifyModel, const List&, const float4*, const uint8_t*, const VerifyResult*, \
+                                         RefitCandidate*, hipStream_t);                                             \
+    template void launch_refit_accept<List>(VerifyModel, const List&, const float4*, const RefitCandidate*, float,   \
+                                            VerifyResult*, uint8_t*, MatchRecord*, int*, int*, bool, hipStream_t);
+SIFT_REFIT_LAUNCHERS(VerifyInput)
+SIFT_REFIT_LAUNCHERS(VerifyBatch)
+#undef SIFT_REFIT_LAUNCHERS
 
 }  // namespace sift_amd

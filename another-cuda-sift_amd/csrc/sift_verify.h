@@ -53,9 +53,19 @@ struct VerifyResult {
 };
 static_assert(sizeof(VerifyResult) == 52, "sift_hip_verify_result layout");
 
+// The launchers are templates over the list, instantiated for VerifyInput and VerifyBatch (verify.hip, refit.hip).  A
+// batch runs the same step for all its P pairs in one launch, pair p = blockIdx.y on its own slices -- points, mask
+// and out rows at row0[p]; samples at m K p (m = 8 / 4), models at 9 K p, valid flags and counts at K p; its result,
+// candidate, out_count and accepted at p -- with the seed `seed + p` (wrapping).  A workgroup serves one pair.
+inline int list_pairs(const VerifyInput&) { return 1; }
+inline int list_pairs(const VerifyBatch& b) { return b.P; }
+inline int list_extent(const VerifyInput& in) { return in.cap; }  // the rows the gather's grid covers
+inline int list_extent(const VerifyBatch& b) { return b.max_cap; }
+
 // k_verify_gather: match j -> pts[j] = (qx, qy, tx, ty), NaN x 4 for a record
 // with an index outside its position array; j in [n, cap) is not written.
-void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s);
+template <class List>
+void launch_verify_gather(const List& list, float4* pts, hipStream_t s);
 
 // The model a verify call fits: it selects the hypothesis kernel and the
 // predicate the score and select kernels are instantiated with.
@@ -65,40 +75,28 @@ enum class VerifyModel { Fundamental = 1, Homography = 2 };
 // m matches (m = 8 for the fundamental matrix, 4 for the homography;
 // samples[m k ..], -1 when n < m) and solves them: F[9 k ..] and valid[k] (an
 // invalid hypothesis has F all zero).
-void launch_verify_hypotheses(VerifyModel model, const VerifyInput& in, const float4* pts, int K, unsigned seed,
-                              int* samples, float* F, int* valid, hipStream_t s);
+template <class List>
+void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, int* samples,
+                              float* F, int* valid, hipStream_t s);
 
 // k_verify_score: counts[k] = the matches j < n that pass the model's predicate
 // (Sampson distance / forward transfer error) under F[9 k ..] with
 // e2 = max_error^2; 0 where valid (nullable) says the hypothesis is invalid.
-void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
-                         int K, float e2, int* counts, hipStream_t s);
+template <class List>
+void launch_verify_score(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid, int K,
+                         float e2, int* counts, hipStream_t s);
 
 // k_verify_select: the winner (most inliers among the valid, ties to the lowest
 // k) into *result (sift_hip_homography_result has the same layout), its inlier
 // mask (cap bytes, nullable), the inlier records in input order (out, nullable)
-// and their number (out_count, nullable).
-void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+// and their number (out_count, nullable).  A batch: P results and out_counts, batch.rows rows of out and mask.
+template <class List>
+void launch_verify_select(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid,
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s);
 
-// The batched twins: the same four steps for all P pairs of a batch in one
-// launch each, pair p = blockIdx.y running the single-pair body on its own
-// slices -- points at row0[p], samples at m K p (m = 8 / 4), models at 9 K p,
-// valid flags and counts at K p -- with the seed `seed + p` (wrapping).
-// results, out_counts: P entries; out, mask: batch.rows rows (each nullable as
-// above).  A workgroup serves one pair.
-void launch_verify_gather_batched(const VerifyBatch& batch, float4* pts, hipStream_t s);
-void launch_verify_hypotheses_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, int K,
-                                      unsigned seed, int* samples, float* F, int* valid, hipStream_t s);
-void launch_verify_score_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
-                                 const int* valid, int K, float e2, int* counts, hipStream_t s);
-void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
-                                  const int* valid, const int* counts, int K, float e2, VerifyResult* results,
-                                  MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s);
-
 // The refit of a verified model on its inliers (refit.hip; sift_hip_refine_*, the rule is in include/sift_hip.h).
-// One round is two launches, both with one workgroup per pair (blockIdx.y in a batch):
+// One round is two launches, both with one workgroup per pair:
 // k_refit_fit: the least-squares model of the records j < n with mask[j] != 0 and finite gathered points, under the
 //   current record *result, into the verifier's scratch record *cand (valid = 0: no refit, the model all zero).
 // k_refit_accept: the candidate rescored over the n records with the model's predicate; when it is valid and counts
@@ -109,17 +107,13 @@ struct RefitCandidate {
     float m[9];
     int valid;
 };
-void launch_refit_fit(VerifyModel model, const VerifyInput& in, const float4* pts, const uint8_t* mask,
+template <class List>
+void launch_refit_fit(VerifyModel model, const List& list, const float4* pts, const uint8_t* mask,
                       const VerifyResult* result, RefitCandidate* cand, hipStream_t s);
-void launch_refit_accept(VerifyModel model, const VerifyInput& in, const float4* pts, const RefitCandidate* cand,
-                         float e2, VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
+template <class List>
+void launch_refit_accept(VerifyModel model, const List& list, const float4* pts, const RefitCandidate* cand, float e2,
+                         VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
                          bool first_round, hipStream_t s);
-// The batched twins: pair p's points, mask and out rows at row0[p], its result, candidate, out_count and accepted at p.
-void launch_refit_fit_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const uint8_t* mask,
-                              const VerifyResult* results, RefitCandidate* cand, hipStream_t s);
-void launch_refit_accept_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts,
-                                 const RefitCandidate* cand, float e2, VerifyResult* results, uint8_t* mask,
-                                 MatchRecord* out, int* out_counts, int* accepted, bool first_round, hipStream_t s);
 
 // k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
 // `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.

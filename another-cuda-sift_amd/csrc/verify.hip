@@ -571,79 +571,60 @@ __global__ __launch_bounds__(256) void k_project_homography_batch(const char* ge
     pr.out[(size_t)i * out_stride + 1] = front ? py / w : NAN;
 }
 
-void launch_verify_gather(const VerifyInput& in, float4* pts, hipStream_t s) {
-    if (in.cap > 0)
-        hipLaunchKernelGGL(k_verify_gather<VerifyInput>, dim3((in.cap + 255) / 256), dim3(256), 0, s, in, pts);
+// The launchers: one per step over the list type.  The grid's y and the gather's extent are the list's (list_pairs,
+// list_extent), the model picks the instantiation.
+template <class List>
+void launch_verify_gather(const List& list, float4* pts, hipStream_t s) {
+    if (list_extent(list) > 0)
+        hipLaunchKernelGGL(k_verify_gather<List>, dim3((list_extent(list) + 255) / 256, list_pairs(list)), dim3(256), 0, s,
+                           list, pts);
 }
 
-void launch_verify_hypotheses(VerifyModel model, const VerifyInput& in, const float4* pts, int K, unsigned seed,
-                              int* samples, float* F, int* valid, hipStream_t s) {
-    const dim3 grid((K + kHypThreads - 1) / kHypThreads), block(kHypThreads);
+template <class List>
+void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, int* samples,
+                              float* F, int* valid, hipStream_t s) {
+    const dim3 grid((K + kHypThreads - 1) / kHypThreads, list_pairs(list)), block(kHypThreads);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_hypotheses_h<VerifyInput>, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
+        hipLaunchKernelGGL(k_verify_hypotheses_h<List>, grid, block, 0, s, list, pts, K, seed, samples, F, valid);
     else
-        hipLaunchKernelGGL(k_verify_hypotheses<VerifyInput>, grid, block, 0, s, in, pts, K, seed, samples, F, valid);
+        hipLaunchKernelGGL(k_verify_hypotheses<List>, grid, block, 0, s, list, pts, K, seed, samples, F, valid);
 }
 
-void launch_verify_score(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
-                         int K, float e2, int* counts, hipStream_t s) {
-    const dim3 grid((K + kScoreWaves - 1) / kScoreWaves), block(64 * kScoreWaves);
+template <class List>
+void launch_verify_score(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid, int K,
+                         float e2, int* counts, hipStream_t s) {
+    const dim3 grid((K + kScoreWaves - 1) / kScoreWaves, list_pairs(list)), block(64 * kScoreWaves);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_verify_score<TransferPass, VerifyInput>), grid, block, 0, s, in, pts, F, valid, K, e2,
-                           counts);
+        hipLaunchKernelGGL((k_verify_score<TransferPass, List>), grid, block, 0, s, list, pts, F, valid, K, e2, counts);
     else
-        hipLaunchKernelGGL((k_verify_score<SampsonPass, VerifyInput>), grid, block, 0, s, in, pts, F, valid, K, e2,
-                           counts);
+        hipLaunchKernelGGL((k_verify_score<SampsonPass, List>), grid, block, 0, s, list, pts, F, valid, K, e2, counts);
 }
 
-void launch_verify_select(VerifyModel model, const VerifyInput& in, const float4* pts, const float* F, const int* valid,
+template <class List>
+void launch_verify_select(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid,
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s) {
+    const dim3 grid(1, list_pairs(list)), block(kVSelThreads);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_verify_select<TransferPass, VerifyInput>), dim3(1), dim3(kVSelThreads), 0, s, in, pts, F,
-                           valid, counts, K, e2, result, out, out_count, mask);
+        hipLaunchKernelGGL((k_verify_select<TransferPass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
+                           result, out, out_count, mask);
     else
-        hipLaunchKernelGGL((k_verify_select<SampsonPass, VerifyInput>), dim3(1), dim3(kVSelThreads), 0, s, in, pts, F,
-                           valid, counts, K, e2, result, out, out_count, mask);
+        hipLaunchKernelGGL((k_verify_select<SampsonPass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
+                           result, out, out_count, mask);
 }
 
-void launch_verify_gather_batched(const VerifyBatch& batch, float4* pts, hipStream_t s) {
-    if (batch.max_cap > 0)
-        hipLaunchKernelGGL(k_verify_gather<VerifyBatch>, dim3((batch.max_cap + 255) / 256, batch.P), dim3(256), 0, s,
-                           batch, pts);
-}
-
-void launch_verify_hypotheses_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, int K,
-                                      unsigned seed, int* samples, float* F, int* valid, hipStream_t s) {
-    const dim3 grid((K + kHypThreads - 1) / kHypThreads, batch.P), block(kHypThreads);
-    if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_hypotheses_h<VerifyBatch>, grid, block, 0, s, batch, pts, K, seed, samples, F, valid);
-    else
-        hipLaunchKernelGGL(k_verify_hypotheses<VerifyBatch>, grid, block, 0, s, batch, pts, K, seed, samples, F, valid);
-}
-
-void launch_verify_score_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
-                                 const int* valid, int K, float e2, int* counts, hipStream_t s) {
-    const dim3 grid((K + kScoreWaves - 1) / kScoreWaves, batch.P), block(64 * kScoreWaves);
-    if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_verify_score<TransferPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, K, e2,
-                           counts);
-    else
-        hipLaunchKernelGGL((k_verify_score<SampsonPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, K, e2,
-                           counts);
-}
-
-void launch_verify_select_batched(VerifyModel model, const VerifyBatch& batch, const float4* pts, const float* F,
-                                  const int* valid, const int* counts, int K, float e2, VerifyResult* results,
-                                  MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s) {
-    const dim3 grid(1, batch.P), block(kVSelThreads);
-    if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL((k_verify_select<TransferPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, counts,
-                           K, e2, results, out, out_counts, mask);
-    else
-        hipLaunchKernelGGL((k_verify_select<SampsonPass, VerifyBatch>), grid, block, 0, s, batch, pts, F, valid, counts,
-                           K, e2, results, out, out_counts, mask);
-}
+#define SIFT_VERIFY_LAUNCHERS(List)                                                                                     \
+    template void launch_verify_gather<List>(const List&, float4*, hipStream_t);                                        \
+    template void launch_verify_hypotheses<List>(VerifyModel, const List&, const float4*, int, unsigned, int*, float*,   \
+                                                 int*, hipStream_t);                                                    \
+    template void launch_verify_score<List>(VerifyModel, const List&, const float4*, const float*, const int*, int,     \
+                                            float, int*, hipStream_t);                                                  \
+    template void launch_verify_select<List>(VerifyModel, const List&, const float4*, const float*, const int*,         \
+                                             const int*, int, float, VerifyResult*, MatchRecord*, int*, uint8_t*,       \
+                                             hipStream_t);
+SIFT_VERIFY_LAUNCHERS(VerifyInput)
+SIFT_VERIFY_LAUNCHERS(VerifyBatch)
+#undef SIFT_VERIFY_LAUNCHERS
 
 void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,
                                hipStream_t s) {

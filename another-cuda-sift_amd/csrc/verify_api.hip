@@ -45,205 +45,206 @@ static_assert(sizeof(sift_hip_homography_result) == sizeof(VerifyResult) &&
 
 namespace {
 
-// What can be judged without the handle first (nothing is dereferenced), then the handle's limits.  Nothing is
-// launched on a failure.
-int check_input(const sift_hip_verifier* v, const sift_hip_dmatch* matches, int cap, const float* query_xy,
-                int query_stride, int nq, const float* train_xy, int train_stride, int nt) {
-    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
-    if (cap < 0 || cap > kVerifyMaxMatches)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: cap must lie in 0.." + std::to_string(kVerifyMaxMatches));
-    if (query_stride < 2 || train_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "verify: a position stride below 2 floats");
-    if (nq < 0 || nt < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: a negative position row count");
-    if (cap > 0 && !matches) return fail(SIFT_HIP_ERR_INVALID, "verify: null matches");
-    if (cap > 0 && (!query_xy || !train_xy)) return fail(SIFT_HIP_ERR_INVALID, "verify: null position pointer");
-    return SIFT_HIP_OK;
-}
-int check_error(float max_error) {
-    if (!(max_error > 0.f) || !std::isfinite(max_error))
-        return fail(SIFT_HIP_ERR_INVALID, "verify: max_error must be > 0 and finite");
-    return SIFT_HIP_OK;
-}
-int check_limits(const sift_hip_verifier* v, int cap, int K) {
-    if (K < 1 || K > kVerifyMaxHypotheses || K > v->maxK)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: hypotheses outside 1..max_hypotheses");
-    if (cap > v->maxM) return fail(SIFT_HIP_ERR_INVALID, "verify: cap exceeds the verifier's max_matches");
-    return SIFT_HIP_OK;
-}
-
-int verify_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in, const sift_hip_verify_params& p,
-                  VerifyResult* result, MatchRecord* out, int* out_count, uint8_t* mask, hipStream_t s) {
-    const float e2 = p.max_error * p.max_error;
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather(in, v->dPts, s);
-    launch_verify_hypotheses(model, in, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
-    launch_verify_score(model, in, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
-    launch_verify_select(model, in, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, result, out, out_count, mask,
-                         s);
-    HIPCHK(hipGetLastError());
-    v->lastK = p.hypotheses;
-    v->lastModel = (int)model;
-    v->lastBatch = false;
-    return SIFT_HIP_OK;
-}
-
-// The refit's own argument rules (sift_hip_refine_*), judged without the handle.
-struct RefineArgs {
-    int rounds;
-    const uint8_t* mask;
-};
 constexpr int kRefineMaxRounds = 8;
 
-int check_refine(int rounds, const void* result, const uint8_t* mask, int rows) {
-    if (!result) return fail(SIFT_HIP_ERR_INVALID, "refine: null result");
-    if (rows > 0 && !mask) return fail(SIFT_HIP_ERR_INVALID, "refine: null mask (the mask is the fit set)");
-    if (rounds < 1 || rounds > kRefineMaxRounds)
-        return fail(SIFT_HIP_ERR_INVALID, "refine: rounds must lie in 1.." + std::to_string(kRefineMaxRounds));
-    return SIFT_HIP_OK;
+// One call of the verifier as every entry point hands it down: the operation, the list(s) and the outputs.  A
+// single-pair entry point describes its list as a one-pair table (row0 = 0) and sets `single`: the same rules and the
+// same host path then serve it, and only the launches differ -- they take the 72-byte VerifyInput, not the batch table.
+enum class Op { Verify, Score, Refine };
+struct Call {
+    Op op;
+    VerifyModel model;
+    bool host;    // the synchronous form: result, out, mask, out_counts and accepted are host memory
+    bool single;  // came in through a single-pair entry point
+    const sift_hip_dmatch* matches;
+    const int* counts;
+    int P;
+    const sift_hip_verify_pair* pairs;
+    int qstride, tstride;
+    const sift_hip_verify_params* params;  // verify: the caller's; score and refine: the entry point's (K, -, max_error)
+    void* result;                          // P records of either model (they share a layout)
+    sift_hip_dmatch* out;
+    int* out_counts;
+    uint8_t* mask;
+    int rounds;  // refine
+    int* accepted;
+    const float* models;  // score: the K models to count under, and their counts
+    int* scores;
+    void* stream;
+};
+
+Call make_call(Op op, VerifyModel model, bool host, const sift_hip_dmatch* matches, int qstride, int tstride) {
+    Call c{};
+    c.op = op, c.model = model, c.host = host;
+    c.matches = matches, c.qstride = qstride, c.tstride = tstride;
+    return c;
 }
 
-// The batched call's argument rules: what can be judged without the handle first, then its limits; `b` is the pair
-// table the kernels take.  out: the device form's output rows (may not overlap matches), null otherwise.  refine: a
-// refine call's further arguments, judged before the limits.
-int check_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, const int* counts, int P,
-                const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                const sift_hip_verify_params* params, const void* results, const sift_hip_dmatch* out, VerifyBatch& b,
-                const RefineArgs* refine = nullptr) {
-    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
-    if (!pairs) return fail(SIFT_HIP_ERR_INVALID, "verify: null pairs");
-    if (!params || !results) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
-    if (P < 1 || P > kVerifyMaxPairs)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: pairs outside 1.." + std::to_string(kVerifyMaxPairs));
-    if (query_stride < 2 || train_stride < 2) return fail(SIFT_HIP_ERR_INVALID, "verify: a position stride below 2 floats");
+// The argument rules of every call, each stated once, in the order include/sift_hip.h documents: what can be judged
+// without the handle first (nothing is dereferenced), then the handle's limits.  Nothing is launched or written on a
+// refusal.  On success `b` is the pair table the kernels take.
+int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
+    const auto refuse = [](const std::string& msg) { return fail(SIFT_HIP_ERR_INVALID, msg); };
+    const bool refine = c.op == Op::Refine;
+    if (!v) return refuse("null verifier");
+    if (!c.pairs) return refuse("verify: null pairs");
+    if (c.op == Op::Score) {
+        if (!c.models || !c.scores)
+            return refuse(c.model == VerifyModel::Homography ? "verify: null H or counts" : "verify: null F or counts");
+    } else if (!c.params || !c.result) {
+        return refuse(refine && c.single ? "refine: null result" : "verify: null params or result");
+    }
+    if (c.P < 1 || c.P > kVerifyMaxPairs) return refuse("verify: pairs outside 1.." + std::to_string(kVerifyMaxPairs));
+    if (c.qstride < 2 || c.tstride < 2) return refuse("verify: a position stride below 2 floats");
     int rows = 0, max_cap = 0;  // P x 65536 fits
-    for (int p = 0; p < P; p++) {
-        const sift_hip_verify_pair& e = pairs[p];
-        const std::string at = " (pair " + std::to_string(p) + ")";
+    for (int p = 0; p < c.P; p++) {
+        const sift_hip_verify_pair& e = c.pairs[p];
+        const auto at = [&] { return c.single ? std::string() : " (pair " + std::to_string(p) + ")"; };
         if (e.cap < 0 || e.cap > kVerifyMaxMatches)
-            return fail(SIFT_HIP_ERR_INVALID, "verify: cap must lie in 0.." + std::to_string(kVerifyMaxMatches) + at);
-        if (e.nq < 0 || e.nt < 0) return fail(SIFT_HIP_ERR_INVALID, "verify: a negative position row count" + at);
-        if (e.cap > 0 && (!e.query_xy || !e.train_xy))
-            return fail(SIFT_HIP_ERR_INVALID, "verify: null position pointer" + at);
+            return refuse("verify: cap must lie in 0.." + std::to_string(kVerifyMaxMatches) + at());
+        if (e.nq < 0 || e.nt < 0) return refuse("verify: a negative position row count" + at());
+        if (e.cap > 0 && (!e.query_xy || !e.train_xy)) return refuse("verify: null position pointer" + at());
         b.pair[p] = VerifyBatchPair{e.query_xy, e.train_xy, rows, e.cap, e.nq, e.nt};
         rows += e.cap;
         max_cap = std::max(max_cap, e.cap);
     }
-    if (rows > 0 && !matches) return fail(SIFT_HIP_ERR_INVALID, "verify: null matches");
-    if (int rc = check_error(params->max_error)) return rc;
-    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)rows;
-    if (out && rows > 0 && ob < mb + bytes && mb < ob + bytes)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
-    if (refine)
-        if (int rc = check_refine(refine->rounds, results, refine->mask, rows)) return rc;
-    if (params->hypotheses < 1 || params->hypotheses > kVerifyMaxHypotheses || params->hypotheses > v->maxK)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: hypotheses outside 1..max_hypotheses");
-    if (P > v->maxP) return fail(SIFT_HIP_ERR_INVALID, "verify: more pairs than the verifier's max_pairs");
-    if (rows > v->maxM) return fail(SIFT_HIP_ERR_INVALID, "verify: the caps' sum exceeds the verifier's max_matches");
-    b.matches = reinterpret_cast<const MatchRecord*>(matches);
-    b.counts = counts;
-    b.qstride = query_stride, b.tstride = train_stride;
-    b.P = P, b.rows = rows, b.max_cap = max_cap;
+    if (rows > 0 && !c.matches) return refuse("verify: null matches");
+    if (!(c.params->max_error > 0.f) || !std::isfinite(c.params->max_error))
+        return refuse("verify: max_error must be > 0 and finite");
+    const uintptr_t ob = (uintptr_t)c.out, mb = (uintptr_t)c.matches, bytes = sizeof(sift_hip_dmatch) * (size_t)rows;
+    if (!c.host && c.out && rows > 0 && ob < mb + bytes && mb < ob + bytes) return refuse("verify: out aliases matches");
+    if (refine && rows > 0 && !c.mask) return refuse("refine: null mask (the mask is the fit set)");
+    if (refine && (c.rounds < 1 || c.rounds > kRefineMaxRounds))
+        return refuse("refine: rounds must lie in 1.." + std::to_string(kRefineMaxRounds));
+    const int K = c.params->hypotheses;
+    if (K < 1 || K > kVerifyMaxHypotheses || K > v->maxK) return refuse("verify: hypotheses outside 1..max_hypotheses");
+    if (c.P > v->maxP) return refuse("verify: more pairs than the verifier's max_pairs");
+    if (rows > v->maxM)
+        return refuse(c.single ? "verify: cap exceeds the verifier's max_matches"
+                               : "verify: the caps' sum exceeds the verifier's max_matches");
+    if (!c.single) std::fill(b.pair + c.P, b.pair + kVerifyMaxPairs, VerifyBatchPair{});  // the table goes by value
+    b.matches = reinterpret_cast<const MatchRecord*>(c.matches);
+    b.counts = c.counts;
+    b.qstride = c.qstride, b.tstride = c.tstride;
+    b.P = c.P, b.rows = rows, b.max_cap = max_cap;
     return SIFT_HIP_OK;
 }
 
-// One launch per step for the whole batch.  Every index stays inside the handle's scratch: rows <= maxM,
-// P <= maxP and K <= maxK were checked.
-int verify_batched_device(sift_hip_verifier* v, VerifyModel model, const VerifyBatch& b, const sift_hip_verify_params& p,
-                          VerifyResult* results, MatchRecord* out, int* out_counts, uint8_t* mask, hipStream_t s) {
-    const float e2 = p.max_error * p.max_error;
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather_batched(b, v->dPts, s);
-    launch_verify_hypotheses_batched(model, b, v->dPts, p.hypotheses, p.seed, v->dSamples, v->dF, v->dValid, s);
-    launch_verify_score_batched(model, b, v->dPts, v->dF, v->dValid, p.hypotheses, e2, v->dCounts, s);
-    launch_verify_select_batched(model, b, v->dPts, v->dF, v->dValid, v->dCounts, p.hypotheses, e2, results, out,
-                                 out_counts, mask, s);
+// Where a call's launches write: the caller's device memory, or for a host form the handle's own.
+struct Outputs {
+    VerifyResult* result;
+    MatchRecord* out;
+    int* out_counts;
+    uint8_t* mask;
+    int* accepted;
+    hipStream_t stream;
+};
+
+// The runners, one per operation, over the list type (VerifyInput or VerifyBatch): one launch per step for all the
+// list's pairs.  Every index stays inside the handle's scratch: rows <= maxM, P <= maxP and K <= maxK were checked.
+template <class List>
+int verify_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
+    const int K = c.params->hypotheses;
+    const float e2 = c.params->max_error * c.params->max_error;
+    launch_verify_gather(list, v->dPts, o.stream);
+    launch_verify_hypotheses(c.model, list, v->dPts, K, c.params->seed, v->dSamples, v->dF, v->dValid, o.stream);
+    launch_verify_score(c.model, list, v->dPts, v->dF, v->dValid, K, e2, v->dCounts, o.stream);
+    launch_verify_select(c.model, list, v->dPts, v->dF, v->dValid, v->dCounts, K, e2, o.result, o.out, o.out_counts,
+                         o.mask, o.stream);
     HIPCHK(hipGetLastError());
-    v->lastK = p.hypotheses;
-    v->lastModel = (int)model;
-    v->lastBatch = true;
+    v->lastK = K;
+    v->lastModel = (int)c.model;
+    v->lastBatch = !c.single;
     return SIFT_HIP_OK;
 }
 
-int verify_model_batched_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches,
-                                const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
-                                int train_stride, const sift_hip_verify_params* params, void* results,
-                                sift_hip_dmatch* out, int* out_counts, uint8_t* mask, void* stream) {
-    VerifyBatch b{};
-    if (int rc = check_batch(v, matches, counts, P, pairs, query_stride, train_stride, params, results, out, b)) return rc;
-    return verify_batched_device(v, model, b, *params, static_cast<VerifyResult*>(results),
-                                 reinterpret_cast<MatchRecord*>(out), out_counts, mask, (hipStream_t)stream);
+template <class List>
+int score_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
+    launch_verify_gather(list, v->dPts, o.stream);
+    launch_verify_score(c.model, list, v->dPts, c.models, nullptr, c.params->hypotheses,
+                        c.params->max_error * c.params->max_error, c.scores, o.stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
 }
 
-int verify_model_batched_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
-                              int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                              const sift_hip_verify_params* params, void* results_host, sift_hip_dmatch* out_host,
-                              uint8_t* mask_host) {
-    VerifyBatch b{};
-    if (int rc = check_batch(v, matches, counts, P, pairs, query_stride, train_stride, params, results_host, nullptr, b))
-        return rc;
-    if (int rc = verify_batched_device(v, model, b, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
-    HIPCHK(hipMemcpy(results_host, v->dResult, sizeof(VerifyResult) * (size_t)P, hipMemcpyDeviceToHost));
-    const VerifyResult* r = static_cast<const VerifyResult*>(results_host);
-    for (int p = 0; out_host && p < P; p++) {  // a pair's rows past its inliers stay as they are, as on the device
-        const int n = std::min(r[p].inliers, b.pair[p].cap), row0 = b.pair[p].row0;
-        if (n > 0)
-            HIPCHK(hipMemcpy(out_host + row0, v->dOut + row0, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
+// `rounds` rounds of fit -> rescore -> accept on the gathered list; out is written by the last round only.  The
+// verifier's hypothesis scratch is not touched.
+template <class List>
+int refine_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
+    const float e2 = c.params->max_error * c.params->max_error;
+    launch_verify_gather(list, v->dPts, o.stream);
+    for (int r = 0; r < c.rounds; r++) {
+        const bool last = r == c.rounds - 1;
+        launch_refit_fit(c.model, list, v->dPts, o.mask, o.result, v->dCand, o.stream);
+        launch_refit_accept(c.model, list, v->dPts, v->dCand, e2, o.result, o.mask, last ? o.out : nullptr,
+                            last ? o.out_counts : nullptr, o.accepted, r == 0, o.stream);
     }
-    if (mask_host && b.rows > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-// The entry points of both models (the record types share a layout): argument rules, then the launches.
-int verify_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
-                        const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                        const sift_hip_verify_params* params, void* result, sift_hip_dmatch* out, int* out_count,
-                        uint8_t* mask, void* stream) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!params || !result) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
-    if (int rc = check_error(params->max_error)) return rc;
-    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
-    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
-    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    return verify_device(v, model, in, *params, static_cast<VerifyResult*>(result), reinterpret_cast<MatchRecord*>(out),
-                         out_count, mask, (hipStream_t)stream);
-}
-
-int verify_model_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
-                      const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                      const sift_hip_verify_params* params, void* result_host, sift_hip_dmatch* out_host,
-                      uint8_t* mask_host) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!params || !result_host) return fail(SIFT_HIP_ERR_INVALID, "verify: null params or result");
-    if (int rc = check_error(params->max_error)) return rc;
-    if (int rc = check_limits(v, cap, params->hypotheses)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    if (int rc = verify_device(v, model, in, *params, v->dResult, v->dOut, nullptr, v->dMask, nullptr)) return rc;
-    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
-    const int n = std::min(static_cast<const VerifyResult*>(result_host)->inliers, cap);
-    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
-    if (mask_host && cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-int score_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
-                       const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                       const float* M, int K, float max_error, int* counts, void* stream) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (!M || !counts)
-        return fail(SIFT_HIP_ERR_INVALID, model == VerifyModel::Homography ? "verify: null H or counts"
-                                                                           : "verify: null F or counts");
-    if (int rc = check_error(max_error)) return rc;
-    if (int rc = check_limits(v, cap, K)) return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather(in, v->dPts, (hipStream_t)stream);
-    launch_verify_score(model, in, v->dPts, M, nullptr, K, max_error * max_error, counts, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return SIFT_HIP_OK;
+}
+
+template <class List>
+int enqueue(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
+    return c.op == Op::Verify ? verify_on(v, c, list, o) : c.op == Op::Score ? score_on(v, c, list, o)
+                                                                             : refine_on(v, c, list, o);
+}
+
+// The host forms' copy-back, one loop over the pair table: the records, each pair's first min(n, cap) rows at its row0
+// (the rows past them stay as they are, as on the device), and the mask.
+int copy_rows(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b, const int* n) {
+    for (int p = 0; c.out && p < b.P; p++) {
+        const int rows = std::min(n[p], b.pair[p].cap), row0 = b.pair[p].row0;
+        if (rows > 0)
+            HIPCHK(hipMemcpy(c.out + row0, v->dOut + row0, sizeof(MatchRecord) * (size_t)rows, hipMemcpyDeviceToHost));
+    }
+    return SIFT_HIP_OK;
+}
+
+int verify_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b) {
+    HIPCHK(hipMemcpy(c.result, v->dResult, sizeof(VerifyResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+    int n[kVerifyMaxPairs];
+    for (int p = 0; p < b.P; p++) n[p] = static_cast<const VerifyResult*>(c.result)[p].inliers;
+    if (int rc = copy_rows(v, c, b, n)) return rc;
+    if (c.mask && b.rows > 0) HIPCHK(hipMemcpy(c.mask, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+int refine_from_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b) {
+    HIPCHK(hipMemcpy(v->dResult, c.result, sizeof(VerifyResult) * (size_t)b.P, hipMemcpyHostToDevice));
+    if (b.rows > 0) HIPCHK(hipMemcpy(v->dMask, c.mask, (size_t)b.rows, hipMemcpyHostToDevice));
+    return SIFT_HIP_OK;
+}
+
+int refine_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b) {
+    int n[kVerifyMaxPairs], accepted[kVerifyMaxPairs];
+    HIPCHK(hipMemcpy(n, v->dRefineInts, sizeof(int) * (size_t)b.P, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(accepted, v->dRefineInts + v->maxP, sizeof(int) * (size_t)b.P, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c.result, v->dResult, sizeof(VerifyResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+    if (b.rows > 0) HIPCHK(hipMemcpy(c.mask, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
+    if (int rc = copy_rows(v, c, b, n)) return rc;
+    if (c.out_counts) std::copy(n, n + b.P, c.out_counts);
+    if (c.accepted) std::copy(accepted, accepted + b.P, c.accepted);
+    return SIFT_HIP_OK;
+}
+
+// Every list-taking entry point: the rules, for a host form the uploads, the launches, for a host form the copy-back.
+int run(sift_hip_verifier* v, const Call& c) {
+    VerifyBatch b;
+    if (int rc = check(v, c, b)) return rc;
+    const bool refine = c.op == Op::Refine;
+    HIPCHK(hipSetDevice(v->device));
+    if (c.host && refine)
+        if (int rc = refine_from_host(v, c, b)) return rc;
+    const Outputs o = c.host ? Outputs{v->dResult, v->dOut, refine ? v->dRefineInts : nullptr, v->dMask,
+                                       refine ? v->dRefineInts + v->maxP : nullptr, nullptr}
+                             : Outputs{static_cast<VerifyResult*>(c.result), reinterpret_cast<MatchRecord*>(c.out),
+                                       c.out_counts, c.mask, c.accepted, (hipStream_t)c.stream};
+    const VerifyBatchPair& e = b.pair[0];
+    const int rc = c.single ? enqueue(v, c, VerifyInput{b.matches, b.counts, e.cap, e.qxy, e.txy, b.qstride, b.tstride,
+                                                        e.nq, e.nt}, o)
+                            : enqueue(v, c, b, o);
+    if (rc || !c.host) return rc;
+    return refine ? refine_to_host(v, c, b) : verify_to_host(v, c, b);
 }
 
 // What the last verify call of `model` drew (m indices per hypothesis), solved and counted.
@@ -264,141 +265,13 @@ int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples
     return SIFT_HIP_OK;
 }
 
-// --- The refit (sift_hip_refine_*): `rounds` rounds of fit -> rescore -> accept on the gathered list; out is written
-// by the last round only.  The verifier's hypothesis scratch is not touched.
-
-int refine_device(sift_hip_verifier* v, VerifyModel model, const VerifyInput& in, float max_error, int rounds,
-                  VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted, hipStream_t s) {
-    const float e2 = max_error * max_error;
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather(in, v->dPts, s);
-    for (int r = 0; r < rounds; r++) {
-        const bool last = r == rounds - 1;
-        launch_refit_fit(model, in, v->dPts, mask, result, v->dCand, s);
-        launch_refit_accept(model, in, v->dPts, v->dCand, e2, result, mask, last ? out : nullptr,
-                            last ? out_count : nullptr, accepted, r == 0, s);
-    }
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-int refine_batched_device(sift_hip_verifier* v, VerifyModel model, const VerifyBatch& b, float max_error, int rounds,
-                          VerifyResult* results, uint8_t* mask, MatchRecord* out, int* out_counts, int* accepted,
-                          hipStream_t s) {
-    const float e2 = max_error * max_error;
-    HIPCHK(hipSetDevice(v->device));
-    launch_verify_gather_batched(b, v->dPts, s);
-    for (int r = 0; r < rounds; r++) {
-        const bool last = r == rounds - 1;
-        launch_refit_fit_batched(model, b, v->dPts, mask, results, v->dCand, s);
-        launch_refit_accept_batched(model, b, v->dPts, v->dCand, e2, results, mask, last ? out : nullptr,
-                                    last ? out_counts : nullptr, accepted, r == 0, s);
-    }
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-// The single-pair argument rules: the verify call's, then the refit's own.
-int check_refine_single(const sift_hip_verifier* v, const sift_hip_dmatch* matches, int cap, const float* query_xy,
-                        int query_stride, int nq, const float* train_xy, int train_stride, int nt, float max_error,
-                        int rounds, const void* result, const uint8_t* mask, const sift_hip_dmatch* out) {
-    if (int rc = check_input(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt)) return rc;
-    if (int rc = check_refine(rounds, result, mask, cap)) return rc;
-    if (int rc = check_error(max_error)) return rc;
-    const uintptr_t ob = (uintptr_t)out, mb = (uintptr_t)matches, bytes = sizeof(sift_hip_dmatch) * (size_t)cap;
-    if (out && cap > 0 && ob < mb + bytes && mb < ob + bytes)
-        return fail(SIFT_HIP_ERR_INVALID, "verify: out aliases matches");
-    return check_limits(v, cap, 1);
-}
-
-int refine_model_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
-                        const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                        float max_error, int rounds, void* result, uint8_t* mask, sift_hip_dmatch* out, int* out_count,
-                        int* accepted, void* stream) {
-    if (int rc = check_refine_single(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, max_error,
-                                     rounds, result, mask, out))
-        return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    return refine_device(v, model, in, max_error, rounds, static_cast<VerifyResult*>(result), mask,
-                         reinterpret_cast<MatchRecord*>(out), out_count, accepted, (hipStream_t)stream);
-}
-
-int refine_model_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* count, int cap,
-                      const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                      float max_error, int rounds, void* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,
-                      int* out_count_host, int* accepted_host) {
-    if (int rc = check_refine_single(v, matches, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, max_error,
-                                     rounds, result_host, mask_host, nullptr))
-        return rc;
-    const VerifyInput in{reinterpret_cast<const MatchRecord*>(matches), count, cap, query_xy, train_xy, query_stride,
-                         train_stride, nq, nt};
-    HIPCHK(hipSetDevice(v->device));
-    HIPCHK(hipMemcpy(v->dResult, result_host, sizeof(VerifyResult), hipMemcpyHostToDevice));
-    if (cap > 0) HIPCHK(hipMemcpy(v->dMask, mask_host, (size_t)cap, hipMemcpyHostToDevice));
-    if (int rc = refine_device(v, model, in, max_error, rounds, v->dResult, v->dMask, v->dOut, v->dRefineInts,
-                               v->dRefineInts + v->maxP, nullptr))
-        return rc;
-    int ints[2] = {0, 0};
-    HIPCHK(hipMemcpy(&ints[0], v->dRefineInts, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&ints[1], v->dRefineInts + v->maxP, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(result_host, v->dResult, sizeof(VerifyResult), hipMemcpyDeviceToHost));
-    if (cap > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)cap, hipMemcpyDeviceToHost));
-    const int n = std::min(ints[0], cap);
-    if (out_host && n > 0) HIPCHK(hipMemcpy(out_host, v->dOut, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
-    if (out_count_host) *out_count_host = ints[0];
-    if (accepted_host) *accepted_host = ints[1];
-    return SIFT_HIP_OK;
-}
-
-// The batched argument rules: check_batch's (with the one-hypothesis budget every verifier has), then the refit's own.
-int check_refine_batch(const sift_hip_verifier* v, const sift_hip_dmatch* matches, const int* counts, int P,
-                       const sift_hip_verify_pair* pairs, int query_stride, int train_stride, float max_error, int rounds,
-                       const void* results, const uint8_t* mask, const sift_hip_dmatch* out, VerifyBatch& b) {
-    const sift_hip_verify_params params{1, 0u, max_error};
-    const RefineArgs refine{rounds, mask};
-    return check_batch(v, matches, counts, P, pairs, query_stride, train_stride, &params, results, out, b, &refine);
-}
-
-int refine_model_batched_device(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
-                                int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                                float max_error, int rounds, void* results, uint8_t* mask, sift_hip_dmatch* out,
-                                int* out_counts, int* accepted, void* stream) {
-    VerifyBatch b{};
-    if (int rc = check_refine_batch(v, matches, counts, P, pairs, query_stride, train_stride, max_error, rounds, results,
-                                    mask, out, b))
-        return rc;
-    return refine_batched_device(v, model, b, max_error, rounds, static_cast<VerifyResult*>(results), mask,
-                                 reinterpret_cast<MatchRecord*>(out), out_counts, accepted, (hipStream_t)stream);
-}
-
-int refine_model_batched_host(sift_hip_verifier* v, VerifyModel model, const sift_hip_dmatch* matches, const int* counts,
-                              int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                              float max_error, int rounds, void* results_host, uint8_t* mask_host,
-                              sift_hip_dmatch* out_host, int* out_counts_host, int* accepted_host) {
-    VerifyBatch b{};
-    if (int rc = check_refine_batch(v, matches, counts, P, pairs, query_stride, train_stride, max_error, rounds,
-                                    results_host, mask_host, nullptr, b))
-        return rc;
-    HIPCHK(hipSetDevice(v->device));
-    HIPCHK(hipMemcpy(v->dResult, results_host, sizeof(VerifyResult) * (size_t)P, hipMemcpyHostToDevice));
-    if (b.rows > 0) HIPCHK(hipMemcpy(v->dMask, mask_host, (size_t)b.rows, hipMemcpyHostToDevice));
-    if (int rc = refine_batched_device(v, model, b, max_error, rounds, v->dResult, v->dMask, v->dOut, v->dRefineInts,
-                                       v->dRefineInts + v->maxP, nullptr))
-        return rc;
-    int ints[2 * kVerifyMaxPairs];
-    HIPCHK(hipMemcpy(ints, v->dRefineInts, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ints + kVerifyMaxPairs, v->dRefineInts + v->maxP, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(results_host, v->dResult, sizeof(VerifyResult) * (size_t)P, hipMemcpyDeviceToHost));
-    if (b.rows > 0) HIPCHK(hipMemcpy(mask_host, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
-    for (int p = 0; p < P; p++) {  // a pair's rows past its records stay as they are, as on the device
-        const int n = std::min(ints[p], b.pair[p].cap), row0 = b.pair[p].row0;
-        if (out_host && n > 0)
-            HIPCHK(hipMemcpy(out_host + row0, v->dOut + row0, sizeof(MatchRecord) * (size_t)n, hipMemcpyDeviceToHost));
-        if (out_counts_host) out_counts_host[p] = ints[p];
-        if (accepted_host) accepted_host[p] = ints[kVerifyMaxPairs + p];
-    }
-    return SIFT_HIP_OK;
+// The projection's rows: in place (the same rows: a thread reads its row before it writes it) or apart; anything
+// between is refused.  (differences, not sums: an extent may be as large as the address space)
+bool rows_overlap(const float* xy, int stride, const float* out_xy, int out_stride, int n) {
+    const uintptr_t ib = (uintptr_t)xy, ob = (uintptr_t)out_xy;
+    const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
+    const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
+    return !(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes);
 }
 
 }  // namespace
@@ -456,137 +329,91 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
     return SIFT_HIP_OK;
 }
 
-int sift_hip_verify_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                       const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                       int train_stride, int nt, const sift_hip_verify_params* params,
-                                       sift_hip_verify_result* result, sift_hip_dmatch* out, int* out_count,
-                                       uint8_t* mask, void* stream) {
-    return verify_model_device(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                               train_stride, nt, params, result, out, out_count, mask, stream);
+// The sixteen verify and refine entry points: {fundamental, homography} x {one pair, batch} x {verify, refine} x
+// {device, host}.  Each fills the call record and runs it.
+#define SIFT_ONE_PAIR                                                                                               \
+    const int* count, int cap, const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, \
+        int nt
+#define SIFT_ONE_PAIR_LIST(c)                                         \
+    const sift_hip_verify_pair one{query_xy, train_xy, nq, nt, cap}; \
+    c.single = true, c.counts = count, c.P = 1, c.pairs = &one
+#define SIFT_BATCH const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride
+#define SIFT_BATCH_LIST(c) c.single = false, c.counts = counts, c.P = P, c.pairs = pairs
+
+#define SIFT_VERIFIER_ENTRIES(name, MODEL, RESULT, LIST_ARGS, LIST)                                                      \
+    int sift_hip_verify_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                \
+                                        const sift_hip_verify_params* params, RESULT* result, sift_hip_dmatch* out,      \
+                                        int* out_count, uint8_t* mask, void* stream) {                                   \
+        Call c = make_call(Op::Verify, MODEL, false, matches, query_stride, train_stride);                               \
+        LIST(c);                                                                                                         \
+        c.params = params, c.result = result, c.out = out, c.out_counts = out_count, c.mask = mask, c.stream = stream;   \
+        return run(v, c);                                                                                                \
+    }                                                                                                                    \
+    int sift_hip_verify_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                  \
+                                      const sift_hip_verify_params* params, RESULT* result_host,                         \
+                                      sift_hip_dmatch* out_host, uint8_t* mask_host) {                                   \
+        Call c = make_call(Op::Verify, MODEL, true, matches, query_stride, train_stride);                                \
+        LIST(c);                                                                                                         \
+        c.params = params, c.result = result_host, c.out = out_host, c.mask = mask_host;                                 \
+        return run(v, c);                                                                                                \
+    }                                                                                                                    \
+    int sift_hip_refine_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                \
+                                        float max_error, int rounds, RESULT* result, uint8_t* mask, sift_hip_dmatch* out, \
+                                        int* out_count, int* accepted, void* stream) {                                   \
+        const sift_hip_verify_params params{1, 0u, max_error}; /* the one-hypothesis budget every verifier has */        \
+        Call c = make_call(Op::Refine, MODEL, false, matches, query_stride, train_stride);                               \
+        LIST(c);                                                                                                         \
+        c.params = &params, c.rounds = rounds, c.result = result, c.mask = mask, c.out = out, c.out_counts = out_count;  \
+        c.accepted = accepted, c.stream = stream;                                                                        \
+        return run(v, c);                                                                                                \
+    }                                                                                                                    \
+    int sift_hip_refine_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS, float max_error, \
+                                      int rounds, RESULT* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,    \
+                                      int* out_count_host, int* accepted_host) {                                         \
+        const sift_hip_verify_params params{1, 0u, max_error};                                                           \
+        Call c = make_call(Op::Refine, MODEL, true, matches, query_stride, train_stride);                                \
+        LIST(c);                                                                                                         \
+        c.params = &params, c.rounds = rounds, c.result = result_host, c.mask = mask_host, c.out = out_host;             \
+        c.out_counts = out_count_host, c.accepted = accepted_host;                                                       \
+        return run(v, c);                                                                                                \
+    }
+SIFT_VERIFIER_ENTRIES(fundamental, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
+SIFT_VERIFIER_ENTRIES(homography, VerifyModel::Homography, sift_hip_homography_result, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
+SIFT_VERIFIER_ENTRIES(fundamental_batched, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_BATCH, SIFT_BATCH_LIST)
+SIFT_VERIFIER_ENTRIES(homography_batched, VerifyModel::Homography, sift_hip_homography_result, SIFT_BATCH, SIFT_BATCH_LIST)
+#undef SIFT_VERIFIER_ENTRIES
+#undef SIFT_BATCH_LIST
+#undef SIFT_BATCH
+
+static int score_entry(sift_hip_verifier_t v, Call c, const float* M, int K, float max_error, int* counts, void* stream) {
+    const sift_hip_verify_params params{K, 0u, max_error};
+    c.params = &params, c.models = M, c.scores = counts, c.stream = stream;
+    return run(v, c);
 }
 
-int sift_hip_verify_fundamental_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                     int train_stride, int nt, const sift_hip_verify_params* params,
-                                     sift_hip_verify_result* result_host, sift_hip_dmatch* out_host,
-                                     uint8_t* mask_host) {
-    return verify_model_host(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                             train_stride, nt, params, result_host, out_host, mask_host);
+int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, SIFT_ONE_PAIR, const float* F,
+                                      int K, float max_error, int* counts, void* stream) {
+    Call c = make_call(Op::Score, VerifyModel::Fundamental, false, matches, query_stride, train_stride);
+    SIFT_ONE_PAIR_LIST(c);
+    return score_entry(v, c, F, K, max_error, counts, stream);
 }
 
-int sift_hip_score_fundamental_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                      int train_stride, int nt, const float* F, int K, float max_error, int* counts,
-                                      void* stream) {
-    return score_model_device(v, VerifyModel::Fundamental, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                              train_stride, nt, F, K, max_error, counts, stream);
+int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, SIFT_ONE_PAIR, const float* H,
+                                     int K, float max_error, int* counts, void* stream) {
+    Call c = make_call(Op::Score, VerifyModel::Homography, false, matches, query_stride, train_stride);
+    SIFT_ONE_PAIR_LIST(c);
+    return score_entry(v, c, H, K, max_error, counts, stream);
 }
+#undef SIFT_ONE_PAIR_LIST
+#undef SIFT_ONE_PAIR
 
 int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap) {
     return hypotheses_host(v, VerifyModel::Fundamental, 8, samples, F, counts, cap);
 }
 
-int sift_hip_verify_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                      const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                      int train_stride, int nt, const sift_hip_verify_params* params,
-                                      sift_hip_homography_result* result, sift_hip_dmatch* out, int* out_count,
-                                      uint8_t* mask, void* stream) {
-    return verify_model_device(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                               train_stride, nt, params, result, out, out_count, mask, stream);
-}
-
-int sift_hip_verify_homography_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                    const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                    int train_stride, int nt, const sift_hip_verify_params* params,
-                                    sift_hip_homography_result* result_host, sift_hip_dmatch* out_host,
-                                    uint8_t* mask_host) {
-    return verify_model_host(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                             train_stride, nt, params, result_host, out_host, mask_host);
-}
-
-int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
-                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
-                                     int train_stride, int nt, const float* H, int K, float max_error, int* counts,
-                                     void* stream) {
-    return score_model_device(v, VerifyModel::Homography, matches, count, cap, query_xy, query_stride, nq, train_xy,
-                              train_stride, nt, H, K, max_error, counts, stream);
-}
-
 int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* samples, float* H, int* counts, int cap) {
     return hypotheses_host(v, VerifyModel::Homography, 4, samples, H, counts, cap);
 }
-
-int sift_hip_verify_fundamental_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
-                                               int P, const sift_hip_verify_pair* pairs, int query_stride,
-                                               int train_stride, const sift_hip_verify_params* params,
-                                               sift_hip_verify_result* results, sift_hip_dmatch* out, int* out_counts,
-                                               uint8_t* mask, void* stream) {
-    return verify_model_batched_device(v, VerifyModel::Fundamental, matches, counts, P, pairs, query_stride, train_stride,
-                                       params, results, out, out_counts, mask, stream);
-}
-
-int sift_hip_verify_fundamental_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
-                                             int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                                             const sift_hip_verify_params* params, sift_hip_verify_result* results_host,
-                                             sift_hip_dmatch* out_host, uint8_t* mask_host) {
-    return verify_model_batched_host(v, VerifyModel::Fundamental, matches, counts, P, pairs, query_stride, train_stride,
-                                     params, results_host, out_host, mask_host);
-}
-
-int sift_hip_verify_homography_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
-                                              int P, const sift_hip_verify_pair* pairs, int query_stride,
-                                              int train_stride, const sift_hip_verify_params* params,
-                                              sift_hip_homography_result* results, sift_hip_dmatch* out, int* out_counts,
-                                              uint8_t* mask, void* stream) {
-    return verify_model_batched_device(v, VerifyModel::Homography, matches, counts, P, pairs, query_stride, train_stride,
-                                       params, results, out, out_counts, mask, stream);
-}
-
-int sift_hip_verify_homography_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
-                                            int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
-                                            const sift_hip_verify_params* params,
-                                            sift_hip_homography_result* results_host, sift_hip_dmatch* out_host,
-                                            uint8_t* mask_host) {
-    return verify_model_batched_host(v, VerifyModel::Homography, matches, counts, P, pairs, query_stride, train_stride,
-                                     params, results_host, out_host, mask_host);
-}
-
-#define SIFT_REFINE_ENTRIES(name, MODEL, RESULT)                                                                          \
-    int sift_hip_refine_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap, \
-                                        const float* query_xy, int query_stride, int nq, const float* train_xy,          \
-                                        int train_stride, int nt, float max_error, int rounds, RESULT* result,           \
-                                        uint8_t* mask, sift_hip_dmatch* out, int* out_count, int* accepted,              \
-                                        void* stream) {                                                                  \
-        return refine_model_device(v, MODEL, matches, count, cap, query_xy, query_stride, nq, train_xy, train_stride, nt, \
-                                   max_error, rounds, result, mask, out, out_count, accepted, stream);                   \
-    }                                                                                                                    \
-    int sift_hip_refine_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,  \
-                                      const float* query_xy, int query_stride, int nq, const float* train_xy,            \
-                                      int train_stride, int nt, float max_error, int rounds, RESULT* result_host,        \
-                                      uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_count_host,                \
-                                      int* accepted_host) {                                                              \
-        return refine_model_host(v, MODEL, matches, count, cap, query_xy, query_stride, nq, train_xy, train_stride, nt,   \
-                                 max_error, rounds, result_host, mask_host, out_host, out_count_host, accepted_host);    \
-    }                                                                                                                    \
-    int sift_hip_refine_##name##_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts, \
-                                                int P, const sift_hip_verify_pair* pairs, int query_stride,              \
-                                                int train_stride, float max_error, int rounds, RESULT* results,          \
-                                                uint8_t* mask, sift_hip_dmatch* out, int* out_counts, int* accepted,     \
-                                                void* stream) {                                                          \
-        return refine_model_batched_device(v, MODEL, matches, counts, P, pairs, query_stride, train_stride, max_error,   \
-                                           rounds, results, mask, out, out_counts, accepted, stream);                    \
-    }                                                                                                                    \
-    int sift_hip_refine_##name##_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,  \
-                                              int P, const sift_hip_verify_pair* pairs, int query_stride,                \
-                                              int train_stride, float max_error, int rounds, RESULT* results_host,       \
-                                              uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,       \
-                                              int* accepted_host) {                                                      \
-        return refine_model_batched_host(v, MODEL, matches, counts, P, pairs, query_stride, train_stride, max_error,     \
-                                         rounds, results_host, mask_host, out_host, out_counts_host, accepted_host);     \
-    }
-SIFT_REFINE_ENTRIES(fundamental, VerifyModel::Fundamental, sift_hip_verify_result)
-SIFT_REFINE_ENTRIES(homography, VerifyModel::Homography, sift_hip_homography_result)
-#undef SIFT_REFINE_ENTRIES
 
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,
                                        void* stream) {
@@ -595,12 +422,7 @@ int sift_hip_project_homography_device(const float* H, const float* xy, int stri
     if (n < 0) return fail(SIFT_HIP_ERR_INVALID, "project: a negative row count");
     if (n == 0) return SIFT_HIP_OK;
     if (!xy || !out_xy) return fail(SIFT_HIP_ERR_INVALID, "project: null position pointer");
-    // In place (the same rows: a thread reads its row before it writes it) or apart; anything between is refused.
-    const uintptr_t ib = (uintptr_t)xy, ob = (uintptr_t)out_xy;
-    const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
-    const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
-    // (differences, not sums: an extent may be as large as the address space)
-    if (!(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes))
+    if (rows_overlap(xy, stride, out_xy, out_stride, n))
         return fail(SIFT_HIP_ERR_INVALID, "project: out_xy overlaps xy (only out_xy == xy with equal strides may)");
     launch_project_homography(H, xy, stride, n, out_xy, out_stride, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
@@ -624,11 +446,7 @@ int sift_hip_project_homography_batched_device(const void* geometry, int geometr
         b.max_n = std::max(b.max_n, n);
         if (n == 0) continue;
         if (!sets[p].xy || !sets[p].out_xy) return fail(SIFT_HIP_ERR_INVALID, "project: null position pointer");
-        // Per pair as in the single call: in place (the same rows) or apart.
-        const uintptr_t ib = (uintptr_t)sets[p].xy, ob = (uintptr_t)sets[p].out_xy;
-        const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
-        const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
-        if (!(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes))
+        if (rows_overlap(sets[p].xy, stride, sets[p].out_xy, out_stride, n))  // per pair as in the single call
             return fail(SIFT_HIP_ERR_INVALID, "project: out_xy overlaps xy (only out_xy == xy with equal strides may)");
     }
     if (b.max_n == 0) return SIFT_HIP_OK;

@@ -48,6 +48,8 @@ struct DeviceBlock {
 const sift_hip_verify_pair* toAbi(const std::vector<VerifyPair>& pairs) {
     return reinterpret_cast<const sift_hip_verify_pair*>(pairs.data());
 }
+sift_hip_dmatch* abi(DMatch* p) { return reinterpret_cast<sift_hip_dmatch*>(p); }
+const sift_hip_dmatch* abi(const DMatch* p) { return reinterpret_cast<const sift_hip_dmatch*>(p); }
 
 // The rows of a batch (0 for caps the ABI refuses: the call throws before anything is read).
 size_t batchRows(const std::vector<VerifyPair>& pairs) {
@@ -58,20 +60,172 @@ size_t batchRows(const std::vector<VerifyPair>& pairs) {
     return rows;
 }
 
-// One geometry per pair from the host forms' outputs: pair p's records are the first r[p].inliers of its rows.
-template <class Geometry, class Record>
-std::vector<Geometry> geometries(const std::vector<VerifyPair>& pairs, const std::vector<Record>& r,
-                                 const std::vector<DMatch>& list, float (Geometry::*model)[9],
-                                 float (Record::*from)[9]) {
-    std::vector<Geometry> out(pairs.size());
+// The host forms' mask: one byte per row, or the ABI's refusal of the rows themselves (nothing is read then).
+void check_mask(const std::vector<uint8_t>& mask, size_t rows, const char* what) {
+    if (mask.size() != rows) throw std::invalid_argument(std::string(what) + ": mask must hold one byte per row");
+}
+
+// The list a call works on as the methods take it -- one pair's, or a batch's -- and the ABI call that spreads it into
+// the leading arguments of an entry point.
+struct OnePair {
+    const DMatch* matches;
+    const int* count;
+    int cap;
+    const float* query_xy;
+    int query_stride, nq;
+    const float* train_xy;
+    int train_stride, nt;
+};
+struct Batch {
+    const DMatch* matches;
+    const int* counts;
+    const std::vector<VerifyPair>& pairs;
+    int query_stride, train_stride;
+};
+template <class Fn, class... Rest>
+int abiCall(Fn fn, sift_hip_verifier* h, const OnePair& l, Rest... rest) {
+    return fn(h, abi(l.matches), l.count, l.cap, l.query_xy, l.query_stride, l.nq, l.train_xy, l.train_stride, l.nt, rest...);
+}
+template <class Fn, class... Rest>
+int abiCall(Fn fn, sift_hip_verifier* h, const Batch& l, Rest... rest) {
+    return fn(h, abi(l.matches), l.counts, (int)l.pairs.size(), toAbi(l.pairs), l.query_stride, l.train_stride, rest...);
+}
+
+// A model: its ABI record, the C++ record and geometry that mirror it, the matrix member they share, its entry points
+// by list type, and the names its host methods throw under.
+#define SIFT_MODEL(Name, name, Cxx, RECORD, RESULT, GEOMETRY, M)                                         \
+    struct Name {                                                                                        \
+        using Record = RECORD;                                                                           \
+        using Result = RESULT;                                                                           \
+        using Geometry = GEOMETRY;                                                                       \
+        static constexpr const char* verifyHostName = "Verifier::verify" #Cxx "Host";                    \
+        static constexpr const char* refineHostName = "Verifier::refine" #Cxx "Host";                    \
+        static const float (&matrix(const Record& r))[9] { return r.M; }                                 \
+        static float (&matrix(Geometry& g))[9] { return g.M; }                                           \
+        static auto verifyDevice(const OnePair&) { return sift_hip_verify_##name##_device; }             \
+        static auto verifyDevice(const Batch&) { return sift_hip_verify_##name##_batched_device; }       \
+        static auto verifyHost(const OnePair&) { return sift_hip_verify_##name##_host; }                 \
+        static auto verifyHost(const Batch&) { return sift_hip_verify_##name##_batched_host; }           \
+        static auto refineDevice(const OnePair&) { return sift_hip_refine_##name##_device; }             \
+        static auto refineDevice(const Batch&) { return sift_hip_refine_##name##_batched_device; }       \
+        static auto refineHost(const OnePair&) { return sift_hip_refine_##name##_host; }                 \
+        static auto refineHost(const Batch&) { return sift_hip_refine_##name##_batched_host; }           \
+    };
+SIFT_MODEL(Fundamental, fundamental, , sift_hip_verify_result, VerifyResult, TwoViewGeometry, F)
+SIFT_MODEL(Planar, homography, Homography, sift_hip_homography_result, HomographyResult, PlanarGeometry, H)
+#undef SIFT_MODEL
+
+template <class M>
+typename M::Record* abi(typename M::Result* r) {
+    return reinterpret_cast<typename M::Record*>(r);
+}
+
+// The geometry of a record and its inlier records.
+template <class M>
+typename M::Geometry geometry(const typename M::Record& r, std::vector<DMatch> inliers) {
+    typename M::Geometry g;
+    for (int i = 0; i < 9; i++) M::matrix(g)[i] = M::matrix(r)[i];
+    g.hypothesis = r.hypothesis;
+    g.inliers = std::move(inliers);
+    return g;
+}
+
+// The method shapes, one template each over the model (and, for the device forms, the list).
+template <class M, class List>
+void verifyDeviceT(sift_hip_verifier* h, const char* what, const List& l, const VerifyParams& params,
+                   typename M::Result* result, DMatch* out, int* out_count, uint8_t* mask, void* stream) {
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(abiCall(M::verifyDevice(l), h, l, &p, abi<M>(result), abi(out), out_count, mask, stream), what);
+}
+
+template <class M>
+typename M::Geometry verifyHostT(sift_hip_verifier* h, const char* what, const OnePair& l, const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    typename M::Record r{};
+    std::vector<DMatch> list(l.cap > 0 ? (size_t)l.cap : 0);
+    check_throw(abiCall(M::verifyHost(l), h, l, &p, &r, abi(list.data()), nullptr), what);
+    list.resize((size_t)r.inliers);
+    return geometry<M>(r, std::move(list));
+}
+
+// One geometry per pair from the host form's outputs: pair p's records are the first r[p].inliers of its rows.
+template <class M>
+std::vector<typename M::Geometry> verifyBatchedHostT(sift_hip_verifier* h, const char* what, const Batch& l,
+                                                     const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    std::vector<typename M::Record> r(l.pairs.size());
+    std::vector<DMatch> list(batchRows(l.pairs));
+    check_throw(abiCall(M::verifyHost(l), h, l, &p, r.data(), abi(list.data()), nullptr), what);
+    std::vector<typename M::Geometry> out(l.pairs.size());
     size_t row0 = 0;
-    for (size_t p = 0; p < pairs.size(); p++) {
-        for (int i = 0; i < 9; i++) (out[p].*model)[i] = (r[p].*from)[i];
-        out[p].hypothesis = r[p].hypothesis;
-        out[p].inliers.assign(list.begin() + row0, list.begin() + row0 + (size_t)r[p].inliers);
-        row0 += (size_t)pairs[p].cap;
+    for (size_t i = 0; i < l.pairs.size(); i++) {
+        out[i] = geometry<M>(r[i], {list.begin() + row0, list.begin() + row0 + (size_t)r[i].inliers});
+        row0 += (size_t)l.pairs[i].cap;
     }
     return out;
+}
+
+template <class M, class List>
+void refineDeviceT(sift_hip_verifier* h, const char* what, const List& l, float max_error, int rounds,
+                   typename M::Result* result, uint8_t* mask, DMatch* out, int* out_count, int* accepted, void* stream) {
+    check_throw(abiCall(M::refineDevice(l), h, l, max_error, rounds, abi<M>(result), mask, abi(out), out_count, accepted,
+                        stream),
+                what);
+}
+
+template <class M>
+int refineHostT(sift_hip_verifier* h, const char* what, const OnePair& l, float max_error, int rounds,
+                typename M::Result& result, std::vector<uint8_t>& mask, std::vector<DMatch>* inliers) {
+    if (l.cap >= 0 && l.cap <= 65536) check_mask(mask, (size_t)l.cap, what);
+    std::vector<DMatch> list(inliers && l.cap > 0 && l.cap <= 65536 ? (size_t)l.cap : 0);
+    int n = 0, accepted = 0;
+    check_throw(abiCall(M::refineHost(l), h, l, max_error, rounds, abi<M>(&result), mask.empty() ? nullptr : mask.data(),
+                        inliers ? abi(list.data()) : nullptr, &n, &accepted),
+                what);
+    if (inliers) {
+        list.resize((size_t)n);
+        *inliers = std::move(list);
+    }
+    return accepted;
+}
+
+template <class M>
+std::vector<int> refineBatchedHostT(sift_hip_verifier* h, const char* what, const Batch& l, float max_error, int rounds,
+                                    std::vector<typename M::Result>& results, std::vector<uint8_t>& mask,
+                                    std::vector<DMatch>* out, std::vector<int>* out_counts) {
+    if (results.size() != l.pairs.size()) throw std::invalid_argument(std::string(what) + ": one result record per pair");
+    const size_t rows = batchRows(l.pairs);
+    if (rows > 0) check_mask(mask, rows, what);
+    std::vector<DMatch> list(out ? rows : 0);
+    std::vector<int> n(l.pairs.size()), accepted(l.pairs.size());
+    check_throw(abiCall(M::refineHost(l), h, l, max_error, rounds, abi<M>(results.data()),
+                        mask.empty() ? nullptr : mask.data(), out ? abi(list.data()) : nullptr, n.data(), accepted.data()),
+                what);
+    if (out) *out = std::move(list);
+    if (out_counts) *out_counts = n;
+    return accepted;
+}
+
+// The convenience call on a host list: a verifier sized to it (the argument rules come first, they need no device
+// memory), the list uploaded, the host form, and with refit > 0 that many refit rounds on its record and mask.
+template <class M>
+typename M::Geometry verifyT(const char* what, const std::vector<DMatch>& matches, const OnePair& positions,
+                             const VerifyParams& params, int refit) {
+    const int n = (int)matches.size();
+    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), what);
+    OnePair l = positions;
+    l.matches = static_cast<const DMatch*>(d.p), l.count = nullptr, l.cap = n;
+    if (refit == 0) return verifyHostT<M>(v.handle(), M::verifyHostName, l, params);
+    const sift_hip_verify_params p = toAbi(params);
+    typename M::Result r{};
+    std::vector<uint8_t> mask(matches.size());
+    check_throw(abiCall(M::verifyHost(l), v.handle(), l, &p, abi<M>(&r), nullptr, mask.empty() ? nullptr : mask.data()),
+                what);
+    std::vector<DMatch> inliers;
+    refineHostT<M>(v.handle(), M::refineHostName, l, params.max_error, refit, r, mask, &inliers);
+    return geometry<M>(*abi<M>(&r), std::move(inliers));
 }
 
 }  // namespace
@@ -81,324 +235,92 @@ Verifier::Verifier(int max_matches, int max_hypotheses, int device, int max_pair
                 "Verifier::Verifier");
 }
 
-void Verifier::verifyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
-                                   int query_stride, int train_stride, const VerifyParams& params, VerifyResult* results,
-                                   DMatch* out, int* out_counts, uint8_t* mask, void* stream) {
-    const sift_hip_verify_params p = toAbi(params);
-    check_throw(sift_hip_verify_fundamental_batched_device(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
-                    query_stride, train_stride, &p, reinterpret_cast<sift_hip_verify_result*>(results),
-                    reinterpret_cast<sift_hip_dmatch*>(out), out_counts, mask, stream),
-                "Verifier::verifyBatchedDevice");
-}
-
-void Verifier::verifyHomographyBatchedDevice(const DMatch* matches, const int* counts,
-                                             const std::vector<VerifyPair>& pairs, int query_stride, int train_stride,
-                                             const VerifyParams& params, HomographyResult* results, DMatch* out,
-                                             int* out_counts, uint8_t* mask, void* stream) {
-    const sift_hip_verify_params p = toAbi(params);
-    check_throw(sift_hip_verify_homography_batched_device(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
-                    query_stride, train_stride, &p, reinterpret_cast<sift_hip_homography_result*>(results),
-                    reinterpret_cast<sift_hip_dmatch*>(out), out_counts, mask, stream),
-                "Verifier::verifyHomographyBatchedDevice");
-}
-
-std::vector<TwoViewGeometry> Verifier::verifyBatchedHost(const DMatch* matches, const int* counts,
-                                                         const std::vector<VerifyPair>& pairs, int query_stride,
-                                                         int train_stride, const VerifyParams& params) {
-    const sift_hip_verify_params p = toAbi(params);
-    std::vector<sift_hip_verify_result> r(pairs.size());
-    std::vector<DMatch> list(batchRows(pairs));
-    check_throw(sift_hip_verify_fundamental_batched_host(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
-                    query_stride, train_stride, &p, r.data(), reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
-                "Verifier::verifyBatchedHost");
-    return geometries<TwoViewGeometry>(pairs, r, list, &TwoViewGeometry::F, &sift_hip_verify_result::F);
-}
-
-std::vector<PlanarGeometry> Verifier::verifyHomographyBatchedHost(const DMatch* matches, const int* counts,
-                                                                  const std::vector<VerifyPair>& pairs, int query_stride,
-                                                                  int train_stride, const VerifyParams& params) {
-    const sift_hip_verify_params p = toAbi(params);
-    std::vector<sift_hip_homography_result> r(pairs.size());
-    std::vector<DMatch> list(batchRows(pairs));
-    check_throw(sift_hip_verify_homography_batched_host(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), counts, (int)pairs.size(), toAbi(pairs),
-                    query_stride, train_stride, &p, r.data(), reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
-                "Verifier::verifyHomographyBatchedHost");
-    return geometries<PlanarGeometry>(pairs, r, list, &PlanarGeometry::H, &sift_hip_homography_result::H);
-}
-
 Verifier::Verifier(int max_matches, int max_hypotheses, int device) {
     check_throw(sift_hip_verifier_create(device, max_matches, max_hypotheses, &m_handle), "Verifier::Verifier");
 }
 
 Verifier::~Verifier() { (void)sift_hip_verifier_destroy(m_handle); }
 
-void Verifier::verifyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
-                            int nq, const float* train_xy, int train_stride, int nt, const VerifyParams& params,
-                            VerifyResult* result, DMatch* out, int* out_count, uint8_t* mask, void* stream) {
-    const sift_hip_verify_params p = toAbi(params);
-    check_throw(sift_hip_verify_fundamental_device(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap, query_xy, query_stride, nq,
-                    train_xy, train_stride, nt, &p, reinterpret_cast<sift_hip_verify_result*>(result),
-                    reinterpret_cast<sift_hip_dmatch*>(out), out_count, mask, stream),
-                "Verifier::verifyDevice");
-}
+// The methods: each names its model, its list and itself.
+#define ONE_PAIR_ARGS                                                                                                  \
+    const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,                \
+        const float* train_xy, int train_stride, int nt
+#define ONE_PAIR OnePair{matches, count, cap, query_xy, query_stride, nq, train_xy, train_stride, nt}
+#define BATCH_ARGS \
+    const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs, int query_stride, int train_stride
+#define BATCH Batch{matches, counts, pairs, query_stride, train_stride}
 
-TwoViewGeometry Verifier::verifyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
-                                     int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                                     const VerifyParams& params) {
-    const sift_hip_verify_params p = toAbi(params);
-    sift_hip_verify_result r{};
-    std::vector<DMatch> list(cap > 0 ? (size_t)cap : 0);
-    check_throw(sift_hip_verify_fundamental_host(m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap,
-                                                 query_xy, query_stride, nq, train_xy, train_stride, nt, &p, &r,
-                                                 reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
-                "Verifier::verifyHost");
-    TwoViewGeometry g;
-    for (int i = 0; i < 9; i++) g.F[i] = r.F[i];
-    g.hypothesis = r.hypothesis;
-    list.resize((size_t)r.inliers);
-    g.inliers = std::move(list);
-    return g;
-}
+#define SIFT_VERIFIER_METHODS(Model, Cxx)                                                                              \
+    void Verifier::verify##Cxx##Device(ONE_PAIR_ARGS, const VerifyParams& params, Model::Result* result, DMatch* out,  \
+                                       int* out_count, uint8_t* mask, void* stream) {                                  \
+        verifyDeviceT<Model>(m_handle, "Verifier::verify" #Cxx "Device", ONE_PAIR, params, result, out, out_count,     \
+                             mask, stream);                                                                            \
+    }                                                                                                                  \
+    void Verifier::verify##Cxx##BatchedDevice(BATCH_ARGS, const VerifyParams& params, Model::Result* results,          \
+                                              DMatch* out, int* out_counts, uint8_t* mask, void* stream) {             \
+        verifyDeviceT<Model>(m_handle, "Verifier::verify" #Cxx "BatchedDevice", BATCH, params, results, out,           \
+                             out_counts, mask, stream);                                                                \
+    }                                                                                                                  \
+    Model::Geometry Verifier::verify##Cxx##Host(ONE_PAIR_ARGS, const VerifyParams& params) {                           \
+        return verifyHostT<Model>(m_handle, Model::verifyHostName, ONE_PAIR, params);                                  \
+    }                                                                                                                  \
+    std::vector<Model::Geometry> Verifier::verify##Cxx##BatchedHost(BATCH_ARGS, const VerifyParams& params) {          \
+        return verifyBatchedHostT<Model>(m_handle, "Verifier::verify" #Cxx "BatchedHost", BATCH, params);              \
+    }                                                                                                                  \
+    void Verifier::refine##Cxx##Device(ONE_PAIR_ARGS, float max_error, int rounds, Model::Result* result,              \
+                                       uint8_t* mask, DMatch* out, int* out_count, int* accepted, void* stream) {      \
+        refineDeviceT<Model>(m_handle, "Verifier::refine" #Cxx "Device", ONE_PAIR, max_error, rounds, result, mask,    \
+                             out, out_count, accepted, stream);                                                        \
+    }                                                                                                                  \
+    void Verifier::refine##Cxx##BatchedDevice(BATCH_ARGS, float max_error, int rounds, Model::Result* results,         \
+                                              uint8_t* mask, DMatch* out, int* out_counts, int* accepted,              \
+                                              void* stream) {                                                          \
+        refineDeviceT<Model>(m_handle, "Verifier::refine" #Cxx "BatchedDevice", BATCH, max_error, rounds, results,     \
+                             mask, out, out_counts, accepted, stream);                                                 \
+    }                                                                                                                  \
+    int Verifier::refine##Cxx##Host(ONE_PAIR_ARGS, float max_error, int rounds, Model::Result& result,                 \
+                                    std::vector<uint8_t>& mask, std::vector<DMatch>* inliers) {                        \
+        return refineHostT<Model>(m_handle, Model::refineHostName, ONE_PAIR, max_error, rounds, result, mask, inliers); \
+    }                                                                                                                  \
+    std::vector<int> Verifier::refine##Cxx##BatchedHost(BATCH_ARGS, float max_error, int rounds,                       \
+                                                        std::vector<Model::Result>& results,                           \
+                                                        std::vector<uint8_t>& mask, std::vector<DMatch>* out,          \
+                                                        std::vector<int>* out_counts) {                                \
+        return refineBatchedHostT<Model>(m_handle, "Verifier::refine" #Cxx "BatchedHost", BATCH, max_error, rounds,    \
+                                         results, mask, out, out_counts);                                              \
+    }
+SIFT_VERIFIER_METHODS(Fundamental, )
+SIFT_VERIFIER_METHODS(Planar, Homography)
+#undef SIFT_VERIFIER_METHODS
+#undef BATCH
+#undef BATCH_ARGS
+#undef ONE_PAIR
+#undef ONE_PAIR_ARGS
 
-void Verifier::verifyHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy,
-                                      int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                                      const VerifyParams& params, HomographyResult* result, DMatch* out, int* out_count,
-                                      uint8_t* mask, void* stream) {
-    const sift_hip_verify_params p = toAbi(params);
-    check_throw(sift_hip_verify_homography_device(
-                    m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap, query_xy, query_stride, nq,
-                    train_xy, train_stride, nt, &p, reinterpret_cast<sift_hip_homography_result*>(result),
-                    reinterpret_cast<sift_hip_dmatch*>(out), out_count, mask, stream),
-                "Verifier::verifyHomographyDevice");
-}
-
-PlanarGeometry Verifier::verifyHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
-                                              int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                                              const VerifyParams& params) {
-    const sift_hip_verify_params p = toAbi(params);
-    sift_hip_homography_result r{};
-    std::vector<DMatch> list(cap > 0 ? (size_t)cap : 0);
-    check_throw(sift_hip_verify_homography_host(m_handle, reinterpret_cast<const sift_hip_dmatch*>(matches), count, cap,
-                                                query_xy, query_stride, nq, train_xy, train_stride, nt, &p, &r,
-                                                reinterpret_cast<sift_hip_dmatch*>(list.data()), nullptr),
-                "Verifier::verifyHomographyHost");
-    PlanarGeometry g;
-    for (int i = 0; i < 9; i++) g.H[i] = r.H[i];
-    g.hypothesis = r.hypothesis;
-    list.resize((size_t)r.inliers);
-    g.inliers = std::move(list);
-    return g;
+TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
+                                  const float* train_xy, int nt, const VerifyParams& params, int query_stride,
+                                  int train_stride, int refit) {
+    return verifyT<Fundamental>("verifyFundamental", matches,
+                                OnePair{nullptr, nullptr, 0, query_xy, query_stride, nq, train_xy, train_stride, nt}, params,
+                                refit);
 }
 
 TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
                                   const float* train_xy, int nt, const VerifyParams& params, int query_stride,
                                   int train_stride) {
-    const int n = (int)matches.size();
-    // The argument rules first (they need no device memory): a verifier sized to this call.
-    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
-    DeviceBlock d(sizeof(DMatch) * matches.size());
-    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyFundamental");
-    return v.verifyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
-                        nt, params);
-}
-
-PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
-                                int nt, const VerifyParams& params, int query_stride, int train_stride) {
-    const int n = (int)matches.size();
-    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
-    DeviceBlock d(sizeof(DMatch) * matches.size());
-    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyHomography");
-    return v.verifyHomographyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy,
-                                  train_stride, nt, params);
-}
-
-// --- The refit (sift_hip_refine_*).
-
-namespace {
-
-sift_hip_dmatch* abi(DMatch* p) { return reinterpret_cast<sift_hip_dmatch*>(p); }
-const sift_hip_dmatch* abi(const DMatch* p) { return reinterpret_cast<const sift_hip_dmatch*>(p); }
-
-// The host forms' mask: one byte per row, or the ABI's refusal of the rows themselves (nothing is read then).
-void check_mask(const std::vector<uint8_t>& mask, size_t rows, const char* what) {
-    if (mask.size() != rows) throw std::invalid_argument(std::string(what) + ": mask must hold one byte per row");
-}
-
-}  // namespace
-
-void Verifier::refineDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
-                            int nq, const float* train_xy, int train_stride, int nt, float max_error, int rounds,
-                            VerifyResult* result, uint8_t* mask, DMatch* out, int* out_count, int* accepted,
-                            void* stream) {
-    check_throw(sift_hip_refine_fundamental_device(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
-                                                   train_stride, nt, max_error, rounds,
-                                                   reinterpret_cast<sift_hip_verify_result*>(result), mask, abi(out),
-                                                   out_count, accepted, stream),
-                "Verifier::refineDevice");
-}
-
-void Verifier::refineHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy,
-                                      int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                                      float max_error, int rounds, HomographyResult* result, uint8_t* mask, DMatch* out,
-                                      int* out_count, int* accepted, void* stream) {
-    check_throw(sift_hip_refine_homography_device(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
-                                                  train_stride, nt, max_error, rounds,
-                                                  reinterpret_cast<sift_hip_homography_result*>(result), mask, abi(out),
-                                                  out_count, accepted, stream),
-                "Verifier::refineHomographyDevice");
-}
-
-int Verifier::refineHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
-                         const float* train_xy, int train_stride, int nt, float max_error, int rounds,
-                         VerifyResult& result, std::vector<uint8_t>& mask, std::vector<DMatch>* inliers) {
-    if (cap >= 0 && cap <= 65536) check_mask(mask, (size_t)cap, "Verifier::refineHost");
-    std::vector<DMatch> list(inliers && cap > 0 && cap <= 65536 ? (size_t)cap : 0);
-    int n = 0, accepted = 0;
-    check_throw(sift_hip_refine_fundamental_host(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
-                                                 train_stride, nt, max_error, rounds,
-                                                 reinterpret_cast<sift_hip_verify_result*>(&result),
-                                                 mask.empty() ? nullptr : mask.data(),
-                                                 inliers ? abi(list.data()) : nullptr, &n, &accepted),
-                "Verifier::refineHost");
-    if (inliers) {
-        list.resize((size_t)n);
-        *inliers = std::move(list);
-    }
-    return accepted;
-}
-
-int Verifier::refineHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
-                                   int query_stride, int nq, const float* train_xy, int train_stride, int nt,
-                                   float max_error, int rounds, HomographyResult& result, std::vector<uint8_t>& mask,
-                                   std::vector<DMatch>* inliers) {
-    if (cap >= 0 && cap <= 65536) check_mask(mask, (size_t)cap, "Verifier::refineHomographyHost");
-    std::vector<DMatch> list(inliers && cap > 0 && cap <= 65536 ? (size_t)cap : 0);
-    int n = 0, accepted = 0;
-    check_throw(sift_hip_refine_homography_host(m_handle, abi(matches), count, cap, query_xy, query_stride, nq, train_xy,
-                                                train_stride, nt, max_error, rounds,
-                                                reinterpret_cast<sift_hip_homography_result*>(&result),
-                                                mask.empty() ? nullptr : mask.data(),
-                                                inliers ? abi(list.data()) : nullptr, &n, &accepted),
-                "Verifier::refineHomographyHost");
-    if (inliers) {
-        list.resize((size_t)n);
-        *inliers = std::move(list);
-    }
-    return accepted;
-}
-
-void Verifier::refineBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
-                                   int query_stride, int train_stride, float max_error, int rounds, VerifyResult* results,
-                                   uint8_t* mask, DMatch* out, int* out_counts, int* accepted, void* stream) {
-    check_throw(sift_hip_refine_fundamental_batched_device(m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs),
-                                                           query_stride, train_stride, max_error, rounds,
-                                                           reinterpret_cast<sift_hip_verify_result*>(results), mask,
-                                                           abi(out), out_counts, accepted, stream),
-                "Verifier::refineBatchedDevice");
-}
-
-void Verifier::refineHomographyBatchedDevice(const DMatch* matches, const int* counts,
-                                             const std::vector<VerifyPair>& pairs, int query_stride, int train_stride,
-                                             float max_error, int rounds, HomographyResult* results, uint8_t* mask,
-                                             DMatch* out, int* out_counts, int* accepted, void* stream) {
-    check_throw(sift_hip_refine_homography_batched_device(m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs),
-                                                          query_stride, train_stride, max_error, rounds,
-                                                          reinterpret_cast<sift_hip_homography_result*>(results), mask,
-                                                          abi(out), out_counts, accepted, stream),
-                "Verifier::refineHomographyBatchedDevice");
-}
-
-std::vector<int> Verifier::refineBatchedHost(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
-                                             int query_stride, int train_stride, float max_error, int rounds,
-                                             std::vector<VerifyResult>& results, std::vector<uint8_t>& mask,
-                                             std::vector<DMatch>* out, std::vector<int>* out_counts) {
-    if (results.size() != pairs.size())
-        throw std::invalid_argument("Verifier::refineBatchedHost: one result record per pair");
-    const size_t rows = batchRows(pairs);
-    if (rows > 0) check_mask(mask, rows, "Verifier::refineBatchedHost");
-    std::vector<DMatch> list(out ? rows : 0);
-    std::vector<int> n(pairs.size()), accepted(pairs.size());
-    check_throw(sift_hip_refine_fundamental_batched_host(
-                    m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs), query_stride, train_stride, max_error,
-                    rounds, reinterpret_cast<sift_hip_verify_result*>(results.data()), mask.empty() ? nullptr : mask.data(),
-                    out ? abi(list.data()) : nullptr, n.data(), accepted.data()),
-                "Verifier::refineBatchedHost");
-    if (out) *out = std::move(list);
-    if (out_counts) *out_counts = n;
-    return accepted;
-}
-
-std::vector<int> Verifier::refineHomographyBatchedHost(const DMatch* matches, const int* counts,
-                                                       const std::vector<VerifyPair>& pairs, int query_stride,
-                                                       int train_stride, float max_error, int rounds,
-                                                       std::vector<HomographyResult>& results, std::vector<uint8_t>& mask,
-                                                       std::vector<DMatch>* out, std::vector<int>* out_counts) {
-    if (results.size() != pairs.size())
-        throw std::invalid_argument("Verifier::refineHomographyBatchedHost: one result record per pair");
-    const size_t rows = batchRows(pairs);
-    if (rows > 0) check_mask(mask, rows, "Verifier::refineHomographyBatchedHost");
-    std::vector<DMatch> list(out ? rows : 0);
-    std::vector<int> n(pairs.size()), accepted(pairs.size());
-    check_throw(sift_hip_refine_homography_batched_host(
-                    m_handle, abi(matches), counts, (int)pairs.size(), toAbi(pairs), query_stride, train_stride, max_error,
-                    rounds, reinterpret_cast<sift_hip_homography_result*>(results.data()),
-                    mask.empty() ? nullptr : mask.data(), out ? abi(list.data()) : nullptr, n.data(), accepted.data()),
-                "Verifier::refineHomographyBatchedHost");
-    if (out) *out = std::move(list);
-    if (out_counts) *out_counts = n;
-    return accepted;
-}
-
-TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const float* query_xy, int nq,
-                                  const float* train_xy, int nt, const VerifyParams& params, int query_stride,
-                                  int train_stride, int refit) {
-    if (refit == 0) return verifyFundamental(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride);
-    const int n = (int)matches.size();
-    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
-    DeviceBlock d(sizeof(DMatch) * matches.size());
-    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyFundamental");
-    const sift_hip_verify_params p = toAbi(params);
-    VerifyResult r{};
-    std::vector<uint8_t> mask(matches.size());
-    check_throw(sift_hip_verify_fundamental_host(v.handle(), abi(static_cast<const DMatch*>(d.p)), nullptr, n, query_xy,
-                                                 query_stride, nq, train_xy, train_stride, nt, &p,
-                                                 reinterpret_cast<sift_hip_verify_result*>(&r), nullptr,
-                                                 mask.empty() ? nullptr : mask.data()),
-                "verifyFundamental");
-    TwoViewGeometry g;
-    v.refineHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride, nt,
-                 params.max_error, refit, r, mask, &g.inliers);
-    for (int i = 0; i < 9; i++) g.F[i] = r.F[i];
-    g.hypothesis = r.hypothesis;
-    return g;
+    return verifyFundamental(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride, 0);
 }
 
 PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                                 int nt, const VerifyParams& params, int query_stride, int train_stride, int refit) {
-    if (refit == 0) return verifyHomography(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride);
-    const int n = (int)matches.size();
-    Verifier v(n > 0 ? n : 1, params.hypotheses > 0 && params.hypotheses <= 4096 ? params.hypotheses : 1);
-    DeviceBlock d(sizeof(DMatch) * matches.size());
-    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "verifyHomography");
-    const sift_hip_verify_params p = toAbi(params);
-    HomographyResult r{};
-    std::vector<uint8_t> mask(matches.size());
-    check_throw(sift_hip_verify_homography_host(v.handle(), abi(static_cast<const DMatch*>(d.p)), nullptr, n, query_xy,
-                                                query_stride, nq, train_xy, train_stride, nt, &p,
-                                                reinterpret_cast<sift_hip_homography_result*>(&r), nullptr,
-                                                mask.empty() ? nullptr : mask.data()),
-                "verifyHomography");
-    PlanarGeometry g;
-    v.refineHomographyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
-                           nt, params.max_error, refit, r, mask, &g.inliers);
-    for (int i = 0; i < 9; i++) g.H[i] = r.H[i];
-    g.hypothesis = r.hypothesis;
-    return g;
+    return verifyT<Planar>("verifyHomography", matches,
+                           OnePair{nullptr, nullptr, 0, query_xy, query_stride, nq, train_xy, train_stride, nt}, params,
+                           refit);
+}
+
+PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const VerifyParams& params, int query_stride, int train_stride) {
+    return verifyHomography(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride, 0);
 }
 
 void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

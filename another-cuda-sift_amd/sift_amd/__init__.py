@@ -1199,6 +1199,33 @@ class Verifier:
             _lib.sift_hip_verifier_destroy(v)
             self._v = None
 
+    # --- one pair (sift_hip_verify_*_device / _host, sift_hip_score_*_device): the two models' methods differ in the
+    # entry point and the record type only.
+
+    def _device(self, fn, what, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, out_ptr,
+                out_count_ptr, mask_ptr, max_error, hypotheses, seed, q_stride, t_stride, stream):
+        p = _VerifyParams(hypotheses, seed, max_error)
+        _check(fn(self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+                  t_stride, nt, ctypes.byref(p), result_ptr or None, out_ptr or None, out_count_ptr or None,
+                  mask_ptr or None, stream), what)
+
+    def _host(self, fn, what, record, dtype, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, max_error, hypotheses, seed,
+              q_stride, t_stride, full):
+        p = _VerifyParams(hypotheses, seed, max_error)
+        r = record()
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        mask = np.zeros(max(cap, 0), np.uint8)
+        _check(fn(self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+                  t_stride, nt, ctypes.byref(p), ctypes.byref(r), _ptr(out), _ptr(mask)), what)
+        if full:
+            return np.frombuffer(bytes(r), dtype)[0], out[: r.inliers], mask
+        return np.array(getattr(r, dtype.names[0]), np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+
+    def _score(self, fn, what, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, M_ptr, K, max_error, counts_ptr,
+               q_stride, t_stride, stream):
+        _check(fn(self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+                  t_stride, nt, M_ptr or None, K, max_error, counts_ptr or None, stream), what)
+
     def verify_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
                       result_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0, mask_ptr: int = 0,
                       max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
@@ -1206,12 +1233,9 @@ class Verifier:
         """Enqueue the operation (sift_hip_verify_fundamental_device); every pointer is device memory.  count_ptr: the
         device int holding the number of records (0: all `cap` count) -- e.g. match_list_device's count; result_ptr: a
         VERIFY_RESULT_DTYPE record; out_ptr (room for cap records), out_count_ptr and mask_ptr (cap bytes) may be 0."""
-        p = _VerifyParams(hypotheses, seed, max_error)
-        _check(lib().sift_hip_verify_fundamental_device(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                        q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                        ctypes.byref(p), result_ptr or None, out_ptr or None,
-                                                        out_count_ptr or None, mask_ptr or None, stream),
-               "verify_fundamental_device")
+        self._device(lib().sift_hip_verify_fundamental_device, "verify_fundamental_device", matches_ptr, count_ptr, cap,
+                     q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, out_ptr, out_count_ptr, mask_ptr, max_error, hypotheses, seed,
+                     q_stride, t_stride, stream)
         self._hypotheses = hypotheses
 
     def verify_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
@@ -1219,27 +1243,18 @@ class Verifier:
                     t_stride: int = 3, full: bool = False):
         """Synchronous (sift_hip_verify_fundamental_host): (F 3 x 3 float32, the inlier records as a DMATCH_DTYPE array,
         the winning hypothesis or -1).  full: (the VERIFY_RESULT_DTYPE record, the records, the mask of cap bytes)."""
-        p = _VerifyParams(hypotheses, seed, max_error)
-        r = _VerifyResult()
-        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
-        mask = np.zeros(max(cap, 0), np.uint8)
-        _check(lib().sift_hip_verify_fundamental_host(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                      q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                      ctypes.byref(p), ctypes.byref(r), _ptr(out), _ptr(mask)),
-               "verify_fundamental_host")
+        got = self._host(lib().sift_hip_verify_fundamental_host, "verify_fundamental_host", _VerifyResult,
+                         VERIFY_RESULT_DTYPE, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, max_error,
+                         hypotheses, seed, q_stride, t_stride, full)
         self._hypotheses = hypotheses
-        if full:
-            return np.frombuffer(bytes(r), VERIFY_RESULT_DTYPE)[0], out[: r.inliers], mask
-        return np.array(r.F, np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+        return got
 
     def score_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
                      F_ptr: int, K: int, max_error: float, counts_ptr: int, q_stride: int = 3, t_stride: int = 3,
                      stream: Optional[int] = None) -> None:
         """The score alone on the caller's K hypotheses (device, K x 9 floats): counts (device, K ints)."""
-        _check(lib().sift_hip_score_fundamental_device(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                       q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                       F_ptr or None, K, max_error, counts_ptr or None, stream),
-               "score_fundamental_device")
+        self._score(lib().sift_hip_score_fundamental_device, "score_fundamental_device", matches_ptr, count_ptr, cap,
+                    q_xy_ptr, nq, t_xy_ptr, nt, F_ptr, K, max_error, counts_ptr, q_stride, t_stride, stream)
 
     def hypotheses(self):
         """What the last verify call drew, solved and counted: (samples (K, 8) int32, F (K, 9) float32, valid (K,) bool
@@ -1257,12 +1272,9 @@ class Verifier:
         """verify_device for the homography (sift_hip_verify_homography_device), argument for argument; result_ptr: a
         HOMOGRAPHY_RESULT_DTYPE record, whose address is also the H project_homography_device takes; max_error: the
         transfer error in pixels."""
-        p = _VerifyParams(hypotheses, seed, max_error)
-        _check(lib().sift_hip_verify_homography_device(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                       q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                       ctypes.byref(p), result_ptr or None, out_ptr or None,
-                                                       out_count_ptr or None, mask_ptr or None, stream),
-               "verify_homography_device")
+        self._device(lib().sift_hip_verify_homography_device, "verify_homography_device", matches_ptr, count_ptr, cap,
+                     q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, out_ptr, out_count_ptr, mask_ptr, max_error, hypotheses, seed,
+                     q_stride, t_stride, stream)
         self._h_hypotheses = hypotheses
 
     def verify_homography_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
@@ -1271,28 +1283,19 @@ class Verifier:
         """Synchronous (sift_hip_verify_homography_host): (H 3 x 3 float32 of unit norm, the inlier records as a
         DMATCH_DTYPE array, the winning hypothesis or -1).  full: (the HOMOGRAPHY_RESULT_DTYPE record, the records, the
         mask of cap bytes)."""
-        p = _VerifyParams(hypotheses, seed, max_error)
-        r = _HomographyResult()
-        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
-        mask = np.zeros(max(cap, 0), np.uint8)
-        _check(lib().sift_hip_verify_homography_host(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                     q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                     ctypes.byref(p), ctypes.byref(r), _ptr(out), _ptr(mask)),
-               "verify_homography_host")
+        got = self._host(lib().sift_hip_verify_homography_host, "verify_homography_host", _HomographyResult,
+                         HOMOGRAPHY_RESULT_DTYPE, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, max_error,
+                         hypotheses, seed, q_stride, t_stride, full)
         self._h_hypotheses = hypotheses
-        if full:
-            return np.frombuffer(bytes(r), HOMOGRAPHY_RESULT_DTYPE)[0], out[: r.inliers], mask
-        return np.array(r.H, np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+        return got
 
     def score_homography_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
                                 nt: int, H_ptr: int, K: int, max_error: float, counts_ptr: int, q_stride: int = 3,
                                 t_stride: int = 3, stream: Optional[int] = None) -> None:
         """The transfer-error score alone on the caller's K homographies (device, K x 9 floats): counts (device, K
         ints)."""
-        _check(lib().sift_hip_score_homography_device(self._v, matches_ptr or None, count_ptr or None, cap,
-                                                      q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride, nt,
-                                                      H_ptr or None, K, max_error, counts_ptr or None, stream),
-               "score_homography_device")
+        self._score(lib().sift_hip_score_homography_device, "score_homography_device", matches_ptr, count_ptr, cap,
+                    q_xy_ptr, nq, t_xy_ptr, nt, H_ptr, K, max_error, counts_ptr, q_stride, t_stride, stream)
 
     def homography_hypotheses(self):
         """What the last verify call drew, solved and counted, when it was a homography call: (samples (K, 4) int32, H

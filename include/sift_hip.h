@@ -881,6 +881,23 @@ int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_
  * CU count; 256 without a device), for tests and tools. */
 int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, int* waves);
 
+/* --- The verifier's refusals ----------------------------------------------------
+ *
+ * Every verifier call that takes a match list (sift_hip_verify_*, sift_hip_score_*
+ * and sift_hip_refine_*, single-pair and batched, device and host form) judges
+ * its arguments in ONE order and reports the first rule broken, with nothing
+ * launched and nothing written.  First what needs no look at the verifier:
+ *   a null verifier; null pairs; a null params or result (the score calls: a
+ *   null F / H or counts); P outside 1..64; a stride < 2; then pair by pair a cap
+ *   outside 0..65536, a negative nq or nt, a null position pointer with cap > 0;
+ *   null matches with a row to read; max_error not > 0 and finite; out
+ *   overlapping matches (device forms); the refine calls' null mask, then rounds
+ *   outside 1..8;
+ * then the verifier's limits: hypotheses outside 1..max_hypotheses, P over
+ * max_pairs, the caps' sum (the cap) over max_matches.  A single-pair call is
+ * judged as the batch of its one pair; a batched call names the pair in the
+ * message of a per-pair rule. */
+
 /* --- Two-view verification: RANSAC for the fundamental matrix ------------------
  *
  * The step between a putative match list and guided matching under F (COLMAP's

@@ -238,6 +238,38 @@ def test_limits_of_a_real_verifier_and_the_host_forms(sift):
     assert F2.tobytes() == F.tobytes() and inl3.tobytes() == inl.tobytes() and hyp2 == hyp
 
 
+@pytest.mark.parametrize("model", ["fundamental", "homography"])
+def test_host_form_leaves_the_rows_past_the_inliers_as_they_were(sift, model):
+    """sift_hip_verify_*_host on the C ABI with the caller's out_host prefilled: the first `inliers` rows are the
+    rule's list, every byte behind them is the caller's still (the Python host forms hand in a fresh array and return
+    its head, so they cannot see this).  cap 12 with a device count of 9: the mask is cap bytes, zero from n on."""
+    import ctypes
+
+    from sift_amd import cv
+
+    cap, count, K = 12, 9, 16
+    m, q_xy, t_xy, _ = vc.case(9, 3)
+    assert len(m) == cap
+    rule, field, dtype = {"fundamental": (cv.ransac_fundamental, "F", sift.VERIFY_RESULT_DTYPE),
+                          "homography": (cv.ransac_homography, "H", sift.HOMOGRAPHY_RESULT_DTYPE)}[model]
+    ref = rule(m[:count], q_xy, t_xy, vc.MAX_ERROR, K, 0)
+    n = int(ref["inliers"])
+    assert 0 < n < count
+    v = sift.Verifier(cap, K)
+    dm, dq, dt, dc = dev(sift, m), dev(sift, q_xy), dev(sift, t_xy), dev(sift, np.int32([count]))
+    rec, out, mask = np.zeros(1, dtype), np.full(16 * cap, FILL, np.uint8), np.full(cap, FILL, np.uint8)
+    fn = getattr(sift.lib(), f"sift_hip_verify_{model}_host")
+    p = sift._VerifyParams(K, 0, vc.MAX_ERROR)
+    rc = fn(v._v, dm.value, dc.value, cap, dq.value, 2, len(q_xy), dt.value, 2, len(t_xy), ctypes.byref(p),
+            ctypes.cast(rec.ctypes.data, fn.argtypes[11]), out.ctypes.data, mask.ctypes.data)
+    assert rc == 0, sift.lib().sift_hip_last_error()
+    assert rec[field][0].tobytes() == ref[field].tobytes()
+    assert (rec["inliers"][0], rec["hypothesis"][0], rec["matches"][0]) == (n, ref["hypothesis"], count)
+    assert out[:16 * n].tobytes() == ref["list"].tobytes()
+    assert (out[16 * n:] == FILL).all()
+    assert np.array_equal(mask[:count], ref["mask"]) and not mask[count:].any()
+
+
 def test_chain_on_one_stream(sift):
     """match_list_device -> verify_device (its count taken from the list's device counter) on one stream with no host
     synchronisation in between; F is read back once and match_list_epipolar_device follows.  Equal to the same three
