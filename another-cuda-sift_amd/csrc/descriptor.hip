@@ -43,6 +43,7 @@
 #include "sift_desc_rows.h"
 #include "sift_kernels.h"
 #include "sift_math.h"
+#include "sift_rootsift.h"
 
 namespace sift_amd {
 
@@ -189,7 +190,9 @@ __device__ __forceinline__ float wave_sum(float x) {
     x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x143, 0xc, 0xf, false));
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }
-template <int kDT>
+// kRoot: the RootSIFT epilogue (sift_hip_set_descriptor_norm, sift_rootsift.h);
+// the kRoot = false instantiations carry none of it.
+template <int kDT, bool kRoot>
 __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* __restrict__ jobs, const Counters* __restrict__ ctr,
                                                    const unsigned* __restrict__ range_keys,
                                                    uint16_t* __restrict__ desc, Sidecar sidecar,
@@ -523,6 +526,16 @@ __global__ __launch_bounds__(kDT, kDescWaves) void k_descriptor(const DescJob* _
         for (int h = 0; h < kPer; h++) {
             int v = cv_round(val[h] * scale);
             v = v < 0 ? 0 : (v > 255 ? 255 : v);
+            if constexpr (kRoot) {
+                // The row's byte sum (small integers: exact in float, in any
+                // order): a wave sum of the 128 owners' bytes, the two
+                // partials through LDS.  s_norm[8..11] are next written after
+                // the barriers of the following keypoint.
+                const float ws = wave_sum(own ? (float)v : 0.f);
+                if (lane == 0) s_norm[8 + (tid >> 6)] = ws;
+                lds_barrier();
+                v = root_byte(v, (int)(s_norm[8] + s_norm[9]));
+            }
             const _Float16 hv = (_Float16)(float)v;
             if (tid + kDT * h < 128) {
                 desc[(size_t)po * 128 + tid + kDT * h] = __builtin_bit_cast(uint16_t, hv);
@@ -628,6 +641,7 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int x) {
         : "+v"(x));
     return x;
 }
+template <bool kRoot>
 __global__ __launch_bounds__(kExactWG, kExactMinWaves) void k_descriptor_exact(const DescJob* __restrict__ jobs,
                                                                     const Counters* __restrict__ ctr,
                                                                     uint16_t* __restrict__ desc, Sidecar sidecar,
@@ -913,6 +927,11 @@ __global__ __launch_bounds__(kExactWG, kExactMinWaves) void k_descriptor_exact(c
         int b0 = cv_round(v0 * scale), b1 = cv_round(v1 * scale);
         b0 = b0 < 0 ? 0 : (b0 > 255 ? 255 : b0);
         b1 = b1 < 0 ? 0 : (b1 > 255 ? 255 : b1);
+        if constexpr (kRoot) {  // RootSIFT (sift_rootsift.h): one wave sum of the row's bytes
+            const int s = __builtin_amdgcn_readlane(wave_incl_scan(b0 + b1), 63);
+            b0 = root_byte(b0, s);
+            b1 = root_byte(b1, s);
+        }
         const _Float16 h0 = (_Float16)(float)b0, h1 = (_Float16)(float)b1;
         const unsigned po = (unsigned)jb.out;
         const unsigned pair = (unsigned)__builtin_bit_cast(uint16_t, h0) | (unsigned)__builtin_bit_cast(uint16_t, h1) << 16;
@@ -932,19 +951,22 @@ __global__ __launch_bounds__(kExactWG, kExactMinWaves) void k_descriptor_exact(c
 void launch_descriptor(const DescJob* jobs, const Counters* ctr, const unsigned* range_keys, uint16_t* desc,
                        Sidecar sidecar, Counters* host_ctr, HostOut host, const KeypointParams& kp, const Frames& fr,
                        hipStream_t s) {
+    const bool root = kp.descRoot != 0;  // picks the instantiation: a root-less handle runs the kernels without the epilogue
     if (kp.descExact) {
         // One wave per keypoint; each workgroup loops over keypoints.
         const int per = fr.nf <= 1 ? 2048 : std::max(512, 8192 / fr.nf);
-        hipLaunchKernelGGL(k_descriptor_exact, dim3(per * fr.nf),
-                           dim3(kExactWG), 0, s, jobs, ctr, desc, sidecar, host_ctr, host, fr.stride, (unsigned)fr.nf);
+        const auto k = root ? k_descriptor_exact<true> : k_descriptor_exact<false>;
+        hipLaunchKernelGGL(k, dim3(per * fr.nf), dim3(kExactWG), 0, s, jobs, ctr, desc, sidecar, host_ctr, host,
+                           fr.stride, (unsigned)fr.nf);
         return;
     }
     // Threads per keypoint: 256 for a single frame (128: 34.6 us, 512: 47.6 vs
     // 36.1 per frame, round 3), 128 for frame batches.
     constexpr int kSingleDT = 256, kBatchDT = 128;
     if (fr.nf <= 1) {
-        hipLaunchKernelGGL(k_descriptor<kSingleDT>, dim3(8192), dim3(kSingleDT), 0, s, jobs, ctr, range_keys, desc,
-                           sidecar, host_ctr, host, fr.stride, 1u);
+        const auto k = root ? k_descriptor<kSingleDT, true> : k_descriptor<kSingleDT, false>;
+        hipLaunchKernelGGL(k, dim3(8192), dim3(kSingleDT), 0, s, jobs, ctr, range_keys, desc, sidecar, host_ctr, host,
+                           fr.stride, 1u);
     } else {
         // Workgroups per frame: 2048 at 8 frames (16384 in all).  The bigger
         // grids this kernel once had filled every CU slot and kept the other
@@ -952,8 +974,9 @@ void launch_descriptor(const DescJob* jobs, const Counters* ctr, const unsigned*
         // over more keypoints) the two co-reside: +2-3 % frame rate
         // (tools/grid_sweep.sh).
         const int per = std::max(1024, 16384 / fr.nf);
-        hipLaunchKernelGGL(k_descriptor<kBatchDT>, dim3(per * fr.nf), dim3(kBatchDT), 0, s, jobs, ctr, range_keys,
-                           desc, sidecar, host_ctr, host, fr.stride, (unsigned)fr.nf);
+        const auto k = root ? k_descriptor<kBatchDT, true> : k_descriptor<kBatchDT, false>;
+        hipLaunchKernelGGL(k, dim3(per * fr.nf), dim3(kBatchDT), 0, s, jobs, ctr, range_keys, desc, sidecar, host_ctr,
+                           host, fr.stride, (unsigned)fr.nf);
     }
 }
 

@@ -1228,6 +1228,26 @@ int sift_hip_descriptor_mode(sift_hip_t d, int* mode) {
     return SIFT_HIP_OK;
 }
 
+// Independent of the descriptor mode: either kernel has a RootSIFT epilogue.
+// Stage dumps are compared with the oracle's L2 rows, so ROOT and datagen
+// exclude each other (as the masked calls and datagen do).
+int sift_hip_set_descriptor_norm(sift_hip_t d, int norm) {
+    if (!d) return fail(SIFT_HIP_ERR_INVALID, "null handle");
+    if (norm != SIFT_HIP_NORM_L2 && norm != SIFT_HIP_NORM_ROOT) return fail(SIFT_HIP_ERR_INVALID, "unknown descriptor norm");
+    if (d->allocated) return fail(SIFT_HIP_ERR_STATE, "sift_hip_set_descriptor_norm after sift_hip_warmup");
+    if (norm == SIFT_HIP_NORM_ROOT && !d->dgDir.empty())
+        return fail(SIFT_HIP_ERR_STATE,
+                    "SIFT_HIP_NORM_ROOT while sift_hip_set_datagen is active (stage dumps hold the oracle's L2 rows)");
+    d->kp.descRoot = norm == SIFT_HIP_NORM_ROOT;
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_descriptor_norm(sift_hip_t d, int* norm) {
+    if (!d || !norm) return fail(SIFT_HIP_ERR_INVALID, "null argument");
+    *norm = d->kp.descRoot ? SIFT_HIP_NORM_ROOT : SIFT_HIP_NORM_L2;
+    return SIFT_HIP_OK;
+}
+
 int sift_hip_batch_capacity(sift_hip_t d, int* frames) {
     if (!d || !frames) return fail(SIFT_HIP_ERR_INVALID, "null argument");
     *frames = d->B;
@@ -1386,6 +1406,9 @@ int sift_hip_copy_descriptors_device(sift_hip_t d, uint16_t* dst, int cap, void*
 
 int sift_hip_set_datagen(sift_hip_t d, const char* dir) {
     if (!d) return fail(SIFT_HIP_ERR_INVALID, "null handle");
+    if (dir && *dir && d->kp.descRoot)
+        return fail(SIFT_HIP_ERR_STATE,
+                    "sift_hip_set_datagen on a SIFT_HIP_NORM_ROOT handle (stage dumps hold the oracle's L2 rows)");
     d->dgDir = dir ? dir : "";
     return SIFT_HIP_OK;
 }

@@ -288,6 +288,17 @@ void Detector::setExactDescriptors(bool exact) {
               "setExactDescriptors");
 }
 
+void Detector::setRootSift(bool root) {
+    if (m_handle)
+        check_throw(sift_hip_set_descriptor_norm(m_handle, root ? SIFT_HIP_NORM_ROOT : SIFT_HIP_NORM_L2), "setRootSift");
+}
+
+bool Detector::rootSift() const {
+    int norm = SIFT_HIP_NORM_L2;
+    if (m_handle) (void)sift_hip_descriptor_norm(m_handle, &norm);
+    return norm == SIFT_HIP_NORM_ROOT;
+}
+
 void Detector::replayStage(const std::string& dump_dir, const std::string& stage, const std::string& out_dir) {
     if (!m_initialized && !gpuWarmUpAndAllocate()) return;
     check(sift_hip_replay_stage(m_handle, dump_dir.c_str(), stage.c_str(), out_dir.c_str()), "replayStage");
@@ -324,6 +335,16 @@ struct MatcherDeleter {
 };
 
 }  // namespace
+
+void rootSiftDevice(const Half* in, int n, Half* out, void* stream) {
+    check_throw(sift_hip_rootsift_device(reinterpret_cast<const uint16_t*>(in), n, reinterpret_cast<uint16_t*>(out), stream),
+                "rootSiftDevice");
+}
+
+void rootSiftHost(const Half* in, int n, Half* out) {
+    check_throw(sift_hip_rootsift_host(reinterpret_cast<const uint16_t*>(in), n, reinterpret_cast<uint16_t*>(out)),
+                "rootSiftHost");
+}
 
 std::vector<int> matchBruteForce(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
                                  int num_src) {

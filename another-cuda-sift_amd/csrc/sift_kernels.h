@@ -164,6 +164,7 @@ struct KeypointParams {
     int oriRmax, descRmax;  // LDS patch bounds for orientation / descriptor radii
     int descNrec;           // LDS record bound of the descriptor's counting sort
     int descExact;          // 1: OpenCV's sequential float histogram (k_descriptor_exact)
+    int descRoot;           // 1: RootSIFT rows (SIFT_HIP_NORM_ROOT, sift_rootsift.h), either kernel
 };
 // Detection mask (cv::SIFT::detectAndCompute's mask argument; OpenCV's
 // KeyPointsFilter::runByPixelsMask): W x H bytes in device-readable memory,

@@ -35,6 +35,7 @@ LIB_PATH = os.environ.get("SIFT_HIP_LIB") or os.path.join(LIB_DIR, "libsift_hip.
 SIFT_HIP_OK = 0
 SIFT_HIP_F32, SIFT_HIP_U8 = 0, 1  # pixel formats (include/sift_hip.h)
 SIFT_HIP_DESC_FAST, SIFT_HIP_DESC_EXACT = 0, 1  # descriptor modes (sift_hip_set_descriptor_mode)
+SIFT_HIP_NORM_L2, SIFT_HIP_NORM_ROOT = 0, 1  # descriptor norms (sift_hip_set_descriptor_norm)
 SIFT_HIP_FLAG_BAD_KEYPOINT = 16  # overflow_flags() bit: computeDevice met an invalid keypoint
 # sift_hip_keypoint (cv::KeyPoint minus class_id, 24 bytes): the records Detector.compute takes.
 # octave is OpenCV's packed form (octave & 255 | layer << 8 | xi << 16).
@@ -243,6 +244,10 @@ def lib() -> ctypes.CDLL:
         "sift_hip_batch_capacity": (i, [vp, ip]),
         "sift_hip_set_descriptor_mode": (i, [vp, i]),
         "sift_hip_descriptor_mode": (i, [vp, ip]),
+        "sift_hip_set_descriptor_norm": (i, [vp, i]),
+        "sift_hip_descriptor_norm": (i, [vp, ip]),
+        "sift_hip_rootsift_device": (i, [vp, i, vp, vp]),
+        "sift_hip_rootsift_host": (i, [vp, i, vp]),
         "sift_hip_capacities": (i, [vp, ip, ip, ip, ip]),
         "sift_hip_detect_batch_device": (i, [vp, vp, i, sz, sz, i, vp]),
         "sift_hip_batch_frames": (i, [vp, ip]),
@@ -447,7 +452,8 @@ class Detector:
     """sift_cuda::Detector (Detector.hh:24-96) over the C ABI."""
 
     def __init__(self, config: CudaSiftConfig, device: int = -1, batch: int = 1, exact_descriptors: bool = False,
-                 lanes: Optional[int] = None, micro_batch: int = 1, auto_micro_batch: Optional[int] = None):
+                 lanes: Optional[int] = None, micro_batch: int = 1, auto_micro_batch: Optional[int] = None,
+                 root_sift: bool = False):
         """batch > 1: frame-batch handle (sift_hip_set_batch): detectBatchDevice runs up to `batch`
         frames per launch; the single-frame methods keep working (frame 0's arena).
         exact_descriptors: OpenCV's sequential float histogram (SIFT_HIP_DESC_EXACT), descriptors
@@ -457,10 +463,14 @@ class Detector:
         micro_batch > 1: frames of submitDevice queue until that many run as one launch group on a
         lane (sift_hip_set_micro_batch; a wait on a queued frame launches the partial group).
         auto_micro_batch: automatic launch groups of up to that many frames once every lane is busy
-        (sift_hip_set_auto_micro_batch; library default 8, 0 = off)."""
+        (sift_hip_set_auto_micro_batch; library default 8, 0 = off).
+        root_sift: RootSIFT rows (SIFT_HIP_NORM_ROOT): every descriptor row the detector writes is
+        cv.rootsift of the row it would have written, computed in the descriptor kernel; keypoints
+        are unchanged.  Independent of exact_descriptors."""
         self.config = config
         self.batch = int(batch)
         self.exact_descriptors = bool(exact_descriptors)
+        self.root_sift = bool(root_sift)
         self._h = ctypes.c_void_p()
         _check(lib().sift_hip_create(ctypes.byref(config._abi()), device, ctypes.byref(self._h)), "sift_hip_create")
         if self.batch != 1:
@@ -473,6 +483,8 @@ class Detector:
             _check(lib().sift_hip_set_auto_micro_batch(self._h, int(auto_micro_batch)), "set_auto_micro_batch")
         if self.exact_descriptors:
             _check(lib().sift_hip_set_descriptor_mode(self._h, SIFT_HIP_DESC_EXACT), "set_descriptor_mode")
+        if self.root_sift:
+            _check(lib().sift_hip_set_descriptor_norm(self._h, SIFT_HIP_NORM_ROOT), "set_descriptor_norm")
         n = ctypes.c_int()
         lib().sift_hip_num_octaves(self._h, ctypes.byref(n))
         self.nOctaves = n.value
@@ -1652,6 +1664,26 @@ def matchBruteForce(des: DeviceBuffer, num_des: int, src: DeviceBuffer, num_src:
     if num_des <= 0:
         return np.zeros(0, np.int32)
     return _default_matcher.match_host(des.data(), num_des, src.data(), num_src, 0.8, True)
+
+
+def rootsift_device(src_ptr: int, n: int, dst_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
+    """The RootSIFT rule (sift_hip_rootsift_device, cv.rootsift) on n device rows of 128 fp16 values
+    the detector did not write with root_sift: src -> dst, dst_ptr=None in place.  One launch on
+    `stream` (None: the default stream), not synchronised.  A detector's own buffer is passed as
+    mutable_data(), so that later matches convert the written rows."""
+    dst = src_ptr if dst_ptr is None else dst_ptr
+    _check(lib().sift_hip_rootsift_device(src_ptr, int(n), dst, stream), "rootsift_device")
+
+
+def rootsift(desc: np.ndarray) -> np.ndarray:
+    """The same rule on a host array of rows (n, 128), through the device (sift_hip_rootsift_host,
+    synchronous): float16 rows of integers 0..255, equal to cv.rootsift(desc) byte for byte."""
+    a = np.ascontiguousarray(np.asarray(desc), dtype=np.float16)
+    if a.ndim != 2 or a.shape[1] != 128:
+        raise ValueError(f"rootsift: rows of 128 values expected, got shape {a.shape}")
+    out = np.empty_like(a)
+    _check(lib().sift_hip_rootsift_host(_ptr(a), a.shape[0], _ptr(out)), "rootsift_host")
+    return out
 
 
 class DeviceArray:

@@ -65,6 +65,22 @@ def mask_keep(x, y, mask: np.ndarray) -> np.ndarray:
     return m[iy, ix] != 0
 
 
+def rootsift(desc) -> np.ndarray:
+    """The RootSIFT rule of include/sift_hip.h in numpy (Detector(root_sift=True), sift_amd.rootsift_device): rows of
+    128 values -> uint8 (n, 128).  b = clip(rint(v), 0, 255) with NaN -> 0 (the identity on descriptor bytes); s = the
+    row's integer sum; out = min(255, rint(512 * sqrt(b / s))) in float32 -- one correctly rounded division, one
+    correctly rounded square root -- and the zero row stays zero.  The device equals this byte for byte."""
+    v = np.asarray(desc)
+    if v.ndim != 2 or v.shape[1] != 128:
+        raise ValueError(f"rows of 128 values expected, got shape {v.shape}")
+    with np.errstate(invalid="ignore"):
+        b = np.clip(np.rint(np.nan_to_num(v.astype(np.float32), nan=0.0, posinf=255.0, neginf=0.0)), 0, 255).astype(np.int32)
+    s = b.sum(axis=1, keepdims=True)
+    q = b.astype(np.float32) / np.maximum(s, 1).astype(np.float32)  # s == 0: b is all zero
+    r = np.sqrt(q, dtype=np.float32)
+    return np.minimum(np.rint(np.float32(512) * r), np.float32(255)).astype(np.uint8)
+
+
 def descriptor_matrix(descriptors: np.ndarray, num_pts: int) -> np.ndarray:
     """ConversionImpl.hpp:66-82: row-major 128-wide descriptors -> float32 (n, 128)."""
     d = np.asarray(descriptors).reshape(-1, 128)

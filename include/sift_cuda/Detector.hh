@@ -121,6 +121,14 @@ public:
     // descriptors; sift_hip_set_descriptor_mode(SIFT_HIP_DESC_EXACT)).  Call
     // before gpuWarmUpAndAllocate; the default is the fixed-point histogram.
     void setExactDescriptors(bool exact);
+    // Extra: RootSIFT rows (sift_hip_set_descriptor_norm(SIFT_HIP_NORM_ROOT): the
+    // square root of the L1-normalised row at OpenCV's scale, computed in the
+    // descriptor kernel; the rule is spelled out in include/sift_hip.h).  Every
+    // row the detector writes follows it; keypoints are unchanged.  Call before
+    // gpuWarmUpAndAllocate: afterwards, or with setDataGen active, it throws
+    // std::runtime_error.  Independent of setExactDescriptors.
+    void setRootSift(bool root);
+    bool rootSift() const;
     // tool/perf.cu:43-100 (HostInterface.hh:11-69 run<Stage>): one stage --
     // "pyramid", "extrema", "refine", "orientation", "order", "descriptor" --
     // alone on a setDataGen dump's recorded input; its outputs go to out_dir
@@ -157,6 +165,16 @@ private:
 // (d1^2 < 0.8 d2^2, the reference's Match.cu:172 convention), else -1.
 std::vector<int> matchBruteForce(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
                                  int num_src);
+
+// Extra: the RootSIFT rule for n rows of 128 values the detector did not write
+// with setRootSift (a database's rows, a kept frame, another extractor's):
+// device rows on `stream` (not synchronised; out == in transforms in place), or
+// host rows through the device, synchronously (sift_hip_rootsift_device / _host).
+// A detector's own buffer is passed as mutable_data(), so that later matches
+// convert the written rows.  Rows of the two norms must not be matched against
+// each other.  What the ABI refuses throws std::invalid_argument.
+void rootSiftDevice(const Half* in, int n, Half* out, void* stream = nullptr);
+void rootSiftHost(const Half* in, int n, Half* out);
 
 // Extra: the usable match list in one device operation (sift_hip_match_list_host)
 // -- top-2 search in both directions, the filter (ratio test, distance cap,

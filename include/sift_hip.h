@@ -251,6 +251,62 @@ int sift_hip_batch_capacity(sift_hip_t h, int* frames);
 int sift_hip_set_descriptor_mode(sift_hip_t h, int mode);
 int sift_hip_descriptor_mode(sift_hip_t h, int* mode);
 
+/* Descriptor normalisation ("RootSIFT", Arandjelovic & Zisserman 2012: the
+ * square root of the L1-normalised row, so that the Euclidean distance of the
+ * matcher is the Hellinger distance of the histograms; COLMAP's L1_ROOT with
+ * its round(512 x) conversion to 8 bits, applied to OpenCV's bytes).  The rule,
+ * in float32, total, for a row of 128 values v[i]:
+ *   1. b[i] = clamp(cvRound(v[i]), 0, 255): round half even, NaN -> 0.  The
+ *      identity on the bytes the detector would have written without the norm.
+ *   2. s = sum b[i], an integer (<= 32,640: exact in any order).
+ *   3. s == 0: the row is all zero.
+ *   4. Otherwise r[i] = sqrtf((float)b[i] / (float)s): one IEEE correctly
+ *      rounded division and one correctly rounded square root, nothing fused.
+ *   5. out[i] = min(255, cvRound(512.f * r[i])), stored as the fp16 of that
+ *      integer like every descriptor row.
+ *   6. Sidecar code out[i] - 128 and key bias -(256 * sum code^2 + (row & 255)),
+ *      from the new bytes: matches of two ROOT buffers keep the direct path.
+ * sum r^2 = 1, so rows keep the scale of OpenCV's rows (norm ~512; 509.9 to
+ * 513.5 on SIFT-like rows, largest byte ~115).  The clamp of step 5 acts only
+ * where one entry holds more than 24.7 % of the row's L1 mass.
+ * sift_amd.cv.rootsift is the numpy mirror; the device equals it byte for byte.
+ *
+ * Detector norm, called before sift_hip_warmup (part of the captured graphs;
+ * later SIFT_HIP_ERR_STATE; an unknown norm SIFT_HIP_ERR_INVALID):
+ *   SIFT_HIP_NORM_L2   (default) OpenCV's rows.
+ *   SIFT_HIP_NORM_ROOT every descriptor row this handle writes -- single
+ *                      frames, batches, lanes, micro-batches, masked calls,
+ *                      sift_hip_compute*, the pinned host rows, the replay of
+ *                      the descriptor stage -- is the rule applied to the row
+ *                      the call would have written, in the kernel that
+ *                      computes it (no extra pass or launch).  An invalid
+ *                      keypoint of sift_hip_compute* keeps its zero row.
+ * Independent of sift_hip_set_descriptor_mode (four combinations); keypoints
+ * are identical in both norms.  Stage dumps are compared with the oracle's L2
+ * rows: sift_hip_set_datagen on a ROOT handle, and ROOT while dumps are on,
+ * are SIFT_HIP_ERR_STATE.
+ * Rows of different norms must not be matched against each other, and
+ * max_distance caps of the match lists are on the new rows' scale. */
+#define SIFT_HIP_NORM_L2   0
+#define SIFT_HIP_NORM_ROOT 1
+int sift_hip_set_descriptor_norm(sift_hip_t h, int norm);
+int sift_hip_descriptor_norm(sift_hip_t h, int* norm);
+
+/* The same rule for rows the detector did not write in ROOT (a database's
+ * descriptors, a frame the caller kept, another extractor's rows): n rows of
+ * 128 fp16 values in device memory, desc_in -> desc_out.  Handle-free, one
+ * launch on `stream` (NULL = the default stream), not synchronised, no
+ * allocation: capturable.  desc_out == desc_in transforms in place; any other
+ * overlap of the two n * 256-byte ranges, n < 0, a null pointer with n > 0 or
+ * an odd pointer is SIFT_HIP_ERR_INVALID; n == 0 is a no-op.
+ * A caller transforming a detector's own buffer declares the write first
+ * (sift_hip_descriptors_written; C++ / Python: mutable_data()), so that the
+ * matcher converts the written rows instead of reading the stale sidecar.
+ * sift_hip_rootsift_host takes host rows through the device, synchronously
+ * (allocates and frees its staging buffer on the current device). */
+int sift_hip_rootsift_device(const uint16_t* desc_in, int n, uint16_t* desc_out, void* stream);
+int sift_hip_rootsift_host(const uint16_t* desc_in, int n, uint16_t* desc_out);
+
 /* n (1..B) device frames, frame i at dev_frames + i * frame_stride_bytes (0 =
  * row_stride * height), enqueued on `stream` (NULL = internal), NOT
  * synchronised (sift_hip_sync).  The batch becomes the current launch group. */

@@ -5,7 +5,9 @@
 // --pipelined: 8-bit frames through Detector::submit / wait, frame f+1 staged
 // and uploaded while frame f computes; prints the same lines as the default
 // synchronous Imagef loop.  --exact: Detector::setExactDescriptors(true)
-// (OpenCV's descriptor bytes, sift_hip_set_descriptor_mode).  --micro-batch N
+// (OpenCV's descriptor bytes, sift_hip_set_descriptor_mode).  --rootsift:
+// Detector::setRootSift(true) (RootSIFT rows from the descriptor kernel, matched
+// through their sidecar like the default rows); same lines.  --micro-batch N
 // (with --pipelined): Detector::setMicroBatch(N) on 2 lanes, 2N frames
 // submitted ahead, so frames run in N-frame launch groups; same lines.
 // --ahead N (with --pipelined): N frames submitted past the one waited for
@@ -28,7 +30,7 @@
 
 int main(int argc, char** argv) {
     int W = 752, H = 480, frames = 4, dx = 3, dy = 2;
-    bool pipelined = false, exact = false;
+    bool pipelined = false, exact = false, rootsift = false;
     int micro = 1, ahead_arg = 0, border = 0;
     bool cross_check = false;
     float max_distance = 0.f;
@@ -36,6 +38,7 @@ int main(int argc, char** argv) {
         std::string a = argv[i];
         if (a == "--pipelined") pipelined = true;
         else if (a == "--exact") exact = true;
+        else if (a == "--rootsift") rootsift = true;
         else if (a == "--width" && i + 1 < argc) W = std::atoi(argv[++i]);
         else if (a == "--height" && i + 1 < argc) H = std::atoi(argv[++i]);
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
@@ -56,6 +59,7 @@ int main(int argc, char** argv) {
     config.row_width = H;
     sift_cuda::Detector detector(config);
     if (exact) detector.setExactDescriptors(true);  // before the warm-up: part of the captured graphs
+    if (rootsift) detector.setRootSift(true);       // likewise
     if (micro > 1) {
         detector.setLanes(2);
         detector.setMicroBatch(micro);
