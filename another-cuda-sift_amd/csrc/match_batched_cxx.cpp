@@ -1,6 +1,9 @@
 // sift_cuda::BatchMatcher / matchListGuidedBatchedDevice / matchListEpipolarBatchedDevice
 // (include/sift_cuda/Detector.hh) over the C ABI in include/sift_hip.h.  Plain
 // C++ (g++): no HIP headers, no device code.
+#include <algorithm>
+#include <cmath>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -68,6 +71,79 @@ void matchListEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<Gui
                                                      radius, geometry, geometry_stride_bytes, max_error, &f,
                                                      reinterpret_cast<sift_hip_dmatch*>(out), counts, stream),
                 "matchListEpipolarBatchedDevice");
+}
+
+// --- k nearest neighbours (sift_hip_match_knn_*) ---------------------------------
+namespace {
+
+struct MatcherDeleter {
+    void operator()(sift_hip_matcher* m) const { sift_hip_matcher_destroy(m); }
+};
+
+// The thread-local matcher of matchKnn / matchKnnList, grown to hold the call.
+sift_hip_matcher* knn_matcher(int num_des, int num_src, const char* what) {
+    thread_local std::unique_ptr<sift_hip_matcher, MatcherDeleter> matcher;
+    thread_local int capQ = 0, capT = 0;
+    if (!matcher || num_des > capQ || num_src > capT) {
+        capQ = std::max(std::max(num_des, 1), capQ);
+        capT = std::max(std::max(num_src, 1), capT);
+        sift_hip_matcher_t m = nullptr;
+        check_throw(sift_hip_matcher_create(-1, capQ, capT, 1, &m), what);
+        matcher.reset(m);
+    }
+    return matcher.get();
+}
+
+}  // namespace
+
+std::vector<std::vector<DMatch>> matchKnn(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                          int num_src, int k) {
+    if (k < 1 || k > SIFT_HIP_KNN_MAX) throw std::invalid_argument("matchKnn: k outside 1..SIFT_HIP_KNN_MAX");
+    std::vector<std::vector<DMatch>> out((size_t)std::max(num_des, 0));
+    if (num_des <= 0 || num_src <= 0) return out;
+    std::vector<int> idx((size_t)num_des * k);
+    std::vector<float> d2((size_t)num_des * k);
+    check_throw(sift_hip_match_knn_host(knn_matcher(num_des, num_src, "matchKnn"),
+                                        reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                                        reinterpret_cast<const uint16_t*>(src.data()), num_src, k, idx.data(), d2.data()),
+                "matchKnn");
+    for (int i = 0; i < num_des; i++)
+        for (int j = 0; j < k && idx[(size_t)i * k + j] >= 0; j++)
+            out[(size_t)i].push_back(DMatch{i, idx[(size_t)i * k + j], 0, std::sqrt(d2[(size_t)i * k + j])});
+    return out;
+}
+
+std::vector<DMatch> matchKnnList(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                                 int k, float max_distance) {
+    if (k < 1 || k > SIFT_HIP_KNN_MAX) throw std::invalid_argument("matchKnnList: k outside 1..SIFT_HIP_KNN_MAX");
+    std::vector<DMatch> out;
+    if (num_des <= 0 || num_src <= 0) return out;
+    out.resize((size_t)num_des * k);
+    int count = 0;
+    check_throw(sift_hip_match_knn_list_host(knn_matcher(num_des, num_src, "matchKnnList"),
+                                             reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                                             reinterpret_cast<const uint16_t*>(src.data()), num_src, k, max_distance,
+                                             reinterpret_cast<sift_hip_dmatch*>(out.data()), (int)out.size(), &count),
+                "matchKnnList");
+    out.resize((size_t)count);
+    return out;
+}
+
+void matchKnnBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int k, int* idx, float* d2,
+                           void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(), a.t.data(),
+                                           a.nt.data(), k, idx, d2, stream),
+                "matchKnnBatchedDevice");
+}
+
+void matchKnnListBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int k, float max_distance,
+                               DMatch* out, int* counts, void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_list_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(), a.t.data(),
+                                                a.nt.data(), k, max_distance, reinterpret_cast<sift_hip_dmatch*>(out),
+                                                counts, stream),
+                "matchKnnListBatchedDevice");
 }
 
 }  // namespace sift_cuda

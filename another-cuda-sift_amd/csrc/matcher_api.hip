@@ -99,12 +99,23 @@ struct sift_hip_matcher {
     float* dSelD = nullptr;
     MatchRecord* dList = nullptr;
     int* dCount = nullptr;
+    // k nearest neighbours (sift_hip_match_knn_*), allocated at the first such call: the split lists (knn_lists()
+    // lists of kKnnMax keys), and for the list and host forms the k-NN table of maxP maxQ rows of kKnnMax entries,
+    // the records of one pair and its count.
+    unsigned long long* dKnnLists = nullptr;
+    int* dKnnIdx = nullptr;
+    float* dKnnD = nullptr;
+    MatchRecord* dKnnRec = nullptr;
+    int* dKnnCount = nullptr;
     ~sift_hip_matcher() {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dKeys, (void*)dDone, (void*)dMatch, (void*)dCodes, (void*)dRowKeys, (void*)dFlags,
-                        (void*)dSelIdx, (void*)dSelD, (void*)dList, (void*)dCount})
+                        (void*)dSelIdx, (void*)dSelD, (void*)dList, (void*)dCount, (void*)dKnnLists, (void*)dKnnIdx,
+                        (void*)dKnnD, (void*)dKnnRec, (void*)dKnnCount})
             if (p) (void)hipFree(p);
     }
+    // Split lists of the k-NN scratch: max_query * max(8, 2 max_pairs) (the formula of include/sift_hip.h).
+    size_t knn_lists() const { return (size_t)maxQ * std::max(kKnnMaxSplits, 2 * maxP); }
     // The sentinel row (row codeRows of dCodes / dRowKeys): zero codes with the padding key, written at creation.
     CodeSet sentinel() const { return CodeSet{dCodes + (size_t)codeRows * 128, dRowKeys + codeRows}; }
     MatchScratch scratch() const { return MatchScratch{dKeys, dDone, maxQ, sentinel()}; }
@@ -473,6 +484,242 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, co
                                             m->dCount, nullptr))
         return rc;
     return read_list(m, out_host, cap, count);
+}
+
+}  // extern "C"
+
+// --- k nearest neighbours and capped radius lists ----------------------------------
+static_assert(SIFT_HIP_KNN_MAX == kKnnMax, "the kernel's largest instantiation");
+
+namespace {
+
+// The k-NN scratch, at the first k-NN call of a matcher (not under stream capture).
+int ensure_knn_scratch(sift_hip_matcher* m) {
+    if (m->dKnnLists) return SIFT_HIP_OK;
+    const size_t rows = (size_t)m->maxP * m->maxQ * kKnnMax;
+    HIPCHK(hipSetDevice(m->device));
+    if (hipMalloc((void**)&m->dKnnLists, sizeof(unsigned long long) * kKnnMax * m->knn_lists()) != hipSuccess ||
+        hipMalloc((void**)&m->dKnnIdx, sizeof(int) * rows) != hipSuccess ||
+        hipMalloc((void**)&m->dKnnD, sizeof(float) * rows) != hipSuccess ||
+        hipMalloc((void**)&m->dKnnRec, sizeof(MatchRecord) * (size_t)m->maxQ * kKnnMax) != hipSuccess ||
+        hipMalloc((void**)&m->dKnnCount, sizeof(int) * (size_t)m->maxP) != hipSuccess) {
+        for (void** p : {(void**)&m->dKnnLists, (void**)&m->dKnnIdx, (void**)&m->dKnnD, (void**)&m->dKnnRec,
+                         (void**)&m->dKnnCount}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return fail(SIFT_HIP_ERR_NOMEM, "k-NN scratch allocation failed");
+    }
+    return SIFT_HIP_OK;
+}
+
+// The refusals, judged before any device call: k (and for a list max_distance) need nothing else, then the matcher,
+// then the pairs.
+int check_knn(const sift_hip_matcher* m, int k) {
+    if (k < 1 || k > kKnnMax) return fail(SIFT_HIP_ERR_INVALID, "k-NN: k outside 1..SIFT_HIP_KNN_MAX");
+    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
+    return SIFT_HIP_OK;
+}
+int check_knn_list(const sift_hip_matcher* m, int k, float max_distance, const void* out, const void* count) {
+    if (std::isnan(max_distance)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: max_distance is NaN");
+    if (int rc = check_knn(m, k)) return rc;
+    if (!out || !count) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
+    return SIFT_HIP_OK;
+}
+int check_knn_pairs(const sift_hip_matcher* m, int P, const int* nq, const int* nt) {
+    if (P <= 0 || P > m->maxP) return fail(SIFT_HIP_ERR_INVALID, "k-NN: P outside 1..max_pairs");
+    if (!nq || !nt) return fail(SIFT_HIP_ERR_INVALID, "k-NN: null size array");
+    for (int p = 0; p < P; p++)
+        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
+            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
+    return SIFT_HIP_OK;
+}
+int check_knn_sets(int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t, const int* nt) {
+    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "k-NN: null descriptor array");
+    for (int p = 0; p < P; p++)
+        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
+    return SIFT_HIP_OK;
+}
+int check_knn_codes(int P, const int8_t* codes, const int* keys, const int* qrow0, const int* qkey0, const int* trow0,
+                    const int* tkey0) {
+    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
+    for (int p = 0; p < P; p++)
+        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
+            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
+    return SIFT_HIP_OK;
+}
+
+bool any_queries(int P, const int* nq) {
+    for (int p = 0; p < P; p++)
+        if (nq[p] > 0) return true;
+    return false;
+}
+
+// One k-NN launch on the pairs of b: the plan's splits, lowered to what the list scratch holds.
+int knn_launch(sift_hip_matcher* m, const MatchBatch& b, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
+               int* idx, float* d2, hipStream_t stream) {
+    int maxq = 1, maxt = 1;
+    for (int p = 0; p < b.P; p++) {
+        maxq = std::max(maxq, b.pair[p].nq);
+        maxt = std::max(maxt, b.pair[p].nt);
+    }
+    const size_t fit = m->knn_lists() / ((size_t)b.P * maxq);  // >= 2: P <= maxP, maxq <= maxQ
+    const int S = (int)std::min<size_t>(match_knn_splits(maxq, maxt, b.P), fit);
+    launch_match_knn(b, S, k, q, t, flags, KnnScratch{m->dKnnLists, m->dDone, maxq, m->sentinel()}, idx, d2, stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// The table of checked fp16 pairs, pair p at row sum_{r<p} nq[r].  A single pair of detector buffers with fresh
+// sidecars matches their codes; otherwise the call's distinct sets are converted once (k_match_prep).
+int knn_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
+             const int* nt, int k, int* idx, float* d2, hipStream_t stream) {
+    if (!any_queries(P, nq)) return SIFT_HIP_OK;
+    MatchBatch b{};
+    MatchSets sets{};
+    b.P = P;
+    auto set_of = [&](const uint16_t* ptr, int n) {
+        for (int s = 0; s < sets.nsets; s++)
+            if (sets.set[s].src == ptr) {
+                sets.set[s].n = std::max(sets.set[s].n, n);
+                return s;
+            }
+        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
+        return sets.nsets++;
+    };
+    int off = 0;
+    for (int p = 0; p < P; p++) {
+        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
+        b.pair[p] = MatchPair{q[p], t[p], nq[p], nt[p], off, qs, ts, 0, 0, 0, 0};
+        off += nq[p];
+    }
+    long row = 0;
+    for (int s = 0; s < sets.nsets; s++) {
+        sets.set[s].row0 = (int)row;
+        row += sets.set[s].n;
+        sets.maxn = std::max(sets.maxn, sets.set[s].n);
+    }
+    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    Sidecar sq{}, st{};
+    if (P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && find_sidecar(q[0], nq[0], &sq) &&
+        find_sidecar(t[0], nt[0], &st))
+        return knn_launch(m, b, k, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags, idx, d2, stream);
+    for (int p = 0; p < P; p++) {
+        b.pair[p].qrow0 = b.pair[p].qkrow0 = sets.set[b.pair[p].qset].row0;
+        b.pair[p].trow0 = b.pair[p].tkrow0 = sets.set[b.pair[p].tset].row0;
+    }
+    const SetFlags flags = m->next_epoch();
+    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
+    HIPCHK(hipGetLastError());
+    const CodeSet set{m->dCodes, m->dRowKeys};
+    return knn_launch(m, b, k, set, set, flags, idx, d2, stream);
+}
+
+// The list of a table in idx / d2 (pair p at row sum_{r<p} nq[r]): pair p's records from row k sum_{r<p} nq[r].
+int knn_select(sift_hip_matcher* m, int P, const int* nq, int k, const int* idx, const float* d2, float max_distance,
+               sift_hip_dmatch* out, int* counts, hipStream_t stream) {
+    SelectBatch sb{};
+    int row = 0;
+    for (int p = 0; p < P; p++) {
+        sb.pair[p] = SelectPair{nq[p], 0, row, 0, k * row};
+        row += nq[p];
+    }
+    HIPCHK(hipSetDevice(m->device));
+    launch_knn_select(sb, P, k, idx, d2, max_distance, reinterpret_cast<MatchRecord*>(out), counts, stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_hip_match_knn_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                               const uint16_t* const* t, const int* nt, int k, int* idx, float* d2, void* stream) {
+    if (int rc = check_knn(m, k)) return rc;
+    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
+    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
+    return knn_fp16(m, P, q, nq, t, nt, k, idx, d2, (hipStream_t)stream);
+}
+
+int sift_hip_match_knn_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                              int* idx, float* d2, void* stream) {
+    return sift_hip_match_knn_batched(m, 1, &q, &nq, &t, &nt, k, idx, d2, stream);
+}
+
+int sift_hip_match_knn_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                     const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                     const int* tkey0, const int* nt, int k, int* idx, float* d2, void* stream) {
+    if (int rc = check_knn(m, k)) return rc;
+    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
+    if (int rc = check_knn_codes(P, codes, keys, qrow0, qkey0, trow0, tkey0)) return rc;
+    if (!any_queries(P, nq)) return SIFT_HIP_OK;
+    MatchBatch b{};
+    b.P = P;
+    int off = 0;
+    for (int p = 0; p < P; p++) {
+        b.pair[p] = MatchPair{nullptr, nullptr, nq[p], nt[p], off, 0, 0, qrow0[p], trow0[p], qkey0[p], tkey0[p]};
+        off += nq[p];
+    }
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    const CodeSet set{codes, keys};
+    return knn_launch(m, b, k, set, set, kNoFlags, idx, d2, (hipStream_t)stream);
+}
+
+int sift_hip_match_knn_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                            int* idx_host, float* d2_host) {
+    if (int rc = check_knn(m, k)) return rc;
+    if (int rc = check_knn_pairs(m, 1, &nq, &nt)) return rc;
+    if (int rc = check_knn_sets(1, &q, &nq, &t, &nt)) return rc;
+    if (nq == 0) return SIFT_HIP_OK;
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = knn_fp16(m, 1, &q, &nq, &t, &nt, k, m->dKnnIdx, m->dKnnD, nullptr)) return rc;
+    if (idx_host) HIPCHK(hipMemcpy(idx_host, m->dKnnIdx, sizeof(int) * (size_t)nq * k, hipMemcpyDeviceToHost));
+    if (d2_host) HIPCHK(hipMemcpy(d2_host, m->dKnnD, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_match_knn_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                    const uint16_t* const* t, const int* nt, int k, float max_distance,
+                                    sift_hip_dmatch* out, int* counts, void* stream) {
+    if (int rc = check_knn_list(m, k, max_distance, out, counts)) return rc;
+    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
+    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = knn_fp16(m, P, q, nq, t, nt, k, m->dKnnIdx, m->dKnnD, (hipStream_t)stream)) return rc;
+    return knn_select(m, P, nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, counts, (hipStream_t)stream);
+}
+
+int sift_hip_match_knn_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                                   float max_distance, sift_hip_dmatch* out, int* count, void* stream) {
+    return sift_hip_match_knn_list_batched(m, 1, &q, &nq, &t, &nt, k, max_distance, out, count, stream);
+}
+
+int sift_hip_match_knn_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                                 float max_distance, sift_hip_dmatch* out_host, int cap, int* count) {
+    if (!count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
+    *count = 0;
+    if (int rc = check_knn_list(m, k, max_distance, m, m)) return rc;  // the device outputs are the matcher's own
+    if (int rc = check_knn_pairs(m, 1, &nq, &nt)) return rc;
+    if (int rc = check_knn_sets(1, &q, &nq, &t, &nt)) return rc;
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = sift_hip_match_knn_list_device(m, q, nq, t, nt, k, max_distance,
+                                                reinterpret_cast<sift_hip_dmatch*>(m->dKnnRec), m->dKnnCount, nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(count, m->dKnnCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dKnnRec, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_match_knn_plan(int nq, int nt, int pairs, int k, int* splits) {
+    if (nq < 0 || nt < 0 || pairs < 1 || k < 1 || k > kKnnMax || !splits)
+        return fail(SIFT_HIP_ERR_INVALID, "bad k-NN shape");
+    *splits = match_knn_splits(nq, nt, pairs);
+    return SIFT_HIP_OK;
 }
 
 }  // extern "C"

@@ -220,4 +220,37 @@ struct SelectBatch {
 void launch_match_select(const SelectBatch& batch, int P, const int* idx2, const float* d2, const MatchFilter& filter,
                          MatchRecord* out, int* counts, hipStream_t s);
 
+// --- k nearest neighbours (sift_hip_match_knn_*): k_match_knn, k_knn_select.
+constexpr int kKnnMax = 8;        // SIFT_HIP_KNN_MAX; the kernel is instantiated for 4 and 8 entries
+constexpr int kKnnMaxSplits = 8;  // train splits of a k-NN launch at most
+
+// The k-NN scratch of a matcher (allocated at its first k-NN call).  lists: a
+// sorted list of u64 output keys per (pair, split, query) -- P S nq_stride lists
+// of at most kKnnMax keys must fit; nothing in it outlives a launch.  done: the
+// matcher's done counters (MatchScratch), zero between calls.
+struct KnnScratch {
+    unsigned long long* lists;
+    unsigned* done;
+    int nq_stride;
+    CodeSet zero;
+};
+
+// Splits (whole key groups) of a k-NN launch of this shape, before the cap of
+// the matcher's list scratch.
+int match_knn_splits(int max_nq, int max_nt, int P);
+
+// The k nearest neighbours of every query of every pair: idx / d2 rows of k
+// entries, pair p at row out_off.  Pair p reads code rows qrow0.. of q and
+// trow0.. of t (the same buffer for prepared or gathered sets; two sidecars for
+// one pair of detector buffers); a flagged set sends its pair down the fp16
+// path.
+void launch_match_knn(const MatchBatch& batch, int S, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
+                      const KnnScratch& sc, int* idx, float* d2, hipStream_t s);
+
+// One workgroup per pair: the table entries (rows fwd.. of idx / d2, k per row)
+// that hold a neighbour within max_distance, in (query, rank) order at out +
+// out_off, their number in counts[p].
+void launch_knn_select(const SelectBatch& batch, int P, int k, const int* idx, const float* d2, float max_distance,
+                       MatchRecord* out, int* counts, hipStream_t s);
+
 }  // namespace sift_amd

@@ -42,6 +42,7 @@ SIFT_HIP_FLAG_BAD_KEYPOINT = 16  # overflow_flags() bit: computeDevice met an in
 KPT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
 # sift_hip_dmatch (cv::DMatch's fields in its order, 16 bytes): the records of Matcher.match_list_*.
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
+KNN_MAX = 8  # SIFT_HIP_KNN_MAX: the largest k of Matcher.match_knn_*
 _lib = None
 
 
@@ -283,6 +284,14 @@ def lib() -> ctypes.CDLL:
         "sift_hip_match_list_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, ctypes.POINTER(_MatchFilter),
                                                   vp, vp, vp]),
         "sift_hip_match_list_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchFilter), vp, i, ip]),
+        "sift_hip_match_knn_device": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
+        "sift_hip_match_knn_batched": (i, [vp, i, vp, vp, vp, vp, i, vp, vp, vp]),
+        "sift_hip_match_knn_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp]),
+        "sift_hip_match_knn_host": (i, [vp, vp, i, vp, i, i, vp, vp]),
+        "sift_hip_match_knn_list_device": (i, [vp, vp, i, vp, i, i, f, vp, vp, vp]),
+        "sift_hip_match_knn_list_batched": (i, [vp, i, vp, vp, vp, vp, i, f, vp, vp, vp]),
+        "sift_hip_match_knn_list_host": (i, [vp, vp, i, vp, i, i, f, vp, i, ip]),
+        "sift_hip_match_knn_plan": (i, [i, i, i, i, ip]),
         "sift_hip_match_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), f, i, vp, vp, vp, vp]),
         "sift_hip_match_guided_plan": (i, [i, i, ip]),
         "sift_hip_match_list_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate),
@@ -953,6 +962,81 @@ class Matcher:
                                               ctypes.byref(n)), "match_list_host")
         return out[: n.value]
 
+    # --- k nearest neighbours (k <= KNN_MAX) and capped radius lists (the rule: include/sift_hip.h, and in numpy
+    # sift_amd.cv.knn / knn_records).  Tables are (nq, k) int32 indices (-1: none) and float32 squared distances
+    # (FLT_MAX: none) in ascending (d2, train index) order.  The first k-NN call of a matcher allocates its scratch
+    # (not under stream capture).
+
+    @staticmethod
+    def knn_plan(nq: int, nt: int, pairs: int = 1, k: int = KNN_MAX) -> int:
+        """Train splits a k-NN call of this shape launches with (sift_hip_match_knn_plan; host-only)."""
+        S = ctypes.c_int()
+        _check(lib().sift_hip_match_knn_plan(nq, nt, pairs, k, ctypes.byref(S)), "match_knn_plan")
+        return S.value
+
+    def match_knn_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, k: int, idx_ptr: int = 0, d2_ptr: int = 0,
+                         stream: Optional[int] = None) -> None:
+        """The table of one pair at idx_ptr / d2_ptr (device, nq * k entries each; 0 skips one); enqueued on `stream`
+        (sift_hip_match_knn_device)."""
+        _check(lib().sift_hip_match_knn_device(self._m, q_ptr or None, nq, t_ptr or None, nt, k, idx_ptr or None,
+                                               d2_ptr or None, stream), "match_knn_device")
+
+    def match_knn_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int], nts: Sequence[int],
+                          k: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """P pairs in one launch: pair p's rows from row sum(nqs[:p]) (sift_hip_match_knn_batched)."""
+        P = len(q_ptrs)
+        qa = (ctypes.c_void_p * P)(*q_ptrs)
+        ta = (ctypes.c_void_p * P)(*t_ptrs)
+        na = (ctypes.c_int * P)(*nqs)
+        ma = (ctypes.c_int * P)(*nts)
+        _check(lib().sift_hip_match_knn_batched(self._m, P, qa, na, ta, ma, k, idx_ptr or None, d2_ptr or None, stream),
+               "match_knn_batched")
+
+    def match_knn_codes_batched(self, codes_ptr: int, keys_ptr: int, pairs: Sequence, k: int, idx_ptr: int = 0,
+                                d2_ptr: int = 0, stream: Optional[int] = None) -> None:
+        """The same for pairs (qrow0, qkey0, nq, trow0, tkey0, nt) of ready code sets, as match_codes_batched takes
+        them (sift_hip_match_knn_codes_batched)."""
+        P = len(pairs)
+        qr, qk, nq, tr, tk, nt = ((ctypes.c_int * P)(*[p[j] for p in pairs]) for j in range(6))
+        _check(lib().sift_hip_match_knn_codes_batched(self._m, codes_ptr, keys_ptr, P, qr, qk, nq, tr, tk, nt, k,
+                                                      idx_ptr or None, d2_ptr or None, stream), "match_knn_codes_batched")
+
+    def match_knn_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, k: int):
+        """Synchronous; (idx int32 (nq, k), d2 float32 (nq, k)) (sift_hip_match_knn_host)."""
+        shape = (max(nq, 0), max(k, 0))
+        idx, d2 = np.full(shape, -1, np.int32), np.full(shape, np.finfo(np.float32).max, np.float32)
+        _check(lib().sift_hip_match_knn_host(self._m, q_ptr or None, nq, t_ptr or None, nt, k, _ptr(idx), _ptr(d2)),
+               "match_knn_host")
+        return idx, d2
+
+    def match_knn_list_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, k: int, out_ptr: int, count_ptr: int,
+                              max_distance: float = 0.0, stream: Optional[int] = None) -> None:
+        """DMATCH_DTYPE records of the neighbours within max_distance (<= 0: all), (queryIdx, rank) order, at out_ptr
+        (device, room for nq * k) and their number at count_ptr (device int32) (sift_hip_match_knn_list_device)."""
+        _check(lib().sift_hip_match_knn_list_device(self._m, q_ptr or None, nq, t_ptr or None, nt, k, max_distance,
+                                                    out_ptr or None, count_ptr or None, stream), "match_knn_list_device")
+
+    def match_knn_list_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                               nts: Sequence[int], k: int, out_ptr: int, counts_ptr: int, max_distance: float = 0.0,
+                               stream: Optional[int] = None) -> None:
+        """P pairs: pair p's records from row k * sum(nqs[:p]) of out_ptr with imgIdx = p, its count at counts_ptr[p]
+        (sift_hip_match_knn_list_batched)."""
+        P = len(q_ptrs)
+        qa = (ctypes.c_void_p * P)(*q_ptrs)
+        ta = (ctypes.c_void_p * P)(*t_ptrs)
+        na = (ctypes.c_int * P)(*nqs)
+        ma = (ctypes.c_int * P)(*nts)
+        _check(lib().sift_hip_match_knn_list_batched(self._m, P, qa, na, ta, ma, k, max_distance, out_ptr or None,
+                                                     counts_ptr or None, stream), "match_knn_list_batched")
+
+    def match_knn_list_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, k: int, max_distance: float = 0.0) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_knn_list_host)."""
+        out = np.zeros(max(nq, 0) * max(k, 0), DMATCH_DTYPE)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_knn_list_host(self._m, q_ptr or None, nq, t_ptr or None, nt, k, max_distance,
+                                                  _ptr(out), len(out), ctypes.byref(n)), "match_knn_list_host")
+        return out[: n.value]
+
     # --- guided matching: the same operations restricted to a search window (the rule: include/sift_hip.h, and in
     # numpy sift_amd.cv.gate_mask / guided_top2).  q_xy_ptr / t_xy_ptr: device float rows with x, y first (stride 3
     # passes a detector's device_kpts as it is); train row t is a candidate of query i when |tx - qx| <= radius and
@@ -1152,6 +1236,23 @@ def _list_matcher(num_des: int, num_src: int) -> Matcher:
         # two pairs: foreign buffers match both directions in one launch (detector buffers use their sidecars)
         _default_matcher = Matcher(cap, cap, max_pairs=2)
     return _default_matcher
+
+
+def knnMatch(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src: int, k: int):
+    """cv::BFMatcher::knnMatch(des, src, k) as arrays: (idx int32 (num_des, k), d2 float32 (num_des, k)), the k
+    nearest rows of src for every row of des in ascending (squared distance, index) order, -1 / FLT_MAX where src has
+    fewer than k rows (1 <= k <= KNN_MAX; the rule is sift_amd.cv.knn)."""
+    m = _list_matcher(num_des, num_src)
+    return m.match_knn_host(des.data(), num_des, src.data(), num_src, k)
+
+
+def matchKnnList(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src: int, k: int,
+                 max_distance: float = 0.0) -> np.ndarray:
+    """cv::BFMatcher::radiusMatch capped at k per query: DMATCH_DTYPE records (queryIdx, trainIdx, imgIdx 0, L2
+    distance) of the k nearest rows of src within max_distance (<= 0: no cap) of every row of des, in (queryIdx,
+    rank) order -- the candidates a verifier chooses among (the rule is sift_amd.cv.knn_records)."""
+    m = _list_matcher(num_des, num_src)
+    return m.match_knn_list_host(des.data(), num_des, src.data(), num_src, k, max_distance)
 
 
 def matchListGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, radius: float,

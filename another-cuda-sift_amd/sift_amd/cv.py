@@ -155,6 +155,78 @@ def filter_matches(idx2_fwd, d2_fwd, idx2_rev=None, d2_rev=None, ratio: float = 
     return out
 
 
+KNN_MAX = 8  # SIFT_HIP_KNN_MAX
+
+
+def knn(q, t, k: int):
+    """The k-NN rule of include/sift_hip.h (Matcher.match_knn_*, knnMatch) in numpy: (idx int32 (nq, k), d2 float32
+    (nq, k)).  Row i holds the min(k, candidates) train rows of smallest squared L2 distance to query i in ascending
+    (d2, train index) order -- a stable argsort, so a tie at any rank goes to the lower train index -- and -1 / FLT_MAX
+    in the remaining entries.  Sets of integers 0..255: exact int64 distances (what the device returns, as bytes).
+    Otherwise float64, term by term on the values given: a train row holding NaN or an infinity is nobody's
+    neighbour, a query row holding one has none (the device's general path is within its stated bound of this)."""
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError(f"k = {k} outside 1..{KNN_MAX}")
+    q, t = np.asarray(q), np.asarray(t)
+    nq, nt = len(q), len(t)
+    q = q.reshape(nq, q.size // max(nq, 1))
+    t = t.reshape(nt, t.size // max(nt, 1))
+    idx = np.full((nq, k), -1, np.int32)
+    d2 = np.full((nq, k), np.finfo(np.float32).max, np.float32)
+    if nq == 0 or nt == 0:
+        return idx, d2
+
+    def integers(a):
+        a = a.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            return bool(np.all(np.isfinite(a)) and np.all((a == np.rint(a)) & (a >= 0) & (a <= 255))
+                        and not np.any(np.signbit(a)))
+
+    if integers(q) and integers(t):
+        qi, ti = q.astype(np.int64), t.astype(np.int64)
+        D = (qi * qi).sum(1)[:, None] + (ti * ti).sum(1)[None, :] - 2 * (qi @ ti.T)
+        qok, tok = np.ones(nq, bool), np.ones(nt, bool)
+    else:
+        qf, tf = q.astype(np.float64), t.astype(np.float64)
+        qok, tok = np.isfinite(qf).all(1), np.isfinite(tf).all(1)
+        D = np.empty((nq, nt), np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for i0 in range(0, nq, 16):
+                D[i0:i0 + 16] = ((qf[i0:i0 + 16, None, :] - tf[None, :, :]) ** 2).sum(-1)
+    cand = np.flatnonzero(tok)
+    m = min(k, len(cand))
+    if m:
+        Dc = D[:, cand]
+        order = np.argsort(Dc, axis=1, kind="stable")[:, :m]
+        rows = np.flatnonzero(qok)
+        idx[rows, :m] = cand[order[rows]]
+        d2[rows, :m] = np.take_along_axis(Dc, order, 1)[rows].astype(np.float32)
+    return idx, d2
+
+
+def knn_records(idx, d2, max_distance: float = 0.0, img_idx: int = 0) -> np.ndarray:
+    """The capped radius list of a k-NN table (Matcher.match_knn_list_*, matchKnnList) in numpy float32: neighbour j
+    of query i is kept when idx[i, j] >= 0 and (max_distance <= 0 or sqrt(d2[i, j]) <= max_distance); DMATCH_DTYPE
+    records (i, idx[i, j], img_idx, sqrt(d2[i, j])) in (queryIdx, rank) order."""
+    from . import DMATCH_DTYPE
+
+    idx = np.asarray(idx, np.int32)
+    d2 = np.asarray(d2, np.float32)
+    if idx.shape != d2.shape or idx.ndim != 2:
+        raise ValueError("idx and d2 are (nq, k) arrays of one shape")
+    if np.isnan(max_distance):
+        raise ValueError("max_distance is NaN")
+    with np.errstate(invalid="ignore"):
+        dist = np.sqrt(d2)
+    keep = idx >= 0
+    if np.float32(max_distance) > 0:
+        keep &= dist <= np.float32(max_distance)
+    i, j = np.nonzero(keep)  # row-major: (queryIdx, rank) order
+    out = np.zeros(len(i), DMATCH_DTYPE)
+    out["queryIdx"], out["trainIdx"], out["imgIdx"], out["distance"] = i, idx[i, j], img_idx, dist[i, j]
+    return out
+
+
 def gate_mask(q_xy, t_xy, radius) -> np.ndarray:
     """The guided-matching gate of include/sift_hip.h in numpy float32: an (nq, nt) bool array, True where train row
     t is a candidate of query i -- fabsf(tx - qx) <= radius and fabsf(ty - qy) <= radius, one float32 subtraction per

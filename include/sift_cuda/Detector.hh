@@ -268,4 +268,33 @@ void matchListEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<Gui
                                     float max_error, const MatchFilter& filter, DMatch* out, int* counts,
                                     void* stream = nullptr);
 
+// Extra: cv::BFMatcher::knnMatch(des, src, k), 1 <= k <= SIFT_HIP_KNN_MAX (8),
+// on the device without a distance matrix (sift_hip_match_knn_host): for each
+// of the num_des rows its min(k, num_src) nearest rows of src in ascending
+// (distance, trainIdx) order -- a tie at any rank goes to the lower index --
+// with real L2 distances, imgIdx 0.  OpencvUtils::cvtMatchToDMatch converts each
+// row.  Synchronous; a thread-local matcher as matchBruteForce's.  A k outside
+// the range throws std::invalid_argument.
+std::vector<std::vector<DMatch>> matchKnn(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                          int num_src, int k);
+
+// Extra: cv::BFMatcher::radiusMatch capped at k per query as one flat list
+// (sift_hip_match_knn_list_host): the neighbours of matchKnn within
+// max_distance (<= 0: no cap) in (queryIdx, rank) order -- the candidates a
+// verifier chooses among where the ratio test would discard a repeated
+// structure's right match.  Verifier::verify* take the list as it is.
+std::vector<DMatch> matchKnnList(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src, int num_src,
+                                 int k, float max_distance = 0.f);
+
+// The device forms, enqueued on a stream (sift_hip_match_knn_batched /
+// sift_hip_match_knn_list_batched; the positions of a GuidedPair are not read).
+// idx / d2: device, k entries per des row, pair p from row sum_{r<p} num_des[r]
+// (-1 / FLT_MAX where src has fewer rows; d2 squared).  out: device, pair p's
+// records (imgIdx = p) from row k * sum_{r<p} num_des[r], counts[p] of them.
+// The first k-NN call on a BatchMatcher allocates (not under stream capture).
+void matchKnnBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int k, int* idx, float* d2,
+                           void* stream = nullptr);
+void matchKnnListBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int k, float max_distance,
+                               DMatch* out, int* counts, void* stream = nullptr);
+
 }  // namespace sift_cuda

@@ -694,6 +694,104 @@ int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes,
 int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
                              const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count);
 
+/* --- k nearest neighbours (k <= 8) and capped radius lists -------------------
+ *
+ * cv::BFMatcher::knnMatch(query, train, k) and radiusMatch capped at k per
+ * query, without a distance matrix in memory: the few best candidates of each
+ * query for a verifier to choose from (repetitive structure, where the ratio
+ * test discards the right match because its twin is second), voting and
+ * retrieval.  sift_hip_verify_* accept the lists as they are (repeated
+ * queryIdx).
+ *
+ * The rule.  For a pair (Q: nq rows, T: nt rows) and 1 <= k <= SIFT_HIP_KNN_MAX:
+ *   row i of idx[nq][k] / d2[nq][k] holds the min(k, candidates) train rows of
+ *   smallest squared L2 distance to query i, in ascending (d2, train index)
+ *   order -- a tie at any rank, the k-th included, goes to the lower train
+ *   index -- and -1 / FLT_MAX in the remaining entries.  On integer sets d2 is
+ *   the float32 of the exact integer.  On the general path (a set holding a
+ *   value that is not an integer 0..255) d2 and the special values follow items
+ *   1, 2, 4 and 7 of the general-path contract above, a query row holding NaN
+ *   or an infinity getting -1 / FLT_MAX throughout; the arithmetic is that of
+ *   sift_hip_match_device: the same MFMA sequence, (|t|^2 - 2 q.t) + |q|^2,
+ *   the clamp at 0, candidates ordered on |t|^2 - 2 q.t.
+ *   Routes.  k = 2 gives, byte for byte, what sift_hip_match_device writes to
+ *   idx2 / d2, on both paths.  Column j of a call with k equals column j of a
+ *   call with any k' > j.  The bytes do not depend on the launch plan, on the
+ *   kernel instantiation that served the call, on max_pairs, or on whether the
+ *   sets came as detector buffers, fp16 rows or codes.
+ * The list of a pair is its table as records: neighbour j of query i is kept
+ * when idx[i][j] >= 0 and (max_distance <= 0 or sqrtf(d2[i][j]) <= max_distance,
+ * float32); the kept neighbours come out in (queryIdx, rank) order as
+ * {queryIdx = i, trainIdx = idx[i][j], imgIdx = the pair's index p,
+ * distance = sqrtf(d2[i][j])}, their number in a device int.  Slots come from
+ * prefix sums: the bytes are the same in every run.  max_distance <= 0 gives
+ * the whole table.
+ *
+ * Refusals (SIFT_HIP_ERR_INVALID, nothing launched, nothing written, judged
+ * before any device call): k outside 1..SIFT_HIP_KNN_MAX; a null matcher; a
+ * size over the matcher's limits; P outside 1..max_pairs; a null descriptor
+ * pointer of a non-empty set; for the list calls a null out or count, or a NaN
+ * max_distance.  nq == 0: nothing is written (a list's count is 0).  nt == 0:
+ * every entry is -1 / FLT_MAX and the count is 0.
+ *
+ * Scratch.  Train rows are split over workgroups by whole groups of 256 rows,
+ * at most 8 splits; each split writes a sorted list of 8-byte keys per query,
+ * which the last split of a query block merges.  The matcher allocates, at its
+ * first k-NN call (not under stream capture; later calls only launch),
+ *   64 B * max_query * max(8, 2 * max_pairs)        the split lists,
+ *   2 * 4 B * 8 * max_pairs * max_query             the table of the list and host calls,
+ *   16 B * 8 * max_query + 4 B * max_pairs          the records and counts of the host calls,
+ * and a call of P pairs with the largest nq = Q uses S splits with
+ * P * S * Q <= max_query * max(8, 2 * max_pairs): the plan's S, lowered if need
+ * be.  A matcher that never makes a k-NN call keeps its footprint.  Calls on
+ * one matcher must be ordered, as for sift_hip_match_*.
+ *
+ * Gated forms (the window and the epipolar gate) of k-NN are not provided. */
+#define SIFT_HIP_KNN_MAX 8
+
+/* One pair.  idx / d2: device, nq * k entries; either may be NULL.  Two
+ * detector buffers with fresh sidecars match their codes directly (no prep
+ * launch), subject to sift_hip_matcher_set_sidecars and
+ * sift_hip_descriptors_written as sift_hip_match_device is. */
+int sift_hip_match_knn_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt, int k,
+                              int* idx, float* d2, void* stream);
+
+/* P pairs (host arrays as sift_hip_match_batched); pair p's rows start at row
+ * sum_{r<p} nq[r] of idx / d2. */
+int sift_hip_match_knn_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                               const uint16_t* const* train, const int* nt, int k, int* idx, float* d2, void* stream);
+
+/* The same for pairs of ready code sets (sift_hip_match_codes_batched's
+ * arguments). */
+int sift_hip_match_knn_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                     const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                     const int* tkey0, const int* nt, int k, int* idx, float* d2, void* stream);
+
+/* Synchronous, one pair, the table to host memory (nq * k entries each; either
+ * may be NULL). */
+int sift_hip_match_knn_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt, int k,
+                            int* idx_host, float* d2_host);
+
+/* The list of one pair.  out: device, room for nq * k records; count: device
+ * int. */
+int sift_hip_match_knn_list_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                   int k, float max_distance, sift_hip_dmatch* out, int* count, void* stream);
+
+/* P pairs: pair p's records start at row k * sum_{r<p} nq[r] of out (device,
+ * k * sum nq rows) and carry imgIdx = p; counts: device, P ints. */
+int sift_hip_match_knn_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                    const uint16_t* const* train, const int* nt, int k, float max_distance,
+                                    sift_hip_dmatch* out, int* counts, void* stream);
+
+/* Synchronous, one pair: copies min(count, cap) records to out_host and sets
+ * *count to the full count. */
+int sift_hip_match_knn_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                 int k, float max_distance, sift_hip_dmatch* out_host, int cap, int* count);
+
+/* Train splits a k-NN call of this shape launches with on a matcher whose
+ * scratch holds them (host-only, for tests and tools). */
+int sift_hip_match_knn_plan(int nq, int nt, int pairs, int k, int* splits);
+
 /* --- Guided matching: top-2 and match lists inside a search window ----------
  *
  * A tracker matches a point near its previous position, an SfM front end a
