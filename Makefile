@@ -64,7 +64,7 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_match_knn_args
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
@@ -81,8 +81,9 @@ $(ASAN_DIR)/test_%_args: tests/cpp/test_%_args.cpp $(SRC)/verify_cxx.cpp $(wildc
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'
 
 # Argument validation of the k-NN C++ surface (match_batched_cxx.cpp) and of the k-NN ABI calls that need no matcher,
-# CPU only (run by tests/test_match_knn_asan.py).  An explicit rule: the pattern above links verify_cxx.cpp.
-$(ASAN_DIR)/test_match_knn_args: tests/cpp/test_match_knn_args.cpp $(SRC)/match_batched_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
+# CPU only (run by tests/test_match_knn_asan.py; the gated forms: test_match_knn_gated_args, run by
+# tests/test_match_knn_gated_asan.py).  An explicit rule: the pattern above links verify_cxx.cpp.
+$(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args: $(ASAN_DIR)/%: tests/cpp/%.cpp $(SRC)/match_batched_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ $< $(SRC)/match_batched_cxx.cpp \
 	    -L$(OUT) -lsift_hip -Wl,-rpath,'$$ORIGIN/..'

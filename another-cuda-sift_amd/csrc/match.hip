@@ -38,7 +38,9 @@
 //  k_match_knn     k nearest neighbours (k <= 8) of every query of every pair:
 //                  k_match_batch's streaming loop with a K-entry fold, and
 //                  k_knn_select, the capped radius list of its table (the
-//                  section at the end of this file).
+//                  section at the end of this file).  The gate is a template
+//                  parameter: k_match_knn<K, MatchGate / EpipolarGate> is the
+//                  k-NN inside the window or the epipolar band, single or batched.
 //
 // Exactness: d^2 = sum (t - q)^2 = |c_t|^2 + |c_q|^2 - 2 c_t.c_q for the
 // shifted codes (translation invariant), so the int32 accumulator and every
@@ -1447,9 +1449,18 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 
 // One staged chunk (a key group, nc tiles) against a wave's query block: the
 // keys of each tile into the lane's descending list L.
-template <int K>
-__device__ __forceinline__ void chunk_topk(const int8_t* sc, const int* sk, int nc, int col, int h,
-                                           const i32x4 (&bq)[4], int (&L)[K], int& tail, int thr) {
+// Under a gate (Gate = LaneGate<1> or LaneEpipolar<1>, planes sx / sy and the
+// gate's sn) the key of a (query, row) that fails the gate becomes INT_MIN
+// before the ballot: below kInvalidKey and every thr, so it never enters L (in
+// a chain that runs for another lane it is a no-op: med3(a, b, INT_MIN) = b for
+// a >= b).  The gated fold reads its planes one row group at a time, as
+// chunk_top2 does under the epipolar gate, in place of the four key loads up
+// front: the registers of the K-entry lists leave no room for both.
+template <int K, class Gate>
+__device__ __forceinline__ void chunk_topk(const int8_t* sc, const int* sk, const float* sx, const float* sy, int nc,
+                                           int col, int h, const i32x4 (&bq)[4], const Gate& g, int (&L)[K], int& tail,
+                                           int thr) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int sw = (col >> 1) & 7;
     const int8_t* const ta0 = sc + col * 128;
     const int* const tk1 = sk + 4 * h;
@@ -1459,38 +1470,84 @@ __device__ __forceinline__ void chunk_topk(const int8_t* sc, const int* sk, int 
         for (int kb = 0; kb < 4; kb++)
             a[kb] = *reinterpret_cast<const i32x4*>(ta0 + j * kTileBytes + 16 * ((4 * h + kb) ^ sw));
         // accumulator register i holds train row (i & 3) + 8 (i >> 2) + 4 h
+        if constexpr (!kGated<Gate>) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) tk[r] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * r);
+            for (int r = 0; r < 4; r++) tk[r] = *reinterpret_cast<const i32x4*>(tk1 + j * kMatchTileRows + 8 * r);
+        }
         i32x16 acc = {};
 #pragma unroll
         for (int kb = 0; kb < 4; kb++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kb], bq[kb], acc, 0, 0, 0);
+        if constexpr (kGated<Gate>) {
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int x = (acc[i] << 9) + tk[i >> 2][i & 3];
-            if (__builtin_amdgcn_ballot_w64(x > tail) != 0) {  // wave-uniform
+            for (int r = 0; r < 4; r++) {
+                const int o = 4 * h + j * kMatchTileRows + 8 * r;
+                const i32x4 kr = *reinterpret_cast<const i32x4*>(sk + o);
+                const f32x4 xr = *reinterpret_cast<const f32x4*>(sx + o);
+                const f32x4 yr = *reinterpret_cast<const f32x4*>(sy + o);
+                bool pass[4];
+                if constexpr (kLaneEpipolar<Gate>) {
+                    const f32x4 nr = *reinterpret_cast<const f32x4*>(g.sn + o);
+                    epi_pass2(g.q[0], f32x2{xr[0], xr[1]}, f32x2{yr[0], yr[1]}, f32x2{nr[0], nr[1]}, g.e2, g.radius,
+                              pass[0], pass[1]);
+                    epi_pass2(g.q[0], f32x2{xr[2], xr[3]}, f32x2{yr[2], yr[3]}, f32x2{nr[2], nr[3]}, g.e2, g.radius,
+                              pass[2], pass[3]);
+                } else {
 #pragma unroll
-                for (int s = K - 1; s >= 1; s--) L[s] = med3_i32(L[s - 1], L[s], x);
-                L[0] = max(L[0], x);
-                tail = max(L[K - 1], thr);
+                    for (int e = 0; e < 4; e++) pass[e] = in_gate(xr[e], yr[e], g.qx[0], g.qy[0], g.radius);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int x = pass[e] ? (acc[4 * r + e] << 9) + kr[e] : INT_MIN;
+                    if (__builtin_amdgcn_ballot_w64(x > tail) != 0) {  // wave-uniform
+#pragma unroll
+                        for (int s = K - 1; s >= 1; s--) L[s] = med3_i32(L[s - 1], L[s], x);
+                        L[0] = max(L[0], x);
+                        tail = max(L[K - 1], thr);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int x = (acc[i] << 9) + tk[i >> 2][i & 3];
+                if (__builtin_amdgcn_ballot_w64(x > tail) != 0) {  // wave-uniform
+#pragma unroll
+                    for (int s = K - 1; s >= 1; s--) L[s] = med3_i32(L[s - 1], L[s], x);
+                    L[0] = max(L[0], x);
+                    tail = max(L[K - 1], thr);
+                }
             }
         }
     }
 }
 
-// match_f16_block (NoGate) with a K-entry list: the same loads, norms, MFMA
-// sequence and d = |t|^2 - 2 q.t; a strict '<' insertion in train order, the
-// halves merged in (d, index) order, then + |q|^2, the non-finite query rule
-// and the clamp.  res: output keys, kKnnNone where there is no entry.
-template <int K>
-__device__ void knn_f16_block(const MatchPair& pr, int q0, int tbeg, int tend, int col, int h,
+// match_f16_block with a K-entry list: the same loads, norms, MFMA sequence and
+// d = |t|^2 - 2 q.t; a strict '<' insertion in train order, the halves merged
+// in (d, index) order, then + |q|^2, the non-finite query rule and the clamp.
+// Under a gate the insertion also requires the row to be a candidate of the
+// query, evaluated as match_f16_block does (lane col carries the position of
+// train row t0 + col, under the epipolar gate its nr too, and |q|^2 is formed
+// after the tile loop).  res: output keys, kKnnNone where there is no entry.
+template <int K, class Gate>
+__device__ void knn_f16_block(const MatchPair& pr, const Gate& g, int q0, int tbeg, int tend, int col, int h,
                               unsigned long long (&res)[K]) {
     const int qrow = q0 + col;
     const bool qvalid = qrow < pr.nq;
     half8 bq[8];
 #pragma unroll
     for (int s = 0; s < 8; s++) bq[s] = qvalid ? load_frag(pr.q + (size_t)qrow * 128, 16 * s + 8 * h) : half8{};
-    float qn = sumsq8(bq);
-    qn += __shfl_xor(qn, 32);
+    float qx = NAN, qy = NAN;
+    if constexpr (kGated<Gate>) {
+        qx = qvalid ? g.qxy[(size_t)qrow * g.qstride] : NAN;
+        qy = qvalid ? g.qxy[(size_t)qrow * g.qstride + 1] : NAN;
+    }
+    float qn = 0.f;
+    if constexpr (!kEpipolar<Gate>) {
+        qn = sumsq8(bq);
+        qn += __shfl_xor(qn, 32);
+    }
+    EpiQuery eq{};
+    if constexpr (kEpipolar<Gate>) eq = epi_query(g.F, qx, qy);
     float dl[K];
     int il[K];
 #pragma unroll
@@ -1501,8 +1558,15 @@ __device__ void knn_f16_block(const MatchPair& pr, int q0, int tbeg, int tend, i
         half8 a[8];
 #pragma unroll
         for (int s = 0; s < 8; s++) a[s] = tvalid ? load_frag(pr.t + (size_t)trow * 128, 16 * s + 8 * h) : half8{};
+        float tx = NAN, ty = NAN;
+        if constexpr (kGated<Gate>) {
+            tx = tvalid ? g.txy[(size_t)trow * g.tstride] : NAN;
+            ty = tvalid ? g.txy[(size_t)trow * g.tstride + 1] : NAN;
+        }
         float tn = sumsq8(a);
         tn += __shfl_xor(tn, 32);
+        float tv = 0.f;  // epipolar only
+        if constexpr (kEpipolar<Gate>) tv = epi_row(g.F, tx, ty);
         f32x16 acc = {}, acc2 = {};
 #pragma unroll
         for (int s = 0; s < 8; s += 2) {
@@ -1514,7 +1578,12 @@ __device__ void knn_f16_block(const MatchPair& pr, int q0, int tbeg, int tend, i
         for (int i = 0; i < 16; i++) {
             const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
             const float d = __shfl(tn, row) - 2.f * acc[i];
-            if (t0 + row < pr.nt && d < dl[K - 1]) {
+            bool cand = true;
+            if constexpr (kEpipolar<Gate>)
+                cand = epi_pass(eq, __shfl(tx, row), __shfl(ty, row), __shfl(tv, row), g.e2, g.radius);
+            else if constexpr (kGated<Gate>)
+                cand = in_gate(__shfl(tx, row), __shfl(ty, row), qx, qy, g.radius);
+            if (t0 + row < pr.nt && cand && d < dl[K - 1]) {
 #pragma unroll
                 for (int j = K - 1; j >= 1; j--) {
                     const bool sh = d < dl[j - 1], here = d < dl[j];
@@ -1541,6 +1610,10 @@ __device__ void knn_f16_block(const MatchPair& pr, int q0, int tbeg, int tend, i
         }
         if (better(d, ix, dl[0], il[0])) dl[0] = d, il[0] = ix;
     }
+    if constexpr (kEpipolar<Gate>) {
+        qn = sumsq8(bq);
+        qn += __shfl_xor(qn, 32);
+    }
     // As match_f16_block ends: every candidate carries the same qn, so no selection changes.
     const bool none = !(qn < INFINITY);
 #pragma unroll
@@ -1554,29 +1627,93 @@ __device__ __forceinline__ void write_knn(unsigned long long x, int j, int k, si
     if (d2) d2[o * k + j] = v ? __uint_as_float((unsigned)(x >> 32)) : FLT_MAX;
 }
 
+// The gate of a k-NN launch (Gate = NoGate, MatchGate or EpipolarGate): the
+// batch record the kernel takes and the gate of its pair p.  An ungated launch
+// takes k_match_batch's pairs; a gated one pairs with their position arrays and
+// the call-wide gate fields (KnnGatedBatch).
+template <class Gate>
+struct KnnBatchOf {
+    typedef KnnGatedBatch type;
+};
+template <>
+struct KnnBatchOf<NoGate> {
+    typedef MatchBatch type;
+};
+__device__ __forceinline__ MatchGate knn_gate(const KnnGatedBatch& b, int p, const MatchGate*) {
+    return MatchGate{b.qxy[p], b.txy[p], b.call.qstride, b.call.tstride, b.call.radius};
+}
+// Pair p's nine floats: from device memory as k_match_epipolar_batch reads them
+// (one wave-uniform load, kept in scalar registers), or -- geometry == nullptr,
+// the single-pair calls, whose F the host has checked -- from the kernel
+// arguments.  An unusable record (a value that is not finite, or nine zeros)
+// makes e2 NaN, which fails every compare of the gate: no candidates.
+__device__ __forceinline__ EpipolarGate knn_gate(const KnnGatedBatch& b, int p, const EpipolarGate*) {
+    float f[9];
+    if (b.call.geometry) {
+        const unsigned* const G = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(b.call.geometry) +
+                                                                    (size_t)b.geom[p] * b.call.geometry_stride);
+#pragma unroll
+        for (int e = 0; e < 9; e++) f[e] = __uint_as_float(__builtin_amdgcn_readfirstlane(G[e]));
+    } else {
+#pragma unroll
+        for (int e = 0; e < 9; e++) f[e] = b.F[e];
+    }
+    bool usable = true, zero = true;
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+        usable = usable && __builtin_fabsf(f[e]) < INFINITY;
+        zero = zero && f[e] == 0.f;
+    }
+    usable = usable && !zero;
+    EpipolarGate g{b.qxy[p], b.txy[p], b.call.qstride, b.call.tstride, b.call.radius, usable ? b.call.e2 : NAN, {}};
+#pragma unroll
+    for (int e = 0; e < 9; e++) g.F[e] = f[e];
+    return g;
+}
+
 // grid = (query blocks of kKnnQB, splits S of whole key groups, pairs).  Pair p
 // reads code rows qrow0.. of qs and trow0.. of ts (one buffer for prepared or
-// gathered sets, two for a pair of sidecars).
-template <int K>
-__global__ __launch_bounds__(64 * kKnnNW, (2 * kKnnNW) / 4) void k_match_knn(  // registers for two workgroups per CU
-    MatchBatch batch, int S, int k, int nq_stride, const int8_t* __restrict__ qcodes, const int* __restrict__ qkeys,
-    const int8_t* __restrict__ tcodes, const int* __restrict__ tkeys, const int8_t* __restrict__ zc,
-    const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch,
+// gathered sets, two for a pair of sidecars).  Under a gate the train positions
+// of each chunk are staged beside its keys (two float planes per buffer, under
+// the epipolar gate a third for the rows' nr, filled once per chunk as
+// match_pair does) and the lane keeps its query's side in registers; the group
+// decode, the merges and the split lists do not know the gate.
+//
+// Registers: the integer path of every instantiation fits two workgroups per CU (128 registers), and so does all of
+// the ungated kernel and of <4, MatchGate>.  The general path of the other three gated instantiations does not (the
+// K-entry lists, two operand sets and the gate's state: 20-76 B of scratch at that bound), so those three are built
+// for one workgroup per CU instead of spilling (profiles/knn_gated/resources.json).
+template <int K, class Gate>
+constexpr int knn_wg_per_cu() {
+    return kGated<Gate> && !(K == 4 && std::is_same<Gate, MatchGate>::value) ? 1 : 2;
+}
+template <int K, class Gate = NoGate>
+__global__ __launch_bounds__(64 * kKnnNW, (knn_wg_per_cu<K, Gate>() * kKnnNW) / 4) void k_match_knn(
+    typename KnnBatchOf<Gate>::type batch, int S, int k, int nq_stride, const int8_t* __restrict__ qcodes,
+    const int* __restrict__ qkeys, const int8_t* __restrict__ tcodes, const int* __restrict__ tkeys,
+    const int8_t* __restrict__ zc, const int* __restrict__ zk, const unsigned* __restrict__ flags, unsigned epoch,
     unsigned long long* __restrict__ lists, unsigned* __restrict__ done, int* __restrict__ idx,
     float* __restrict__ d2out) {
     constexpr int NW = kKnnNW, QB = kKnnQB;
     static_assert(sizeof(unsigned long long) * K * QB <= kChunkTiles * kTileBytes, "results alias the code tiles");
     __shared__ __attribute__((aligned(16))) int8_t s_codes[2][kChunkTiles * kTileBytes];
     __shared__ __attribute__((aligned(16))) int s_key[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_px[2][kChunkRows];  // the planes: gated instantiations only
+    __shared__ __attribute__((aligned(16))) float s_py[2][kChunkRows];
+    __shared__ __attribute__((aligned(16))) float s_pn[2][kChunkRows];  // the epipolar gate only
     __shared__ unsigned s_last;
     const int p = blockIdx.z;
     const MatchPair& pr = batch.pair[p];
     const int q0 = blockIdx.x * QB;
     if (q0 >= pr.nq) return;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 31, h = lane >> 5;
+    // The wave's index w: under a gate as a scalar (match_pair: the register that keeps the epipolar body in budget).
+    const int tid = threadIdx.x, lane = tid & 63, w = kGated<Gate> ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6,
+              col = lane & 31, h = lane >> 5;
     const GroupSplit split(match_tiles(pr.nt), S);
     const int tb = split.begin(blockIdx.y), te = split.end(blockIdx.y);
     const int q0w = q0 + 32 * w;
+    Gate g{};
+    if constexpr (kGated<Gate>) g = knn_gate(batch, p, static_cast<const Gate*>(nullptr));
     unsigned long long res[K];
     if (!flags || (flags[pr.qset] != epoch && flags[pr.tset] != epoch)) {
         // ---- integer path ----
@@ -1585,11 +1722,15 @@ __global__ __launch_bounds__(64 * kKnnNW, (2 * kKnnNW) / 4) void k_match_knn(  /
         auto stage = [&](int c0, int buf) {
             stage_dma<NW>(tc, tk, pr.nt, c0 * kMatchTileRows, min(kChunkTiles, te - c0), zc, zk, s_codes[buf], s_key[buf],
                           w, lane);
+            if constexpr (kGated<Gate>)
+                stage_pos_dma<NW>(g.txy, g.tstride, pr.nt, c0 * kMatchTileRows, min(kChunkTiles, te - c0), s_px[buf],
+                                  s_py[buf], w, lane);
         };
         if (tb < te) stage(tb, 0);
         i32x4 bq[1][4];
         int qn[1];
         load_queries<1>(qcodes + (size_t)pr.qrow0 * 128, qkeys + pr.qkrow0, pr.nq, q0w, col, h, bq, qn);
+        auto lg = lane_gate<1>(g, pr.nq, q0w, col);
         unsigned long long R[K];
 #pragma unroll
         for (int j = 0; j < K; j++) R[j] = kKnnNone;
@@ -1604,7 +1745,14 @@ __global__ __launch_bounds__(64 * kKnnNW, (2 * kKnnNW) / 4) void k_match_knn(  /
             int L[K], tail = thr;
 #pragma unroll
             for (int j = 0; j < K; j++) L[j] = INT_MIN;
-            chunk_topk<K>(s_codes[buf], s_key[buf], min(kChunkTiles, te - c0), col, h, bq[0], L, tail, thr);
+            const float *sx = nullptr, *sy = nullptr;
+            if constexpr (kGated<Gate>) sx = s_px[buf], sy = s_py[buf];
+            if constexpr (kEpipolar<Gate>) {
+                for (int r = tid; r < kChunkRows; r += 64 * NW) s_pn[buf][r] = epi_row(g.F, sx[r], sy[r]);
+                lg.sn = s_pn[buf];
+                __syncthreads();
+            }
+            chunk_topk<K>(s_codes[buf], s_key[buf], sx, sy, min(kChunkTiles, te - c0), col, h, bq[0], lg, L, tail, thr);
             const int t0 = c0 * kMatchTileRows;
             if (__builtin_amdgcn_ballot_w64(L[0] > thr) != 0) {  // some lane's group holds a new entry
                 unsigned long long X[K];  // ascending: L descends, and what does not beat thr pads the end
@@ -1627,7 +1775,7 @@ __global__ __launch_bounds__(64 * kKnnNW, (2 * kKnnNW) / 4) void k_match_knn(  /
         }
     } else {
         // ---- general path: fp16 values that are not integers 0..255 ----
-        knn_f16_block<K>(pr, q0w, tb, te, col, h, res);
+        knn_f16_block<K>(pr, g, q0w, tb, te, col, h, res);
     }
     unsigned long long* const s_res = reinterpret_cast<unsigned long long*>(&s_codes[0][0]);
     __syncthreads();  // s_res aliases the code tiles
@@ -1698,6 +1846,30 @@ void launch_match_knn(const MatchBatch& batch, int S, int k, const CodeSet& q, c
     else
         hipLaunchKernelGGL(k_match_knn<8>, g, b, 0, s, batch, S, k, sc.nq_stride, q.codes, q.keys, t.codes, t.keys,
                            sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, sc.lists, sc.done, idx, d2);
+}
+
+// Gated k-NN: the pairs of `batch` (at most kMaxGatedPairs) under its gate, the window's or (epipolar) the epipolar
+// one.  The launch shape, the splits and the scratch are the ungated launch's.
+void launch_match_knn_gated(const KnnGatedBatch& batch, bool epipolar, int S, int k, const CodeSet& q, const CodeSet& t,
+                            const SetFlags& flags, const KnnScratch& sc, int* idx, float* d2, hipStream_t s) {
+    int max_nq = 1;
+    for (int p = 0; p < batch.P; p++) max_nq = max(max_nq, batch.pair[p].nq);
+    const dim3 g((max_nq + kKnnQB - 1) / kKnnQB, S, batch.P), b(64 * kKnnNW);
+#define SIFT_KNN_GATED(K, Gate)                                                                                         \
+    hipLaunchKernelGGL((k_match_knn<K, Gate>), g, b, 0, s, batch, S, k, sc.nq_stride, q.codes, q.keys, t.codes, t.keys, \
+                       sc.zero.codes, sc.zero.keys, flags.flags, flags.epoch, sc.lists, sc.done, idx, d2)
+    if (epipolar) {
+        if (k <= 4)
+            SIFT_KNN_GATED(4, EpipolarGate);
+        else
+            SIFT_KNN_GATED(8, EpipolarGate);
+    } else {
+        if (k <= 4)
+            SIFT_KNN_GATED(4, MatchGate);
+        else
+            SIFT_KNN_GATED(8, MatchGate);
+    }
+#undef SIFT_KNN_GATED
 }
 
 // k_knn_select: the capped radius list.  One workgroup per pair walks the

@@ -146,4 +146,118 @@ void matchKnnListBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPa
                 "matchKnnListBatchedDevice");
 }
 
+// --- k nearest neighbours inside a gate (sift_hip_match_knn_guided_* / *_epipolar_*) ---------
+namespace {
+
+sift_hip_match_gate abi(const MatchGate& g) {
+    return sift_hip_match_gate{g.query_xy, g.query_stride, g.train_xy, g.train_stride, g.radius};
+}
+sift_hip_match_epipolar_gate abi(const EpipolarGate& g) {
+    sift_hip_match_epipolar_gate a{g.query_xy, g.query_stride, g.train_xy, g.train_stride, g.radius, {}, g.max_error};
+    std::copy(g.F, g.F + 9, a.F);
+    return a;
+}
+
+// The bodies for either gate: `call` is the C ABI's host entry point for the gate's type.  The ABI judges k and the
+// gate before it looks at the matcher, so a bad argument throws whatever the sets are.
+template <class AbiGate, class Call>
+std::vector<std::vector<DMatch>> knn_gated(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                           int num_src, const AbiGate& gate, int k, Call call, const char* what) {
+    if (k < 1 || k > SIFT_HIP_KNN_MAX) throw std::invalid_argument(std::string(what) + ": k outside 1..SIFT_HIP_KNN_MAX");
+    std::vector<std::vector<DMatch>> out((size_t)std::max(num_des, 0));
+    std::vector<int> idx((size_t)std::max(num_des, 0) * k, -1);
+    std::vector<float> d2((size_t)std::max(num_des, 0) * k);
+    check_throw(call(knn_matcher(num_des, num_src, what), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                     reinterpret_cast<const uint16_t*>(src.data()), num_src, &gate, k, idx.data(), d2.data()),
+                what);
+    for (int i = 0; i < num_des; i++)
+        for (int j = 0; j < k && idx[(size_t)i * k + j] >= 0; j++)
+            out[(size_t)i].push_back(DMatch{i, idx[(size_t)i * k + j], 0, std::sqrt(d2[(size_t)i * k + j])});
+    return out;
+}
+
+template <class AbiGate, class Call>
+std::vector<DMatch> knn_gated_list(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                   int num_src, const AbiGate& gate, int k, float max_distance, Call call,
+                                   const char* what) {
+    if (k < 1 || k > SIFT_HIP_KNN_MAX) throw std::invalid_argument(std::string(what) + ": k outside 1..SIFT_HIP_KNN_MAX");
+    std::vector<DMatch> out((size_t)std::max(num_des, 0) * k);
+    int count = 0;
+    check_throw(call(knn_matcher(num_des, num_src, what), reinterpret_cast<const uint16_t*>(des.data()), num_des,
+                     reinterpret_cast<const uint16_t*>(src.data()), num_src, &gate, k, max_distance,
+                     reinterpret_cast<sift_hip_dmatch*>(out.data()), (int)out.size(), &count),
+                what);
+    out.resize((size_t)count);
+    return out;
+}
+
+}  // namespace
+
+std::vector<std::vector<DMatch>> matchKnnGuided(const DeviceBuffer<Half>& des, int num_des,
+                                                const DeviceBuffer<Half>& src, int num_src, const MatchGate& gate,
+                                                int k) {
+    return knn_gated(des, num_des, src, num_src, abi(gate), k, sift_hip_match_knn_guided_host, "matchKnnGuided");
+}
+
+std::vector<std::vector<DMatch>> matchKnnEpipolar(const DeviceBuffer<Half>& des, int num_des,
+                                                  const DeviceBuffer<Half>& src, int num_src, const EpipolarGate& gate,
+                                                  int k) {
+    return knn_gated(des, num_des, src, num_src, abi(gate), k, sift_hip_match_knn_epipolar_host, "matchKnnEpipolar");
+}
+
+std::vector<DMatch> matchKnnListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                       int num_src, const MatchGate& gate, int k, float max_distance) {
+    return knn_gated_list(des, num_des, src, num_src, abi(gate), k, max_distance, sift_hip_match_knn_list_guided_host,
+                          "matchKnnListGuided");
+}
+
+std::vector<DMatch> matchKnnListEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                         int num_src, const EpipolarGate& gate, int k, float max_distance) {
+    return knn_gated_list(des, num_des, src, num_src, abi(gate), k, max_distance, sift_hip_match_knn_list_epipolar_host,
+                          "matchKnnListEpipolar");
+}
+
+void matchKnnGuidedBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                 int src_stride, float radius, int k, int* idx, float* d2, void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_guided_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(),
+                                                  a.t.data(), a.nt.data(), a.pos.data(), des_stride, src_stride, radius,
+                                                  k, idx, d2, stream),
+                "matchKnnGuidedBatchedDevice");
+}
+
+void matchKnnEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                   int src_stride, float radius, const void* geometry, int geometry_stride_bytes,
+                                   float max_error, int k, int* idx, float* d2, void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_epipolar_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(),
+                                                    a.t.data(), a.nt.data(), a.pos.data(), des_stride, src_stride, radius,
+                                                    geometry, geometry_stride_bytes, max_error, k, idx, d2, stream),
+                "matchKnnEpipolarBatchedDevice");
+}
+
+void matchKnnListGuidedBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                     int src_stride, float radius, int k, float max_distance, DMatch* out, int* counts,
+                                     void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_list_guided_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(),
+                                                       a.t.data(), a.nt.data(), a.pos.data(), des_stride, src_stride,
+                                                       radius, k, max_distance,
+                                                       reinterpret_cast<sift_hip_dmatch*>(out), counts, stream),
+                "matchKnnListGuidedBatchedDevice");
+}
+
+void matchKnnListEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                       int src_stride, float radius, const void* geometry, int geometry_stride_bytes,
+                                       float max_error, int k, float max_distance, DMatch* out, int* counts,
+                                       void* stream) {
+    const AbiPairs a(pairs);
+    check_throw(sift_hip_match_knn_list_epipolar_batched(matcher.handle(), (int)pairs.size(), a.q.data(), a.nq.data(),
+                                                         a.t.data(), a.nt.data(), a.pos.data(), des_stride, src_stride,
+                                                         radius, geometry, geometry_stride_bytes, max_error, k,
+                                                         max_distance, reinterpret_cast<sift_hip_dmatch*>(out), counts,
+                                                         stream),
+                "matchKnnListEpipolarBatchedDevice");
+}
+
 }  // namespace sift_cuda

@@ -1222,3 +1222,267 @@ int sift_hip_device_sync(void) {
 }
 
 }  // extern "C"
+// --- Gated k nearest neighbours ---------------------------------------------------
+namespace {
+
+// What a gated k-NN call passes beside its pairs: which gate, the call-wide fields and -- the single-pair epipolar
+// call, geometry == nullptr -- the host's F, which travels as a kernel argument.
+struct KnnGate {
+    bool epipolar;
+    GatedCall call;
+    float F[9];
+};
+KnnGate knn_gate_of(const sift_hip_match_gate& g) {
+    return KnnGate{false, gated_call(false, g.query_stride, g.train_stride, g.radius, nullptr, 0, 0.f), {}};
+}
+KnnGate knn_gate_of(const sift_hip_match_epipolar_gate& g) {
+    KnnGate kg{true, GatedCall{g.query_stride, g.train_stride, g.radius, g.max_error * g.max_error, nullptr, 0}, {}};
+    std::copy(g.F, g.F + 9, kg.F);
+    return kg;
+}
+sift_hip_match_positions positions_of(const sift_hip_match_gate& g) { return {g.query_xy, g.train_xy}; }
+sift_hip_match_positions positions_of(const sift_hip_match_epipolar_gate& g) { return {g.query_xy, g.train_xy}; }
+int check_gate_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                    const sift_hip_match_gate* g) {
+    return check_guided_args(m, q, nq, t, nt, g);
+}
+int check_gate_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                    const sift_hip_match_epipolar_gate* g) {
+    return check_epipolar_args(m, q, nq, t, nt, g);
+}
+
+// The refusals that need no matcher, in the order of include/sift_hip.h: k, a list's max_distance (list: the call
+// has one), then the gate's own.
+int check_knn_k(int k, bool list, float max_distance) {
+    if (k < 1 || k > kKnnMax) return fail(SIFT_HIP_ERR_INVALID, "k-NN: k outside 1..SIFT_HIP_KNN_MAX");
+    if (list && std::isnan(max_distance)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: max_distance is NaN");
+    return SIFT_HIP_OK;
+}
+
+// Launches of at most kMaxGatedPairs pairs, ordered on the stream; each takes the plan's splits for its own pairs,
+// lowered to what the list scratch holds, and restores the counters it used.
+int knn_gated_launch(sift_hip_matcher* m, const MatchPair* pairs, const sift_hip_match_positions* pos, int P,
+                     const KnnGate& kg, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags, int* idx,
+                     float* d2, hipStream_t stream) {
+    for (int p0 = 0; p0 < P; p0 += kMaxGatedPairs) {
+        KnnGatedBatch b{};
+        b.P = std::min(kMaxGatedPairs, P - p0);
+        b.call = kg.call;
+        std::copy(kg.F, kg.F + 9, b.F);
+        int maxq = 1, maxt = 1;
+        bool rows = false;
+        for (int i = 0; i < b.P; i++) {
+            b.pair[i] = pairs[p0 + i];
+            b.qxy[i] = pos[p0 + i].query_xy;
+            b.txy[i] = pos[p0 + i].train_xy;
+            b.geom[i] = p0 + i;
+            maxq = std::max(maxq, b.pair[i].nq);
+            maxt = std::max(maxt, b.pair[i].nt);
+            rows = rows || b.pair[i].nq > 0;
+        }
+        if (!rows) continue;
+        const size_t fit = m->knn_lists() / ((size_t)b.P * maxq);  // >= 2: P <= maxP, maxq <= maxQ
+        const int S = (int)std::min<size_t>(match_knn_splits(maxq, maxt, b.P), fit);
+        launch_match_knn_gated(b, kg.epipolar, S, k, q, t, flags, KnnScratch{m->dKnnLists, m->dDone, maxq, m->sentinel()},
+                               idx, d2, stream);
+        HIPCHK(hipGetLastError());
+    }
+    return SIFT_HIP_OK;
+}
+
+// The gated table of checked fp16 pairs, pair p at row sum_{r<p} nq[r] (knn_fp16 under a gate).  sidecars: the
+// single-pair calls, where two detector buffers with fresh sidecars match their codes; the batched forms convert.
+int knn_gated_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
+                   const int* nt, const sift_hip_match_positions* pos, const KnnGate& kg, bool sidecars, int k, int* idx,
+                   float* d2, hipStream_t stream) {
+    if (!any_queries(P, nq)) return SIFT_HIP_OK;
+    MatchPair pairs[kMaxMatchPairs];
+    MatchSets sets{};
+    auto set_of = [&](const uint16_t* ptr, int n) {
+        for (int s = 0; s < sets.nsets; s++)
+            if (sets.set[s].src == ptr) {
+                sets.set[s].n = std::max(sets.set[s].n, n);
+                return s;
+            }
+        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
+        return sets.nsets++;
+    };
+    int off = 0;
+    for (int p = 0; p < P; p++) {
+        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
+        pairs[p] = MatchPair{q[p], t[p], nq[p], nt[p], off, qs, ts, 0, 0, 0, 0};
+        off += nq[p];
+    }
+    long row = 0;
+    for (int s = 0; s < sets.nsets; s++) {
+        sets.set[s].row0 = (int)row;
+        row += sets.set[s].n;
+        sets.maxn = std::max(sets.maxn, sets.set[s].n);
+    }
+    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    Sidecar sq{}, st{};
+    if (sidecars && P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && find_sidecar(q[0], nq[0], &sq) &&
+        find_sidecar(t[0], nt[0], &st))
+        return knn_gated_launch(m, pairs, pos, P, kg, k, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags,
+                                idx, d2, stream);
+    for (int p = 0; p < P; p++) {
+        pairs[p].qrow0 = pairs[p].qkrow0 = sets.set[pairs[p].qset].row0;
+        pairs[p].trow0 = pairs[p].tkrow0 = sets.set[pairs[p].tset].row0;
+    }
+    const SetFlags flags = m->next_epoch();
+    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
+    HIPCHK(hipGetLastError());
+    const CodeSet set{m->dCodes, m->dRowKeys};
+    return knn_gated_launch(m, pairs, pos, P, kg, k, set, set, flags, idx, d2, stream);
+}
+
+// The single-pair forms under either gate (Gate: sift_hip_match_gate or sift_hip_match_epipolar_gate).
+template <class Gate>
+int knn_gated_device(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate, int k,
+                     int* idx, float* d2, hipStream_t stream) {
+    if (int rc = check_knn_k(k, false, 0.f)) return rc;
+    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
+    const sift_hip_match_positions pos = positions_of(*gate);
+    return knn_gated_fp16(m, 1, &q, &nq, &t, &nt, &pos, knn_gate_of(*gate), true, k, idx, d2, stream);
+}
+template <class Gate>
+int knn_gated_list_device(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate,
+                          int k, float max_distance, sift_hip_dmatch* out, int* count, hipStream_t stream) {
+    if (int rc = check_knn_k(k, true, max_distance)) return rc;
+    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
+    if (!out || !count) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    const sift_hip_match_positions pos = positions_of(*gate);
+    if (int rc = knn_gated_fp16(m, 1, &q, &nq, &t, &nt, &pos, knn_gate_of(*gate), true, k, m->dKnnIdx, m->dKnnD, stream))
+        return rc;
+    return knn_select(m, 1, &nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, count, stream);
+}
+template <class Gate>
+int knn_gated_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate, int k,
+                   int* idx_host, float* d2_host) {
+    if (int rc = check_knn_k(k, false, 0.f)) return rc;
+    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
+    if (nq == 0) return SIFT_HIP_OK;
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = knn_gated_device(m, q, nq, t, nt, gate, k, m->dKnnIdx, m->dKnnD, nullptr)) return rc;
+    if (idx_host) HIPCHK(hipMemcpy(idx_host, m->dKnnIdx, sizeof(int) * (size_t)nq * k, hipMemcpyDeviceToHost));
+    if (d2_host) HIPCHK(hipMemcpy(d2_host, m->dKnnD, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+template <class Gate>
+int knn_gated_list_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate,
+                        int k, float max_distance, sift_hip_dmatch* out_host, int cap, int* count) {
+    if (!count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
+    *count = 0;
+    if (int rc = check_knn_k(k, true, max_distance)) return rc;
+    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance,
+                                       reinterpret_cast<sift_hip_dmatch*>(m->dKnnRec), m->dKnnCount, nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(count, m->dKnnCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dKnnRec, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+// The batched forms: the table into idx / d2, or (out != nullptr or list) into the matcher's own table and then the
+// list.  The checks in the header's order: k, max_distance, the call's gate fields, then the matcher's and the pairs'.
+int knn_gated_batched(bool epipolar, bool list, sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq,
+                      const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
+                      int query_stride, int train_stride, float radius, const void* geometry, int geometry_stride,
+                      float max_error, int k, float max_distance, int* idx, float* d2, sift_hip_dmatch* out, int* counts,
+                      hipStream_t stream) {
+    if (int rc = check_knn_k(k, list, max_distance)) return rc;
+    if (int rc = check_gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error))
+        return rc;
+    if (int rc = check_gated_pairs(epipolar, m, P, nq, nt, positions)) return rc;
+    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
+    if (list && (!out || !counts)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
+    const KnnGate kg{epipolar,
+                     gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error),
+                     {}};
+    if (!list) return knn_gated_fp16(m, P, q, nq, t, nt, positions, kg, false, k, idx, d2, stream);
+    if (int rc = ensure_knn_scratch(m)) return rc;
+    if (int rc = knn_gated_fp16(m, P, q, nq, t, nt, positions, kg, false, k, m->dKnnIdx, m->dKnnD, stream)) return rc;
+    return knn_select(m, P, nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, counts, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sift_hip_match_knn_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                     const sift_hip_match_gate* gate, int k, int* idx, float* d2, void* stream) {
+    return knn_gated_device(m, q, nq, t, nt, gate, k, idx, d2, (hipStream_t)stream);
+}
+int sift_hip_match_knn_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                       const sift_hip_match_epipolar_gate* gate, int k, int* idx, float* d2,
+                                       void* stream) {
+    return knn_gated_device(m, q, nq, t, nt, gate, k, idx, d2, (hipStream_t)stream);
+}
+int sift_hip_match_knn_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                      const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
+                                      int query_stride, int train_stride, float radius, int k, int* idx, float* d2,
+                                      void* stream) {
+    return knn_gated_batched(false, false, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, nullptr, 0,
+                             0.f, k, 0.f, idx, d2, nullptr, nullptr, (hipStream_t)stream);
+}
+int sift_hip_match_knn_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                        const uint16_t* const* t, const int* nt,
+                                        const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                        float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                        int k, int* idx, float* d2, void* stream) {
+    return knn_gated_batched(true, false, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, geometry,
+                             geometry_stride_bytes, max_error, k, 0.f, idx, d2, nullptr, nullptr, (hipStream_t)stream);
+}
+int sift_hip_match_knn_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                          const sift_hip_match_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out, int* count, void* stream) {
+    return knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance, out, count, (hipStream_t)stream);
+}
+int sift_hip_match_knn_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                            const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                            sift_hip_dmatch* out, int* count, void* stream) {
+    return knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance, out, count, (hipStream_t)stream);
+}
+int sift_hip_match_knn_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                           const uint16_t* const* t, const int* nt,
+                                           const sift_hip_match_positions* positions, int query_stride,
+                                           int train_stride, float radius, int k, float max_distance,
+                                           sift_hip_dmatch* out, int* counts, void* stream) {
+    return knn_gated_batched(false, true, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, nullptr, 0,
+                             0.f, k, max_distance, nullptr, nullptr, out, counts, (hipStream_t)stream);
+}
+int sift_hip_match_knn_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                             const uint16_t* const* t, const int* nt,
+                                             const sift_hip_match_positions* positions, int query_stride,
+                                             int train_stride, float radius, const void* geometry,
+                                             int geometry_stride_bytes, float max_error, int k, float max_distance,
+                                             sift_hip_dmatch* out, int* counts, void* stream) {
+    return knn_gated_batched(true, true, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, geometry,
+                             geometry_stride_bytes, max_error, k, max_distance, nullptr, nullptr, out, counts,
+                             (hipStream_t)stream);
+}
+int sift_hip_match_knn_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                   const sift_hip_match_gate* gate, int k, int* idx_host, float* d2_host) {
+    return knn_gated_host(m, q, nq, t, nt, gate, k, idx_host, d2_host);
+}
+int sift_hip_match_knn_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                     const sift_hip_match_epipolar_gate* gate, int k, int* idx_host, float* d2_host) {
+    return knn_gated_host(m, q, nq, t, nt, gate, k, idx_host, d2_host);
+}
+int sift_hip_match_knn_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                        const sift_hip_match_gate* gate, int k, float max_distance,
+                                        sift_hip_dmatch* out_host, int cap, int* count) {
+    return knn_gated_list_host(m, q, nq, t, nt, gate, k, max_distance, out_host, cap, count);
+}
+int sift_hip_match_knn_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                          const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out_host, int cap, int* count) {
+    return knn_gated_list_host(m, q, nq, t, nt, gate, k, max_distance, out_host, cap, count);
+}
+
+}  // extern "C"

@@ -247,6 +247,27 @@ int match_knn_splits(int max_nq, int max_nt, int P);
 void launch_match_knn(const MatchBatch& batch, int S, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
                       const KnnScratch& sc, int* idx, float* d2, hipStream_t s);
 
+// --- Gated k-NN (sift_hip_match_knn_guided_* / *_epipolar_*): k_match_knn under the window or the epipolar gate.
+//
+// The pairs of one launch as k_match_knn takes them (MatchPair), beside them their position arrays and the index of
+// their geometry record (k-NN has no reverse direction, so nothing is swapped), and what is uniform over the call
+// (GatedCall).  Under the epipolar gate pair p's nine floats are read from device memory at call.geometry + geom[p] *
+// geometry_stride, or -- call.geometry == nullptr, the single-pair calls -- F, checked on the host, travels in the
+// kernel arguments: no host-to-device copy.  Passed by value (2.5 KiB of kernarg), at most kMaxGatedPairs pairs.
+struct KnnGatedBatch {
+    MatchPair pair[kMaxGatedPairs];
+    const float* qxy[kMaxGatedPairs];
+    const float* txy[kMaxGatedPairs];
+    int geom[kMaxGatedPairs];
+    int P;
+    GatedCall call;
+    float F[9];
+};
+
+// S splits as launch_match_knn takes them; the scratch, the code sets and the flag rule are launch_match_knn's.
+void launch_match_knn_gated(const KnnGatedBatch& batch, bool epipolar, int S, int k, const CodeSet& q, const CodeSet& t,
+                            const SetFlags& flags, const KnnScratch& sc, int* idx, float* d2, hipStream_t s);
+
 // One workgroup per pair: the table entries (rows fwd.. of idx / d2, k per row)
 // that hold a neighbour within max_distance, in (query, rank) order at out +
 // out_off, their number in counts[p].

@@ -318,6 +318,24 @@ def lib() -> ctypes.CDLL:
         "sift_hip_match_list_epipolar_codes_batched": (i, [vp, vp, vp, i, vp, vp, vp, vp, vp, vp,
                                                            ctypes.POINTER(_MatchPositions), i, i, f, vp, i, f,
                                                            ctypes.POINTER(_MatchFilter), vp, vp, vp]),
+        "sift_hip_match_knn_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), i, vp, vp, vp]),
+        "sift_hip_match_knn_epipolar_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate), i, vp, vp, vp]),
+        "sift_hip_match_knn_guided_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f, i, vp,
+                                                  vp, vp]),
+        "sift_hip_match_knn_epipolar_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f, vp,
+                                                    i, f, i, vp, vp, vp]),
+        "sift_hip_match_knn_list_guided_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), i, f, vp, vp, vp]),
+        "sift_hip_match_knn_list_epipolar_device": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate), i, f, vp,
+                                                        vp, vp]),
+        "sift_hip_match_knn_list_guided_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f,
+                                                       i, f, vp, vp, vp]),
+        "sift_hip_match_knn_list_epipolar_batched": (i, [vp, i, vp, vp, vp, vp, ctypes.POINTER(_MatchPositions), i, i, f,
+                                                         vp, i, f, i, f, vp, vp, vp]),
+        "sift_hip_match_knn_guided_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), i, vp, vp]),
+        "sift_hip_match_knn_epipolar_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate), i, vp, vp]),
+        "sift_hip_match_knn_list_guided_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchGate), i, f, vp, i, ip]),
+        "sift_hip_match_knn_list_epipolar_host": (i, [vp, vp, i, vp, i, ctypes.POINTER(_MatchEpipolarGate), i, f, vp, i,
+                                                      ip]),
         "sift_hip_project_homography_batched_device": (i, [vp, i, i, ctypes.POINTER(_ProjectSet), i, i, vp]),
         "sift_hip_default_verify_params": (None, [ctypes.POINTER(_VerifyParams)]),
         "sift_hip_verifier_create": (i, [i, i, i, ctypes.POINTER(vp)]),
@@ -1211,6 +1229,138 @@ class Matcher:
                                                                 counts_ptr or None, stream),
                "match_list_epipolar_codes_batched")
 
+    # --- k nearest neighbours inside the two gates (the rule: include/sift_hip.h, "Gated k nearest neighbours"; in
+    # numpy sift_amd.cv.guided_knn / epipolar_knn / mask_knn, the lists sift_amd.cv.knn_records of their tables).
+    # Arguments as the gated top-2 calls above with k (and max_distance) in place of the ratio test; tables and lists
+    # as match_knn_*.  The launch shape is knn_plan's.
+
+    def match_knn_guided_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                                radius: float, k: int, idx_ptr: int = 0, d2_ptr: int = 0, q_stride: int = 3,
+                                t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """match_knn_device over each query's window candidates only (sift_hip_match_knn_guided_device)."""
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        _check(lib().sift_hip_match_knn_guided_device(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g), k,
+                                                      idx_ptr or None, d2_ptr or None, stream), "match_knn_guided_device")
+
+    def match_knn_epipolar_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                  max_error: float, k: int, idx_ptr: int = 0, d2_ptr: int = 0,
+                                  radius: float = float("inf"), q_stride: int = 3, t_stride: int = 3,
+                                  stream: Optional[int] = None) -> None:
+        """match_knn_device over each query's epipolar candidates only (sift_hip_match_knn_epipolar_device)."""
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        _check(lib().sift_hip_match_knn_epipolar_device(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g),
+                                                        k, idx_ptr or None, d2_ptr or None, stream),
+               "match_knn_epipolar_device")
+
+    def match_knn_guided_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                 nts: Sequence[int], positions: Sequence, radius: float, k: int, idx_ptr: int = 0,
+                                 d2_ptr: int = 0, q_stride: int = 3, t_stride: int = 3,
+                                 stream: Optional[int] = None) -> None:
+        """match_knn_batched under the window gate (sift_hip_match_knn_guided_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_knn_guided_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                       q_stride, t_stride, radius, k, idx_ptr or None, d2_ptr or None,
+                                                       stream), "match_knn_guided_batched")
+
+    def match_knn_epipolar_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                   nts: Sequence[int], positions: Sequence, geometry_ptr: int, max_error: float, k: int,
+                                   idx_ptr: int = 0, d2_ptr: int = 0, radius: float = float("inf"),
+                                   geometry_stride: int = 52, q_stride: int = 3, t_stride: int = 3,
+                                   stream: Optional[int] = None) -> None:
+        """match_knn_batched under the epipolar gate, F read on the device (sift_hip_match_knn_epipolar_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_knn_epipolar_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                         q_stride, t_stride, radius, geometry_ptr or None,
+                                                         geometry_stride, max_error, k, idx_ptr or None, d2_ptr or None,
+                                                         stream), "match_knn_epipolar_batched")
+
+    def match_knn_list_guided_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                                     radius: float, k: int, out_ptr: int, count_ptr: int, max_distance: float = 0.0,
+                                     q_stride: int = 3, t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """match_knn_list_device under the window gate (sift_hip_match_knn_list_guided_device)."""
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        _check(lib().sift_hip_match_knn_list_guided_device(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g),
+                                                           k, max_distance, out_ptr or None, count_ptr or None, stream),
+               "match_knn_list_guided_device")
+
+    def match_knn_list_epipolar_device(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                       max_error: float, k: int, out_ptr: int, count_ptr: int,
+                                       max_distance: float = 0.0, radius: float = float("inf"), q_stride: int = 3,
+                                       t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """match_knn_list_device under the epipolar gate (sift_hip_match_knn_list_epipolar_device)."""
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        _check(lib().sift_hip_match_knn_list_epipolar_device(self._m, q_ptr or None, nq, t_ptr or None, nt,
+                                                             ctypes.byref(g), k, max_distance, out_ptr or None,
+                                                             count_ptr or None, stream), "match_knn_list_epipolar_device")
+
+    def match_knn_list_guided_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                      nts: Sequence[int], positions: Sequence, radius: float, k: int, out_ptr: int,
+                                      counts_ptr: int, max_distance: float = 0.0, q_stride: int = 3, t_stride: int = 3,
+                                      stream: Optional[int] = None) -> None:
+        """match_knn_list_batched under the window gate (sift_hip_match_knn_list_guided_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_knn_list_guided_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                            q_stride, t_stride, radius, k, max_distance, out_ptr or None,
+                                                            counts_ptr or None, stream), "match_knn_list_guided_batched")
+
+    def match_knn_list_epipolar_batched(self, q_ptrs: Sequence[int], nqs: Sequence[int], t_ptrs: Sequence[int],
+                                        nts: Sequence[int], positions: Sequence, geometry_ptr: int, max_error: float,
+                                        k: int, out_ptr: int, counts_ptr: int, max_distance: float = 0.0,
+                                        radius: float = float("inf"), geometry_stride: int = 52, q_stride: int = 3,
+                                        t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """match_knn_list_batched under the epipolar gate (sift_hip_match_knn_list_epipolar_batched)."""
+        P, qa, na, ta, ma = self._sets(q_ptrs, nqs, t_ptrs, nts)
+        _check(lib().sift_hip_match_knn_list_epipolar_batched(self._m, P, qa, na, ta, ma, self._positions(positions, P),
+                                                              q_stride, t_stride, radius, geometry_ptr or None,
+                                                              geometry_stride, max_error, k, max_distance,
+                                                              out_ptr or None, counts_ptr or None, stream),
+               "match_knn_list_epipolar_batched")
+
+    def match_knn_guided_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                              radius: float, k: int, q_stride: int = 3, t_stride: int = 3):
+        """Synchronous; (idx int32 (nq, k), d2 float32 (nq, k)) (sift_hip_match_knn_guided_host)."""
+        idx = np.full((max(nq, 0), max(k, 0)), -1, np.int32)
+        d2 = np.full((max(nq, 0), max(k, 0)), np.finfo(np.float32).max, np.float32)
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        _check(lib().sift_hip_match_knn_guided_host(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g), k,
+                                                    _ptr(idx), _ptr(d2)), "match_knn_guided_host")
+        return idx, d2
+
+    def match_knn_epipolar_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                max_error: float, k: int, radius: float = float("inf"), q_stride: int = 3,
+                                t_stride: int = 3):
+        """Synchronous; (idx int32 (nq, k), d2 float32 (nq, k)) (sift_hip_match_knn_epipolar_host)."""
+        idx = np.full((max(nq, 0), max(k, 0)), -1, np.int32)
+        d2 = np.full((max(nq, 0), max(k, 0)), np.finfo(np.float32).max, np.float32)
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        _check(lib().sift_hip_match_knn_epipolar_host(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g), k,
+                                                      _ptr(idx), _ptr(d2)), "match_knn_epipolar_host")
+        return idx, d2
+
+    def match_knn_list_guided_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int,
+                                   radius: float, k: int, max_distance: float = 0.0, q_stride: int = 3,
+                                   t_stride: int = 3) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_knn_list_guided_host)."""
+        out = np.zeros(max(nq, 0) * max(k, 0), DMATCH_DTYPE)
+        g = _MatchGate(q_xy_ptr or None, q_stride, t_xy_ptr or None, t_stride, radius)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_knn_list_guided_host(self._m, q_ptr or None, nq, t_ptr or None, nt, ctypes.byref(g),
+                                                         k, max_distance, _ptr(out), len(out), ctypes.byref(n)),
+               "match_knn_list_guided_host")
+        return out[: n.value]
+
+    def match_knn_list_epipolar_host(self, q_ptr: int, nq: int, t_ptr: int, nt: int, q_xy_ptr: int, t_xy_ptr: int, F,
+                                     max_error: float, k: int, max_distance: float = 0.0, radius: float = float("inf"),
+                                     q_stride: int = 3, t_stride: int = 3) -> np.ndarray:
+        """Synchronous; the kept records as a DMATCH_DTYPE array (sift_hip_match_knn_list_epipolar_host)."""
+        out = np.zeros(max(nq, 0) * max(k, 0), DMATCH_DTYPE)
+        g = _epipolar_gate(q_xy_ptr, q_stride, t_xy_ptr, t_stride, radius, F, max_error)
+        n = ctypes.c_int(0)
+        _check(lib().sift_hip_match_knn_list_epipolar_host(self._m, q_ptr or None, nq, t_ptr or None, nt,
+                                                           ctypes.byref(g), k, max_distance, _ptr(out), len(out),
+                                                           ctypes.byref(n)), "match_knn_list_epipolar_host")
+        return out[: n.value]
+
 
 _default_matcher: Optional[Matcher] = None
 
@@ -1253,6 +1403,51 @@ def matchKnnList(des: "DeviceBuffer", num_des: int, src: "DeviceBuffer", num_src
     rank) order -- the candidates a verifier chooses among (the rule is sift_amd.cv.knn_records)."""
     m = _list_matcher(num_des, num_src)
     return m.match_knn_list_host(des.data(), num_des, src.data(), num_src, k, max_distance)
+
+
+def _xy_ptrs(des_xy, src_xy):
+    return tuple(p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+
+
+def knnMatchGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, radius: float,
+                   k: int, des_stride: int = 3, src_stride: int = 3):
+    """knnMatch inside a search window -- cv::DescriptorMatcher::knnMatch(des, src, k, mask) with the window of
+    matchListGuided as the mask: (idx, d2) as knnMatch returns them, the k nearest candidates of every row of des
+    (the rule: sift_amd.cv.guided_knn).  des_xy / src_xy as matchListGuided."""
+    m = _list_matcher(num_des, num_src)
+    qxy, txy = _xy_ptrs(des_xy, src_xy)
+    return m.match_knn_guided_host(des.data(), num_des, src.data(), num_src, qxy, txy, radius, k, des_stride, src_stride)
+
+
+def knnMatchEpipolar(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, F,
+                     max_error: float, k: int, radius: float = float("inf"), des_stride: int = 3, src_stride: int = 3):
+    """knnMatch under a fundamental matrix: the k nearest rows of src inside the epipolar band of every row of des
+    (F, max_error and radius as matchListEpipolar; the rule: sift_amd.cv.epipolar_knn)."""
+    m = _list_matcher(num_des, num_src)
+    qxy, txy = _xy_ptrs(des_xy, src_xy)
+    return m.match_knn_epipolar_host(des.data(), num_des, src.data(), num_src, qxy, txy, F, max_error, k, radius,
+                                     des_stride, src_stride)
+
+
+def matchKnnListGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy,
+                       radius: float, k: int, max_distance: float = 0.0, des_stride: int = 3,
+                       src_stride: int = 3) -> np.ndarray:
+    """matchKnnList inside a search window: the records of knnMatchGuided's table within max_distance (<= 0: no cap),
+    in (queryIdx, rank) order (the rule: sift_amd.cv.knn_records of sift_amd.cv.guided_knn)."""
+    m = _list_matcher(num_des, num_src)
+    qxy, txy = _xy_ptrs(des_xy, src_xy)
+    return m.match_knn_list_guided_host(des.data(), num_des, src.data(), num_src, qxy, txy, radius, k, max_distance,
+                                        des_stride, src_stride)
+
+
+def matchKnnListEpipolar(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, F,
+                         max_error: float, k: int, max_distance: float = 0.0, radius: float = float("inf"),
+                         des_stride: int = 3, src_stride: int = 3) -> np.ndarray:
+    """matchKnnList under a fundamental matrix: the records of knnMatchEpipolar's table within max_distance."""
+    m = _list_matcher(num_des, num_src)
+    qxy, txy = _xy_ptrs(des_xy, src_xy)
+    return m.match_knn_list_epipolar_host(des.data(), num_des, src.data(), num_src, qxy, txy, F, max_error, k,
+                                          max_distance, radius, des_stride, src_stride)
 
 
 def matchListGuided(des: "DeviceBuffer", num_des: int, des_xy, src: "DeviceBuffer", num_src: int, src_xy, radius: float,

@@ -326,6 +326,57 @@ def epipolar_top2(q, t, q_xy, t_xy, F, max_error, radius=np.inf):
     return mask_top2(q, t, lambda: epipolar_mask(q_xy, t_xy, F, max_error, radius))
 
 
+def mask_knn(q, t, cand, k: int):
+    """knn restricted to a candidate mask -- the gated k-NN rule of include/sift_hip.h, and cv::DescriptorMatcher::
+    knnMatch(query, train, k, mask): (idx int32 (nq, k), d2 float32 (nq, k)).  Row i holds the min(k, |cand[i]|) rows
+    of t among cand[i] of smallest squared L2 distance to row i of q, in ascending (d2, train index) order (a stable
+    argsort: a tie at any rank goes to the lower train index), -1 / FLT_MAX in the remaining entries.  Sets of
+    integers go through the exact int64 product; otherwise float64 as |q|^2 + |t|^2 - 2 q.t (mask_top2's form),
+    rounded to float32 once, so exactly representable inputs compare byte for byte; a train row holding NaN or an
+    infinity is nobody's neighbour and a query row holding one has none.  cand: the (nq, nt) bool array, or a function
+    returning it, called only when neither set is empty."""
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError(f"k = {k} outside 1..{KNN_MAX}")
+    q, t = np.asarray(q), np.asarray(t)
+    nq, nt = len(q), len(t)
+    q = q.reshape(nq, q.size // max(nq, 1))
+    t = t.reshape(nt, t.size // max(nt, 1))
+    idx = np.full((nq, k), -1, np.int32)
+    d2 = np.full((nq, k), np.finfo(np.float32).max, np.float32)
+    if nq == 0 or nt == 0:
+        return idx, d2
+    qok, tok = np.isfinite(q.astype(np.float64)).all(1), np.isfinite(t.astype(np.float64)).all(1)
+    with np.errstate(invalid="ignore"):
+        integers = bool(qok.all() and tok.all() and np.all(q == np.rint(q)) and np.all(t == np.rint(t)))
+    a, b = (q.astype(np.int64), t.astype(np.int64)) if integers else (q.astype(np.float64), t.astype(np.float64))
+    with np.errstate(invalid="ignore", over="ignore"):
+        dist = (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2 * (a @ b.T)
+    cand = np.asarray(cand() if callable(cand) else cand, bool)
+    if cand.shape != dist.shape:
+        raise ValueError("positions and descriptor sets differ in length")
+    cand = cand & qok[:, None] & tok[None, :]
+    order = np.argsort(np.where(cand, dist, np.inf), axis=1, kind="stable")[:, :k]  # stable: ties to the lower index
+    rows = np.arange(nq)
+    for j in range(order.shape[1]):
+        col = order[:, j]
+        ok = cand[rows, col]
+        idx[ok, j] = col[ok]
+        d2[ok, j] = dist[rows, col][ok]
+    return idx, d2
+
+
+def guided_knn(q, t, q_xy, t_xy, radius, k: int):
+    """Matcher.match_knn_guided_device in numpy: mask_knn of every query among its candidates (gate_mask).
+    knn_records turns the table into the list of Matcher.match_knn_list_guided_*."""
+    return mask_knn(q, t, lambda: gate_mask(q_xy, t_xy, radius), k)
+
+
+def epipolar_knn(q, t, q_xy, t_xy, F, max_error, k: int, radius=np.inf):
+    """Matcher.match_knn_epipolar_device in numpy: mask_knn of every query among its candidates (epipolar_mask).  A
+    batched call's pair whose geometry record is not usable (geometry_usable) has no candidates instead."""
+    return mask_knn(q, t, lambda: epipolar_mask(q_xy, t_xy, F, max_error, radius), k)
+
+
 # --- Two-view verification: the rule of sift_hip_verify_* (include/sift_hip.h) in numpy float32.  Every function
 # below works on whole arrays of hypotheses at once; each array operation is one float32 operation per element, rounded
 # to nearest, in the header's order (numpy fuses nothing), so the device's bytes are the reference's.

@@ -297,4 +297,42 @@ void matchKnnBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>&
 void matchKnnListBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int k, float max_distance,
                                DMatch* out, int* counts, void* stream = nullptr);
 
+// Extra: matchKnn / matchKnnList inside a gate -- cv::DescriptorMatcher::
+// knnMatch(des, src, k, mask) with the window of MatchGate or the epipolar band
+// of EpipolarGate as the mask (sift_hip_match_knn_guided_host and its kin; the
+// rule is in include/sift_hip.h, "Gated k nearest neighbours"): for each des row
+// its min(k, candidates) nearest candidates in ascending (distance, trainIdx)
+// order.  After a first verify pass the rematch under its F keeps every twin
+// inside the band for a second pass to choose from.  Synchronous; the
+// thread-local matcher of matchKnn.  A k outside 1..8 or a bad gate throws
+// std::invalid_argument.
+std::vector<std::vector<DMatch>> matchKnnGuided(const DeviceBuffer<Half>& des, int num_des,
+                                                const DeviceBuffer<Half>& src, int num_src, const MatchGate& gate,
+                                                int k);
+std::vector<std::vector<DMatch>> matchKnnEpipolar(const DeviceBuffer<Half>& des, int num_des,
+                                                  const DeviceBuffer<Half>& src, int num_src, const EpipolarGate& gate,
+                                                  int k);
+std::vector<DMatch> matchKnnListGuided(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                       int num_src, const MatchGate& gate, int k, float max_distance = 0.f);
+std::vector<DMatch> matchKnnListEpipolar(const DeviceBuffer<Half>& des, int num_des, const DeviceBuffer<Half>& src,
+                                         int num_src, const EpipolarGate& gate, int k, float max_distance = 0.f);
+
+// The device forms, enqueued on a stream (sift_hip_match_knn_guided_batched and
+// its kin): outputs laid out as matchKnnBatchedDevice's / matchKnnListBatchedDevice's,
+// strides, radius, geometry and max_error as matchListEpipolarBatchedDevice's.
+// A pair whose geometry record is not usable gets -1 / FLT_MAX entries and an
+// empty list.
+void matchKnnGuidedBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                 int src_stride, float radius, int k, int* idx, float* d2, void* stream = nullptr);
+void matchKnnEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                   int src_stride, float radius, const void* geometry, int geometry_stride_bytes,
+                                   float max_error, int k, int* idx, float* d2, void* stream = nullptr);
+void matchKnnListGuidedBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                     int src_stride, float radius, int k, float max_distance, DMatch* out, int* counts,
+                                     void* stream = nullptr);
+void matchKnnListEpipolarBatchedDevice(BatchMatcher& matcher, const std::vector<GuidedPair>& pairs, int des_stride,
+                                       int src_stride, float radius, const void* geometry, int geometry_stride_bytes,
+                                       float max_error, int k, float max_distance, DMatch* out, int* counts,
+                                       void* stream = nullptr);
+
 }  // namespace sift_cuda

@@ -746,7 +746,10 @@ int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* query, int nq
  * be.  A matcher that never makes a k-NN call keeps its footprint.  Calls on
  * one matcher must be ordered, as for sift_hip_match_*.
  *
- * Gated forms (the window and the epipolar gate) of k-NN are not provided. */
+ * k-NN inside the window and the epipolar gate: the section "Gated k nearest
+ * neighbours" after the batched gated calls below.  Gated k-NN forms on ready
+ * code sets (a _codes_batched family over all-gathered codes) are not
+ * provided. */
 #define SIFT_HIP_KNN_MAX 8
 
 /* One pair.  idx / d2: device, nq * k entries; either may be NULL.  Two
@@ -789,7 +792,8 @@ int sift_hip_match_knn_list_host(sift_hip_matcher_t m, const uint16_t* query, in
                                  int k, float max_distance, sift_hip_dmatch* out_host, int cap, int* count);
 
 /* Train splits a k-NN call of this shape launches with on a matcher whose
- * scratch holds them (host-only, for tests and tools). */
+ * scratch holds them (host-only, for tests and tools).  The gated k-NN calls
+ * take the same launch shape and splits: this describes them too. */
 int sift_hip_match_knn_plan(int nq, int nt, int pairs, int k, int* splits);
 
 /* --- Guided matching: top-2 and match lists inside a search window ----------
@@ -1028,6 +1032,122 @@ int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_
                                                int geometry_stride_bytes, float max_error,
                                                const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
                                                void* stream);
+
+/* --- Gated k nearest neighbours: k-NN inside the window and the epipolar gate ---
+ *
+ * cv::DescriptorMatcher::knnMatch(query, train, k, mask).  On repetitive
+ * structure the band around an epipolar line, or a window on a facade, still
+ * holds several twins of the right match: the rematch under a verified F or H
+ * keeps the k best candidates inside the gate for a second verify pass, for
+ * voting or for a multi-view consistency test.  As with the top-2 gates, the k
+ * nearest rows inside a gate are not the global k nearest, so this cannot be
+ * filtered out of sift_hip_match_knn_device's output; here the gate is a
+ * per-key predicate in the matcher's K-entry fold.
+ *
+ * The rule.  For a pair (Q: nq rows, T: nt rows), 1 <= k <= SIFT_HIP_KNN_MAX
+ * and a gate, cand(i) is the set of train rows the gate admits for query i: the
+ * window predicate of sift_hip_match_gate, or the epipolar predicate of
+ * sift_hip_match_epipolar_gate, both unchanged (float32, the stated order of
+ * operations, nothing fused, inclusive compares, a NaN is a candidate of
+ * nothing).
+ *   The table.  Row i of idx[nq][k] / d2[nq][k] holds the min(k, |cand(i)|)
+ *   rows of cand(i) of smallest squared L2 distance to query i, in ascending
+ *   (d2, train index) order -- a tie at any rank goes to the lower train index
+ *   -- and -1 / FLT_MAX in the remaining entries.  Distances follow the ungated
+ *   k-NN rule: exact integers as float32 on integer sets, the general-path
+ *   contract otherwise.
+ *   Consequences.  radius = +inf under the window gate gives
+ *   sift_hip_match_knn_device's bytes, and so does the epipolar gate with
+ *   max_error = 1e30 and no window.  k = 2 gives the idx2 / d2 bytes of
+ *   sift_hip_match_guided_device / sift_hip_match_epipolar_device.  Column j of
+ *   a call with k equals column j of a call with any k' > j.  The bytes do not
+ *   depend on the launch plan, on the kernel instantiation that served the
+ *   call, on max_pairs, or on whether the sets came as detector buffers
+ *   (sidecar codes) or fp16 rows.
+ *   The list is the k-NN list rule above (max_distance, (queryIdx, rank) order,
+ *   slots from prefix sums) applied to the gated table.
+ *   Batched.  Pair p gives, byte for byte, the single-pair call's table or list
+ *   under {pair p's positions, the call's strides, radius and max_error, F =
+ *   its nine floats read from device memory at geometry + p *
+ *   geometry_stride_bytes}; the geometry follows sift_hip_match_epipolar_batched
+ *   (stride >= 36 and a multiple of 4; 52 takes verifier records as they lie).
+ *   An unusable record (a value that is not finite, or nine zeros) gives its
+ *   pair no candidates: every entry -1 / FLT_MAX and a list count of 0.  Table
+ *   rows lie at sum_{r<p} nq[r], list records at k * sum_{r<p} nq[r] with
+ *   imgIdx = p; rows of `out` past a pair's count are not written.
+ * k-NN has no reverse direction: there is no cross check and no transposed F.
+ * Gated k-NN on ready code sets (_codes_batched) is not provided.
+ *
+ * Routes.  A single-pair call on two detector buffers with fresh sidecars
+ * matches their codes directly (no prep launch), subject to
+ * sift_hip_matcher_set_sidecars / sift_hip_descriptors_written as
+ * sift_hip_match_knn_device is; any other pair is converted first.  The
+ * batched forms always convert (distinct sets once).  A set with non-integer
+ * values sends its pairs down the gated general path.  The single-pair epipolar
+ * call checks F on the host and passes it as a kernel argument (no copy to the
+ * device).  A launch holds at most 32 pairs; a call of more is several launches
+ * ordered on the stream.  Scratch, splits and the first call's allocation are
+ * those of the k-NN calls above (the first k-NN call of either kind allocates,
+ * not under stream capture); every call restores the counters it used.
+ *
+ * Refusals (SIFT_HIP_ERR_INVALID, nothing launched, nothing written).  First
+ * what needs no matcher: k outside 1..SIFT_HIP_KNN_MAX; for the list calls a
+ * NaN max_distance; a null gate; a stride < 2; a radius that is not > 0; a
+ * max_error that is not > 0 or not finite; an unusable host F; a null geometry;
+ * a geometry stride below 36 or not a multiple of 4.  Then: a null matcher, a
+ * size over the matcher's limits, P outside 1..max_pairs or a null pair array,
+ * a null descriptor or position pointer of a non-empty set, the list calls'
+ * null out or count.  nq == 0: nothing is written (a list's count is 0).
+ * nt == 0: every entry is -1 / FLT_MAX and the count is 0.
+ * sift_amd.cv.guided_knn / epipolar_knn / mask_knn are the rule in numpy. */
+int sift_hip_match_knn_guided_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                     const sift_hip_match_gate* gate, int k, int* idx, float* d2, void* stream);
+int sift_hip_match_knn_epipolar_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                       int nt, const sift_hip_match_epipolar_gate* gate, int k, int* idx, float* d2,
+                                       void* stream);
+int sift_hip_match_knn_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                      const uint16_t* const* train, const int* nt,
+                                      const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                      float radius, int k, int* idx, float* d2, void* stream);
+int sift_hip_match_knn_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                        const uint16_t* const* train, const int* nt,
+                                        const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                        float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                        int k, int* idx, float* d2, void* stream);
+
+/* The lists: out / count(s) as sift_hip_match_knn_list_device / _batched. */
+int sift_hip_match_knn_list_guided_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                          int nt, const sift_hip_match_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out, int* count, void* stream);
+int sift_hip_match_knn_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                            int nt, const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                            sift_hip_dmatch* out, int* count, void* stream);
+int sift_hip_match_knn_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                           const uint16_t* const* train, const int* nt,
+                                           const sift_hip_match_positions* positions, int query_stride,
+                                           int train_stride, float radius, int k, float max_distance,
+                                           sift_hip_dmatch* out, int* counts, void* stream);
+int sift_hip_match_knn_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* query, const int* nq,
+                                             const uint16_t* const* train, const int* nt,
+                                             const sift_hip_match_positions* positions, int query_stride,
+                                             int train_stride, float radius, const void* geometry,
+                                             int geometry_stride_bytes, float max_error, int k, float max_distance,
+                                             sift_hip_dmatch* out, int* counts, void* stream);
+
+/* Synchronous, one pair, to host memory: the table (nq * k entries each; either
+ * may be NULL) as sift_hip_match_knn_host, the list as
+ * sift_hip_match_knn_list_host (min(count, cap) records, *count the full
+ * count). */
+int sift_hip_match_knn_guided_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                   const sift_hip_match_gate* gate, int k, int* idx_host, float* d2_host);
+int sift_hip_match_knn_epipolar_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train, int nt,
+                                     const sift_hip_match_epipolar_gate* gate, int k, int* idx_host, float* d2_host);
+int sift_hip_match_knn_list_guided_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                        int nt, const sift_hip_match_gate* gate, int k, float max_distance,
+                                        sift_hip_dmatch* out_host, int cap, int* count);
+int sift_hip_match_knn_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* query, int nq, const uint16_t* train,
+                                          int nt, const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out_host, int cap, int* count);
 
 /* The launch plan a match call of this shape gets: train splits S per query
  * block (S > 1: split workgroups merge their top-2 through the scratch's

@@ -3,13 +3,16 @@
 
     hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o a.s   (old tree)
     hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o b.s   (new tree)
-    tools/kernel_isa_diff.py a.s b.s [--json out.json] [--count v_mfma ds_read ...]
+    tools/kernel_isa_diff.py a.s b.s [--json out.json] [--count v_mfma ds_read ...] [--rename OLD=NEW ...]
 
 Per kernel (symbol .. function-end label) the text is compared after the local
 label numbers (.LBB<n>_, BB<n>_ in comments) are normalised; the resources are
 read from the compiler's own summary after the function.  A kernel of one build
 only is listed with its resources.  Exit status 1 when a kernel's text differs
-or a kernel is in one build only.
+or a kernel is in one build only.  --rename OLD=NEW compares kernel OLD of the
+old build with kernel NEW of the new one (a kernel whose template parameters or
+argument types were renamed): OLD is replaced by NEW in the old build's name and
+text first, and the report keeps the old name under "renamed_from".
 """
 import argparse
 import json
@@ -55,8 +58,17 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--count", nargs="*", default=["v_mfma", "ds_read", "global_load_lds", "v_med3", "v_max3"],
                     help="opcode prefixes counted for kernels whose text differs")
+    ap.add_argument("--rename", nargs="*", default=[], metavar="OLD=NEW",
+                    help="kernel OLD of the old build is kernel NEW of the new one")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
+    renamed = {}
+    for pair in a.rename:
+        o, n = pair.split("=", 1)
+        if o in old:
+            d = old.pop(o)
+            d["text"] = [line.replace(o, n) for line in d["text"]]
+            old[n], renamed[n] = d, o
     rep, same = {}, True
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
@@ -75,6 +87,8 @@ def main():
             e[side]["instructions"] = len(ops)
             if not e["equal"]:
                 e[side]["counts"] = {p: sum(o.startswith(p) for o in ops) for p in a.count}
+        if k in renamed:
+            e["renamed_from"] = renamed[k]
         rep[k] = e
         same &= e["equal"]
         print(("equal   " if e["equal"] else "DIFFERS ") + k, e["old"], "->", e["new"])
