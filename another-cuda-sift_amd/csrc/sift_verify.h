@@ -3,6 +3,7 @@
 // include/sift_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "sift_match.h"
@@ -114,6 +115,39 @@ template <class List>
 void launch_refit_accept(VerifyModel model, const List& list, const float4* pts, const RefitCandidate* cand, float e2,
                          VerifyResult* result, uint8_t* mask, MatchRecord* out, int* out_count, int* accepted,
                          bool first_round, hipStream_t s);
+
+// The relative pose from a verified fundamental matrix (pose.hip; sift_hip_recover_pose_*, the rule is in
+// include/sift_hip.h).  Two launches on the gathered list:
+// k_pose_decompose: one wave per pair.  E = Kt^T F Kq of the pair's record under its two cameras, the eigenvectors of
+//   E^T E by the refit's Jacobi routine, and the two rotations and the translation of the four candidates into the
+//   verifier's scratch record cand[p] (usable = 0: an empty or unusable record, or an E of rank <= 1).
+// k_pose_select: one workgroup per pair.  The fit records' depths under the four candidates, their counts, the winner
+//   into pose[p]; then mask_out (cap bytes, may be the mask itself), the points (3 floats per row j < n) and the
+//   in-front records in input order (out, out_count), each nullable.
+struct PoseResult {  // sift_hip_pose_result's layout
+    float R[9], t[3];
+    int in_front, with_parallax, counts[4], candidate, fit;
+};
+static_assert(sizeof(PoseResult) == 80, "sift_hip_pose_result layout");
+struct PoseCamera {
+    float fx, fy, cx, cy;
+};
+struct PoseCameras {  // by value, as VerifyBatch is: pair p's query and train camera
+    PoseCamera q[kVerifyMaxPairs], t[kVerifyMaxPairs];
+};
+struct PoseCandidates {  // k_pose_select reads the 29 leading doubles as an array
+    double R[2][9];  // R1, R2 row-major; the candidates are (R1, t), (R2, t), (R1, -t), (R2, -t)
+    double t[3];
+    double kq[4], kt[4];  // the cameras' fx, fy, cx, cy
+    int usable, pad;
+};
+static_assert(offsetof(PoseCandidates, usable) == 29 * sizeof(double), "k_pose_select's view of the record");
+void launch_pose_decompose(const PoseCameras& cams, int P, const VerifyResult* result, PoseCandidates* cand,
+                           hipStream_t s);
+template <class List>
+void launch_pose_select(const List& list, const float4* pts, const uint8_t* mask, const PoseCandidates* cand,
+                        float max_depth, float max_cos_parallax, PoseResult* pose, uint8_t* mask_out, float* points,
+                        MatchRecord* out, int* out_count, hipStream_t s);
 
 // k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
 // `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.

@@ -27,13 +27,17 @@ struct sift_hip_verifier {
     uint8_t* dMask = nullptr;
     RefitCandidate* dCand = nullptr;  // the refit's candidate model per pair (sift_hip_refine_*), maxP records
     int* dRefineInts = nullptr;       // sift_hip_refine_*_host: maxP out counts, then maxP accepted rounds
+    PoseCandidates* dPoseCand = nullptr;  // the pose calls' candidates per pair (sift_hip_recover_pose_*), maxP records
+    PoseResult* dPose = nullptr;          // sift_hip_recover_pose_*_host: maxP pose records and maxM x 3 point floats
+    float* dPoints = nullptr;
     int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
     int lastModel = 0;           // its VerifyModel, 0: none
     bool lastBatch = false;      // it was a batched call (the getters read one pair's scratch layout)
     ~sift_hip_verifier() {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
-                        (void*)dOut, (void*)dMask, (void*)dCand, (void*)dRefineInts})
+                        (void*)dOut, (void*)dMask, (void*)dCand, (void*)dRefineInts, (void*)dPoseCand, (void*)dPose,
+                        (void*)dPoints})
             if (p) (void)hipFree(p);
     }
 };
@@ -42,6 +46,10 @@ static_assert(sizeof(sift_hip_verify_result) == sizeof(VerifyResult), "the resul
 static_assert(sizeof(sift_hip_homography_result) == sizeof(VerifyResult) &&
                   offsetof(sift_hip_homography_result, inliers) == offsetof(VerifyResult, inliers),
               "both models' result records share the kernel's layout");
+static_assert(sizeof(sift_hip_pose_result) == sizeof(PoseResult) &&
+                  offsetof(sift_hip_pose_result, candidate) == offsetof(PoseResult, candidate),
+              "the pose record is written by the kernel");
+static_assert(sizeof(sift_hip_camera) == sizeof(PoseCamera), "the cameras go to the kernel as they are");
 
 namespace {
 
@@ -50,7 +58,7 @@ constexpr int kRefineMaxRounds = 8;
 // One call of the verifier as every entry point hands it down: the operation, the list(s) and the outputs.  A
 // single-pair entry point describes its list as a one-pair table (row0 = 0) and sets `single`: the same rules and the
 // same host path then serve it, and only the launches differ -- they take the 72-byte VerifyInput, not the batch table.
-enum class Op { Verify, Score, Refine };
+enum class Op { Verify, Score, Refine, Pose };
 struct Call {
     Op op;
     VerifyModel model;
@@ -70,6 +78,12 @@ struct Call {
     int* accepted;
     const float* models;  // score: the K models to count under, and their counts
     int* scores;
+    const sift_hip_camera* cams_q;  // pose: P cameras per side (host memory), the thresholds, the P pose records and
+    const sift_hip_camera* cams_t;  // the optional mask and points; `result` and `mask` are the inputs
+    const sift_hip_pose_params* pose_params;
+    void* pose;
+    uint8_t* mask_out;
+    float* points;
     void* stream;
 };
 
@@ -85,13 +99,13 @@ Call make_call(Op op, VerifyModel model, bool host, const sift_hip_dmatch* match
 // refusal.  On success `b` is the pair table the kernels take.
 int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
     const auto refuse = [](const std::string& msg) { return fail(SIFT_HIP_ERR_INVALID, msg); };
-    const bool refine = c.op == Op::Refine;
+    const bool refine = c.op == Op::Refine, pose = c.op == Op::Pose;
     if (!v) return refuse("null verifier");
     if (!c.pairs) return refuse("verify: null pairs");
     if (c.op == Op::Score) {
         if (!c.models || !c.scores)
             return refuse(c.model == VerifyModel::Homography ? "verify: null H or counts" : "verify: null F or counts");
-    } else if (!c.params || !c.result) {
+    } else if (!pose && (!c.params || !c.result)) {
         return refuse(refine && c.single ? "refine: null result" : "verify: null params or result");
     }
     if (c.P < 1 || c.P > kVerifyMaxPairs) return refuse("verify: pairs outside 1.." + std::to_string(kVerifyMaxPairs));
@@ -109,14 +123,29 @@ int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
         max_cap = std::max(max_cap, e.cap);
     }
     if (rows > 0 && !c.matches) return refuse("verify: null matches");
-    if (!(c.params->max_error > 0.f) || !std::isfinite(c.params->max_error))
+    if (pose) {  // the pose calls' own rules stand where max_error stands for the others
+        if (!c.cams_q || !c.cams_t) return refuse("pose: null camera pointer");
+        for (int p = 0; p < c.P; p++)
+            for (const sift_hip_camera* k : {c.cams_q + p, c.cams_t + p}) {
+                const auto at = [&] { return c.single ? std::string() : " (pair " + std::to_string(p) + ")"; };
+                if (!(k->fx > 0.f) || !(k->fy > 0.f) || !std::isfinite(k->fx) || !std::isfinite(k->fy))
+                    return refuse("pose: fx and fy must be > 0 and finite" + at());
+                if (!std::isfinite(k->cx) || !std::isfinite(k->cy)) return refuse("pose: cx and cy must be finite" + at());
+            }
+        if (!c.pose_params || !c.result || !c.pose) return refuse("pose: null params or result");
+        if (!(c.pose_params->max_depth > 0.f)) return refuse("pose: max_depth must be > 0");
+        if (!(c.pose_params->max_cos_parallax >= -1.f && c.pose_params->max_cos_parallax <= 1.f))
+            return refuse("pose: max_cos_parallax must lie in [-1, 1]");
+        if (rows > 0 && !c.mask) return refuse("pose: null mask (the mask is the fit set)");
+    } else if (!(c.params->max_error > 0.f) || !std::isfinite(c.params->max_error)) {
         return refuse("verify: max_error must be > 0 and finite");
+    }
     const uintptr_t ob = (uintptr_t)c.out, mb = (uintptr_t)c.matches, bytes = sizeof(sift_hip_dmatch) * (size_t)rows;
     if (!c.host && c.out && rows > 0 && ob < mb + bytes && mb < ob + bytes) return refuse("verify: out aliases matches");
     if (refine && rows > 0 && !c.mask) return refuse("refine: null mask (the mask is the fit set)");
     if (refine && (c.rounds < 1 || c.rounds > kRefineMaxRounds))
         return refuse("refine: rounds must lie in 1.." + std::to_string(kRefineMaxRounds));
-    const int K = c.params->hypotheses;
+    const int K = pose ? 1 : c.params->hypotheses;  // a pose call draws nothing
     if (K < 1 || K > kVerifyMaxHypotheses || K > v->maxK) return refuse("verify: hypotheses outside 1..max_hypotheses");
     if (c.P > v->maxP) return refuse("verify: more pairs than the verifier's max_pairs");
     if (rows > v->maxM)
@@ -138,6 +167,9 @@ struct Outputs {
     uint8_t* mask;
     int* accepted;
     hipStream_t stream;
+    PoseResult* pose = nullptr;  // the pose calls' outputs; result and mask are then read only
+    uint8_t* mask_out = nullptr;
+    float* points = nullptr;
 };
 
 // The runners, one per operation, over the list type (VerifyInput or VerifyBatch): one launch per step for all the
@@ -183,10 +215,29 @@ int refine_on(sift_hip_verifier* v, const Call& c, const List& list, const Outpu
     return SIFT_HIP_OK;
 }
 
+// The gather, the candidates of every pair's record under its cameras, and the counts, winner and outputs.  The
+// cameras travel by value; the verifier's hypothesis scratch is not touched.
+template <class List>
+int pose_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
+    PoseCameras cams{};
+    for (int p = 0; p < c.P; p++) {
+        cams.q[p] = PoseCamera{c.cams_q[p].fx, c.cams_q[p].fy, c.cams_q[p].cx, c.cams_q[p].cy};
+        cams.t[p] = PoseCamera{c.cams_t[p].fx, c.cams_t[p].fy, c.cams_t[p].cx, c.cams_t[p].cy};
+    }
+    launch_verify_gather(list, v->dPts, o.stream);
+    launch_pose_decompose(cams, c.P, o.result, v->dPoseCand, o.stream);
+    launch_pose_select(list, v->dPts, o.mask, v->dPoseCand, c.pose_params->max_depth, c.pose_params->max_cos_parallax,
+                       o.pose, o.mask_out, o.points, o.out, o.out_counts, o.stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
 template <class List>
 int enqueue(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
-    return c.op == Op::Verify ? verify_on(v, c, list, o) : c.op == Op::Score ? score_on(v, c, list, o)
-                                                                             : refine_on(v, c, list, o);
+    return c.op == Op::Verify  ? verify_on(v, c, list, o)
+           : c.op == Op::Score ? score_on(v, c, list, o)
+           : c.op == Op::Pose  ? pose_on(v, c, list, o)
+                               : refine_on(v, c, list, o);
 }
 
 // The host forms' copy-back, one loop over the pair table: the records, each pair's first min(n, cap) rows at its row0
@@ -227,24 +278,51 @@ int refine_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch&
     return SIFT_HIP_OK;
 }
 
+// The pose calls' host form: the records and masks go up as for a refine call; the mask comes back as mask_out (on
+// the device it is written over the uploaded mask, which the call allows), the points pair by pair up to each n.
+int pose_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b) {
+    int n[kVerifyMaxPairs];
+    HIPCHK(hipMemcpy(n, v->dRefineInts, sizeof(int) * (size_t)b.P, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c.pose, v->dPose, sizeof(PoseResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+    if (c.mask_out && b.rows > 0) HIPCHK(hipMemcpy(c.mask_out, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
+    if (c.points && b.rows > 0) {
+        int counts[kVerifyMaxPairs];
+        if (b.counts) HIPCHK(hipMemcpy(counts, b.counts, sizeof(int) * (size_t)b.P, hipMemcpyDeviceToHost));
+        for (int p = 0; p < b.P; p++) {
+            const int cap = b.pair[p].cap, rows = b.counts ? std::min(std::max(counts[p], 0), cap) : cap;
+            if (rows > 0)
+                HIPCHK(hipMemcpy(c.points + 3 * (size_t)b.pair[p].row0, v->dPoints + 3 * (size_t)b.pair[p].row0,
+                                 sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost));
+        }
+    }
+    if (int rc = copy_rows(v, c, b, n)) return rc;
+    if (c.out_counts) std::copy(n, n + b.P, c.out_counts);
+    return SIFT_HIP_OK;
+}
+
 // Every list-taking entry point: the rules, for a host form the uploads, the launches, for a host form the copy-back.
 int run(sift_hip_verifier* v, const Call& c) {
     VerifyBatch b;
     if (int rc = check(v, c, b)) return rc;
-    const bool refine = c.op == Op::Refine;
+    const bool pose = c.op == Op::Pose, refine = c.op == Op::Refine || pose;  // both read a record and a mask
     HIPCHK(hipSetDevice(v->device));
     if (c.host && refine)
         if (int rc = refine_from_host(v, c, b)) return rc;
-    const Outputs o = c.host ? Outputs{v->dResult, v->dOut, refine ? v->dRefineInts : nullptr, v->dMask,
-                                       refine ? v->dRefineInts + v->maxP : nullptr, nullptr}
-                             : Outputs{static_cast<VerifyResult*>(c.result), reinterpret_cast<MatchRecord*>(c.out),
-                                       c.out_counts, c.mask, c.accepted, (hipStream_t)c.stream};
+    Outputs o = c.host ? Outputs{v->dResult, v->dOut, refine ? v->dRefineInts : nullptr, v->dMask,
+                                 refine ? v->dRefineInts + v->maxP : nullptr, nullptr}
+                       : Outputs{static_cast<VerifyResult*>(c.result), reinterpret_cast<MatchRecord*>(c.out), c.out_counts,
+                                 c.mask, c.accepted, (hipStream_t)c.stream};
+    if (pose) {  // a host form writes the in-front mask over the uploaded mask, which the call allows
+        o.pose = c.host ? v->dPose : static_cast<PoseResult*>(c.pose);
+        o.mask_out = !c.host ? c.mask_out : c.mask_out ? v->dMask : nullptr;
+        o.points = !c.host ? c.points : c.points ? v->dPoints : nullptr;
+    }
     const VerifyBatchPair& e = b.pair[0];
     const int rc = c.single ? enqueue(v, c, VerifyInput{b.matches, b.counts, e.cap, e.qxy, e.txy, b.qstride, b.tstride,
                                                         e.nq, e.nt}, o)
                             : enqueue(v, c, b, o);
     if (rc || !c.host) return rc;
-    return refine ? refine_to_host(v, c, b) : verify_to_host(v, c, b);
+    return pose ? pose_to_host(v, c, b) : refine ? refine_to_host(v, c, b) : verify_to_host(v, c, b);
 }
 
 // What the last verify call of `model` drew (m indices per hypothesis), solved and counted.
@@ -277,6 +355,12 @@ bool rows_overlap(const float* xy, int stride, const float* out_xy, int out_stri
 }  // namespace
 
 extern "C" {
+
+void sift_hip_default_pose_params(sift_hip_pose_params* p) {
+    if (!p) return;
+    p->max_depth = 50.f;
+    p->max_cos_parallax = 0.99998f;
+}
 
 void sift_hip_default_verify_params(sift_hip_verify_params* p) {
     if (!p) return;
@@ -316,6 +400,9 @@ int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypoth
         hipMalloc((void**)&v->dMask, M) != hipSuccess ||
         hipMalloc((void**)&v->dCand, sizeof(RefitCandidate) * (size_t)max_pairs) != hipSuccess ||
         hipMalloc((void**)&v->dRefineInts, sizeof(int) * 2 * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dPoseCand, sizeof(PoseCandidates) * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dPose, sizeof(PoseResult) * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dPoints, sizeof(float) * 3 * M) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         delete v;
         return fail(SIFT_HIP_ERR_NOMEM, "verifier allocation failed");
@@ -382,6 +469,38 @@ SIFT_VERIFIER_ENTRIES(homography, VerifyModel::Homography, sift_hip_homography_r
 SIFT_VERIFIER_ENTRIES(fundamental_batched, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_BATCH, SIFT_BATCH_LIST)
 SIFT_VERIFIER_ENTRIES(homography_batched, VerifyModel::Homography, sift_hip_homography_result, SIFT_BATCH, SIFT_BATCH_LIST)
 #undef SIFT_VERIFIER_ENTRIES
+
+// The four pose entry points: {one pair, batch} x {device, host}.
+#define SIFT_POSE_ENTRIES(name, LIST_ARGS, LIST)                                                                        \
+    int sift_hip_recover_pose##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,          \
+                                             const sift_hip_verify_result* result, const uint8_t* mask,                 \
+                                             const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,        \
+                                             const sift_hip_pose_params* params, sift_hip_pose_result* pose,            \
+                                             uint8_t* mask_out, float* points, sift_hip_dmatch* out, int* out_count,    \
+                                             void* stream) {                                                            \
+        Call c = make_call(Op::Pose, VerifyModel::Fundamental, false, matches, query_stride, train_stride);             \
+        LIST(c);                                                                                                        \
+        c.result = const_cast<sift_hip_verify_result*>(result), c.mask = const_cast<uint8_t*>(mask);                    \
+        c.cams_q = cam_query, c.cams_t = cam_train, c.pose_params = params, c.pose = pose, c.mask_out = mask_out;       \
+        c.points = points, c.out = out, c.out_counts = out_count, c.stream = stream;                                    \
+        return run(v, c);                                                                                               \
+    }                                                                                                                   \
+    int sift_hip_recover_pose##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,            \
+                                           const sift_hip_verify_result* result_host, const uint8_t* mask_host,         \
+                                           const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,          \
+                                           const sift_hip_pose_params* params, sift_hip_pose_result* pose_host,         \
+                                           uint8_t* mask_out_host, float* points_host, sift_hip_dmatch* out_host,       \
+                                           int* out_count_host) {                                                       \
+        Call c = make_call(Op::Pose, VerifyModel::Fundamental, true, matches, query_stride, train_stride);              \
+        LIST(c);                                                                                                        \
+        c.result = const_cast<sift_hip_verify_result*>(result_host), c.mask = const_cast<uint8_t*>(mask_host);          \
+        c.cams_q = cam_query, c.cams_t = cam_train, c.pose_params = params, c.pose = pose_host;                         \
+        c.mask_out = mask_out_host, c.points = points_host, c.out = out_host, c.out_counts = out_count_host;            \
+        return run(v, c);                                                                                               \
+    }
+SIFT_POSE_ENTRIES(, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
+SIFT_POSE_ENTRIES(_batched, SIFT_BATCH, SIFT_BATCH_LIST)
+#undef SIFT_POSE_ENTRIES
 #undef SIFT_BATCH_LIST
 #undef SIFT_BATCH
 

@@ -4,6 +4,8 @@
 #include "sift_cuda/Verify.hh"
 
 #include <cstddef>
+#include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 
@@ -26,6 +28,13 @@ static_assert(sizeof(VerifyPair) == sizeof(sift_hip_verify_pair) &&
                   offsetof(VerifyPair, nt) == offsetof(sift_hip_verify_pair, nt) &&
                   offsetof(VerifyPair, cap) == offsetof(sift_hip_verify_pair, cap),
               "sift_cuda::VerifyPair is sift_hip_verify_pair");
+
+static_assert(sizeof(PoseResult) == sizeof(sift_hip_pose_result) &&
+                  offsetof(PoseResult, counts) == offsetof(sift_hip_pose_result, counts) &&
+                  offsetof(PoseResult, candidate) == offsetof(sift_hip_pose_result, candidate),
+              "sift_cuda::PoseResult is sift_hip_pose_result");
+static_assert(sizeof(Camera) == sizeof(sift_hip_camera) && offsetof(Camera, cx) == offsetof(sift_hip_camera, cx),
+              "sift_cuda::Camera is sift_hip_camera");
 
 void check_throw(int rc, const char* what) {
     if (rc == SIFT_HIP_OK) return;
@@ -206,6 +215,42 @@ std::vector<int> refineBatchedHostT(sift_hip_verifier* h, const char* what, cons
     return accepted;
 }
 
+const sift_hip_camera* abi(const Camera* c) { return reinterpret_cast<const sift_hip_camera*>(c); }
+sift_hip_pose_params toAbi(const PoseParams& p) { return sift_hip_pose_params{p.max_depth, p.max_cos_parallax}; }
+auto poseDevice(const OnePair&) { return sift_hip_recover_pose_device; }
+auto poseDevice(const Batch&) { return sift_hip_recover_pose_batched_device; }
+auto poseHost(const OnePair&) { return sift_hip_recover_pose_host; }
+auto poseHost(const Batch&) { return sift_hip_recover_pose_batched_host; }
+
+// The pose calls' host form over either list: `rows` rows of mask, points and records, `P` records.
+template <class List>
+std::vector<RelativePose> recoverPoseHostT(sift_hip_verifier* h, const char* what, const List& l, size_t rows,
+                                           const std::vector<size_t>& caps, const sift_hip_verify_result* results,
+                                           const std::vector<uint8_t>& mask, const Camera* cq, const Camera* ct,
+                                           const PoseParams& params) {
+    const sift_hip_pose_params p = toAbi(params);
+    const size_t P = caps.size();
+    std::vector<sift_hip_pose_result> poses(P ? P : 1);
+    std::vector<uint8_t> front(rows);
+    std::vector<float> points(3 * rows, std::numeric_limits<float>::quiet_NaN());
+    std::vector<DMatch> list(rows);
+    std::vector<int> n(P ? P : 1);
+    check_throw(abiCall(poseHost(l), h, l, results, mask.empty() ? nullptr : mask.data(), abi(cq), abi(ct), &p,
+                        poses.data(), front.data(), points.data(), abi(list.data()), n.data()),
+                what);
+    std::vector<RelativePose> out(P);
+    size_t row0 = 0;
+    for (size_t i = 0; i < P; i++) {
+        static_assert(sizeof(PoseResult) == sizeof(sift_hip_pose_result), "copied as bytes");
+        std::memcpy(&out[i].pose, &poses[i], sizeof(PoseResult));
+        out[i].mask.assign(front.begin() + row0, front.begin() + row0 + caps[i]);
+        out[i].points.assign(points.begin() + 3 * row0, points.begin() + 3 * (row0 + caps[i]));
+        out[i].inliers.assign(list.begin() + row0, list.begin() + row0 + (size_t)n[i]);
+        row0 += caps[i];
+    }
+    return out;
+}
+
 // The convenience call on a host list: a verifier sized to it (the argument rules come first, they need no device
 // memory), the list uploaded, the host form, and with refit > 0 that many refit rounds on its record and mask.
 template <class M>
@@ -292,6 +337,60 @@ Verifier::~Verifier() { (void)sift_hip_verifier_destroy(m_handle); }
 SIFT_VERIFIER_METHODS(Fundamental, )
 SIFT_VERIFIER_METHODS(Planar, Homography)
 #undef SIFT_VERIFIER_METHODS
+
+void Verifier::recoverPoseDevice(ONE_PAIR_ARGS, const VerifyResult* result, const uint8_t* mask, const Camera& cam_query,
+                                 const Camera& cam_train, const PoseParams& params, PoseResult* pose, uint8_t* mask_out,
+                                 float* points, DMatch* out, int* out_count, void* stream) {
+    const sift_hip_pose_params p = toAbi(params);
+    const OnePair l = ONE_PAIR;
+    check_throw(abiCall(poseDevice(l), m_handle, l, reinterpret_cast<const sift_hip_verify_result*>(result), mask,
+                        abi(&cam_query), abi(&cam_train), &p, reinterpret_cast<sift_hip_pose_result*>(pose), mask_out,
+                        points, abi(out), out_count, stream),
+                "Verifier::recoverPoseDevice");
+}
+
+void Verifier::recoverPoseBatchedDevice(BATCH_ARGS, const VerifyResult* results, const uint8_t* mask,
+                                        const std::vector<Camera>& cams_query, const std::vector<Camera>& cams_train,
+                                        const PoseParams& params, PoseResult* poses, uint8_t* mask_out, float* points,
+                                        DMatch* out, int* out_counts, void* stream) {
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument("Verifier::recoverPoseBatchedDevice: one camera per pair and side");
+    const sift_hip_pose_params p = toAbi(params);
+    const Batch l = BATCH;
+    check_throw(abiCall(poseDevice(l), m_handle, l, reinterpret_cast<const sift_hip_verify_result*>(results), mask,
+                        abi(cams_query.data()), abi(cams_train.data()), &p, reinterpret_cast<sift_hip_pose_result*>(poses),
+                        mask_out, points, abi(out), out_counts, stream),
+                "Verifier::recoverPoseBatchedDevice");
+}
+
+RelativePose Verifier::recoverPoseHost(ONE_PAIR_ARGS, const VerifyResult& result, const std::vector<uint8_t>& mask,
+                                       const Camera& cam_query, const Camera& cam_train, const PoseParams& params) {
+    const char* what = "Verifier::recoverPoseHost";
+    const bool sized = cap >= 0 && cap <= 65536;
+    if (sized) check_mask(mask, (size_t)cap, what);
+    const size_t rows = sized ? (size_t)cap : 0;
+    return recoverPoseHostT(m_handle, what, ONE_PAIR, rows, {rows},
+                            reinterpret_cast<const sift_hip_verify_result*>(&result), mask, &cam_query, &cam_train,
+                            params)[0];
+}
+
+std::vector<RelativePose> Verifier::recoverPoseBatchedHost(BATCH_ARGS, const std::vector<VerifyResult>& results,
+                                                           const std::vector<uint8_t>& mask,
+                                                           const std::vector<Camera>& cams_query,
+                                                           const std::vector<Camera>& cams_train,
+                                                           const PoseParams& params) {
+    const char* what = "Verifier::recoverPoseBatchedHost";
+    if (results.size() != pairs.size()) throw std::invalid_argument(std::string(what) + ": one result record per pair");
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument(std::string(what) + ": one camera per pair and side");
+    const size_t rows = batchRows(pairs);
+    if (rows > 0) check_mask(mask, rows, what);
+    std::vector<size_t> caps;
+    for (const VerifyPair& p : pairs) caps.push_back(rows > 0 && p.cap > 0 ? (size_t)p.cap : 0);
+    return recoverPoseHostT(m_handle, what, BATCH, rows, caps,
+                            reinterpret_cast<const sift_hip_verify_result*>(results.data()), mask, cams_query.data(),
+                            cams_train.data(), params);
+}
 #undef BATCH
 #undef BATCH_ARGS
 #undef ONE_PAIR
@@ -321,6 +420,23 @@ PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float*
 PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                                 int nt, const VerifyParams& params, int query_stride, int train_stride) {
     return verifyHomography(matches, query_xy, nq, train_xy, nt, params, query_stride, train_stride, 0);
+}
+
+RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy, int nt,
+                         const float (&F)[9], const std::vector<uint8_t>& mask, const Camera& cam_query,
+                         const Camera& cam_train, const PoseParams& params, int query_stride, int train_stride) {
+    const int n = (int)matches.size();
+    if (!mask.empty() && mask.size() != matches.size())
+        throw std::invalid_argument("recoverPose: mask must hold one byte per match, or none");
+    Verifier v(n > 0 ? n : 1, 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "recoverPose");
+    VerifyResult r{};
+    for (int i = 0; i < 9; i++) r.F[i] = F[i];
+    r.matches = n;
+    return v.recoverPoseHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
+                             nt, r, mask.empty() ? std::vector<uint8_t>(matches.size(), 1) : mask, cam_query, cam_train,
+                             params);
 }
 
 void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

@@ -193,6 +193,30 @@ HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f4", (9,)), ("inliers", "<i4"), ("hy
 assert HOMOGRAPHY_RESULT_DTYPE.itemsize == ctypes.sizeof(_HomographyResult)
 
 
+class _Camera(ctypes.Structure):
+    """sift_hip_camera: a skew-free pinhole camera."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float)]
+
+
+class _PoseParams(ctypes.Structure):
+    """sift_hip_pose_params: the far bound on both depths, in baselines, and the cosine below which a record in front
+    counts as one with parallax."""
+    _fields_ = [("max_depth", ctypes.c_float), ("max_cos_parallax", ctypes.c_float)]
+
+
+POSE_RESULT_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("in_front", "<i4"), ("with_parallax", "<i4"),
+                              ("counts", "<i4", (4,)), ("candidate", "<i4"), ("fit", "<i4")])
+assert POSE_RESULT_DTYPE.itemsize == 80
+
+
+def _cameras(cams, P: int):
+    """A ctypes array of P sift_hip_camera from (fx, fy, cx, cy) rows; None when there are none."""
+    a = np.asarray(cams, np.float32).reshape(-1, 4)
+    if len(a) != P:
+        raise ValueError("one (fx, fy, cx, cy) camera per pair and side")
+    return (_Camera * max(P, 1))(*[_Camera(*[float(x) for x in r]) for r in a])
+
+
 def lib() -> ctypes.CDLL:
     """Load libsift_hip.so (once).  Fails loudly when the build is missing."""
     global _lib
@@ -374,6 +398,17 @@ def lib() -> ctypes.CDLL:
                                                           vp, vp, vp, vp]),
         "sift_hip_refine_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
                                                         vp, vp, vp]),
+        "sift_hip_default_pose_params": (None, [ctypes.POINTER(_PoseParams)]),
+        "sift_hip_recover_pose_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp, ctypes.POINTER(_Camera),
+                                             ctypes.POINTER(_Camera), ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp]),
+        "sift_hip_recover_pose_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp, ctypes.POINTER(_Camera),
+                                           ctypes.POINTER(_Camera), ctypes.POINTER(_PoseParams), vp, vp, vp, vp, ip]),
+        "sift_hip_recover_pose_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
+                                                     ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                     ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp]),
+        "sift_hip_recover_pose_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
+                                                   ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                   ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -1813,6 +1848,94 @@ class Verifier:
                                          HOMOGRAPHY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, verified, max_error,
                                          rounds, q_stride, t_stride)
 
+    # --- the relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
+    # in numpy sift_amd.cv.recover_pose).  The list, count, cap and positions are the verify call's; result(s) and mask
+    # are what it (or a refine call) wrote and are only read.  A camera is (fx, fy, cx, cy).
+
+    def recover_pose_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                            nt: int, result_ptr: int, mask_ptr: int, cam_q, cam_t, pose_ptr: int, mask_out_ptr: int = 0,
+                            points_ptr: int = 0, out_ptr: int = 0, out_count_ptr: int = 0, max_depth: float = 50.0,
+                            max_cos_parallax: float = 0.99998, q_stride: int = 3, t_stride: int = 3,
+                            stream: Optional[int] = None) -> None:
+        """Enqueue the pose of the pair (sift_hip_recover_pose_device); every pointer is device memory.  pose_ptr: a
+        POSE_RESULT_DTYPE record; mask_out_ptr (cap bytes, may be mask_ptr), points_ptr (cap x 3 floats), out_ptr (room
+        for cap records) and out_count_ptr may be 0."""
+        p = _PoseParams(max_depth, max_cos_parallax)
+        _check(lib().sift_hip_recover_pose_device(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride,
+            nt, result_ptr or None, mask_ptr or None, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p),
+            pose_ptr or None, mask_out_ptr or None, points_ptr or None, out_ptr or None, out_count_ptr or None, stream),
+            "recover_pose_device")
+
+    def recover_pose_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int, nt: int,
+                          result, mask, cam_q, cam_t, max_depth: float = 50.0, max_cos_parallax: float = 0.99998,
+                          q_stride: int = 3, t_stride: int = 3):
+        """Synchronous (sift_hip_recover_pose_host): result (a VERIFY_RESULT_DTYPE record) and mask (cap bytes) are host
+        values as verify_host(full=True) or refine_host return them; the list and positions are device memory.  Returns
+        (the POSE_RESULT_DTYPE record, the in-front mask of cap bytes, the points (cap, 3) float32 -- rows past the
+        list's count stay NaN --, the in-front records)."""
+        res = np.array([result], VERIFY_RESULT_DTYPE)
+        mask = np.array(np.asarray(mask, np.uint8).reshape(-1), np.uint8)
+        if len(mask) != max(cap, 0):
+            raise ValueError("one mask byte per row of the list (cap)")
+        p = _PoseParams(max_depth, max_cos_parallax)
+        pose = np.zeros(1, POSE_RESULT_DTYPE)
+        mask_out = np.zeros(max(cap, 0), np.uint8)
+        points = np.full((max(cap, 0), 3), np.nan, np.float32)
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        n_out = ctypes.c_int(0)
+        _check(lib().sift_hip_recover_pose_host(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride,
+            nt, _ptr(res), _ptr(mask) if cap > 0 else None, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p),
+            _ptr(pose), _ptr(mask_out), _ptr(points), _ptr(out), ctypes.byref(n_out)), "recover_pose_host")
+        return pose[0], mask_out, points, out[: n_out.value]
+
+    def recover_pose_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                    mask_ptr: int, cams_q, cams_t, poses_ptr: int, mask_out_ptr: int = 0,
+                                    points_ptr: int = 0, out_ptr: int = 0, out_counts_ptr: int = 0, max_depth: float = 50.0,
+                                    max_cos_parallax: float = 0.99998, q_stride: int = 3, t_stride: int = 3,
+                                    stream: Optional[int] = None) -> None:
+        """Enqueue the pose of every pair (sift_hip_recover_pose_batched_device) on what verify_batched_device and
+        refine_batched_device wrote: results_ptr (len(pairs) records) and mask_ptr (the caps' sum bytes) are read;
+        cams_q / cams_t: len(pairs) cameras each; poses_ptr: len(pairs) POSE_RESULT_DTYPE records.  Pair p's bytes are
+        the single call's."""
+        p = _PoseParams(max_depth, max_cos_parallax)
+        table, _ = self._pairs(pairs)
+        P = len(pairs)
+        _check(lib().sift_hip_recover_pose_batched_device(
+            self._v, matches_ptr or None, counts_ptr or None, P, table, q_stride, t_stride, results_ptr or None,
+            mask_ptr or None, _cameras(cams_q, P), _cameras(cams_t, P), ctypes.byref(p), poses_ptr or None,
+            mask_out_ptr or None, points_ptr or None, out_ptr or None, out_counts_ptr or None, stream),
+            "recover_pose_batched_device")
+
+    def recover_pose_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, verified: Sequence, cams_q,
+                                  cams_t, max_depth: float = 50.0, max_cos_parallax: float = 0.99998, q_stride: int = 3,
+                                  t_stride: int = 3) -> list:
+        """Synchronous (sift_hip_recover_pose_batched_host): verified holds per pair a tuple with the VERIFY_RESULT_DTYPE
+        record first and the mask (cap bytes) last -- (record, mask), or verify_batched_host(full=True)'s (record,
+        records, mask); per pair what recover_pose_host returns."""
+        table, caps = self._pairs(pairs)
+        P = len(pairs)
+        if len(verified) != P:
+            raise ValueError("one verified (record, ..., mask) per pair")
+        row0 = np.concatenate([[0], np.cumsum([c if 0 <= c <= 65536 else 0 for c in caps])]).astype(int)
+        res = np.array([v[0] for v in verified], VERIFY_RESULT_DTYPE) if P else np.zeros(1, VERIFY_RESULT_DTYPE)
+        mask = np.zeros(row0[-1], np.uint8)
+        for i, v in enumerate(verified):
+            mask[row0[i]: row0[i + 1]] = np.asarray(v[-1], np.uint8).reshape(-1)
+        p = _PoseParams(max_depth, max_cos_parallax)
+        poses = np.zeros(max(P, 1), POSE_RESULT_DTYPE)
+        mask_out = np.zeros(row0[-1], np.uint8)
+        points = np.full((row0[-1], 3), np.nan, np.float32)
+        out = np.zeros(row0[-1], DMATCH_DTYPE)
+        n_out = np.zeros(max(P, 1), np.int32)
+        _check(lib().sift_hip_recover_pose_batched_host(
+            self._v, matches_ptr or None, counts_ptr or None, P, table, q_stride, t_stride, _ptr(res),
+            _ptr(mask) if len(mask) else None, _cameras(cams_q, P), _cameras(cams_t, P), ctypes.byref(p), _ptr(poses),
+            _ptr(mask_out), _ptr(points), _ptr(out), _ptr(n_out)), "recover_pose_batched_host")
+        return [(poses[i].copy(), mask_out[row0[i]: row0[i + 1]].copy(), points[row0[i]: row0[i + 1]].copy(),
+                 out[row0[i]: row0[i] + n_out[i]].copy()) for i in range(P)]
+
 
 def _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit):
     if len(matches_per_pair) != len(xy_per_pair):
@@ -1882,6 +2005,49 @@ def verifyHomography(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int
     r, _, mask = v.verify_homography_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True)
     r, recs, _, _ = v.refine_homography_host(*args, r, mask, max_error, refit, des_stride, src_stride)
     return r["H"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
+
+
+def recoverPose(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, result, mask, cam_q, cam_t,
+                max_depth: float = 50.0, max_cos_parallax: float = 0.99998, des_stride: int = 3, src_stride: int = 3):
+    """cv::recoverPose on a verified pair: matches (a DMATCH_DTYPE array, uploaded here), des_xy / src_xy (DeviceBuffers
+    or raw device pointers, as for verifyFundamental), result -- a VERIFY_RESULT_DTYPE record, or F as 9 floats (3 x 3)
+    -- and mask, the inlier mask (one byte per match; None: every match).  cam_q / cam_t: (fx, fy, cx, cy) of the des
+    and the src side.  Returns (R 3 x 3 float32, t (3,) float32 with X_src = R X_des + t and |t| = 1, the in-front mask,
+    the points (n, 3) in the des camera's frame, the POSE_RESULT_DTYPE record); candidate = -1 in the record: no pose."""
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE)).reshape(-1)
+    if not (isinstance(result, np.void) or (isinstance(result, np.ndarray) and result.dtype == VERIFY_RESULT_DTYPE)):
+        rec = np.zeros(1, VERIFY_RESULT_DTYPE)
+        rec["F"][0] = np.asarray(result, np.float32).reshape(9)
+        rec["matches"][0] = len(m)
+        result = rec[0]
+    mask = np.ones(len(m), np.uint8) if mask is None else mask
+    v = Verifier(max(len(m), 1), 1)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    pose, mask_out, points, _ = v.recover_pose_host(d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, result,
+                                                    mask, cam_q, cam_t, max_depth, max_cos_parallax, des_stride,
+                                                    src_stride)
+    return pose["R"].reshape(3, 3).copy(), pose["t"].copy(), mask_out, points, pose
+
+
+def recoverPoseBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, results: Sequence, masks: Sequence,
+                       cams_q, cams_t, max_depth: float = 50.0, max_cos_parallax: float = 0.99998) -> list:
+    """recoverPose for P pairs in one pass: matches_per_pair[p] a DMATCH_DTYPE array, xy_per_pair[p] = (des_xy, src_xy)
+    host float arrays of rows with x, y first, results[p] a VERIFY_RESULT_DTYPE record, masks[p] its inlier mask,
+    cams_q / cams_t P cameras each.  A list of what recoverPose returns per pair."""
+    if not (len(matches_per_pair) == len(xy_per_pair) == len(results) == len(masks)):
+        raise ValueError("one (des_xy, src_xy), record and mask per match list")
+    lists = [np.ascontiguousarray(np.asarray(m, DMATCH_DTYPE)).reshape(-1) for m in matches_per_pair]
+    xy = [[np.ascontiguousarray(np.asarray(a, np.float32)[:, :2]) for a in qt] for qt in xy_per_pair]
+    rows = sum(len(m) for m in lists)
+    v = Verifier(max(rows, 1), 1, max(len(lists), 1))
+    d = DeviceArray.from_numpy(np.concatenate(lists) if lists else np.zeros(0, DMATCH_DTYPE))
+    dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
+    pairs = [(dq.value, len(q), dt.value, len(t), len(m)) for m, (q, t), (dq, dt) in zip(lists, xy, dxy)]
+    got = v.recover_pose_batched_host(d.value if rows else 0, 0, pairs, list(zip(results, masks)), cams_q, cams_t,
+                                      max_depth, max_cos_parallax, 2, 2)
+    return [(pose["R"].reshape(3, 3).copy(), pose["t"].copy(), mask_out, points, pose)
+            for pose, mask_out, points, _ in got]
 
 
 def project_homography_device(H_ptr: int, xy_ptr: int, n: int, out_ptr: int, stride: int = 3, out_stride: int = 2,

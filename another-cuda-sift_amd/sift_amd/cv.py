@@ -797,7 +797,7 @@ def _jacobi_pivots(m: int):
     return [[tuple(sorted(((r + i) % m, (r - i) % m))) for i in range(1, (m - 1) // 2 + 1)] for r in range(m)]
 
 
-def _jacobi(A, sweeps: int = REFIT_SWEEPS):
+def _jacobi_full(A, sweeps: int = REFIT_SWEEPS):
     """Cyclic Jacobi on a symmetric (m, m) float64 matrix, m odd: `sweeps` sweeps over the pivots in round-robin order
     (_jacobi_pivots: m rounds of (m - 1) / 2 pivots on disjoint index pairs, which a device applies side by side -- a
     rotation reads nothing an earlier rotation of its round wrote but the entries it shares with it, and those in
@@ -807,8 +807,7 @@ def _jacobi(A, sweeps: int = REFIT_SWEEPS):
         k != p, q:  A[k][p] = A[p][k] = c A[k][p] - s A[k][q],  A[k][q] = A[q][k] = s A[k][p] + c A[k][q] (old values);
         A[p][p] -= t a;  A[q][q] += t a;  A[p][q] = A[q][p] = 0;
         every k:  V[k][p] = c V[k][p] - s V[k][q],  V[k][q] = s V[k][p] + c V[k][q] (old values), V = I at the start.
-    Returns the column of V whose diagonal entry of A is the smallest (ties to the lowest index) -- the eigenvector of
-    the smallest eigenvalue -- and the diagonal."""
+    Returns V as m rows of Python floats (column i: the eigenvector of diagonal entry i) and the diagonal."""
     m = len(A)
     A = [[float(A[r][c]) for c in range(m)] for r in range(m)]
     V = [[1.0 if r == c else 0.0 for c in range(m)] for r in range(m)]
@@ -838,11 +837,19 @@ def _jacobi(A, sweeps: int = REFIT_SWEEPS):
                     vkp, vkq = V[k][p], V[k][q]
                     V[k][p] = c * vkp - s * vkq
                     V[k][q] = s * vkp + c * vkq
+    return V, [A[i][i] for i in range(m)]
+
+
+def _jacobi(A, sweeps: int = REFIT_SWEEPS):
+    """_jacobi_full's column of V whose diagonal entry of A is the smallest (ties to the lowest index) -- the
+    eigenvector of the smallest eigenvalue -- and the diagonal."""
+    V, d = _jacobi_full(A, sweeps)
+    m = len(d)
     best = 0
     for i in range(1, m):
-        if A[i][i] < A[best][best]:
+        if d[i] < d[best]:
             best = i
-    return np.array([V[k][best] for k in range(m)], np.float64), np.array([A[i][i] for i in range(m)], np.float64)
+    return np.array([V[k][best] for k in range(m)], np.float64), np.array(d, np.float64)
 
 
 def _refit_points(pts_or_matches, q_xy, t_xy):
@@ -1021,6 +1028,172 @@ def refine_fundamental(matches, q_xy, t_xy, result, max_error=1.5, rounds: int =
 def refine_homography(matches, q_xy, t_xy, result, max_error=1.5, rounds: int = 1) -> dict:
     """refine_fundamental for a ransac_homography dict (sift_hip_refine_homography_*)."""
     return _refine("H", _transfer_pass, matches, q_xy, t_xy, result, max_error, rounds)
+
+
+# --- Relative pose from a verified fundamental matrix: the rule of sift_hip_recover_pose_* (include/sift_hip.h,
+# "Relative pose from a verified fundamental matrix") in numpy float64.  As in the refit: every operation below is one
+# IEEE float64 operation in the header's association -- products and sums are written out elementwise, no @, dot,
+# einsum or linalg, which may fuse --, and the outputs are rounded to float32 once.  The device's bytes are this code's.
+
+POSE_MAX_DEPTH = 50.0            # cv::recoverPose's distanceThresh, in baselines
+POSE_MAX_COS_PARALLAX = 0.99998  # ORB-SLAM's parallax bar
+POSE_NAN = np.frombuffer(np.uint32(0x7FC00000).tobytes(), np.float32)[0]  # the one NaN the points carry
+
+
+def _camera(cam, what: str):
+    """(fx, fy, cx, cy) as float64 values of the float32 camera, refused as the calls refuse it."""
+    c = np.asarray(cam, np.float32).reshape(-1)
+    if c.size != 4:
+        raise ValueError(f"{what}: a camera is (fx, fy, cx, cy)")
+    if not (c[0] > 0 and c[1] > 0 and np.isfinite(c[:2]).all()):
+        raise ValueError(f"{what}: fx and fy must be > 0 and finite")
+    if not np.isfinite(c[2:]).all():
+        raise ValueError(f"{what}: cx and cy must be finite")
+    return [float(v) for v in c]
+
+
+def essential_from_fundamental(F, cam_q, cam_t) -> np.ndarray:
+    """E = Kt^T F Kq (3 x 3 float64) for skew-free cameras (fx, fy, cx, cy): G = F Kq column by column, then Kt^T G row
+    by row, each entry in the header's association."""
+    f = np.asarray(F, np.float32).reshape(-1)
+    if f.size != 9:
+        raise ValueError("F must have 9 entries (3 x 3, row-major)")
+    f = [float(v) for v in f]
+    fxq, fyq, cxq, cyq = _camera(cam_q, "cam_q")
+    fxt, fyt, cxt, cyt = _camera(cam_t, "cam_t")
+    G = [[f[3 * r] * fxq, f[3 * r + 1] * fyq, (f[3 * r] * cxq + f[3 * r + 1] * cyq) + f[3 * r + 2]] for r in range(3)]
+    E = np.zeros((3, 3), np.float64)
+    for c in range(3):
+        E[0, c] = fxt * G[0][c]
+        E[1, c] = fyt * G[1][c]
+        E[2, c] = (cxt * G[0][c] + cyt * G[1][c]) + G[2][c]
+    return E
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def decompose_essential(E, sweeps: int = REFIT_SWEEPS) -> list:
+    """The four (R, t) candidates of an essential matrix in cv::decomposeEssentialMat's and cv::recoverPose's order --
+    (R1, t), (R2, t), (R1, -t), (R2, -t), R (3, 3) and t (3,) float64, |t| = 1 -- or [] when E has rank <= 1.  The
+    right singular vectors are the eigenvectors of E^T E by the refit's Jacobi routine (3 x 3, `sweeps` sweeps), taken
+    in descending order of their eigenvalues (ties to the lower index); v3 = v1 x v2, u_i = (E v_i) / s_i,
+    u3 = u1 x u2, so U and V are proper by construction and R1 = U W V^T, R2 = U W^T V^T are rotations."""
+    E = [[float(np.asarray(E, np.float64).reshape(3, 3)[r, c]) for c in range(3)] for r in range(3)]
+    N = [[(E[0][r] * E[0][c] + E[1][r] * E[1][c]) + E[2][r] * E[2][c] for c in range(3)] for r in range(3)]
+    with np.errstate(all="ignore"):
+        V, d = _jacobi_full(N, sweeps)
+    i1 = 0
+    for i in (1, 2):
+        if d[i] > d[i1]:
+            i1 = i
+    i2 = -1
+    for i in range(3):
+        if i != i1 and (i2 < 0 or d[i] > d[i2]):
+            i2 = i
+    with np.errstate(all="ignore"):
+        s1, s2 = np.sqrt(np.float64(d[i1])), np.sqrt(np.float64(d[i2]))
+        if not (np.isfinite(s2) and s2 > 0):
+            return []
+        v1, v2 = [V[k][i1] for k in range(3)], [V[k][i2] for k in range(3)]
+        v3 = _cross(v1, v2)
+        u1 = [float(np.float64((E[r][0] * v1[0] + E[r][1] * v1[1]) + E[r][2] * v1[2]) / s1) for r in range(3)]
+        u2 = [float(np.float64((E[r][0] * v2[0] + E[r][1] * v2[1]) + E[r][2] * v2[2]) / s2) for r in range(3)]
+    u3 = _cross(u1, u2)
+    R1 = np.array([[(u2[r] * v1[c] - u1[r] * v2[c]) + u3[r] * v3[c] for c in range(3)] for r in range(3)], np.float64)
+    R2 = np.array([[(u1[r] * v2[c] - u2[r] * v1[c]) + u3[r] * v3[c] for c in range(3)] for r in range(3)], np.float64)
+    t = np.array(u3, np.float64)
+    return [(R1, t), (R2, t), (R1, -t), (R2, -t)]
+
+
+def triangulate_depths(R, t, xq, xt):
+    """The two depths of every record under the pose X_t = R X_q + t: (a, b, det, cosine), each (n,) float64.  xq, xt:
+    (n, 2) float64 normalised image coordinates (the rays are (x, y, 1)).  With p = R xq, (a, b) minimise
+    |a p + t - b xt|^2 -- the closed form of the 2 x 2 normal equations, det = pp xx - px px -- and cosine =
+    px / sqrt(pp xx) is the cosine of the angle between the two rays."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = np.asarray(t, np.float64).reshape(3)
+    xq, xt = np.asarray(xq, np.float64).reshape(-1, 2), np.asarray(xt, np.float64).reshape(-1, 2)
+    x0, x1, y0, y1 = xq[:, 0], xq[:, 1], xt[:, 0], xt[:, 1]
+    with np.errstate(all="ignore"):
+        p0 = (R[0, 0] * x0 + R[0, 1] * x1) + R[0, 2]
+        p1 = (R[1, 0] * x0 + R[1, 1] * x1) + R[1, 2]
+        p2 = (R[2, 0] * x0 + R[2, 1] * x1) + R[2, 2]
+        pp = (p0 * p0 + p1 * p1) + p2 * p2
+        xx = (y0 * y0 + y1 * y1) + 1.0
+        px = (p0 * y0 + p1 * y1) + p2
+        pt = (p0 * t[0] + p1 * t[1]) + p2 * t[2]
+        xt_t = (y0 * t[0] + y1 * t[1]) + t[2]
+        det = pp * xx - px * px
+        a = (px * xt_t - pt * xx) / det
+        b = (pp * xt_t - px * pt) / det
+        cosine = px / np.sqrt(pp * xx)
+    assert a.dtype == np.float64 and b.dtype == np.float64 and cosine.dtype == np.float64
+    return a, b, det, cosine
+
+
+def recover_pose(matches, q_xy, t_xy, result, mask, cam_q, cam_t, max_depth=POSE_MAX_DEPTH,
+                 max_cos_parallax=POSE_MAX_COS_PARALLAX, sweeps: int = REFIT_SWEEPS) -> dict:
+    """The whole pose operation (sift_hip_recover_pose_*) in numpy.  matches: the n DMATCH_DTYPE records that count;
+    result: a ransac_fundamental / refine_fundamental dict or a VERIFY_RESULT_DTYPE record (read: F, hypothesis); mask:
+    n bytes, the fit set; cam_q / cam_t: (fx, fy, cx, cy).  Returns a dict: R (9,) and t (3,) float32 with
+    X_train = R X_query + t and |t| = 1, in_front, with_parallax, counts (4,) int32, candidate (-1: the empty result),
+    fit, mask (n,) uint8, points (n, 3) float32 in the query camera's frame (POSE_NAN rows where the record is not in
+    front) and list, the in-front records in input order."""
+    from . import DMATCH_DTYPE
+
+    matches = np.asarray(matches, DMATCH_DTYPE).reshape(-1)
+    n = len(matches)
+    mask = np.asarray(mask, np.uint8).reshape(-1)[:n]
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    kq, kt = _camera(cam_q, "cam_q"), _camera(cam_t, "cam_t")
+    md, mc = np.float32(max_depth), np.float32(max_cos_parallax)
+    if not md > 0:
+        raise ValueError("max_depth must be > 0")
+    if not (mc >= -1 and mc <= 1):
+        raise ValueError("max_cos_parallax must lie in [-1, 1]")
+    md, mc = np.float64(md), np.float64(mc)
+    pts = _match_points(matches, q_xy, t_xy)
+    fit = (mask != 0) & np.isfinite(pts).all(1)
+    out = {"R": np.zeros(9, np.float32), "t": np.zeros(3, np.float32), "in_front": 0, "with_parallax": 0,
+           "counts": np.zeros(4, np.int32), "candidate": -1, "fit": int(fit.sum()), "mask": np.zeros(n, np.uint8),
+           "points": np.full((n, 3), POSE_NAN, np.float32), "list": matches[:0].copy()}
+    f = np.asarray(result["F"], np.float32).reshape(-1)
+    if not (int(result["hypothesis"]) >= 0 and geometry_usable(f)):
+        return out
+    cands = decompose_essential(essential_from_fundamental(f, cam_q, cam_t), sweeps)
+    if not cands:
+        return out
+    p = pts.astype(np.float64)
+    with np.errstate(all="ignore"):
+        xq = np.stack([(p[:, 0] - kq[2]) / kq[0], (p[:, 1] - kq[3]) / kq[1]], 1)
+        xt = np.stack([(p[:, 2] - kt[2]) / kt[0], (p[:, 3] - kt[3]) / kt[1]], 1)
+        front, parallax, depth = [], [], []
+        for R, t in cands:
+            a, b, det, cosine = triangulate_depths(R, t, xq, xt)
+            ok = fit & (det > 0) & (a > 0) & (b > 0) & (a < md) & (b < md)
+            front.append(ok)
+            parallax.append(ok & (cosine < mc))
+            depth.append(a)
+    counts = np.array([int(k.sum()) for k in front], np.int32)
+    best = 0
+    for k in range(1, 4):
+        if counts[k] > counts[best]:
+            best = k
+    if counts[best] == 0:
+        return out
+    keep = front[best]
+    with np.errstate(all="ignore"):
+        a = depth[best]
+        X = np.stack([a * xq[:, 0], a * xq[:, 1], a], 1).astype(np.float32)
+    out["points"][keep] = X[keep]
+    out.update(R=cands[best][0].reshape(9).astype(np.float32), t=cands[best][1].astype(np.float32),
+               in_front=int(counts[best]), with_parallax=int(parallax[best].sum()), counts=counts, candidate=best,
+               mask=keep.astype(np.uint8), list=matches[keep])
+    assert out["R"].dtype == np.float32 and out["points"].dtype == np.float32
+    return out
 
 
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):

@@ -62,6 +62,37 @@ struct VerifyPair {
     int cap = 0;
 };
 
+// sift_hip_camera: a skew-free pinhole camera.
+struct Camera {
+    float fx = 1.f, fy = 1.f, cx = 0.f, cy = 0.f;
+};
+
+// sift_hip_pose_params with sift_hip_default_pose_params' defaults.
+struct PoseParams {
+    float max_depth = 50.f;             // > 0, +inf allowed: the far bound on both depths, in baselines
+    float max_cos_parallax = 0.99998f;  // in [-1, 1]: a record in front has parallax below this cosine
+};
+
+// sift_hip_pose_result (device form: the record the kernels write): X_train = R X_query + t, R row-major, |t| = 1;
+// candidate = -1 is the empty result (R and t zero).
+struct PoseResult {
+    float R[9];
+    float t[3];
+    int in_front, with_parallax;
+    int counts[4];
+    int candidate, fit;
+};
+
+// What the host forms return beside the record: the in-front mask (one byte per row), the points in the query camera's
+// frame (3 floats per row; NaN where the record is not in front, and in the rows past the list's count) and the
+// in-front records in input order.
+struct RelativePose {
+    PoseResult pose{};
+    std::vector<uint8_t> mask;
+    std::vector<float> points;
+    std::vector<DMatch> inliers;
+};
+
 // A verifier owns the scratch of its calls; calls on one verifier must be
 // ordered.  What the ABI refuses (sift_hip_verify_fundamental_device) throws
 // std::invalid_argument; a failed allocation or HIP call std::runtime_error.
@@ -156,6 +187,37 @@ public:
                                                  std::vector<uint8_t>& mask, std::vector<DMatch>* out = nullptr,
                                                  std::vector<int>* out_counts = nullptr);
 
+    // The relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
+    // "Relative pose from a verified fundamental matrix"): cv::recoverPose on the list, count and positions of the
+    // verify call that wrote *result and mask (device memory, read only).  pose: a device record; mask_out (cap bytes,
+    // may be mask itself), points (cap x 3 floats), out and out_count may be nullptr.  Enqueued on `stream`, not
+    // synchronised, capturable.
+    void recoverPoseDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                           const float* train_xy, int train_stride, int nt, const VerifyResult* result, const uint8_t* mask,
+                           const Camera& cam_query, const Camera& cam_train, const PoseParams& params, PoseResult* pose,
+                           uint8_t* mask_out = nullptr, float* points = nullptr, DMatch* out = nullptr,
+                           int* out_count = nullptr, void* stream = nullptr);
+    // Synchronous; the list and positions on the device, `result` and `mask` (cap bytes) on the host.
+    RelativePose recoverPoseHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                                 int nq, const float* train_xy, int train_stride, int nt, const VerifyResult& result,
+                                 const std::vector<uint8_t>& mask, const Camera& cam_query, const Camera& cam_train,
+                                 const PoseParams& params = {});
+    // All pairs of a batch: results and poses hold pairs.size() records, cams_query and cams_train pairs.size() cameras,
+    // mask, mask_out and out the caps' sum rows, points three floats per row; pair p's bytes are the single call's.
+    void recoverPoseBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                  int query_stride, int train_stride, const VerifyResult* results, const uint8_t* mask,
+                                  const std::vector<Camera>& cams_query, const std::vector<Camera>& cams_train,
+                                  const PoseParams& params, PoseResult* poses, uint8_t* mask_out = nullptr,
+                                  float* points = nullptr, DMatch* out = nullptr, int* out_counts = nullptr,
+                                  void* stream = nullptr);
+    // Synchronous; one RelativePose per pair, in the pairs' order.
+    std::vector<RelativePose> recoverPoseBatchedHost(const DMatch* matches, const int* counts,
+                                                     const std::vector<VerifyPair>& pairs, int query_stride,
+                                                     int train_stride, const std::vector<VerifyResult>& results,
+                                                     const std::vector<uint8_t>& mask,
+                                                     const std::vector<Camera>& cams_query,
+                                                     const std::vector<Camera>& cams_train, const PoseParams& params = {});
+
     sift_hip_verifier* handle() const { return m_handle; }
 
 private:
@@ -180,6 +242,13 @@ TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const floa
                                   int train_stride, int refit);
 PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                                 int nt, const VerifyParams& params, int query_stride, int train_stride, int refit);
+
+// The all-in-one beside verifyFundamental: uploads the list and recovers the pose of a verified F (9 floats, row-major,
+// x_train^T F x_query = 0) over the records `mask` marks (empty: every record).
+RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy, int nt,
+                         const float (&F)[9], const std::vector<uint8_t>& mask, const Camera& cam_query,
+                         const Camera& cam_train, const PoseParams& params = {}, int query_stride = 3,
+                         int train_stride = 3);
 
 // Enqueued on `stream`, not synchronised (sift_hip_project_homography_device): row i of out_xy = row i of xy carried
 // over by H, NaN where it lands behind the camera.  H: 9 floats of device memory (a HomographyResult's address); xy /

@@ -1157,8 +1157,9 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
 
 /* --- The verifier's refusals ----------------------------------------------------
  *
- * Every verifier call that takes a match list (sift_hip_verify_*, sift_hip_score_*
- * and sift_hip_refine_*, single-pair and batched, device and host form) judges
+ * Every verifier call that takes a match list (sift_hip_verify_*, sift_hip_score_*,
+ * sift_hip_refine_* and sift_hip_recover_pose_*, single-pair and batched, device
+ * and host form) judges
  * its arguments in ONE order and reports the first rule broken, with nothing
  * launched and nothing written.  First what needs no look at the verifier:
  *   a null verifier; null pairs; a null params or result (the score calls: a
@@ -1167,6 +1168,12 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
  *   null matches with a row to read; max_error not > 0 and finite; out
  *   overlapping matches (device forms); the refine calls' null mask, then rounds
  *   outside 1..8;
+ *   the pose calls, which have no params or result among the first rules and no
+ *   max_error, after the list rules (null matches): a null camera pointer; pair
+ *   by pair, query camera first, fx or fy not > 0 and finite, then cx or cy not
+ *   finite; a null params, result or pose; max_depth not > 0 (+inf is allowed, a
+ *   NaN is refused); max_cos_parallax outside [-1, 1]; a null mask with a row to
+ *   read; out overlapping matches (device forms);
  * then the verifier's limits: hypotheses outside 1..max_hypotheses, P over
  * max_pairs, the caps' sum (the cap) over max_matches.  A single-pair call is
  * judged as the batch of its one pair; a batched call names the pair in the
@@ -1676,6 +1683,174 @@ int sift_hip_refine_homography_batched_host(sift_hip_verifier_t v, const sift_hi
                                             float max_error, int rounds, sift_hip_homography_result* results_host,
                                             uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,
                                             int* accepted_host);
+
+/* --- Relative pose from a verified fundamental matrix ---------------------------
+ *
+ * What a calibrated caller does with a verified F (cv::recoverPose, ORB-SLAM's
+ * ReconstructF): E = Kt^T F Kq, its four (R, t) candidates, the inliers
+ * triangulated under each, and the candidate that puts them in front of both
+ * cameras.  A pose call does this on the device from what a verify or refine
+ * call left there -- the list, the 52-byte result record, the mask -- on the
+ * caller's stream, with no read-back.  The numpy mirror
+ * sift_amd.cv.essential_from_fundamental / decompose_essential /
+ * triangulate_depths (the steps) and recover_pose (the operation) is the
+ * specification: the device equals it byte for byte.
+ *
+ * Arithmetic.  IEEE float64 throughout, nothing fused, correctly rounded division
+ * and square root, every sum and product in the association written below.
+ * float32 inputs (F, the cameras, the positions, the two thresholds) convert
+ * exactly; the outputs are rounded to float32 once, at the end.  No cos() is
+ * evaluated anywhere.
+ *
+ * Inputs.  The list, count, cap, positions, strides, nq and nt, read exactly as
+ * the refine calls read them (n, the gathered coordinates qx, qy, tx, ty, NaN
+ * for an index outside its position array).  The current result record in device
+ * memory, whose first nine floats are F with x_train^T F x_query = 0.  The mask.
+ * Two pinhole cameras (fx, fy, cx, cy), query side and train side, and the
+ * thresholds max_depth and max_cos_parallax, from host memory.
+ *
+ * The rule.
+ *   1. Usable record: hypothesis >= 0 and nine floats that are finite and not all
+ *      zero (the refit's test).  Otherwise the result is empty.
+ *   2. E = Kt^T F Kq for skew-free K, row r and column c from 0:
+ *        G[r][0] = F[r][0] fxq;  G[r][1] = F[r][1] fyq;
+ *        G[r][2] = (F[r][0] cxq + F[r][1] cyq) + F[r][2];
+ *        E[0][c] = fxt G[0][c];  E[1][c] = fyt G[1][c];
+ *        E[2][c] = (cxt G[0][c] + cyt G[1][c]) + G[2][c].
+ *   3. N = E^T E with N[r][c] = (E[0][r] E[0][c] + E[1][r] E[1][c]) + E[2][r] E[2][c].
+ *      Its eigen-decomposition by the refit's Jacobi routine (step 6 there: 3 x 3,
+ *      V = I, 8 sweeps, the same pivot order).  i1 = the index of the largest
+ *      diagonal entry, i2 of the largest of the other two, ties to the lower index
+ *      both times; w1, w2 those entries, v1, v2 those columns of V.
+ *      s1 = sqrt(w1), s2 = sqrt(w2); s2 not finite or not > 0 (rank <= 1): the
+ *      result is empty.  v3 = v1 x v2;
+ *      u1[r] = ((E[r][0] v1[0] + E[r][1] v1[1]) + E[r][2] v1[2]) / s1, u2 likewise
+ *      with v2 and s2; u3 = u1 x u2, where (a x b)[0] = a[1] b[2] - a[2] b[1],
+ *      [1] = a[2] b[0] - a[0] b[2], [2] = a[0] b[1] - a[1] b[0].  U = (u1 u2 u3)
+ *      and V = (v1 v2 v3) are proper by construction.
+ *   4. Candidates.  With W = [[0,-1,0],[1,0,0],[0,0,1]], R1 = U W V^T and
+ *      R2 = U W^T V^T; W only permutes and negates columns, so
+ *        R1[r][c] = (u2[r] v1[c] - u1[r] v2[c]) + u3[r] v3[c],
+ *        R2[r][c] = (u1[r] v2[c] - u2[r] v1[c]) + u3[r] v3[c];  t = u3.
+ *      In cv::recoverPose's order: 0 = (R1, t), 1 = (R2, t), 2 = (R1, -t),
+ *      3 = (R2, -t).  The query camera is [I | 0], the train camera [R | t]:
+ *      X_train = R X_query + t, and |t| = 1 up to rounding.
+ *   5. Fit set: the records j < n with mask[j] != 0 whose four gathered
+ *      coordinates are finite (the refit's set); m their number.
+ *   6. Per fit record and candidate (R, t):
+ *        xq = ((qx - cxq) / fxq, (qy - cyq) / fyq), xt = ((tx - cxt) / fxt,
+ *        (ty - cyt) / fyt), the rays being (xq, 1) and (xt, 1);
+ *        p[r] = (R[r][0] xq[0] + R[r][1] xq[1]) + R[r][2];
+ *        pp = (p[0] p[0] + p[1] p[1]) + p[2] p[2];
+ *        xx = (xt[0] xt[0] + xt[1] xt[1]) + 1;
+ *        px = (p[0] xt[0] + p[1] xt[1]) + p[2];
+ *        pt = (p[0] t[0] + p[1] t[1]) + p[2] t[2];
+ *        xt_t = (xt[0] t[0] + xt[1] t[1]) + t[2];
+ *        det = pp xx - px px;
+ *        a = (px xt_t - pt xx) / det;  b = (pp xt_t - px pt) / det
+ *      -- the depths (a in the query camera, b in the train camera) that minimise
+ *      |a p + t - b (xt, 1)|^2, from its 2 x 2 normal equations.  (Negating t
+ *      negates pt and xt_t and with them a and b, exactly.)  The record is IN
+ *      FRONT when det > 0, a > 0, b > 0, a < max_depth and b < max_depth; a NaN
+ *      fails every test.  It has PARALLAX when it is in front and
+ *      px / sqrt(pp xx) < max_cos_parallax.
+ *   7. Winner: the candidate with the most records in front, ties to the lowest
+ *      index.  A winning count of 0 gives the empty result.
+ *   8. Outputs.  The pose record: R (row-major) and t of the winner, rounded to
+ *      float32; in_front and with_parallax, its two counts; counts[4], the records
+ *      in front under each candidate; candidate, its index; fit = m.  mask_out
+ *      (cap bytes): 1 for a fit record in front under the winner, else 0, also for
+ *      the rows in [n, cap).  points (cap x 3 float32): row j < n is (a xq[0],
+ *      a xq[1], a) rounded to float32 -- the point in the query camera's frame, in
+ *      units of the baseline -- for a record in front under the winner, and three
+ *      times the quiet NaN 0x7FC00000 otherwise; rows >= n are not written.  out:
+ *      the records in front in input order, out_count their number (rows past them
+ *      are not written).
+ * The empty result: R and t zero, in_front, with_parallax and counts[] 0,
+ * candidate = -1, fit still m, mask_out all zero, every points row j < n NaN, an
+ * empty list.  It is a success, not an error, as a verify call's n < 8 is.
+ *
+ * Thresholds.  max_depth = 50 is cv::recoverPose's distanceThresh, in baselines
+ * (+inf: no far bound); max_cos_parallax = 0.99998 is ORB-SLAM's bar: with_parallax
+ * counts the records whose rays meet at more than about 0.36 degrees, which tells
+ * a pose with a usable baseline from a near-pure rotation.
+ *
+ * Consequences.  The output is a function of the inputs alone: the same bytes in
+ * every run, and in the single and batched forms (pair p of a batched call equals
+ * the single call on that pair with cam_query[p] and cam_train[p]).  -F gives the
+ * same pose through the candidate with R1 and R2 swapped. */
+typedef struct {
+    float fx, fy, cx, cy;
+} sift_hip_camera;
+
+typedef struct {
+    float max_depth;        /* > 0, +inf allowed; default 50 */
+    float max_cos_parallax; /* in [-1, 1]; default 0.99998 */
+} sift_hip_pose_params;
+
+void sift_hip_default_pose_params(sift_hip_pose_params* p);
+
+typedef struct {
+    float R[9]; /* row-major, X_train = R X_query + t */
+    float t[3]; /* |t| = 1 */
+    int in_front;
+    int with_parallax;
+    int counts[4];
+    int candidate; /* 0..3, -1: the empty result */
+    int fit;
+} sift_hip_pose_result;
+#ifdef __cplusplus
+static_assert(sizeof(sift_hip_pose_result) == 80, "sift_hip_pose_result is 80 bytes");
+#else
+typedef char sift_hip_pose_result_is_80_bytes[sizeof(sift_hip_pose_result) == 80 ? 1 : -1];
+#endif
+
+/* Device form: two launches after the gather, enqueued on `stream`, not
+ * synchronised, no allocation (the candidates' scratch is the verifier's),
+ * capturable.  The list, count, cap and positions are the verify call's; result
+ * and mask (device memory) are what it or a refine call wrote and are only read.
+ * cam_query, cam_train and params: host memory, read before the call returns.
+ * pose: device memory.  mask_out (cap bytes), points (cap x 3 floats), out (cap
+ * records) and out_count may each be NULL; mask_out may be the mask itself (the
+ * same address: the mask then becomes the in-front mask; any other overlap of the
+ * two is not allowed).  The verifier's hypothesis scratch is not touched: what
+ * sift_hip_verify_hypotheses_host answers stays.  SIFT_HIP_ERR_INVALID, with
+ * nothing launched and nothing written, by the rules and in the order of "The
+ * verifier's refusals".
+ * Host form: synchronous; the list, count and positions still live on the device;
+ * result_host and mask_host are host memory, pose_host, mask_out_host,
+ * points_host, out_host and out_count_host (the last four nullable) receive host
+ * copies: mask_out_host all cap bytes, points_host the rows j < n, out_host the
+ * out_count records. */
+int sift_hip_recover_pose_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                 const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride,
+                                 int nt, const sift_hip_verify_result* result, const uint8_t* mask,
+                                 const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                 const sift_hip_pose_params* params, sift_hip_pose_result* pose, uint8_t* mask_out,
+                                 float* points, sift_hip_dmatch* out, int* out_count, void* stream);
+int sift_hip_recover_pose_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                               const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride,
+                               int nt, const sift_hip_verify_result* result_host, const uint8_t* mask_host,
+                               const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                               const sift_hip_pose_params* params, sift_hip_pose_result* pose_host, uint8_t* mask_out_host,
+                               float* points_host, sift_hip_dmatch* out_host, int* out_count_host);
+/* The batched forms: results, poses and out_counts hold P entries, cam_query and
+ * cam_train P cameras each (host memory); mask, mask_out and out hold the caps'
+ * sum rows and points three floats per row, laid out as in the batched verify
+ * calls.  A verifier serves up to its max_pairs pairs per call. */
+int sift_hip_recover_pose_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts, int P,
+                                         const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                         const sift_hip_verify_result* results, const uint8_t* mask,
+                                         const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                         const sift_hip_pose_params* params, sift_hip_pose_result* poses, uint8_t* mask_out,
+                                         float* points, sift_hip_dmatch* out, int* out_counts, void* stream);
+int sift_hip_recover_pose_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts, int P,
+                                       const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                       const sift_hip_verify_result* results_host, const uint8_t* mask_host,
+                                       const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                       const sift_hip_pose_params* params, sift_hip_pose_result* poses_host,
+                                       uint8_t* mask_out_host, float* points_host, sift_hip_dmatch* out_host,
+                                       int* out_counts_host);
 
 /* --- Multi-GPU (the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
