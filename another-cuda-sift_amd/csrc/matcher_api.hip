@@ -1,11 +1,16 @@
 // Matcher handle (sift_hip_matcher_*, sift_hip_match_*) and the descriptor
 // sidecar registry of libsift_hip.so; the kernels are match.hip.  Replaces
 // /root/reference/sift_cuda/sift_func/Match.cu:8-33 (matchBruteForce).
+//
+// Every match entry point fills one MatchCall and hands it to run(): one
+// checker, one staging function for fp16 sets, one reverse-pair builder and
+// direction policy ("The matcher's host path: one call record").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 
 #include "detector_state.h"
@@ -126,9 +131,615 @@ struct sift_hip_matcher {
     }
 };
 
+static_assert(sizeof(sift_hip_dmatch) == sizeof(MatchRecord) && sizeof(sift_hip_dmatch) == 16, "cv::DMatch layout");
+static_assert(sizeof(sift_hip_match_filter) == sizeof(MatchFilter), "the filter is passed to the kernel as it is");
+static_assert(sizeof(sift_hip_match_positions) == 2 * sizeof(void*), "two device pointers per pair");
+static_assert(SIFT_HIP_KNN_MAX == kKnnMax, "the kernel's largest instantiation");
+
+// --- One call record ------------------------------------------------------------
 namespace {
+
 const SetFlags kNoFlags{nullptr, 0u};  // ready code sets: integers by construction
+
+enum class Op { Top2, List, KnnTable, KnnList };
+enum class Gate { None, Window, Epipolar };
+
+// How an entry family words the rules every family has: a null matcher, P outside 1..max_pairs, a null size array,
+// a null descriptor array.  (Null code arrays are "bad code batch", null positions "bad gated batch", everywhere.)
+struct Wording {
+    const char *matcher, *pairs, *sizes, *sets;
+};
+const Wording kBatchWords{"bad batch", "bad batch", "bad batch", "bad batch"};
+const Wording kCodeWords{"bad code batch", "bad code batch", "bad code batch", "bad code batch"};
+const Wording kListWords{"bad match list arguments", "bad match list arguments", "bad match list arguments",
+                         "bad match list arguments"};
+const Wording kKnnWords{"null matcher", "k-NN: P outside 1..max_pairs", "k-NN: null size array",
+                        "k-NN: null descriptor array"};
+const Wording kGatedWords{"null matcher", "bad gated batch", "bad gated batch", "bad gated batch"};
+const Wording kGatedKnnWords{"null matcher", "bad gated batch", "bad gated batch", "k-NN: null descriptor array"};
+
+// What a match entry point asks for.  The entry points fill one and hand it to run().
+struct MatchCall {
+    Op op;
+    const Wording* words;
+    Gate gate = Gate::None;
+    bool single = false;  // a single-pair entry point: its pair is a one-pair table in the entry point's frame
+    bool host = false;    // a _host form: the outputs are the matcher's own buffers (run() fills them in)
+    // The pair table: sizes, and the sets as fp16 pointers or (ready) as rows of a caller's code buffer.
+    int P = 0;
+    const int *nq = nullptr, *nt = nullptr;
+    const uint16_t* const* q = nullptr;
+    const uint16_t* const* t = nullptr;
+    bool ready = false;
+    const int8_t* codes = nullptr;
+    const int* keys = nullptr;
+    const int *qrow0 = nullptr, *qkey0 = nullptr, *trow0 = nullptr, *tkey0 = nullptr;
+    // The gate: positions per pair and the call-wide fields; the epipolar geometry is the host's F (single-pair
+    // calls, checked here, a kernel argument) or a device table the kernel reads (batched calls).
+    bool has_gate = true;  // single-pair calls: the gate record is not null
+    const sift_hip_match_positions* pos = nullptr;
+    int qstride = 0, tstride = 0;
+    float radius = 0.f, max_error = 0.f;
+    const float* F = nullptr;
+    const void* geometry = nullptr;
+    int geometry_stride = 0;
+    // The operation's parameters and outputs.
+    float ratio = 0.f;
+    int ratio_on_squared = 0;
+    const sift_hip_match_filter* filter = nullptr;
+    int k = 0;
+    float max_distance = 0.f;
+    int* idx = nullptr;  // top-2: idx2
+    float* d2 = nullptr;
+    int* match = nullptr;
+    sift_hip_dmatch* out = nullptr;
+    int* counts = nullptr;
+    hipStream_t stream = nullptr;
+
+    bool knn() const { return op == Op::KnnTable || op == Op::KnnList; }
+    const char* gate_name() const { return gate == Gate::Epipolar ? "epipolar gate" : "match gate"; }
+};
+
+// The pair of a single-pair entry point as a one-pair table (and its gate's positions) on that entry point's stack.
+struct OnePair {
+    const uint16_t *q, *t;
+    int nq, nt;
+    sift_hip_match_positions pos;
+};
+
+MatchCall fp16_call(Op op, const Wording& w, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
+                    const int* nt, void* stream) {
+    MatchCall c{op, &w};
+    c.P = P, c.q = q, c.nq = nq, c.t = t, c.nt = nt, c.stream = (hipStream_t)stream;
+    return c;
 }
+MatchCall codes_call(Op op, const Wording& w, const int8_t* codes, const int* keys, int P, const int* qrow0,
+                     const int* qkey0, const int* nq, const int* trow0, const int* tkey0, const int* nt, void* stream) {
+    MatchCall c{op, &w};
+    c.ready = true, c.codes = codes, c.keys = keys, c.P = P, c.nq = nq, c.nt = nt;
+    c.qrow0 = qrow0, c.qkey0 = qkey0, c.trow0 = trow0, c.tkey0 = tkey0, c.stream = (hipStream_t)stream;
+    return c;
+}
+MatchCall single_call(Op op, const Wording& w, const OnePair& o, void* stream) {
+    MatchCall c = fp16_call(op, w, 1, &o.q, &o.nq, &o.t, &o.nt, stream);
+    c.single = true;
+    return c;
+}
+void set_gate(MatchCall& c, OnePair& o, const sift_hip_match_gate* g) {
+    c.gate = Gate::Window, c.has_gate = g != nullptr;
+    if (!g) return;
+    o.pos = {g->query_xy, g->train_xy};
+    c.pos = &o.pos, c.qstride = g->query_stride, c.tstride = g->train_stride, c.radius = g->radius;
+}
+void set_gate(MatchCall& c, OnePair& o, const sift_hip_match_epipolar_gate* g) {
+    c.gate = Gate::Epipolar, c.has_gate = g != nullptr;
+    if (!g) return;
+    o.pos = {g->query_xy, g->train_xy};
+    c.pos = &o.pos, c.qstride = g->query_stride, c.tstride = g->train_stride, c.radius = g->radius;
+    c.max_error = g->max_error, c.F = g->F;
+}
+// The gate of a batched call: geometry == nullptr and epipolar == false is the window.
+void set_gate(MatchCall& c, bool epipolar, const sift_hip_match_positions* pos, int qstride, int tstride, float radius,
+              const void* geometry, int geometry_stride, float max_error) {
+    c.gate = epipolar ? Gate::Epipolar : Gate::Window;
+    c.pos = pos, c.qstride = qstride, c.tstride = tstride, c.radius = radius;
+    c.geometry = geometry, c.geometry_stride = geometry_stride, c.max_error = max_error;
+}
+
+bool needs_reverse(const sift_hip_match_filter& f) { return f.cross_check || f.ratio_both_ways; }
+
+// --- One checker.  The rules in the order of include/sift_hip.h ("Gated k nearest neighbours", which covers every
+// family's): what needs no matcher (k, a NaN max_distance, the gate's fields), the matcher, P and the arrays, the
+// pairs' sizes, the pointers of non-empty sets, the outputs.  The first broken rule is reported, in the family's
+// wording; nothing is launched or written.
+int check(const sift_hip_matcher* m, const MatchCall& c) {
+    auto bad = [](const std::string& msg) { return fail(SIFT_HIP_ERR_INVALID, msg); };
+    if (c.knn() && (c.k < 1 || c.k > kKnnMax)) return bad("k-NN: k outside 1..SIFT_HIP_KNN_MAX");
+    if (c.op == Op::KnnList && std::isnan(c.max_distance)) return bad("k-NN list: max_distance is NaN");
+    if (c.gate != Gate::None) {
+        const std::string what = c.gate_name();
+        if (!c.has_gate) return bad("null " + what);
+        if (c.qstride < 2 || c.tstride < 2) return bad(what + ": a position stride below 2 floats");
+        if (!(c.radius > 0.f)) return bad(what + ": the radius must be > 0");
+    }
+    if (c.gate == Gate::Epipolar) {
+        if (!(c.max_error > 0.f) || !std::isfinite(c.max_error))
+            return bad("epipolar gate: max_error must be > 0 and finite");
+        if (c.single) {
+            bool zero = true;
+            for (int i = 0; i < 9; i++) {
+                if (!std::isfinite(c.F[i])) return bad("epipolar gate: a non-finite entry of F");
+                zero = zero && c.F[i] == 0.f;
+            }
+            if (zero) return bad("epipolar gate: F is all zero");
+        } else {
+            // The nine floats themselves are on the device: the kernel applies the usable-geometry rule to them.
+            if (!c.geometry) return bad("epipolar gate: null geometry");
+            if (c.geometry_stride < 36 || c.geometry_stride % 4)
+                return bad("epipolar gate: geometry_stride_bytes must be >= 36 and a multiple of 4");
+        }
+    }
+    if (!m) return bad(c.words->matcher);
+    if (c.P <= 0 || c.P > m->maxP) return bad(c.words->pairs);
+    if (!c.nq || !c.nt) return bad(c.words->sizes);
+    if (c.gate != Gate::None && !c.pos) return bad("bad gated batch");
+    if (c.op == Op::List && !c.filter) return bad("bad match list arguments");
+    if (c.ready) {
+        if (!c.codes || !c.keys || !c.qrow0 || !c.qkey0 || !c.trow0 || !c.tkey0) return bad("bad code batch");
+    } else if (!c.q || !c.t) {
+        return bad(c.words->sets);
+    }
+    const bool rev = c.op == Op::List && needs_reverse(*c.filter);
+    for (int p = 0; p < c.P; p++) {
+        if (c.nq[p] < 0 || c.nt[p] < 0 || c.nq[p] > m->maxQ || c.nt[p] > m->maxT)
+            return bad("pair size exceeds matcher limits");
+        if (rev && (c.nt[p] > m->maxQ || c.nq[p] > m->maxT))
+            return bad("the reverse pair (roles swapped) exceeds matcher limits");
+    }
+    for (int p = 0; p < c.P; p++) {
+        if (c.ready) {
+            if (c.qrow0[p] < 0 || c.trow0[p] < 0 || c.qkey0[p] < 0 || c.tkey0[p] < 0) return bad("negative set row");
+        } else if ((c.nq[p] && !c.q[p]) || (c.nt[p] && !c.t[p])) {
+            return bad("null descriptor pointer");
+        }
+        if (c.gate != Gate::None && ((c.nq[p] && !c.pos[p].query_xy) || (c.nt[p] && !c.pos[p].train_xy)))
+            return bad(std::string(c.gate_name()) + ": null position pointer");
+    }
+    if (!c.host && c.op == Op::List && (!c.out || !c.counts)) return bad("bad match list arguments");
+    if (!c.host && c.op == Op::KnnList && (!c.out || !c.counts)) return bad("k-NN list: null out or count");
+    return SIFT_HIP_OK;
+}
+
+// Whether the matching stage of a call has an output row to write; the rule is the family's (include/sift_hip.h).  The
+// plain top-2 always launches.  A list of plain or single-pair gated pairs needs a pair with rows on both sides.
+// Everything else -- gated batches, every k-NN form, the single-pair gated top-2 -- needs a query row, or with `rev`
+// a train row (a query without train rows still gets its -1 / FLT_MAX row).
+bool has_output_row(const MatchCall& c, bool rev) {
+    if (c.op == Op::Top2 && c.gate == Gate::None) return true;
+    const bool both = c.op == Op::List && (c.gate == Gate::None || c.single);
+    for (int p = 0; p < c.P; p++)
+        if (both ? c.nq[p] > 0 && c.nt[p] > 0 : c.nq[p] > 0 || (rev && c.nt[p] > 0)) return true;
+    return false;
+}
+
+// --- The matcher's scratch of the list and the k-NN calls, at the first such call (not under stream capture).
+struct Alloc {
+    void** p;
+    size_t bytes;
+};
+int ensure_scratch(sift_hip_matcher* m, std::initializer_list<Alloc> bufs, const char* what) {
+    if (*bufs.begin()->p) return SIFT_HIP_OK;
+    HIPCHK(hipSetDevice(m->device));
+    for (const Alloc& b : bufs)
+        if (hipMalloc(b.p, b.bytes) != hipSuccess) {
+            for (const Alloc& f : bufs) {
+                if (*f.p) (void)hipFree(*f.p);
+                *f.p = nullptr;
+            }
+            return fail(SIFT_HIP_ERR_NOMEM, what);
+        }
+    return SIFT_HIP_OK;
+}
+int ensure_select_scratch(sift_hip_matcher* m) {
+    const size_t rows = 2 * (size_t)m->maxP * m->maxQ;
+    return ensure_scratch(m,
+                          {{(void**)&m->dSelIdx, sizeof(int) * 2 * rows},
+                           {(void**)&m->dSelD, sizeof(float) * 2 * rows},
+                           {(void**)&m->dList, sizeof(MatchRecord) * (size_t)m->maxQ},
+                           {(void**)&m->dCount, sizeof(int) * (size_t)m->maxP}},
+                          "match list scratch allocation failed");
+}
+int ensure_knn_scratch(sift_hip_matcher* m) {
+    const size_t rows = (size_t)m->maxP * m->maxQ * kKnnMax;
+    return ensure_scratch(m,
+                          {{(void**)&m->dKnnLists, sizeof(unsigned long long) * kKnnMax * m->knn_lists()},
+                           {(void**)&m->dKnnIdx, sizeof(int) * rows},
+                           {(void**)&m->dKnnD, sizeof(float) * rows},
+                           {(void**)&m->dKnnRec, sizeof(MatchRecord) * (size_t)m->maxQ * kKnnMax},
+                           {(void**)&m->dKnnCount, sizeof(int) * (size_t)m->maxP}},
+                          "k-NN scratch allocation failed");
+}
+
+// --- The pairs of a call as the launchers take them: the forward pairs [0, P) with their output rows at
+// sum_{r<p} nq[r], and -- when a filter needs them -- the reverse pairs [P, 2P) with the roles swapped, output rows at
+// sum nq + sum_{r<p} nt[r] (select_lists' layout).  A reverse pair shares its forward pair's geometry record.
+struct Pairs {
+    GatedPair pair[2 * kMaxMatchPairs];
+    int n;
+};
+void build_pairs(const MatchCall& c, bool rev, Pairs& g) {
+    int off = 0;
+    for (int p = 0; p < c.P; p++) {
+        const MatchPair pr = c.ready ? MatchPair{nullptr, nullptr, c.nq[p], c.nt[p], off, 0, 0, c.qrow0[p], c.trow0[p],
+                                                 c.qkey0[p], c.tkey0[p]}
+                                     : MatchPair{c.q[p], c.t[p], c.nq[p], c.nt[p], off, 0, 0, 0, 0, 0, 0};
+        g.pair[p] = GatedPair{pr, c.pos ? c.pos[p].query_xy : nullptr, c.pos ? c.pos[p].train_xy : nullptr, p, 0};
+        off += c.nq[p];
+    }
+    for (int p = 0; rev && p < c.P; p++) {
+        const GatedPair& f = g.pair[p];
+        const MatchPair& a = f.pr;
+        g.pair[c.P + p] = GatedPair{MatchPair{a.t, a.q, a.nt, a.nq, off, 0, 0, a.trow0, a.qrow0, a.tkrow0, a.qkrow0},
+                                    f.txy, f.qxy, p, 1};
+        off += a.nt;
+    }
+    g.n = rev ? 2 * c.P : c.P;
+}
+
+// The direction policy: forward and reverse pairs in one pass over 2P pairs when the matcher holds that many (and
+// `one_pass`: the launch takes more than one pair), else in two passes of P.  The bytes are the same either way; the
+// matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
+template <class Pass>
+int directions(const sift_hip_matcher* m, int P, bool rev, bool one_pass, Pass pass) {
+    if (rev && one_pass && 2 * P <= m->maxP) return pass(0, 2 * P);
+    if (int rc = pass(0, P)) return rc;
+    return rev ? pass(P, P) : SIFT_HIP_OK;
+}
+
+// n pairs in launches of at most kMaxGatedPairs (the gated launch records), ordered on the stream.
+template <class Launch>
+int chunked(const GatedPair* pairs, int n, Launch launch) {
+    for (int p0 = 0; p0 < n; p0 += kMaxGatedPairs)
+        if (int rc = launch(pairs + p0, std::min(kMaxGatedPairs, n - p0))) return rc;
+    return SIFT_HIP_OK;
+}
+
+// --- One staging function: what the pairs of a launch read their codes from.
+enum class Route {
+    Ready,     // a caller's code buffer: no conversion, no flags
+    Sidecars,  // one pair of detector buffers with fresh sidecars: q and t are separate code sets, no flags
+    Fused,     // one plain pair of foreign buffers: k_match_single converts as it goes (rows laid out, no prep launch)
+    Prepared,  // the distinct sets converted once by k_match_prep, with their flags
+};
+struct Staged {
+    CodeSet q, t;
+    SetFlags flags;
+};
+
+// The sidecar decision: a single pair -- of a plain call, or of a single-pair gated entry point; the batched gated
+// forms never -- with sidecars enabled, both sets non-empty and both detector buffers with fresh sidecars.
+bool sidecar_route(const sift_hip_matcher* m, const MatchCall& c, Staged* st) {
+    if (c.ready || c.P != 1 || !(c.single || c.gate == Gate::None) || !m->sidecars || c.nq[0] <= 0 || c.nt[0] <= 0)
+        return false;
+    Sidecar sq{}, stt{};
+    if (!find_sidecar(c.q[0], c.nq[0], &sq) || !find_sidecar(c.t[0], c.nt[0], &stt)) return false;
+    *st = Staged{CodeSet{sq.codes, sq.keys}, CodeSet{stt.codes, stt.keys}, kNoFlags};
+    return true;
+}
+
+// Checked pairs in, their set slots and rows filled in, and the code sets and flags to launch with out.  Ready and
+// Sidecars: st is the call's already.  Otherwise the distinct sets by pointer (a set used by several pairs is
+// prepared once, n = the largest use) are laid out in order of first appearance, get a new epoch, and -- Prepared --
+// are converted.
+int stage(sift_hip_matcher* m, const MatchCall& c, Route route, GatedPair* pairs, int n, Staged* st) {
+    if (route == Route::Ready) *st = Staged{CodeSet{c.codes, c.keys}, CodeSet{c.codes, c.keys}, kNoFlags};
+    if (route == Route::Ready || route == Route::Sidecars) return SIFT_HIP_OK;
+    MatchSets sets{};
+    auto set_of = [&](const uint16_t* ptr, int rows) {
+        for (int s = 0; s < sets.nsets; s++)
+            if (sets.set[s].src == ptr) {
+                sets.set[s].n = std::max(sets.set[s].n, rows);
+                return s;
+            }
+        sets.set[sets.nsets] = MatchSet{ptr, rows, 0};
+        return sets.nsets++;
+    };
+    for (int p = 0; p < n; p++) {
+        MatchPair& pr = pairs[p].pr;
+        pr.qset = set_of(pr.q, pr.nq);
+        pr.tset = set_of(pr.t, pr.nt);
+    }
+    long row = 0;
+    for (int s = 0; s < sets.nsets; s++) {
+        sets.set[s].row0 = (int)row;
+        row += sets.set[s].n;
+        sets.maxn = std::max(sets.maxn, sets.set[s].n);
+    }
+    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
+    for (int p = 0; p < n; p++) {
+        MatchPair& pr = pairs[p].pr;
+        pr.qrow0 = pr.qkrow0 = sets.set[pr.qset].row0;
+        pr.trow0 = pr.tkrow0 = sets.set[pr.tset].row0;
+    }
+    const CodeSet set{m->dCodes, m->dRowKeys};
+    *st = Staged{set, set, m->next_epoch()};
+    if (route == Route::Prepared) {
+        launch_match_prep(sets, m->dCodes, m->dRowKeys, st->flags, c.stream);
+        HIPCHK(hipGetLastError());
+    }
+    return SIFT_HIP_OK;
+}
+
+// --- The launches.
+struct Shape {
+    int maxq = 1, maxt = 1;
+    bool queries = false;
+    Shape(const GatedPair* pairs, int n) {
+        for (int p = 0; p < n; p++) {
+            maxq = std::max(maxq, pairs[p].pr.nq);
+            maxt = std::max(maxt, pairs[p].pr.nt);
+            queries = queries || pairs[p].pr.nq > 0;
+        }
+    }
+};
+
+// The plain launch records take a pass relative to its first output row: the pairs' offsets from it, the outputs at it.
+MatchBatch batch_of(const GatedPair* pairs, int n, int base) {
+    MatchBatch b{};
+    b.P = n;
+    for (int p = 0; p < n; p++) {
+        b.pair[p] = pairs[p].pr;
+        b.pair[p].out_off -= base;
+    }
+    return b;
+}
+MatchOut out_at(const MatchOut& o, int base) {
+    return MatchOut{o.ratio, o.ratio_on_squared, o.idx2 ? o.idx2 + 2 * (size_t)base : nullptr,
+                    o.d2 ? o.d2 + 2 * (size_t)base : nullptr, o.match ? o.match + base : nullptr};
+}
+
+// One pair on code sets of its own (k_match_direct, k_match_guided, k_match_epipolar): the sets start at the pair's
+// rows (sidecars: row 0) and the outputs at its row; a reverse pair reads the sets, the strides and F swapped.
+void launch_one(const sift_hip_matcher* m, const MatchCall& c, const GatedPair& g, const Staged& st, const MatchOut& out) {
+    const MatchPair& a = g.pr;
+    const MatchPair pr{a.q, a.t, a.nq, a.nt, 0, a.qset, a.tset, 0, 0, 0, 0};
+    const CodeSet &qs = g.swapped ? st.t : st.q, &ts = g.swapped ? st.q : st.t;
+    const CodeSet qc{qs.codes + (size_t)a.qrow0 * 128, qs.keys + a.qkrow0};
+    const CodeSet tc{ts.codes + (size_t)a.trow0 * 128, ts.keys + a.tkrow0};
+    const int qstride = g.swapped ? c.tstride : c.qstride, tstride = g.swapped ? c.qstride : c.tstride;
+    const MatchOut o = out_at(out, a.out_off);
+    if (c.gate == Gate::Epipolar) {
+        // e2 = max_error^2 is formed here, one float32 product.
+        EpipolarGate eg{g.qxy, g.txy, qstride, tstride, c.radius, c.max_error * c.max_error, {}};
+        for (int r = 0; r < 3; r++)
+            for (int col = 0; col < 3; col++) eg.F[3 * r + col] = c.F[g.swapped ? 3 * col + r : 3 * r + col];
+        launch_match_pair(pr, eg, qc, tc, st.flags, m->scratch(), o, c.stream);
+    } else {
+        const MatchGate mg{g.qxy, g.txy, qstride, tstride, c.radius};
+        launch_match_pair(pr, c.gate == Gate::Window ? &mg : nullptr, qc, tc, st.flags, m->scratch(), o, c.stream);
+    }
+}
+
+// A pass of the plain top-2 (sift_hip_match_batched / _codes_batched on n pairs): staged by itself, since a pass of
+// one pair goes through its sidecars or the fused kernel.  Ready codes keep the batched kernel's plan for one pair.
+int plain_pass(sift_hip_matcher* m, const MatchCall& c, bool direct, Staged& st, GatedPair* pairs, int n,
+               const MatchOut& out) {
+    const Route route = c.ready ? Route::Ready : direct ? Route::Sidecars : n == 1 ? Route::Fused : Route::Prepared;
+    if (int rc = stage(m, c, route, pairs, n, &st)) return rc;
+    const int base = pairs[0].pr.out_off;
+    const Shape sh(pairs, n);
+    if (route == Route::Sidecars)
+        launch_one(m, c, pairs[0], st, out);
+    else if (route == Route::Fused) {
+        MatchPair pr = pairs[0].pr;
+        pr.out_off = 0;
+        launch_match_single(pr, match_plan(sh.maxq, sh.maxt, 1).S, m->scratch(), out_at(out, base), c.stream);
+    } else
+        launch_match_codes(batch_of(pairs, n, base), match_plan(sh.maxq, sh.maxt, c.ready ? std::max(n, 2) : n).S, st.q,
+                           st.flags, m->scratch(), out_at(out, base), c.stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// What is uniform over a gated call as the launchers take it; e2 = max_error^2 is formed here, one float32 product.
+GatedCall gated_call(const MatchCall& c) {
+    const bool epi = c.gate == Gate::Epipolar;
+    return GatedCall{c.qstride, c.tstride, c.radius, epi ? c.max_error * c.max_error : 0.f, epi ? c.geometry : nullptr,
+                     epi ? c.geometry_stride : 0};
+}
+
+// The plan's splits of a k-NN launch, lowered to what the list scratch holds.
+int knn_splits(const sift_hip_matcher* m, const Shape& sh, int P) {
+    const size_t fit = m->knn_lists() / ((size_t)P * sh.maxq);  // >= 2: P <= maxP, maxq <= maxQ
+    return (int)std::min<size_t>(match_knn_splits(sh.maxq, sh.maxt, P), fit);
+}
+
+// The top-2 of a call's pairs (forward, and with `rev` reverse) into `out`.
+int top2(sift_hip_matcher* m, const MatchCall& c, bool rev, const MatchOut& out) {
+    Pairs g;
+    build_pairs(c, rev, g);
+    Staged st{};
+    const bool direct = sidecar_route(m, c, &st);
+    if (c.gate == Gate::None)
+        return directions(m, c.P, rev, !direct,
+                          [&](int p0, int n) { return plain_pass(m, c, direct, st, g.pair + p0, n, out); });
+    // Under a gate the call is staged once; a single-pair entry point launches pair by pair, a batch in chunks.
+    if (int rc = stage(m, c, c.ready ? Route::Ready : direct ? Route::Sidecars : Route::Prepared, g.pair, g.n, &st))
+        return rc;
+    const GatedCall call = gated_call(c);
+    return directions(m, c.P, rev, !c.single, [&](int p0, int n) {
+        if (c.single) {
+            launch_one(m, c, g.pair[p0], st, out);
+            HIPCHK(hipGetLastError());
+            return SIFT_HIP_OK;
+        }
+        return chunked(g.pair + p0, n, [&](const GatedPair* pairs, int np) {
+            GatedBatch b{};
+            b.P = np;
+            std::copy(pairs, pairs + np, b.pair);
+            launch_match_gated(b, call, st.q, st.flags, m->scratch(), out, c.stream);
+            HIPCHK(hipGetLastError());
+            return SIFT_HIP_OK;
+        });
+    });
+}
+
+// The k-NN table of a call's pairs into idx / d2, pair p at row sum_{r<p} nq[r]: one launch of the plain kernel, or
+// under a gate launches of at most kMaxGatedPairs pairs, each with the splits of its own pairs.
+int knn_table(sift_hip_matcher* m, const MatchCall& c, int* idx, float* d2) {
+    Pairs g;
+    build_pairs(c, false, g);
+    Staged st{};
+    const bool direct = sidecar_route(m, c, &st);
+    if (int rc = stage(m, c, c.ready ? Route::Ready : direct ? Route::Sidecars : Route::Prepared, g.pair, g.n, &st))
+        return rc;
+    if (c.gate == Gate::None) {
+        const Shape sh(g.pair, g.n);
+        launch_match_knn(batch_of(g.pair, g.n, 0), knn_splits(m, sh, g.n), c.k, st.q, st.t, st.flags,
+                         KnnScratch{m->dKnnLists, m->dDone, sh.maxq, m->sentinel()}, idx, d2, c.stream);
+        HIPCHK(hipGetLastError());
+        return SIFT_HIP_OK;
+    }
+    return chunked(g.pair, g.n, [&](const GatedPair* pairs, int np) {
+        const Shape sh(pairs, np);
+        if (!sh.queries) return SIFT_HIP_OK;
+        KnnGatedBatch b{};
+        b.P = np;
+        b.call = gated_call(c);
+        if (c.F) std::copy(c.F, c.F + 9, b.F);  // the single-pair epipolar call: the host's F is a kernel argument
+        for (int i = 0; i < np; i++)
+            b.pair[i] = pairs[i].pr, b.qxy[i] = pairs[i].qxy, b.txy[i] = pairs[i].txy, b.geom[i] = pairs[i].geom;
+        launch_match_knn_gated(b, c.gate == Gate::Epipolar, knn_splits(m, sh, np), c.k, st.q, st.t, st.flags,
+                               KnnScratch{m->dKnnLists, m->dDone, sh.maxq, m->sentinel()}, idx, d2, c.stream);
+        HIPCHK(hipGetLastError());
+        return SIFT_HIP_OK;
+    });
+}
+
+// Filter and compact the top-2 arrays in the select scratch: forward pair p at row sum_{r<p} nq[r], reverse pair p at
+// row sum nq + sum_{r<p} nt[r].
+int select_lists(sift_hip_matcher* m, const MatchCall& c) {
+    SelectBatch sb{};
+    int totq = 0;
+    for (int p = 0; p < c.P; p++) totq += c.nq[p];
+    int fwd = 0, rev = totq;
+    for (int p = 0; p < c.P; p++) {
+        // a pair without train rows keeps nothing (its top-2 rows hold no entry)
+        sb.pair[p] = SelectPair{c.nt[p] > 0 ? c.nq[p] : 0, c.nt[p], fwd, rev, fwd};
+        fwd += c.nq[p];
+        rev += c.nt[p];
+    }
+    const sift_hip_match_filter& f = *c.filter;
+    launch_match_select(sb, c.P, m->dSelIdx, m->dSelD,
+                        MatchFilter{f.ratio, f.ratio_on_squared, f.ratio_both_ways, f.max_distance, f.cross_check},
+                        reinterpret_cast<MatchRecord*>(c.out), c.counts, c.stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// The list of the matcher's k-NN table (pair p at row sum_{r<p} nq[r]): pair p's records from row k sum_{r<p} nq[r].
+int knn_select(sift_hip_matcher* m, const MatchCall& c) {
+    SelectBatch sb{};
+    int row = 0;
+    for (int p = 0; p < c.P; p++) {
+        sb.pair[p] = SelectPair{c.nq[p], 0, row, 0, c.k * row};
+        row += c.nq[p];
+    }
+    launch_knn_select(sb, c.P, c.k, m->dKnnIdx, m->dKnnD, c.max_distance, reinterpret_cast<MatchRecord*>(c.out),
+                      c.counts, c.stream);
+    HIPCHK(hipGetLastError());
+    return SIFT_HIP_OK;
+}
+
+// --- One host path: check, the matching stage where the call has an output row, then a list's selection.
+int run(sift_hip_matcher* m, MatchCall c) {
+    if (int rc = check(m, c)) return rc;
+    const bool rev = c.op == Op::List && needs_reverse(*c.filter), rows = has_output_row(c, rev);
+    // The operation's scratch, at the matcher's first such call; a table into the caller's buffers needs it to launch.
+    if (c.op == Op::List)
+        if (int rc = ensure_select_scratch(m)) return rc;
+    if (c.op == Op::KnnList || (c.op == Op::KnnTable && (c.host || rows)))
+        if (int rc = ensure_knn_scratch(m)) return rc;
+    if (c.op == Op::KnnList || (c.op == Op::KnnTable && c.host)) c.idx = m->dKnnIdx, c.d2 = m->dKnnD;
+    if (c.host) {
+        c.match = m->dMatch;
+        c.out = reinterpret_cast<sift_hip_dmatch*>(c.op == Op::List ? m->dList : m->dKnnRec);
+        c.counts = c.op == Op::List ? m->dCount : m->dKnnCount;
+    }
+    if (rows) {
+        HIPCHK(hipSetDevice(m->device));
+        if (c.knn()) {
+            if (int rc = knn_table(m, c, c.idx, c.d2)) return rc;
+        } else {
+            const MatchOut out = c.op == Op::List ? MatchOut{0.f, 0, m->dSelIdx, m->dSelD, nullptr}
+                                                  : MatchOut{c.ratio, c.ratio_on_squared, c.idx, c.d2, c.match};
+            if (int rc = top2(m, c, rev, out)) return rc;
+        }
+    }
+    if (c.op == Op::Top2 || c.op == Op::KnnTable) return SIFT_HIP_OK;
+    HIPCHK(hipSetDevice(m->device));
+    return c.op == Op::List ? select_lists(m, c) : knn_select(m, c);
+}
+
+// The _host forms: run into the matcher's own buffers, synchronously, then one read-back each for the lists (the
+// count, then min(count, cap) records) and the k-NN tables.  The host outputs are judged first (the count is zeroed
+// before anything else can refuse); the plain list call words a null matcher or filter with them.
+int run_list_host(sift_hip_matcher* m, MatchCall c, sift_hip_dmatch* out_host, int cap, int* count) {
+    const bool list = c.op == Op::List;
+    if ((list && (!c.filter || (!m && c.gate == Gate::None))) || !count || cap < 0 || (cap > 0 && !out_host))
+        return fail(SIFT_HIP_ERR_INVALID, list ? "null argument" : "k-NN list: null out or count");
+    *count = 0;
+    c.host = true;
+    if (int rc = run(m, c)) return rc;
+    HIPCHK(hipMemcpy(count, list ? m->dCount : m->dKnnCount, sizeof(int), hipMemcpyDeviceToHost));
+    const int n = std::min(*count, cap);
+    if (n > 0)
+        HIPCHK(hipMemcpy(out_host, list ? m->dList : m->dKnnRec, sizeof(sift_hip_dmatch) * (size_t)n,
+                         hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+int run_knn_host(sift_hip_matcher* m, MatchCall c, int* idx_host, float* d2_host) {
+    c.host = true;
+    if (int rc = run(m, c)) return rc;
+    const size_t n = (size_t)c.nq[0] * c.k;
+    if (n && idx_host) HIPCHK(hipMemcpy(idx_host, m->dKnnIdx, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (n && d2_host) HIPCHK(hipMemcpy(d2_host, m->dKnnD, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return SIFT_HIP_OK;
+}
+
+// The call records of the entry families.
+MatchCall top2_call(MatchCall c, float ratio, int ratio_on_squared, int* idx2, float* d2, int* match) {
+    c.ratio = ratio, c.ratio_on_squared = ratio_on_squared, c.idx = idx2, c.d2 = d2, c.match = match;
+    return c;
+}
+MatchCall list_call(MatchCall c, const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts) {
+    c.filter = filter, c.out = out, c.counts = counts;
+    return c;
+}
+MatchCall knn_call(MatchCall c, int k, int* idx, float* d2) {
+    c.k = k, c.idx = idx, c.d2 = d2;
+    return c;
+}
+MatchCall knn_list_call(MatchCall c, int k, float max_distance, sift_hip_dmatch* out, int* counts) {
+    c.k = k, c.max_distance = max_distance, c.out = out, c.counts = counts;
+    return c;
+}
+template <class G>
+MatchCall gated_single(Op op, OnePair& o, const G* gate, void* stream) {
+    MatchCall c = single_call(op, kGatedWords, o, stream);
+    set_gate(c, o, gate);
+    return c;
+}
+MatchCall gated_batch(Op op, bool epipolar, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
+                      const int* nt, const sift_hip_match_positions* pos, int qstride, int tstride, float radius,
+                      const void* geometry, int geometry_stride, float max_error, void* stream) {
+    MatchCall c = fp16_call(op, op == Op::KnnTable || op == Op::KnnList ? kGatedKnnWords : kGatedWords, P, q, nq, t, nt,
+                            stream);
+    set_gate(c, epipolar, pos, qstride, tstride, radius, geometry, geometry_stride, max_error);
+    return c;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -180,106 +791,10 @@ int sift_hip_matcher_destroy(sift_hip_matcher_t m) {
     return SIFT_HIP_OK;
 }
 
-int sift_hip_match_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                           const uint16_t* const* t, const int* nt, float ratio, int ratio_on_squared, int* idx2,
-                           float* d2, int* match, void* stream) {
-    if (!m || P <= 0 || P > m->maxP || !q || !nq || !t || !nt) return fail(SIFT_HIP_ERR_INVALID, "bad batch");
-    const MatchOut out{ratio, ratio_on_squared, idx2, d2, match};
-    Sidecar sq{}, st{};
-    if (P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && nq[0] <= m->maxQ && nt[0] <= m->maxT &&
-        find_sidecar(q[0], nq[0], &sq) && find_sidecar(t[0], nt[0], &st)) {
-        // Both sets are detector buffers: their codes are ready (no conversion).
-        HIPCHK(hipSetDevice(m->device));
-        const MatchPair pr{q[0], t[0], nq[0], nt[0], 0, 0, 0, 0, 0, 0, 0};
-        launch_match_pair(pr, nullptr, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags, m->scratch(), out,
-                          (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return SIFT_HIP_OK;
-    }
-    MatchBatch b{};
-    MatchSets sets{};
-    b.P = P;
-    // Distinct sets by pointer (a set used by several pairs is prepared once).
-    auto set_of = [&](const uint16_t* ptr, int n) {
-        for (int k = 0; k < sets.nsets; k++)
-            if (sets.set[k].src == ptr) {
-                sets.set[k].n = std::max(sets.set[k].n, n);
-                return k;
-            }
-        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
-        return sets.nsets++;
-    };
-    int off = 0, maxq = 1, maxt = 1;
-    for (int p = 0; p < P; p++) {
-        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
-            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
-        b.pair[p] = MatchPair{q[p], t[p], nq[p], nt[p], off, qs, ts, 0, 0, 0, 0};
-        off += nq[p];
-        maxq = std::max(maxq, nq[p]);
-        maxt = std::max(maxt, nt[p]);
-    }
-    long row = 0;
-    for (int k = 0; k < sets.nsets; k++) {
-        sets.set[k].row0 = (int)row;
-        row += sets.set[k].n;
-        sets.maxn = std::max(sets.maxn, sets.set[k].n);
-    }
-    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-    for (int p = 0; p < P; p++) {
-        b.pair[p].qrow0 = b.pair[p].qkrow0 = sets.set[b.pair[p].qset].row0;
-        b.pair[p].trow0 = b.pair[p].tkrow0 = sets.set[b.pair[p].tset].row0;
-    }
-    const SetFlags flags = m->next_epoch();
-    HIPCHK(hipSetDevice(m->device));
-    const int S = match_plan(maxq, maxt, P).S;
-    if (P == 1) {
-        // One pair of foreign buffers: the fused kernel converts as it goes (no prep launch).
-        launch_match_single(b.pair[0], S, m->scratch(), out, (hipStream_t)stream);
-    } else {
-        launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, (hipStream_t)stream);
-        launch_match_codes(b, S, CodeSet{m->dCodes, m->dRowKeys}, flags, m->scratch(), out, (hipStream_t)stream);
-    }
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-int sift_hip_match_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P, const int* qrow0,
-                                 const int* qkey0, const int* nq, const int* trow0, const int* tkey0, const int* nt,
-                                 float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, void* stream) {
-    if (!m || P <= 0 || P > m->maxP || !codes || !keys || !qrow0 || !qkey0 || !nq || !trow0 || !tkey0 || !nt)
-        return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
-    MatchBatch b{};
-    b.P = P;
-    int off = 0, maxq = 1, maxt = 1;
-    for (int p = 0; p < P; p++) {
-        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
-            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
-            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
-        b.pair[p] = MatchPair{nullptr, nullptr, nq[p], nt[p], off, 0, 0, qrow0[p], trow0[p], qkey0[p], tkey0[p]};
-        off += nq[p];
-        maxq = std::max(maxq, nq[p]);
-        maxt = std::max(maxt, nt[p]);
-    }
-    HIPCHK(hipSetDevice(m->device));
-    const int S = match_plan(maxq, maxt, std::max(P, 2)).S;  // the batched kernel's plan, also for one pair
-    launch_match_codes(b, S, CodeSet{codes, keys}, kNoFlags, m->scratch(),
-                       MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
 int sift_hip_descriptors_written(const uint16_t* desc) {
     if (!desc) return fail(SIFT_HIP_ERR_INVALID, "null descriptor buffer");
     (void)sidecar_written(desc);  // a foreign buffer has no sidecar: nothing to drop
     return SIFT_HIP_OK;
-}
-
-int sift_hip_match_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, float ratio,
-                          int ratio_on_squared, int* idx2, float* d2, int* match, void* stream) {
-    return sift_hip_match_batched(m, 1, &q, &nq, &t, &nt, ratio, ratio_on_squared, idx2, d2, match, stream);
 }
 
 int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, int* waves) {
@@ -290,428 +805,9 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
     return SIFT_HIP_OK;
 }
 
-int sift_hip_match_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, float ratio,
-                        int ratio_on_squared, int* out) {
-    if (!m || !out) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    if (nq <= 0) return SIFT_HIP_OK;
-    int rc = sift_hip_match_device(m, q, nq, t, nt, ratio, ratio_on_squared, nullptr, nullptr, m->dMatch, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out, m->dMatch, sizeof(int) * nq, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-}  // extern "C"
-
-// --- Match lists -------------------------------------------------------------
-static_assert(sizeof(sift_hip_dmatch) == sizeof(MatchRecord) && sizeof(sift_hip_dmatch) == 16, "cv::DMatch layout");
-static_assert(sizeof(sift_hip_match_filter) == sizeof(MatchFilter), "the filter is passed to the kernel as it is");
-
-namespace {
-
-bool needs_reverse(const sift_hip_match_filter& f) { return f.cross_check || f.ratio_both_ways; }
-
-// The select scratch, at the first list call of a matcher (not under stream capture).
-int ensure_select_scratch(sift_hip_matcher* m) {
-    if (m->dSelIdx) return SIFT_HIP_OK;
-    const size_t rows = 2 * (size_t)m->maxP * m->maxQ;
-    HIPCHK(hipSetDevice(m->device));
-    if (hipMalloc((void**)&m->dSelIdx, sizeof(int) * 2 * rows) != hipSuccess ||
-        hipMalloc((void**)&m->dSelD, sizeof(float) * 2 * rows) != hipSuccess ||
-        hipMalloc((void**)&m->dList, sizeof(MatchRecord) * (size_t)m->maxQ) != hipSuccess ||
-        hipMalloc((void**)&m->dCount, sizeof(int) * (size_t)m->maxP) != hipSuccess) {
-        for (void** p : {(void**)&m->dSelIdx, (void**)&m->dSelD, (void**)&m->dList, (void**)&m->dCount}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        return fail(SIFT_HIP_ERR_NOMEM, "match list scratch allocation failed");
-    }
-    return SIFT_HIP_OK;
-}
-
-// Argument rules shared by the list entry points (nothing is launched on a failure).
-int check_list_args(sift_hip_matcher* m, int P, const int* nq, const int* nt, const sift_hip_match_filter* filter,
-                    const void* out, const void* counts) {
-    if (!m || !filter || !out || !counts || P <= 0 || P > m->maxP || !nq || !nt)
-        return fail(SIFT_HIP_ERR_INVALID, "bad match list arguments");
-    const bool rev = needs_reverse(*filter);
-    for (int p = 0; p < P; p++) {
-        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
-            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-        if (rev && (nt[p] > m->maxQ || nq[p] > m->maxT))
-            return fail(SIFT_HIP_ERR_INVALID, "the reverse pair (roles swapped) exceeds matcher limits");
-    }
-    return SIFT_HIP_OK;
-}
-
-// Filter and compact the top-2 arrays in the select scratch: forward pair p at row sum_{r<p} nq[r], reverse pair p at
-// row sum nq + sum_{r<p} nt[r].
-int select_lists(sift_hip_matcher* m, int P, const int* nq, const int* nt, const sift_hip_match_filter& filter,
-                 sift_hip_dmatch* out, int* counts, hipStream_t stream) {
-    SelectBatch sb{};
-    int totq = 0;
-    for (int p = 0; p < P; p++) totq += nq[p];
-    int fwd = 0, rev = totq;
-    for (int p = 0; p < P; p++) {
-        // a pair without train rows keeps nothing (its top-2 rows hold no entry)
-        sb.pair[p] = SelectPair{nt[p] > 0 ? nq[p] : 0, nt[p], fwd, rev, fwd};
-        fwd += nq[p];
-        rev += nt[p];
-    }
-    const MatchFilter f{filter.ratio, filter.ratio_on_squared, filter.ratio_both_ways, filter.max_distance,
-                        filter.cross_check};
-    launch_match_select(sb, P, m->dSelIdx, m->dSelD, f, reinterpret_cast<MatchRecord*>(out), counts, stream);
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-bool any_pair(int P, const int* nq, const int* nt) {
-    for (int p = 0; p < P; p++)
-        if (nq[p] > 0 && nt[p] > 0) return true;
-    return false;
-}
-
-// The matcher's own list (dList, dCount: one pair) back to the host: the count, then min(count, cap) records.
-int read_list(sift_hip_matcher* m, sift_hip_dmatch* out_host, int cap, int* count) {
-    HIPCHK(hipMemcpy(count, m->dCount, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min(*count, cap);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dList, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-void sift_hip_default_match_filter(sift_hip_match_filter* f) {
-    if (!f) return;
-    f->ratio = 0.8f;
-    f->ratio_on_squared = 0;
-    f->ratio_both_ways = 0;
-    f->max_distance = 0.f;
-    f->cross_check = 1;
-}
-
-int sift_hip_match_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                const uint16_t* const* t, const int* nt, const sift_hip_match_filter* filter,
-                                sift_hip_dmatch* out, int* counts, void* stream) {
-    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
-    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "bad match list arguments");
-    for (int p = 0; p < P; p++)
-        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-    if (int rc = ensure_select_scratch(m)) return rc;
-    const bool rev = needs_reverse(*filter);
-    if (any_pair(P, nq, nt)) {
-        int totq = 0;
-        for (int p = 0; p < P; p++) totq += nq[p];
-        Sidecar sq{}, st{};
-        // A single pair of detector buffers goes through its sidecars in both directions (two direct launches).
-        const bool direct = P == 1 && m->sidecars && find_sidecar(q[0], nq[0], &sq) && find_sidecar(t[0], nt[0], &st);
-        if (rev && 2 * P <= m->maxP && !direct) {
-            // Forward and reverse pairs in one launch; the sets are deduplicated by pointer, so each is converted once.
-            const uint16_t *q2[kMaxMatchPairs], *t2[kMaxMatchPairs];
-            int nq2[kMaxMatchPairs], nt2[kMaxMatchPairs];
-            for (int p = 0; p < P; p++) {
-                q2[p] = q[p], t2[p] = t[p], nq2[p] = nq[p], nt2[p] = nt[p];
-                q2[P + p] = t[p], t2[P + p] = q[p], nq2[P + p] = nt[p], nt2[P + p] = nq[p];
-            }
-            if (int rc = sift_hip_match_batched(m, 2 * P, q2, nq2, t2, nt2, 0.f, 0, m->dSelIdx, m->dSelD, nullptr, stream))
-                return rc;
-        } else {
-            // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
-            if (int rc = sift_hip_match_batched(m, P, q, nq, t, nt, 0.f, 0, m->dSelIdx, m->dSelD, nullptr, stream))
-                return rc;
-            if (rev)
-                if (int rc = sift_hip_match_batched(m, P, t, nt, q, nq, 0.f, 0, m->dSelIdx + 2 * (size_t)totq,
-                                                    m->dSelD + 2 * (size_t)totq, nullptr, stream))
-                    return rc;
-        }
-    }
-    HIPCHK(hipSetDevice(m->device));
-    return select_lists(m, P, nq, nt, *filter, out, counts, (hipStream_t)stream);
-}
-
-int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
-                                      const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
-                                      const int* tkey0, const int* nt, const sift_hip_match_filter* filter,
-                                      sift_hip_dmatch* out, int* counts, void* stream) {
-    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
-    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
-    for (int p = 0; p < P; p++)
-        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
-            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
-    if (int rc = ensure_select_scratch(m)) return rc;
-    const bool rev = needs_reverse(*filter);
-    if (any_pair(P, nq, nt)) {
-        int totq = 0;
-        for (int p = 0; p < P; p++) totq += nq[p];
-        if (rev && 2 * P <= m->maxP) {
-            int a[6][kMaxMatchPairs];  // qrow0, qkey0, nq, trow0, tkey0, nt of the 2P pairs
-            for (int p = 0; p < P; p++) {
-                a[0][p] = qrow0[p], a[1][p] = qkey0[p], a[2][p] = nq[p], a[3][p] = trow0[p], a[4][p] = tkey0[p], a[5][p] = nt[p];
-                a[0][P + p] = trow0[p], a[1][P + p] = tkey0[p], a[2][P + p] = nt[p];
-                a[3][P + p] = qrow0[p], a[4][P + p] = qkey0[p], a[5][P + p] = nq[p];
-            }
-            if (int rc = sift_hip_match_codes_batched(m, codes, keys, 2 * P, a[0], a[1], a[2], a[3], a[4], a[5], 0.f, 0,
-                                                      m->dSelIdx, m->dSelD, nullptr, stream))
-                return rc;
-        } else {
-            if (int rc = sift_hip_match_codes_batched(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, 0.f, 0,
-                                                      m->dSelIdx, m->dSelD, nullptr, stream))
-                return rc;
-            if (rev)
-                if (int rc = sift_hip_match_codes_batched(m, codes, keys, P, trow0, tkey0, nt, qrow0, qkey0, nq, 0.f, 0,
-                                                          m->dSelIdx + 2 * (size_t)totq, m->dSelD + 2 * (size_t)totq,
-                                                          nullptr, stream))
-                    return rc;
-        }
-    }
-    HIPCHK(hipSetDevice(m->device));
-    return select_lists(m, P, nq, nt, *filter, out, counts, (hipStream_t)stream);
-}
-
-int sift_hip_match_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, void* stream) {
-    return sift_hip_match_list_batched(m, 1, &q, &nq, &t, &nt, filter, out, count, stream);
-}
-
-int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                             const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count) {
-    if (!m || !filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    *count = 0;
-    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
-    if (int rc = ensure_select_scratch(m)) return rc;
-    if (int rc = sift_hip_match_list_device(m, q, nq, t, nt, filter, reinterpret_cast<sift_hip_dmatch*>(m->dList),
-                                            m->dCount, nullptr))
-        return rc;
-    return read_list(m, out_host, cap, count);
-}
-
-}  // extern "C"
-
-// --- k nearest neighbours and capped radius lists ----------------------------------
-static_assert(SIFT_HIP_KNN_MAX == kKnnMax, "the kernel's largest instantiation");
-
-namespace {
-
-// The k-NN scratch, at the first k-NN call of a matcher (not under stream capture).
-int ensure_knn_scratch(sift_hip_matcher* m) {
-    if (m->dKnnLists) return SIFT_HIP_OK;
-    const size_t rows = (size_t)m->maxP * m->maxQ * kKnnMax;
-    HIPCHK(hipSetDevice(m->device));
-    if (hipMalloc((void**)&m->dKnnLists, sizeof(unsigned long long) * kKnnMax * m->knn_lists()) != hipSuccess ||
-        hipMalloc((void**)&m->dKnnIdx, sizeof(int) * rows) != hipSuccess ||
-        hipMalloc((void**)&m->dKnnD, sizeof(float) * rows) != hipSuccess ||
-        hipMalloc((void**)&m->dKnnRec, sizeof(MatchRecord) * (size_t)m->maxQ * kKnnMax) != hipSuccess ||
-        hipMalloc((void**)&m->dKnnCount, sizeof(int) * (size_t)m->maxP) != hipSuccess) {
-        for (void** p : {(void**)&m->dKnnLists, (void**)&m->dKnnIdx, (void**)&m->dKnnD, (void**)&m->dKnnRec,
-                         (void**)&m->dKnnCount}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        return fail(SIFT_HIP_ERR_NOMEM, "k-NN scratch allocation failed");
-    }
-    return SIFT_HIP_OK;
-}
-
-// The refusals, judged before any device call: k (and for a list max_distance) need nothing else, then the matcher,
-// then the pairs.
-int check_knn(const sift_hip_matcher* m, int k) {
-    if (k < 1 || k > kKnnMax) return fail(SIFT_HIP_ERR_INVALID, "k-NN: k outside 1..SIFT_HIP_KNN_MAX");
-    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
-    return SIFT_HIP_OK;
-}
-int check_knn_list(const sift_hip_matcher* m, int k, float max_distance, const void* out, const void* count) {
-    if (std::isnan(max_distance)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: max_distance is NaN");
-    if (int rc = check_knn(m, k)) return rc;
-    if (!out || !count) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
-    return SIFT_HIP_OK;
-}
-int check_knn_pairs(const sift_hip_matcher* m, int P, const int* nq, const int* nt) {
-    if (P <= 0 || P > m->maxP) return fail(SIFT_HIP_ERR_INVALID, "k-NN: P outside 1..max_pairs");
-    if (!nq || !nt) return fail(SIFT_HIP_ERR_INVALID, "k-NN: null size array");
-    for (int p = 0; p < P; p++)
-        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
-            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-    return SIFT_HIP_OK;
-}
-int check_knn_sets(int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t, const int* nt) {
-    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "k-NN: null descriptor array");
-    for (int p = 0; p < P; p++)
-        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-    return SIFT_HIP_OK;
-}
-int check_knn_codes(int P, const int8_t* codes, const int* keys, const int* qrow0, const int* qkey0, const int* trow0,
-                    const int* tkey0) {
-    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
-    for (int p = 0; p < P; p++)
-        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
-            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
-    return SIFT_HIP_OK;
-}
-
-bool any_queries(int P, const int* nq) {
-    for (int p = 0; p < P; p++)
-        if (nq[p] > 0) return true;
-    return false;
-}
-
-// One k-NN launch on the pairs of b: the plan's splits, lowered to what the list scratch holds.
-int knn_launch(sift_hip_matcher* m, const MatchBatch& b, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
-               int* idx, float* d2, hipStream_t stream) {
-    int maxq = 1, maxt = 1;
-    for (int p = 0; p < b.P; p++) {
-        maxq = std::max(maxq, b.pair[p].nq);
-        maxt = std::max(maxt, b.pair[p].nt);
-    }
-    const size_t fit = m->knn_lists() / ((size_t)b.P * maxq);  // >= 2: P <= maxP, maxq <= maxQ
-    const int S = (int)std::min<size_t>(match_knn_splits(maxq, maxt, b.P), fit);
-    launch_match_knn(b, S, k, q, t, flags, KnnScratch{m->dKnnLists, m->dDone, maxq, m->sentinel()}, idx, d2, stream);
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-// The table of checked fp16 pairs, pair p at row sum_{r<p} nq[r].  A single pair of detector buffers with fresh
-// sidecars matches their codes; otherwise the call's distinct sets are converted once (k_match_prep).
-int knn_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
-             const int* nt, int k, int* idx, float* d2, hipStream_t stream) {
-    if (!any_queries(P, nq)) return SIFT_HIP_OK;
-    MatchBatch b{};
-    MatchSets sets{};
-    b.P = P;
-    auto set_of = [&](const uint16_t* ptr, int n) {
-        for (int s = 0; s < sets.nsets; s++)
-            if (sets.set[s].src == ptr) {
-                sets.set[s].n = std::max(sets.set[s].n, n);
-                return s;
-            }
-        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
-        return sets.nsets++;
-    };
-    int off = 0;
-    for (int p = 0; p < P; p++) {
-        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
-        b.pair[p] = MatchPair{q[p], t[p], nq[p], nt[p], off, qs, ts, 0, 0, 0, 0};
-        off += nq[p];
-    }
-    long row = 0;
-    for (int s = 0; s < sets.nsets; s++) {
-        sets.set[s].row0 = (int)row;
-        row += sets.set[s].n;
-        sets.maxn = std::max(sets.maxn, sets.set[s].n);
-    }
-    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    Sidecar sq{}, st{};
-    if (P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && find_sidecar(q[0], nq[0], &sq) &&
-        find_sidecar(t[0], nt[0], &st))
-        return knn_launch(m, b, k, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags, idx, d2, stream);
-    for (int p = 0; p < P; p++) {
-        b.pair[p].qrow0 = b.pair[p].qkrow0 = sets.set[b.pair[p].qset].row0;
-        b.pair[p].trow0 = b.pair[p].tkrow0 = sets.set[b.pair[p].tset].row0;
-    }
-    const SetFlags flags = m->next_epoch();
-    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
-    HIPCHK(hipGetLastError());
-    const CodeSet set{m->dCodes, m->dRowKeys};
-    return knn_launch(m, b, k, set, set, flags, idx, d2, stream);
-}
-
-// The list of a table in idx / d2 (pair p at row sum_{r<p} nq[r]): pair p's records from row k sum_{r<p} nq[r].
-int knn_select(sift_hip_matcher* m, int P, const int* nq, int k, const int* idx, const float* d2, float max_distance,
-               sift_hip_dmatch* out, int* counts, hipStream_t stream) {
-    SelectBatch sb{};
-    int row = 0;
-    for (int p = 0; p < P; p++) {
-        sb.pair[p] = SelectPair{nq[p], 0, row, 0, k * row};
-        row += nq[p];
-    }
-    HIPCHK(hipSetDevice(m->device));
-    launch_knn_select(sb, P, k, idx, d2, max_distance, reinterpret_cast<MatchRecord*>(out), counts, stream);
-    HIPCHK(hipGetLastError());
-    return SIFT_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int sift_hip_match_knn_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                               const uint16_t* const* t, const int* nt, int k, int* idx, float* d2, void* stream) {
-    if (int rc = check_knn(m, k)) return rc;
-    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
-    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
-    return knn_fp16(m, P, q, nq, t, nt, k, idx, d2, (hipStream_t)stream);
-}
-
-int sift_hip_match_knn_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
-                              int* idx, float* d2, void* stream) {
-    return sift_hip_match_knn_batched(m, 1, &q, &nq, &t, &nt, k, idx, d2, stream);
-}
-
-int sift_hip_match_knn_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
-                                     const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
-                                     const int* tkey0, const int* nt, int k, int* idx, float* d2, void* stream) {
-    if (int rc = check_knn(m, k)) return rc;
-    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
-    if (int rc = check_knn_codes(P, codes, keys, qrow0, qkey0, trow0, tkey0)) return rc;
-    if (!any_queries(P, nq)) return SIFT_HIP_OK;
-    MatchBatch b{};
-    b.P = P;
-    int off = 0;
-    for (int p = 0; p < P; p++) {
-        b.pair[p] = MatchPair{nullptr, nullptr, nq[p], nt[p], off, 0, 0, qrow0[p], trow0[p], qkey0[p], tkey0[p]};
-        off += nq[p];
-    }
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    const CodeSet set{codes, keys};
-    return knn_launch(m, b, k, set, set, kNoFlags, idx, d2, (hipStream_t)stream);
-}
-
-int sift_hip_match_knn_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
-                            int* idx_host, float* d2_host) {
-    if (int rc = check_knn(m, k)) return rc;
-    if (int rc = check_knn_pairs(m, 1, &nq, &nt)) return rc;
-    if (int rc = check_knn_sets(1, &q, &nq, &t, &nt)) return rc;
-    if (nq == 0) return SIFT_HIP_OK;
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = knn_fp16(m, 1, &q, &nq, &t, &nt, k, m->dKnnIdx, m->dKnnD, nullptr)) return rc;
-    if (idx_host) HIPCHK(hipMemcpy(idx_host, m->dKnnIdx, sizeof(int) * (size_t)nq * k, hipMemcpyDeviceToHost));
-    if (d2_host) HIPCHK(hipMemcpy(d2_host, m->dKnnD, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-int sift_hip_match_knn_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                    const uint16_t* const* t, const int* nt, int k, float max_distance,
-                                    sift_hip_dmatch* out, int* counts, void* stream) {
-    if (int rc = check_knn_list(m, k, max_distance, out, counts)) return rc;
-    if (int rc = check_knn_pairs(m, P, nq, nt)) return rc;
-    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = knn_fp16(m, P, q, nq, t, nt, k, m->dKnnIdx, m->dKnnD, (hipStream_t)stream)) return rc;
-    return knn_select(m, P, nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, counts, (hipStream_t)stream);
-}
-
-int sift_hip_match_knn_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
-                                   float max_distance, sift_hip_dmatch* out, int* count, void* stream) {
-    return sift_hip_match_knn_list_batched(m, 1, &q, &nq, &t, &nt, k, max_distance, out, count, stream);
-}
-
-int sift_hip_match_knn_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
-                                 float max_distance, sift_hip_dmatch* out_host, int cap, int* count) {
-    if (!count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
-    *count = 0;
-    if (int rc = check_knn_list(m, k, max_distance, m, m)) return rc;  // the device outputs are the matcher's own
-    if (int rc = check_knn_pairs(m, 1, &nq, &nt)) return rc;
-    if (int rc = check_knn_sets(1, &q, &nq, &t, &nt)) return rc;
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = sift_hip_match_knn_list_device(m, q, nq, t, nt, k, max_distance,
-                                                reinterpret_cast<sift_hip_dmatch*>(m->dKnnRec), m->dKnnCount, nullptr))
-        return rc;
-    HIPCHK(hipMemcpy(count, m->dKnnCount, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min(*count, cap);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dKnnRec, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
+int sift_hip_match_guided_plan(int nq, int nt, int* splits) {
+    if (nq < 0 || nt < 0 || !splits) return fail(SIFT_HIP_ERR_INVALID, "bad match shape");
+    *splits = match_direct_splits(nq, nt);
     return SIFT_HIP_OK;
 }
 
@@ -722,384 +818,70 @@ int sift_hip_match_knn_plan(int nq, int nt, int pairs, int k, int* splits) {
     return SIFT_HIP_OK;
 }
 
-}  // extern "C"
+void sift_hip_default_match_filter(sift_hip_match_filter* f) {
+    if (!f) return;
+    f->ratio = 0.8f;
+    f->ratio_on_squared = 0;
+    f->ratio_both_ways = 0;
+    f->max_distance = 0.f;
+    f->cross_check = 1;
+}
 
-// --- Guided matching -----------------------------------------------------------
-namespace {
+// --- Top-2 ----------------------------------------------------------------------
+int sift_hip_match_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                           const uint16_t* const* t, const int* nt, float ratio, int ratio_on_squared, int* idx2,
+                           float* d2, int* match, void* stream) {
+    return run(m, top2_call(fp16_call(Op::Top2, kBatchWords, P, q, nq, t, nt, stream), ratio, ratio_on_squared, idx2, d2,
+                            match));
+}
 
-// The rules both gates share (`what` names the gate in the message): the position fields, which need no matcher ...
-int check_gate_positions(const char* what, int query_stride, int train_stride, float radius) {
-    if (query_stride < 2 || train_stride < 2)
-        return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": a position stride below 2 floats");
-    if (!(radius > 0.f)) return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": the radius must be > 0");
+int sift_hip_match_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P, const int* qrow0,
+                                 const int* qkey0, const int* nq, const int* trow0, const int* tkey0, const int* nt,
+                                 float ratio, int ratio_on_squared, int* idx2, float* d2, int* match, void* stream) {
+    return run(m, top2_call(codes_call(Op::Top2, kCodeWords, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, stream),
+                            ratio, ratio_on_squared, idx2, d2, match));
+}
+
+int sift_hip_match_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, float ratio,
+                          int ratio_on_squared, int* idx2, float* d2, int* match, void* stream) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run(m, top2_call(single_call(Op::Top2, kBatchWords, o, stream), ratio, ratio_on_squared, idx2, d2, match));
+}
+
+int sift_hip_match_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, float ratio,
+                        int ratio_on_squared, int* out) {
+    if (!m || !out) return fail(SIFT_HIP_ERR_INVALID, "null argument");
+    if (nq <= 0) return SIFT_HIP_OK;
+    const OnePair o{q, t, nq, nt, {}};
+    MatchCall c = top2_call(single_call(Op::Top2, kBatchWords, o, nullptr), ratio, ratio_on_squared, nullptr, nullptr,
+                            nullptr);
+    c.host = true;
+    if (int rc = run(m, c)) return rc;
+    HIPCHK(hipMemcpy(out, m->dMatch, sizeof(int) * nq, hipMemcpyDeviceToHost));
     return SIFT_HIP_OK;
 }
-// ... then the matcher's and the sets'.
-int check_gated_sets(const char* what, const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                     const float* query_xy, const float* train_xy) {
-    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
-    if (nq < 0 || nt < 0 || nq > m->maxQ || nt > m->maxT)
-        return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-    if ((nq && !q) || (nt && !t)) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-    if ((nq && !query_xy) || (nt && !train_xy))
-        return fail(SIFT_HIP_ERR_INVALID, std::string(what) + ": null position pointer");
-    return SIFT_HIP_OK;
-}
-
-// The gate's own rules first (they need no matcher), then the matcher's.  Nothing is launched on a failure.
-int check_guided_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                      const sift_hip_match_gate* g) {
-    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null match gate");
-    if (int rc = check_gate_positions("match gate", g->query_stride, g->train_stride, g->radius)) return rc;
-    return check_gated_sets("match gate", m, q, nq, t, nt, g->query_xy, g->train_xy);
-}
-
-int check_epipolar_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                        const sift_hip_match_epipolar_gate* g) {
-    if (!g) return fail(SIFT_HIP_ERR_INVALID, "null epipolar gate");
-    if (int rc = check_gate_positions("epipolar gate", g->query_stride, g->train_stride, g->radius)) return rc;
-    if (!(g->max_error > 0.f) || !std::isfinite(g->max_error))
-        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: max_error must be > 0 and finite");
-    bool zero = true;
-    for (float f : g->F) {
-        if (!std::isfinite(f)) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: a non-finite entry of F");
-        zero = zero && f == 0.f;
-    }
-    if (zero) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: F is all zero");
-    return check_gated_sets("epipolar gate", m, q, nq, t, nt, g->query_xy, g->train_xy);
-}
-
-// The two directions of a pair under a gate, as the kernels take it: the forward gate, and the reverse direction's
-// with the roles swapped (the epipolar gate: and F transposed; e2 = max_error^2 is formed here, one float32 product).
-struct WindowGates {
-    MatchGate fwd, rev;
-    explicit WindowGates(const sift_hip_match_gate& g)
-        : fwd{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius},
-          rev{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius} {}
-};
-struct EpipolarGates {
-    EpipolarGate fwd, rev;
-    explicit EpipolarGates(const sift_hip_match_epipolar_gate& g) {
-        const float e2 = g.max_error * g.max_error;
-        fwd = EpipolarGate{g.query_xy, g.train_xy, g.query_stride, g.train_stride, g.radius, e2, {}};
-        rev = EpipolarGate{g.train_xy, g.query_xy, g.train_stride, g.query_stride, g.radius, e2, {}};
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) fwd.F[3 * r + c] = rev.F[3 * c + r] = g.F[3 * r + c];
-    }
-};
-void launch_gated_pair(const MatchPair& pr, const MatchGate& g, const CodeSet& q, const CodeSet& t, const SetFlags& flags,
-                       const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
-    launch_match_pair(pr, &g, q, t, flags, sc, out, s);
-}
-void launch_gated_pair(const MatchPair& pr, const EpipolarGate& g, const CodeSet& q, const CodeSet& t,
-                       const SetFlags& flags, const MatchScratch& sc, const MatchOut& out, hipStream_t s) {
-    launch_match_pair(pr, g, q, t, flags, sc, out, s);
-}
-
-// The guided top-2 of (q, t) into idx2 / d2 / match and, with rev_idx2, of (t, q) under the reverse gate into
-// rev_idx2 / rev_d2 (Gates: WindowGates or EpipolarGates).  Arguments are checked by the caller; nq > 0.  Detector
-// buffers with fresh sidecars: one launch per direction on their codes.  Otherwise k_match_prep once for both sets,
-// then one launch per direction.
-template <class Gates>
-int guided_top2(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g, float ratio,
-                int ratio_on_squared, int* idx2, float* d2, int* match, int* rev_idx2, float* rev_d2,
-                hipStream_t stream) {
-    CodeSet qc, tc;
-    SetFlags flags = kNoFlags;
-    int qs = 0, ts = 0;
-    Sidecar sq{}, st{};
-    HIPCHK(hipSetDevice(m->device));
-    if (m->sidecars && nt > 0 && find_sidecar(q, nq, &sq) && find_sidecar(t, nt, &st)) {
-        qc = CodeSet{sq.codes, sq.keys}, tc = CodeSet{st.codes, st.keys};
-    } else {
-        MatchSets sets{};
-        sets.set[sets.nsets++] = MatchSet{q, nq, 0};
-        if (t == q)
-            sets.set[0].n = std::max(nq, nt);
-        else
-            sets.set[ts = sets.nsets++] = MatchSet{t, nt, nq};
-        sets.maxn = std::max(nq, nt);
-        if ((long)nq + nt > m->codeRows)
-            return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-        flags = m->next_epoch();
-        launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
-        HIPCHK(hipGetLastError());
-        const int trow0 = sets.set[ts].row0;
-        qc = CodeSet{m->dCodes, m->dRowKeys}, tc = CodeSet{m->dCodes + (size_t)trow0 * 128, m->dRowKeys + trow0};
-    }
-    const MatchPair fwd{q, t, nq, nt, 0, qs, ts, 0, 0, 0, 0};
-    launch_gated_pair(fwd, g.fwd, qc, tc, flags, m->scratch(), MatchOut{ratio, ratio_on_squared, idx2, d2, match},
-                      stream);
-    HIPCHK(hipGetLastError());
-    if (rev_idx2 && nt > 0) {
-        // The matcher's scratch is restored when a launch ends, so launches ordered on the stream may share it.
-        const MatchPair rev{t, q, nt, nq, 0, ts, qs, 0, 0, 0, 0};
-        launch_gated_pair(rev, g.rev, tc, qc, flags, m->scratch(), MatchOut{0.f, 0, rev_idx2, rev_d2, nullptr}, stream);
-        HIPCHK(hipGetLastError());
-    }
-    return SIFT_HIP_OK;
-}
-
-// The guided match list of a checked pair: the guided top-2 of the directions the filter needs into the select
-// scratch, then the filter and the compaction.
-template <class Gates>
-int guided_list(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g,
-                const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, hipStream_t stream) {
-    if (int rc = check_list_args(m, 1, &nq, &nt, filter, out, count)) return rc;
-    if (int rc = ensure_select_scratch(m)) return rc;
-    if (nq > 0 && nt > 0) {
-        const bool rev = needs_reverse(*filter);
-        if (int rc = guided_top2(m, q, nq, t, nt, g, 0.f, 0, m->dSelIdx, m->dSelD, nullptr,
-                                 rev ? m->dSelIdx + 2 * (size_t)nq : nullptr, m->dSelD + 2 * (size_t)nq, stream))
-            return rc;
-    }
-    HIPCHK(hipSetDevice(m->device));
-    return select_lists(m, 1, &nq, &nt, *filter, out, count, stream);
-}
-
-// The same into the matcher's own list, synchronously, and back to the host.
-template <class Gates>
-int guided_list_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gates& g,
-                     const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count) {
-    if (int rc = check_list_args(m, 1, &nq, &nt, filter, m, m)) return rc;  // the device outputs are the matcher's own
-    if (int rc = ensure_select_scratch(m)) return rc;
-    if (int rc = guided_list(m, q, nq, t, nt, g, filter, reinterpret_cast<sift_hip_dmatch*>(m->dList), m->dCount, nullptr))
-        return rc;
-    return read_list(m, out_host, cap, count);
-}
-
-}  // namespace
-
-extern "C" {
 
 int sift_hip_match_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
                                  const sift_hip_match_gate* gate, float ratio, int ratio_on_squared, int* idx2,
                                  float* d2, int* match, void* stream) {
-    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
-    if (nq == 0) return SIFT_HIP_OK;
-    return guided_top2(m, q, nq, t, nt, WindowGates(*gate), ratio, ratio_on_squared, idx2, d2, match, nullptr, nullptr,
-                       (hipStream_t)stream);
-}
-
-int sift_hip_match_guided_plan(int nq, int nt, int* splits) {
-    if (nq < 0 || nt < 0 || !splits) return fail(SIFT_HIP_ERR_INVALID, "bad match shape");
-    *splits = match_direct_splits(nq, nt);
-    return SIFT_HIP_OK;
-}
-
-int sift_hip_match_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                      const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
-                                      sift_hip_dmatch* out, int* count, void* stream) {
-    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
-    return guided_list(m, q, nq, t, nt, WindowGates(*gate), filter, out, count, (hipStream_t)stream);
-}
-
-int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                    const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
-                                    sift_hip_dmatch* out_host, int cap, int* count) {
-    if (!filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    *count = 0;
-    if (int rc = check_guided_args(m, q, nq, t, nt, gate)) return rc;
-    return guided_list_host(m, q, nq, t, nt, WindowGates(*gate), filter, out_host, cap, count);
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, top2_call(gated_single(Op::Top2, o, gate, stream), ratio, ratio_on_squared, idx2, d2, match));
 }
 
 int sift_hip_match_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
                                    const sift_hip_match_epipolar_gate* gate, float ratio, int ratio_on_squared,
                                    int* idx2, float* d2, int* match, void* stream) {
-    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
-    if (nq == 0) return SIFT_HIP_OK;
-    return guided_top2(m, q, nq, t, nt, EpipolarGates(*gate), ratio, ratio_on_squared, idx2, d2, match, nullptr,
-                       nullptr, (hipStream_t)stream);
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, top2_call(gated_single(Op::Top2, o, gate, stream), ratio, ratio_on_squared, idx2, d2, match));
 }
-
-int sift_hip_match_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                        const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
-                                        sift_hip_dmatch* out, int* count, void* stream) {
-    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
-    return guided_list(m, q, nq, t, nt, EpipolarGates(*gate), filter, out, count, (hipStream_t)stream);
-}
-
-int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                      const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
-                                      sift_hip_dmatch* out_host, int cap, int* count) {
-    if (!filter || !count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "null argument");
-    *count = 0;
-    if (int rc = check_epipolar_args(m, q, nq, t, nt, gate)) return rc;
-    return guided_list_host(m, q, nq, t, nt, EpipolarGates(*gate), filter, out_host, cap, count);
-}
-
-}  // extern "C"
-
-// --- Batched guided matching ------------------------------------------------------
-static_assert(sizeof(sift_hip_match_positions) == 2 * sizeof(void*), "two device pointers per pair");
-
-namespace {
-
-// The call-wide rules of a gated batch, which need no matcher: the position fields, then under the epipolar gate
-// (epipolar: geometry, its stride and max_error are looked at) the geometry's.  The nine floats themselves are on the
-// device: the kernel applies the usable-geometry rule to them.
-int check_gated_call(bool epipolar, int query_stride, int train_stride, float radius, const void* geometry,
-                     int geometry_stride, float max_error) {
-    const char* what = epipolar ? "epipolar gate" : "match gate";
-    if (int rc = check_gate_positions(what, query_stride, train_stride, radius)) return rc;
-    if (!epipolar) return SIFT_HIP_OK;
-    if (!(max_error > 0.f) || !std::isfinite(max_error))
-        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: max_error must be > 0 and finite");
-    if (!geometry) return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: null geometry");
-    if (geometry_stride < 36 || geometry_stride % 4)
-        return fail(SIFT_HIP_ERR_INVALID, "epipolar gate: geometry_stride_bytes must be >= 36 and a multiple of 4");
-    return SIFT_HIP_OK;
-}
-
-// ... then the matcher's and the pairs'.
-int check_gated_pairs(bool epipolar, const sift_hip_matcher* m, int P, const int* nq, const int* nt,
-                      const sift_hip_match_positions* positions) {
-    if (!m) return fail(SIFT_HIP_ERR_INVALID, "null matcher");
-    if (P <= 0 || P > m->maxP || !nq || !nt || !positions) return fail(SIFT_HIP_ERR_INVALID, "bad gated batch");
-    for (int p = 0; p < P; p++) {
-        if (nq[p] < 0 || nt[p] < 0 || nq[p] > m->maxQ || nt[p] > m->maxT)
-            return fail(SIFT_HIP_ERR_INVALID, "pair size exceeds matcher limits");
-        if ((nq[p] && !positions[p].query_xy) || (nt[p] && !positions[p].train_xy))
-            return fail(SIFT_HIP_ERR_INVALID,
-                        std::string(epipolar ? "epipolar gate" : "match gate") + ": null position pointer");
-    }
-    return SIFT_HIP_OK;
-}
-
-// A gated call as the launcher takes it; e2 = max_error^2 is formed here, one float32 product.
-GatedCall gated_call(bool epipolar, int query_stride, int train_stride, float radius, const void* geometry,
-                     int geometry_stride, float max_error) {
-    return GatedCall{query_stride, train_stride, radius, epipolar ? max_error * max_error : 0.f,
-                     epipolar ? geometry : nullptr, epipolar ? geometry_stride : 0};
-}
-
-// The pairs of a call: the forward pairs [0, P) with their rows at sum_{r<p} nq[r], and -- when a filter needs them --
-// the reverse pairs [P, 2P) with the roles swapped, rows at sum nq + sum_{r<p} nt[r] (select_lists' layout).
-struct GatedPairs {
-    GatedPair pair[2 * kMaxMatchPairs];
-    void fill(int P, bool rev, const sift_hip_match_positions* pos) {
-        int totq = 0;
-        for (int p = 0; p < P; p++) totq += pair[p].pr.nq;
-        int fwd = 0, roff = totq;
-        for (int p = 0; p < P; p++) {
-            GatedPair& f = pair[p];
-            f.pr.out_off = fwd;
-            f.qxy = pos[p].query_xy, f.txy = pos[p].train_xy, f.geom = p, f.swapped = 0;
-            fwd += f.pr.nq;
-            if (!rev) continue;
-            const MatchPair& a = f.pr;
-            pair[P + p] = GatedPair{MatchPair{a.t, a.q, a.nt, a.nq, roff, a.tset, a.qset, a.trow0, a.qrow0, a.tkrow0,
-                                              a.qkrow0},
-                                    f.txy, f.qxy, p, 1};
-            roff += a.nt;
-        }
-    }
-};
-
-// Whether a call has an output row to write at all (a query without train rows still gets its -1 / FLT_MAX row).
-bool any_rows(int P, const int* nq, const int* nt, bool rev) {
-    for (int p = 0; p < P; p++)
-        if (nq[p] > 0 || (rev && nt[p] > 0)) return true;
-    return false;
-}
-
-// n pairs in launches of at most kMaxGatedPairs, ordered on the stream (the scratch is restored when each ends).
-int launch_gated(sift_hip_matcher* m, const GatedPair* pairs, int n, const GatedCall& call, const CodeSet& set,
-                 const SetFlags& flags, const MatchOut& out, hipStream_t stream) {
-    for (int p0 = 0; p0 < n; p0 += kMaxGatedPairs) {
-        GatedBatch b{};
-        b.P = std::min(kMaxGatedPairs, n - p0);
-        std::copy(pairs + p0, pairs + p0 + b.P, b.pair);
-        launch_match_gated(b, call, set, flags, m->scratch(), out, stream);
-        HIPCHK(hipGetLastError());
-    }
-    return SIFT_HIP_OK;
-}
-
-// Forward pairs, and with `rev` the reverse pairs: in one pass over 2P pairs when the matcher holds that many,
-// else in two of P.  The bytes are the same either way.
-int launch_gated_directions(sift_hip_matcher* m, const GatedPairs& g, int P, bool rev, const GatedCall& call,
-                            const CodeSet& set, const SetFlags& flags, const MatchOut& out, hipStream_t stream) {
-    if (rev && 2 * P <= m->maxP) return launch_gated(m, g.pair, 2 * P, call, set, flags, out, stream);
-    if (int rc = launch_gated(m, g.pair, P, call, set, flags, out, stream)) return rc;
-    return rev ? launch_gated(m, g.pair + P, P, call, set, flags, out, stream) : SIFT_HIP_OK;
-}
-
-// fp16 sets: always converted (k_match_prep, distinct sets once, as sift_hip_match_batched does for P > 1), then the
-// gated launches on the prepared codes with their flags.  Arguments are checked by the caller.
-int gated_batch_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
-                     const int* nt, const sift_hip_match_positions* pos, bool rev, const GatedCall& call,
-                     const MatchOut& out, hipStream_t stream) {
-    if (!q || !t) return fail(SIFT_HIP_ERR_INVALID, "bad gated batch");
-    for (int p = 0; p < P; p++)
-        if ((nq[p] && !q[p]) || (nt[p] && !t[p])) return fail(SIFT_HIP_ERR_INVALID, "null descriptor pointer");
-    if (!any_rows(P, nq, nt, rev)) return SIFT_HIP_OK;
-    MatchSets sets{};
-    auto set_of = [&](const uint16_t* ptr, int n) {
-        for (int k = 0; k < sets.nsets; k++)
-            if (sets.set[k].src == ptr) {
-                sets.set[k].n = std::max(sets.set[k].n, n);
-                return k;
-            }
-        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
-        return sets.nsets++;
-    };
-    GatedPairs g{};
-    for (int p = 0; p < P; p++) {
-        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
-        g.pair[p].pr = MatchPair{q[p], t[p], nq[p], nt[p], 0, qs, ts, 0, 0, 0, 0};
-    }
-    long row = 0;
-    for (int k = 0; k < sets.nsets; k++) {
-        sets.set[k].row0 = (int)row;
-        row += sets.set[k].n;
-        sets.maxn = std::max(sets.maxn, sets.set[k].n);
-    }
-    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-    for (int p = 0; p < P; p++) {
-        MatchPair& pr = g.pair[p].pr;
-        pr.qrow0 = pr.qkrow0 = sets.set[pr.qset].row0;
-        pr.trow0 = pr.tkrow0 = sets.set[pr.tset].row0;
-    }
-    g.fill(P, rev, pos);
-    const SetFlags flags = m->next_epoch();
-    HIPCHK(hipSetDevice(m->device));
-    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
-    HIPCHK(hipGetLastError());
-    return launch_gated_directions(m, g, P, rev, call, CodeSet{m->dCodes, m->dRowKeys}, flags, out, stream);
-}
-
-// Ready code sets (sift_hip_match_list_codes_batched's arguments): no conversion, no flags.
-int gated_batch_codes(sift_hip_matcher* m, const int8_t* codes, const int* keys, int P, const int* qrow0,
-                      const int* qkey0, const int* nq, const int* trow0, const int* tkey0, const int* nt,
-                      const sift_hip_match_positions* pos, bool rev, const GatedCall& call, const MatchOut& out,
-                      hipStream_t stream) {
-    if (!codes || !keys || !qrow0 || !qkey0 || !trow0 || !tkey0) return fail(SIFT_HIP_ERR_INVALID, "bad code batch");
-    for (int p = 0; p < P; p++)
-        if (qrow0[p] < 0 || trow0[p] < 0 || qkey0[p] < 0 || tkey0[p] < 0)
-            return fail(SIFT_HIP_ERR_INVALID, "negative set row");
-    if (!any_rows(P, nq, nt, rev)) return SIFT_HIP_OK;
-    GatedPairs g{};
-    for (int p = 0; p < P; p++)
-        g.pair[p].pr = MatchPair{nullptr, nullptr, nq[p], nt[p], 0, 0, 0, qrow0[p], trow0[p], qkey0[p], tkey0[p]};
-    g.fill(P, rev, pos);
-    HIPCHK(hipSetDevice(m->device));
-    return launch_gated_directions(m, g, P, rev, call, CodeSet{codes, keys}, kNoFlags, out, stream);
-}
-
-}  // namespace
-
-extern "C" {
 
 int sift_hip_match_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
                                   const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
                                   int query_stride, int train_stride, float radius, float ratio, int ratio_on_squared,
                                   int* idx2, float* d2, int* match, void* stream) {
-    if (int rc = check_gated_call(false, query_stride, train_stride, radius, nullptr, 0, 0.f)) return rc;
-    if (int rc = check_gated_pairs(false, m, P, nq, nt, positions)) return rc;
-    return gated_batch_fp16(m, P, q, nq, t, nt, positions, false,
-                            gated_call(false, query_stride, train_stride, radius, nullptr, 0, 0.f),
-                            MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
+    return run(m, top2_call(gated_batch(Op::Top2, false, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                        nullptr, 0, 0.f, stream),
+                            ratio, ratio_on_squared, idx2, d2, match));
 }
 
 int sift_hip_match_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
@@ -1107,50 +889,77 @@ int sift_hip_match_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t*
                                     int query_stride, int train_stride, float radius, const void* geometry,
                                     int geometry_stride_bytes, float max_error, float ratio, int ratio_on_squared,
                                     int* idx2, float* d2, int* match, void* stream) {
-    if (int rc = check_gated_call(true, query_stride, train_stride, radius, geometry, geometry_stride_bytes, max_error))
-        return rc;
-    if (int rc = check_gated_pairs(true, m, P, nq, nt, positions)) return rc;
-    return gated_batch_fp16(m, P, q, nq, t, nt, positions, false,
-                            gated_call(true, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
-                                       max_error),
-                            MatchOut{ratio, ratio_on_squared, idx2, d2, match}, (hipStream_t)stream);
+    return run(m, top2_call(gated_batch(Op::Top2, true, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                        geometry, geometry_stride_bytes, max_error, stream),
+                            ratio, ratio_on_squared, idx2, d2, match));
 }
 
-}  // extern "C"
-
-namespace {
-
-// The four list forms: the gated top-2 of the directions the filter needs into the select scratch, then the filter
-// and the compaction (select_lists: sift_hip_match_list_batched's layout, imgIdx = p, counts on the device).
-template <class Top2>
-int gated_list(bool epipolar, sift_hip_matcher* m, int P, const int* nq, const int* nt,
-               const sift_hip_match_positions* positions, int query_stride, int train_stride, float radius,
-               const void* geometry, int geometry_stride, float max_error, const sift_hip_match_filter* filter,
-               sift_hip_dmatch* out, int* counts, hipStream_t stream, Top2 top2) {
-    if (int rc = check_gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error))
-        return rc;
-    if (int rc = check_gated_pairs(epipolar, m, P, nq, nt, positions)) return rc;
-    if (int rc = check_list_args(m, P, nq, nt, filter, out, counts)) return rc;
-    if (int rc = ensure_select_scratch(m)) return rc;
-    const GatedCall call = gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error);
-    if (int rc = top2(needs_reverse(*filter), call, MatchOut{0.f, 0, m->dSelIdx, m->dSelD, nullptr})) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    return select_lists(m, P, nq, nt, *filter, out, counts, stream);
+// --- Match lists ----------------------------------------------------------------
+int sift_hip_match_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                const uint16_t* const* t, const int* nt, const sift_hip_match_filter* filter,
+                                sift_hip_dmatch* out, int* counts, void* stream) {
+    return run(m, list_call(fp16_call(Op::List, kListWords, P, q, nq, t, nt, stream), filter, out, counts));
 }
 
-}  // namespace
+int sift_hip_match_list_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                      const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                      const int* tkey0, const int* nt, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* counts, void* stream) {
+    return run(m, list_call(codes_call(Op::List, kListWords, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, stream),
+                            filter, out, counts));
+}
 
-extern "C" {
+int sift_hip_match_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                               const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* count, void* stream) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run(m, list_call(single_call(Op::List, kListWords, o, stream), filter, out, count));
+}
+
+int sift_hip_match_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                             const sift_hip_match_filter* filter, sift_hip_dmatch* out_host, int cap, int* count) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, list_call(single_call(Op::List, kListWords, o, nullptr), filter, nullptr, nullptr), out_host,
+                         cap, count);
+}
+
+int sift_hip_match_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                      const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out, int* count, void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, list_call(gated_single(Op::List, o, gate, stream), filter, out, count));
+}
+
+int sift_hip_match_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                    const sift_hip_match_gate* gate, const sift_hip_match_filter* filter,
+                                    sift_hip_dmatch* out_host, int cap, int* count) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, list_call(gated_single(Op::List, o, gate, nullptr), filter, nullptr, nullptr), out_host, cap,
+                         count);
+}
+
+int sift_hip_match_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                        const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
+                                        sift_hip_dmatch* out, int* count, void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, list_call(gated_single(Op::List, o, gate, stream), filter, out, count));
+}
+
+int sift_hip_match_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                      const sift_hip_match_epipolar_gate* gate, const sift_hip_match_filter* filter,
+                                      sift_hip_dmatch* out_host, int cap, int* count) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, list_call(gated_single(Op::List, o, gate, nullptr), filter, nullptr, nullptr), out_host, cap,
+                         count);
+}
 
 int sift_hip_match_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
                                        const uint16_t* const* t, const int* nt,
                                        const sift_hip_match_positions* positions, int query_stride, int train_stride,
                                        float radius, const sift_hip_match_filter* filter, sift_hip_dmatch* out,
                                        int* counts, void* stream) {
-    return gated_list(false, m, P, nq, nt, positions, query_stride, train_stride, radius, nullptr, 0, 0.f, filter, out,
-                      counts, (hipStream_t)stream, [&](bool rev, const GatedCall& call, const MatchOut& o) {
-                          return gated_batch_fp16(m, P, q, nq, t, nt, positions, rev, call, o, (hipStream_t)stream);
-                      });
+    return run(m, list_call(gated_batch(Op::List, false, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                        nullptr, 0, 0.f, stream),
+                            filter, out, counts));
 }
 
 int sift_hip_match_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
@@ -1159,11 +968,9 @@ int sift_hip_match_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint
                                          float radius, const void* geometry, int geometry_stride_bytes, float max_error,
                                          const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
                                          void* stream) {
-    return gated_list(true, m, P, nq, nt, positions, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
-                      max_error, filter, out, counts, (hipStream_t)stream,
-                      [&](bool rev, const GatedCall& call, const MatchOut& o) {
-                          return gated_batch_fp16(m, P, q, nq, t, nt, positions, rev, call, o, (hipStream_t)stream);
-                      });
+    return run(m, list_call(gated_batch(Op::List, true, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                        geometry, geometry_stride_bytes, max_error, stream),
+                            filter, out, counts));
 }
 
 int sift_hip_match_list_guided_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
@@ -1172,11 +979,9 @@ int sift_hip_match_list_guided_codes_batched(sift_hip_matcher_t m, const int8_t*
                                              const sift_hip_match_positions* positions, int query_stride,
                                              int train_stride, float radius, const sift_hip_match_filter* filter,
                                              sift_hip_dmatch* out, int* counts, void* stream) {
-    return gated_list(false, m, P, nq, nt, positions, query_stride, train_stride, radius, nullptr, 0, 0.f, filter, out,
-                      counts, (hipStream_t)stream, [&](bool rev, const GatedCall& call, const MatchOut& o) {
-                          return gated_batch_codes(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, positions, rev,
-                                                   call, o, (hipStream_t)stream);
-                      });
+    MatchCall c = codes_call(Op::List, kGatedWords, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, stream);
+    set_gate(c, false, positions, query_stride, train_stride, radius, nullptr, 0, 0.f);
+    return run(m, list_call(c, filter, out, counts));
 }
 
 int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
@@ -1187,14 +992,142 @@ int sift_hip_match_list_epipolar_codes_batched(sift_hip_matcher_t m, const int8_
                                                int geometry_stride_bytes, float max_error,
                                                const sift_hip_match_filter* filter, sift_hip_dmatch* out, int* counts,
                                                void* stream) {
-    return gated_list(true, m, P, nq, nt, positions, query_stride, train_stride, radius, geometry, geometry_stride_bytes,
-                      max_error, filter, out, counts, (hipStream_t)stream,
-                      [&](bool rev, const GatedCall& call, const MatchOut& o) {
-                          return gated_batch_codes(m, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, positions, rev,
-                                                   call, o, (hipStream_t)stream);
-                      });
+    MatchCall c = codes_call(Op::List, kGatedWords, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, stream);
+    set_gate(c, true, positions, query_stride, train_stride, radius, geometry, geometry_stride_bytes, max_error);
+    return run(m, list_call(c, filter, out, counts));
 }
 
+// --- k nearest neighbours and capped radius lists ----------------------------------
+int sift_hip_match_knn_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                               const uint16_t* const* t, const int* nt, int k, int* idx, float* d2, void* stream) {
+    return run(m, knn_call(fp16_call(Op::KnnTable, kKnnWords, P, q, nq, t, nt, stream), k, idx, d2));
+}
+
+int sift_hip_match_knn_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                              int* idx, float* d2, void* stream) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_call(single_call(Op::KnnTable, kKnnWords, o, stream), k, idx, d2));
+}
+
+int sift_hip_match_knn_codes_batched(sift_hip_matcher_t m, const int8_t* codes, const int* keys, int P,
+                                     const int* qrow0, const int* qkey0, const int* nq, const int* trow0,
+                                     const int* tkey0, const int* nt, int k, int* idx, float* d2, void* stream) {
+    return run(m, knn_call(codes_call(Op::KnnTable, kKnnWords, codes, keys, P, qrow0, qkey0, nq, trow0, tkey0, nt, stream),
+                           k, idx, d2));
+}
+
+int sift_hip_match_knn_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                            int* idx_host, float* d2_host) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run_knn_host(m, knn_call(single_call(Op::KnnTable, kKnnWords, o, nullptr), k, nullptr, nullptr), idx_host,
+                        d2_host);
+}
+
+int sift_hip_match_knn_list_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                    const uint16_t* const* t, const int* nt, int k, float max_distance,
+                                    sift_hip_dmatch* out, int* counts, void* stream) {
+    return run(m, knn_list_call(fp16_call(Op::KnnList, kKnnWords, P, q, nq, t, nt, stream), k, max_distance, out, counts));
+}
+
+int sift_hip_match_knn_list_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                                   float max_distance, sift_hip_dmatch* out, int* count, void* stream) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_list_call(single_call(Op::KnnList, kKnnWords, o, stream), k, max_distance, out, count));
+}
+
+int sift_hip_match_knn_list_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt, int k,
+                                 float max_distance, sift_hip_dmatch* out_host, int cap, int* count) {
+    const OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, knn_list_call(single_call(Op::KnnList, kKnnWords, o, nullptr), k, max_distance, nullptr, nullptr),
+                         out_host, cap, count);
+}
+
+// --- Gated k nearest neighbours ---------------------------------------------------
+int sift_hip_match_knn_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                     const sift_hip_match_gate* gate, int k, int* idx, float* d2, void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_call(gated_single(Op::KnnTable, o, gate, stream), k, idx, d2));
+}
+int sift_hip_match_knn_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                       const sift_hip_match_epipolar_gate* gate, int k, int* idx, float* d2,
+                                       void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_call(gated_single(Op::KnnTable, o, gate, stream), k, idx, d2));
+}
+int sift_hip_match_knn_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                      const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
+                                      int query_stride, int train_stride, float radius, int k, int* idx, float* d2,
+                                      void* stream) {
+    return run(m, knn_call(gated_batch(Op::KnnTable, false, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                       nullptr, 0, 0.f, stream),
+                           k, idx, d2));
+}
+int sift_hip_match_knn_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                        const uint16_t* const* t, const int* nt,
+                                        const sift_hip_match_positions* positions, int query_stride, int train_stride,
+                                        float radius, const void* geometry, int geometry_stride_bytes, float max_error,
+                                        int k, int* idx, float* d2, void* stream) {
+    return run(m, knn_call(gated_batch(Op::KnnTable, true, P, q, nq, t, nt, positions, query_stride, train_stride, radius,
+                                       geometry, geometry_stride_bytes, max_error, stream),
+                           k, idx, d2));
+}
+int sift_hip_match_knn_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                          const sift_hip_match_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out, int* count, void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_list_call(gated_single(Op::KnnList, o, gate, stream), k, max_distance, out, count));
+}
+int sift_hip_match_knn_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                            const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                            sift_hip_dmatch* out, int* count, void* stream) {
+    OnePair o{q, t, nq, nt, {}};
+    return run(m, knn_list_call(gated_single(Op::KnnList, o, gate, stream), k, max_distance, out, count));
+}
+int sift_hip_match_knn_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                           const uint16_t* const* t, const int* nt,
+                                           const sift_hip_match_positions* positions, int query_stride,
+                                           int train_stride, float radius, int k, float max_distance,
+                                           sift_hip_dmatch* out, int* counts, void* stream) {
+    return run(m, knn_list_call(gated_batch(Op::KnnList, false, P, q, nq, t, nt, positions, query_stride, train_stride,
+                                            radius, nullptr, 0, 0.f, stream),
+                                k, max_distance, out, counts));
+}
+int sift_hip_match_knn_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
+                                             const uint16_t* const* t, const int* nt,
+                                             const sift_hip_match_positions* positions, int query_stride,
+                                             int train_stride, float radius, const void* geometry,
+                                             int geometry_stride_bytes, float max_error, int k, float max_distance,
+                                             sift_hip_dmatch* out, int* counts, void* stream) {
+    return run(m, knn_list_call(gated_batch(Op::KnnList, true, P, q, nq, t, nt, positions, query_stride, train_stride,
+                                            radius, geometry, geometry_stride_bytes, max_error, stream),
+                                k, max_distance, out, counts));
+}
+int sift_hip_match_knn_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                   const sift_hip_match_gate* gate, int k, int* idx_host, float* d2_host) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_knn_host(m, knn_call(gated_single(Op::KnnTable, o, gate, nullptr), k, nullptr, nullptr), idx_host, d2_host);
+}
+int sift_hip_match_knn_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                     const sift_hip_match_epipolar_gate* gate, int k, int* idx_host, float* d2_host) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_knn_host(m, knn_call(gated_single(Op::KnnTable, o, gate, nullptr), k, nullptr, nullptr), idx_host, d2_host);
+}
+int sift_hip_match_knn_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                        const sift_hip_match_gate* gate, int k, float max_distance,
+                                        sift_hip_dmatch* out_host, int cap, int* count) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, knn_list_call(gated_single(Op::KnnList, o, gate, nullptr), k, max_distance, nullptr, nullptr),
+                         out_host, cap, count);
+}
+int sift_hip_match_knn_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
+                                          const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
+                                          sift_hip_dmatch* out_host, int cap, int* count) {
+    OnePair o{q, t, nq, nt, {}};
+    return run_list_host(m, knn_list_call(gated_single(Op::KnnList, o, gate, nullptr), k, max_distance, nullptr, nullptr),
+                         out_host, cap, count);
+}
+
+// --- Plain device memory for callers without a HIP runtime of their own -------------
 int sift_hip_device_count(int* n) {
     if (!n) return fail(SIFT_HIP_ERR_INVALID, "null argument");
     if (hipGetDeviceCount(n) != hipSuccess) *n = 0;
@@ -1219,270 +1152,6 @@ int sift_hip_memcpy_d2h(void* dst, const void* src, size_t bytes) {
 int sift_hip_device_sync(void) {
     HIPCHK(hipDeviceSynchronize());
     return SIFT_HIP_OK;
-}
-
-}  // extern "C"
-// --- Gated k nearest neighbours ---------------------------------------------------
-namespace {
-
-// What a gated k-NN call passes beside its pairs: which gate, the call-wide fields and -- the single-pair epipolar
-// call, geometry == nullptr -- the host's F, which travels as a kernel argument.
-struct KnnGate {
-    bool epipolar;
-    GatedCall call;
-    float F[9];
-};
-KnnGate knn_gate_of(const sift_hip_match_gate& g) {
-    return KnnGate{false, gated_call(false, g.query_stride, g.train_stride, g.radius, nullptr, 0, 0.f), {}};
-}
-KnnGate knn_gate_of(const sift_hip_match_epipolar_gate& g) {
-    KnnGate kg{true, GatedCall{g.query_stride, g.train_stride, g.radius, g.max_error * g.max_error, nullptr, 0}, {}};
-    std::copy(g.F, g.F + 9, kg.F);
-    return kg;
-}
-sift_hip_match_positions positions_of(const sift_hip_match_gate& g) { return {g.query_xy, g.train_xy}; }
-sift_hip_match_positions positions_of(const sift_hip_match_epipolar_gate& g) { return {g.query_xy, g.train_xy}; }
-int check_gate_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                    const sift_hip_match_gate* g) {
-    return check_guided_args(m, q, nq, t, nt, g);
-}
-int check_gate_args(const sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                    const sift_hip_match_epipolar_gate* g) {
-    return check_epipolar_args(m, q, nq, t, nt, g);
-}
-
-// The refusals that need no matcher, in the order of include/sift_hip.h: k, a list's max_distance (list: the call
-// has one), then the gate's own.
-int check_knn_k(int k, bool list, float max_distance) {
-    if (k < 1 || k > kKnnMax) return fail(SIFT_HIP_ERR_INVALID, "k-NN: k outside 1..SIFT_HIP_KNN_MAX");
-    if (list && std::isnan(max_distance)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: max_distance is NaN");
-    return SIFT_HIP_OK;
-}
-
-// Launches of at most kMaxGatedPairs pairs, ordered on the stream; each takes the plan's splits for its own pairs,
-// lowered to what the list scratch holds, and restores the counters it used.
-int knn_gated_launch(sift_hip_matcher* m, const MatchPair* pairs, const sift_hip_match_positions* pos, int P,
-                     const KnnGate& kg, int k, const CodeSet& q, const CodeSet& t, const SetFlags& flags, int* idx,
-                     float* d2, hipStream_t stream) {
-    for (int p0 = 0; p0 < P; p0 += kMaxGatedPairs) {
-        KnnGatedBatch b{};
-        b.P = std::min(kMaxGatedPairs, P - p0);
-        b.call = kg.call;
-        std::copy(kg.F, kg.F + 9, b.F);
-        int maxq = 1, maxt = 1;
-        bool rows = false;
-        for (int i = 0; i < b.P; i++) {
-            b.pair[i] = pairs[p0 + i];
-            b.qxy[i] = pos[p0 + i].query_xy;
-            b.txy[i] = pos[p0 + i].train_xy;
-            b.geom[i] = p0 + i;
-            maxq = std::max(maxq, b.pair[i].nq);
-            maxt = std::max(maxt, b.pair[i].nt);
-            rows = rows || b.pair[i].nq > 0;
-        }
-        if (!rows) continue;
-        const size_t fit = m->knn_lists() / ((size_t)b.P * maxq);  // >= 2: P <= maxP, maxq <= maxQ
-        const int S = (int)std::min<size_t>(match_knn_splits(maxq, maxt, b.P), fit);
-        launch_match_knn_gated(b, kg.epipolar, S, k, q, t, flags, KnnScratch{m->dKnnLists, m->dDone, maxq, m->sentinel()},
-                               idx, d2, stream);
-        HIPCHK(hipGetLastError());
-    }
-    return SIFT_HIP_OK;
-}
-
-// The gated table of checked fp16 pairs, pair p at row sum_{r<p} nq[r] (knn_fp16 under a gate).  sidecars: the
-// single-pair calls, where two detector buffers with fresh sidecars match their codes; the batched forms convert.
-int knn_gated_fp16(sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq, const uint16_t* const* t,
-                   const int* nt, const sift_hip_match_positions* pos, const KnnGate& kg, bool sidecars, int k, int* idx,
-                   float* d2, hipStream_t stream) {
-    if (!any_queries(P, nq)) return SIFT_HIP_OK;
-    MatchPair pairs[kMaxMatchPairs];
-    MatchSets sets{};
-    auto set_of = [&](const uint16_t* ptr, int n) {
-        for (int s = 0; s < sets.nsets; s++)
-            if (sets.set[s].src == ptr) {
-                sets.set[s].n = std::max(sets.set[s].n, n);
-                return s;
-            }
-        sets.set[sets.nsets] = MatchSet{ptr, n, 0};
-        return sets.nsets++;
-    };
-    int off = 0;
-    for (int p = 0; p < P; p++) {
-        const int qs = set_of(q[p], nq[p]), ts = set_of(t[p], nt[p]);
-        pairs[p] = MatchPair{q[p], t[p], nq[p], nt[p], off, qs, ts, 0, 0, 0, 0};
-        off += nq[p];
-    }
-    long row = 0;
-    for (int s = 0; s < sets.nsets; s++) {
-        sets.set[s].row0 = (int)row;
-        row += sets.set[s].n;
-        sets.maxn = std::max(sets.maxn, sets.set[s].n);
-    }
-    if (row > m->codeRows) return fail(SIFT_HIP_ERR_INVALID, "descriptor sets exceed the matcher's code buffer");
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    Sidecar sq{}, st{};
-    if (sidecars && P == 1 && m->sidecars && nq[0] > 0 && nt[0] > 0 && find_sidecar(q[0], nq[0], &sq) &&
-        find_sidecar(t[0], nt[0], &st))
-        return knn_gated_launch(m, pairs, pos, P, kg, k, CodeSet{sq.codes, sq.keys}, CodeSet{st.codes, st.keys}, kNoFlags,
-                                idx, d2, stream);
-    for (int p = 0; p < P; p++) {
-        pairs[p].qrow0 = pairs[p].qkrow0 = sets.set[pairs[p].qset].row0;
-        pairs[p].trow0 = pairs[p].tkrow0 = sets.set[pairs[p].tset].row0;
-    }
-    const SetFlags flags = m->next_epoch();
-    launch_match_prep(sets, m->dCodes, m->dRowKeys, flags, stream);
-    HIPCHK(hipGetLastError());
-    const CodeSet set{m->dCodes, m->dRowKeys};
-    return knn_gated_launch(m, pairs, pos, P, kg, k, set, set, flags, idx, d2, stream);
-}
-
-// The single-pair forms under either gate (Gate: sift_hip_match_gate or sift_hip_match_epipolar_gate).
-template <class Gate>
-int knn_gated_device(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate, int k,
-                     int* idx, float* d2, hipStream_t stream) {
-    if (int rc = check_knn_k(k, false, 0.f)) return rc;
-    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
-    const sift_hip_match_positions pos = positions_of(*gate);
-    return knn_gated_fp16(m, 1, &q, &nq, &t, &nt, &pos, knn_gate_of(*gate), true, k, idx, d2, stream);
-}
-template <class Gate>
-int knn_gated_list_device(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate,
-                          int k, float max_distance, sift_hip_dmatch* out, int* count, hipStream_t stream) {
-    if (int rc = check_knn_k(k, true, max_distance)) return rc;
-    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
-    if (!out || !count) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    const sift_hip_match_positions pos = positions_of(*gate);
-    if (int rc = knn_gated_fp16(m, 1, &q, &nq, &t, &nt, &pos, knn_gate_of(*gate), true, k, m->dKnnIdx, m->dKnnD, stream))
-        return rc;
-    return knn_select(m, 1, &nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, count, stream);
-}
-template <class Gate>
-int knn_gated_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate, int k,
-                   int* idx_host, float* d2_host) {
-    if (int rc = check_knn_k(k, false, 0.f)) return rc;
-    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
-    if (nq == 0) return SIFT_HIP_OK;
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = knn_gated_device(m, q, nq, t, nt, gate, k, m->dKnnIdx, m->dKnnD, nullptr)) return rc;
-    if (idx_host) HIPCHK(hipMemcpy(idx_host, m->dKnnIdx, sizeof(int) * (size_t)nq * k, hipMemcpyDeviceToHost));
-    if (d2_host) HIPCHK(hipMemcpy(d2_host, m->dKnnD, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-template <class Gate>
-int knn_gated_list_host(sift_hip_matcher* m, const uint16_t* q, int nq, const uint16_t* t, int nt, const Gate* gate,
-                        int k, float max_distance, sift_hip_dmatch* out_host, int cap, int* count) {
-    if (!count || cap < 0 || (cap > 0 && !out_host)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
-    *count = 0;
-    if (int rc = check_knn_k(k, true, max_distance)) return rc;
-    if (int rc = check_gate_args(m, q, nq, t, nt, gate)) return rc;
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance,
-                                       reinterpret_cast<sift_hip_dmatch*>(m->dKnnRec), m->dKnnCount, nullptr))
-        return rc;
-    HIPCHK(hipMemcpy(count, m->dKnnCount, sizeof(int), hipMemcpyDeviceToHost));
-    const int n = std::min(*count, cap);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, m->dKnnRec, sizeof(sift_hip_dmatch) * (size_t)n, hipMemcpyDeviceToHost));
-    return SIFT_HIP_OK;
-}
-
-// The batched forms: the table into idx / d2, or (out != nullptr or list) into the matcher's own table and then the
-// list.  The checks in the header's order: k, max_distance, the call's gate fields, then the matcher's and the pairs'.
-int knn_gated_batched(bool epipolar, bool list, sift_hip_matcher* m, int P, const uint16_t* const* q, const int* nq,
-                      const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
-                      int query_stride, int train_stride, float radius, const void* geometry, int geometry_stride,
-                      float max_error, int k, float max_distance, int* idx, float* d2, sift_hip_dmatch* out, int* counts,
-                      hipStream_t stream) {
-    if (int rc = check_knn_k(k, list, max_distance)) return rc;
-    if (int rc = check_gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error))
-        return rc;
-    if (int rc = check_gated_pairs(epipolar, m, P, nq, nt, positions)) return rc;
-    if (int rc = check_knn_sets(P, q, nq, t, nt)) return rc;
-    if (list && (!out || !counts)) return fail(SIFT_HIP_ERR_INVALID, "k-NN list: null out or count");
-    const KnnGate kg{epipolar,
-                     gated_call(epipolar, query_stride, train_stride, radius, geometry, geometry_stride, max_error),
-                     {}};
-    if (!list) return knn_gated_fp16(m, P, q, nq, t, nt, positions, kg, false, k, idx, d2, stream);
-    if (int rc = ensure_knn_scratch(m)) return rc;
-    if (int rc = knn_gated_fp16(m, P, q, nq, t, nt, positions, kg, false, k, m->dKnnIdx, m->dKnnD, stream)) return rc;
-    return knn_select(m, P, nq, k, m->dKnnIdx, m->dKnnD, max_distance, out, counts, stream);
-}
-
-}  // namespace
-
-extern "C" {
-
-int sift_hip_match_knn_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                     const sift_hip_match_gate* gate, int k, int* idx, float* d2, void* stream) {
-    return knn_gated_device(m, q, nq, t, nt, gate, k, idx, d2, (hipStream_t)stream);
-}
-int sift_hip_match_knn_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                       const sift_hip_match_epipolar_gate* gate, int k, int* idx, float* d2,
-                                       void* stream) {
-    return knn_gated_device(m, q, nq, t, nt, gate, k, idx, d2, (hipStream_t)stream);
-}
-int sift_hip_match_knn_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                      const uint16_t* const* t, const int* nt, const sift_hip_match_positions* positions,
-                                      int query_stride, int train_stride, float radius, int k, int* idx, float* d2,
-                                      void* stream) {
-    return knn_gated_batched(false, false, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, nullptr, 0,
-                             0.f, k, 0.f, idx, d2, nullptr, nullptr, (hipStream_t)stream);
-}
-int sift_hip_match_knn_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                        const uint16_t* const* t, const int* nt,
-                                        const sift_hip_match_positions* positions, int query_stride, int train_stride,
-                                        float radius, const void* geometry, int geometry_stride_bytes, float max_error,
-                                        int k, int* idx, float* d2, void* stream) {
-    return knn_gated_batched(true, false, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, geometry,
-                             geometry_stride_bytes, max_error, k, 0.f, idx, d2, nullptr, nullptr, (hipStream_t)stream);
-}
-int sift_hip_match_knn_list_guided_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                          const sift_hip_match_gate* gate, int k, float max_distance,
-                                          sift_hip_dmatch* out, int* count, void* stream) {
-    return knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance, out, count, (hipStream_t)stream);
-}
-int sift_hip_match_knn_list_epipolar_device(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                            const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
-                                            sift_hip_dmatch* out, int* count, void* stream) {
-    return knn_gated_list_device(m, q, nq, t, nt, gate, k, max_distance, out, count, (hipStream_t)stream);
-}
-int sift_hip_match_knn_list_guided_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                           const uint16_t* const* t, const int* nt,
-                                           const sift_hip_match_positions* positions, int query_stride,
-                                           int train_stride, float radius, int k, float max_distance,
-                                           sift_hip_dmatch* out, int* counts, void* stream) {
-    return knn_gated_batched(false, true, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, nullptr, 0,
-                             0.f, k, max_distance, nullptr, nullptr, out, counts, (hipStream_t)stream);
-}
-int sift_hip_match_knn_list_epipolar_batched(sift_hip_matcher_t m, int P, const uint16_t* const* q, const int* nq,
-                                             const uint16_t* const* t, const int* nt,
-                                             const sift_hip_match_positions* positions, int query_stride,
-                                             int train_stride, float radius, const void* geometry,
-                                             int geometry_stride_bytes, float max_error, int k, float max_distance,
-                                             sift_hip_dmatch* out, int* counts, void* stream) {
-    return knn_gated_batched(true, true, m, P, q, nq, t, nt, positions, query_stride, train_stride, radius, geometry,
-                             geometry_stride_bytes, max_error, k, max_distance, nullptr, nullptr, out, counts,
-                             (hipStream_t)stream);
-}
-int sift_hip_match_knn_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                   const sift_hip_match_gate* gate, int k, int* idx_host, float* d2_host) {
-    return knn_gated_host(m, q, nq, t, nt, gate, k, idx_host, d2_host);
-}
-int sift_hip_match_knn_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                     const sift_hip_match_epipolar_gate* gate, int k, int* idx_host, float* d2_host) {
-    return knn_gated_host(m, q, nq, t, nt, gate, k, idx_host, d2_host);
-}
-int sift_hip_match_knn_list_guided_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                        const sift_hip_match_gate* gate, int k, float max_distance,
-                                        sift_hip_dmatch* out_host, int cap, int* count) {
-    return knn_gated_list_host(m, q, nq, t, nt, gate, k, max_distance, out_host, cap, count);
-}
-int sift_hip_match_knn_list_epipolar_host(sift_hip_matcher_t m, const uint16_t* q, int nq, const uint16_t* t, int nt,
-                                          const sift_hip_match_epipolar_gate* gate, int k, float max_distance,
-                                          sift_hip_dmatch* out_host, int cap, int* count) {
-    return knn_gated_list_host(m, q, nq, t, nt, gate, k, max_distance, out_host, cap, count);
 }
 
 }  // extern "C"
