@@ -75,10 +75,11 @@ enum class VerifyModel { Fundamental = 1, Homography = 2 };
 // k_verify_hypotheses / k_verify_hypotheses_h: hypothesis k in [0, K) draws its
 // m matches (m = 8 for the fundamental matrix, 4 for the homography;
 // samples[m k ..], -1 when n < m) and solves them: F[9 k ..] and valid[k] (an
-// invalid hypothesis has F all zero).
+// invalid hypothesis has F all zero).  e2 = max_error^2 serves the homography's
+// own-sample rule; the fundamental kernel does not read it.
 template <class List>
-void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, int* samples,
-                              float* F, int* valid, hipStream_t s);
+void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, float e2,
+                              int* samples, float* F, int* valid, hipStream_t s);
 
 // k_verify_score: counts[k] = the matches j < n that pass the model's predicate
 // (Sampson distance / forward transfer error) under F[9 k ..] with

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses(List list, co
 
 template <class List>
 __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, const float4* __restrict__ pts, int K,
-                                                                    unsigned seed, int* __restrict__ samples,
+                                                                    unsigned seed, float e2, int* __restrict__ samples,
                                                                     float* __restrict__ Hout, int* __restrict__ valid) {
 #pragma clang fp contract(off)
     if constexpr (kBatched<List>) {
@@ -335,15 +335,17 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, 
 #pragma unroll
     for (int i = 0; i < 9; i++) g[i] = 0.f;
     float qx[4], qy[4], tx[4], ty[4];
-    float qx0 = 0.f, qy0 = 0.f;
+    float4 own[4];  // the sample's raw pairs: the sign rule reads pair 0, the own-sample rule all four
+#pragma unroll
+    for (int j = 0; j < 4; j++) own[j] = float4{0.f, 0.f, 0.f, 0.f};
     if (ok) {
         draw<4>(seed, k, n, pick);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const float4 p = pts[pick[j]];
+            own[j] = p;
             qx[j] = p.x, qy[j] = p.y, tx[j] = p.z, ty[j] = p.w;
         }
-        qx0 = qx[0], qy0 = qy[0];
         // The orientation test on the raw coordinates: every triple keeps, or every triple flips, its orientation.
         // A zero (three collinear points) or a NaN fails both.
         bool keeps = true, flips = true;
@@ -389,13 +391,16 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, 
         }
         unit_norm(H);
         // The sign that puts sample 0 in front (w > 0), so the score's chirality test means something.
-        const float w0 = (H[6] * qx0 + H[7] * qy0) + H[8];
+        const float w0 = (H[6] * own[0].x + H[7] * own[0].y) + H[8];
         ok = w0 != 0.f;
 #pragma unroll
         for (int i = 0; i < 9; i++) {
             g[i] = w0 < 0.f ? -H[i] : H[i];
             ok = ok && finite_f(g[i]);
         }
+        // The own-sample rule: a hypothesis that does not count each of its four pairs is invalid.
+#pragma unroll
+        for (int j = 0; j < 4; j++) ok = ok && TransferPass::pass(g, own[j], e2);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) samples[4 * (size_t)k + j] = pick[j];
@@ -581,11 +586,11 @@ void launch_verify_gather(const List& list, float4* pts, hipStream_t s) {
 }
 
 template <class List>
-void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, int* samples,
-                              float* F, int* valid, hipStream_t s) {
+void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, float e2,
+                              int* samples, float* F, int* valid, hipStream_t s) {
     const dim3 grid((K + kHypThreads - 1) / kHypThreads, list_pairs(list)), block(kHypThreads);
     if (model == VerifyModel::Homography)
-        hipLaunchKernelGGL(k_verify_hypotheses_h<List>, grid, block, 0, s, list, pts, K, seed, samples, F, valid);
+        hipLaunchKernelGGL(k_verify_hypotheses_h<List>, grid, block, 0, s, list, pts, K, seed, e2, samples, F, valid);
     else
         hipLaunchKernelGGL(k_verify_hypotheses<List>, grid, block, 0, s, list, pts, K, seed, samples, F, valid);
 }
@@ -615,8 +620,8 @@ void launch_verify_select(VerifyModel model, const List& list, const float4* pts
 
 #define SIFT_VERIFY_LAUNCHERS(List)                                                                                     \
     template void launch_verify_gather<List>(const List&, float4*, hipStream_t);                                        \
-    template void launch_verify_hypotheses<List>(VerifyModel, const List&, const float4*, int, unsigned, int*, float*,   \
-                                                 int*, hipStream_t);                                                    \
+    template void launch_verify_hypotheses<List>(VerifyModel, const List&, const float4*, int, unsigned, float, int*,   \
+                                                 float*, int*, hipStream_t);                                            \
     template void launch_verify_score<List>(VerifyModel, const List&, const float4*, const float*, const int*, int,     \
                                             float, int*, hipStream_t);                                                  \
     template void launch_verify_select<List>(VerifyModel, const List&, const float4*, const float*, const int*,         \

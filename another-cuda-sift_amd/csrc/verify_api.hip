@@ -179,7 +179,7 @@ int verify_on(sift_hip_verifier* v, const Call& c, const List& list, const Outpu
     const int K = c.params->hypotheses;
     const float e2 = c.params->max_error * c.params->max_error;
     launch_verify_gather(list, v->dPts, o.stream);
-    launch_verify_hypotheses(c.model, list, v->dPts, K, c.params->seed, v->dSamples, v->dF, v->dValid, o.stream);
+    launch_verify_hypotheses(c.model, list, v->dPts, K, c.params->seed, e2, v->dSamples, v->dF, v->dValid, o.stream);
     launch_verify_score(c.model, list, v->dPts, v->dF, v->dValid, K, e2, v->dCounts, o.stream);
     launch_verify_select(c.model, list, v->dPts, v->dF, v->dValid, v->dCounts, K, e2, o.result, o.out, o.out_counts,
                          o.mask, o.stream);

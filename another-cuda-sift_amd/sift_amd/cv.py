@@ -631,11 +631,13 @@ def _oriented(q, t):
     return (p > 0).all(1) | (p < 0).all(1)
 
 
-def homography_from_4(q_xy4, t_xy4):
+def homography_from_4(q_xy4, t_xy4, max_error=None):
     """The solver of the homography rule: the normalised 4-point H of 4 pairs (the orientation test, the 8 x 9 system
     through the fundamental rule's elimination, unit Frobenius norm, the sign that makes w positive at sample 0).
     q_xy4 / t_xy4: (4, 2) -> (H (9,) float32, valid bool), or (K, 4, 2) -> (H (K, 9), valid (K,)).  An invalid
-    hypothesis (a failed orientation test, a zero or non-finite pivot or result, w0 = 0) has H all zero."""
+    hypothesis (a failed orientation test, a zero or non-finite pivot or result, w0 = 0) has H all zero.  With a
+    max_error the rule's last step applies too, as in a verify call: a hypothesis that does not count each of its own
+    four pairs under the transfer predicate is invalid."""
     q = np.asarray(q_xy4, np.float32)
     t = np.asarray(t_xy4, np.float32)
     single = q.ndim == 2
@@ -668,6 +670,14 @@ def homography_from_4(q_xy4, t_xy4):
         w0 = (H[:, 6] * q[:, 0, 0] + H[:, 7] * q[:, 0, 1]) + H[:, 8]
         H = np.where((w0 < 0)[:, None], -H, H)
         ok &= np.isfinite(H).all(1) & (w0 != 0)
+        if max_error is not None:  # the own-sample rule: _transfer_pass's operations, hypothesis k on its own pair i
+            e = np.float32(max_error)
+            for i in range(4):
+                px = (H[:, 0] * q[:, i, 0] + H[:, 1] * q[:, i, 1]) + H[:, 2]
+                py = (H[:, 3] * q[:, i, 0] + H[:, 4] * q[:, i, 1]) + H[:, 5]
+                w = (H[:, 6] * q[:, i, 0] + H[:, 7] * q[:, i, 1]) + H[:, 8]
+                dx, dy = px - t[:, i, 0] * w, py - t[:, i, 1] * w
+                ok &= (w > 0) & (dx * dx + dy * dy <= (e * e) * (w * w))
     assert A.dtype == np.float32 and g.dtype == np.float32 and H.dtype == np.float32 and ss.dtype == np.float32
     assert M.dtype == np.float32 and w0.dtype == np.float32
     H[~ok] = 0
@@ -713,7 +723,7 @@ def ransac_homography(matches, q_xy, t_xy, max_error=1.5, K: int = 1024, seed: i
     pts = _match_points(matches, q_xy, t_xy)
     samples = homography_samples(n, K, seed)
     if n >= 4:
-        Hs, valid = homography_from_4(pts[samples][:, :, :2], pts[samples][:, :, 2:])
+        Hs, valid = homography_from_4(pts[samples][:, :, :2], pts[samples][:, :, 2:], max_error)
         passes = _transfer_pass(pts, Hs, max_error) & valid[:, None]
     else:
         Hs, valid, passes = np.zeros((K, 9), np.float32), np.zeros(K, bool), np.zeros((K, n), bool)

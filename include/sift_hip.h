@@ -1249,7 +1249,11 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
  * Score.  Match j is an inlier of a valid hypothesis when the epipolar
  * predicate above holds for its own pair under the hypothesis' F, with
  * e2 = max_error*max_error and radius = +inf (no window):
- * r*r <= e2 * (nq + nr), inclusive.  A NaN is an inlier of nothing.
+ * r*r <= e2 * (nq + nr), inclusive.  A NaN is an inlier of nothing.  An
+ * overflow is no NaN: for a finite position so large that both sides of the
+ * compare overflow (coordinates of about 1e18 and beyond) the compare reads
+ * +inf <= +inf and holds, so such a record is an inlier of every hypothesis
+ * that does not turn it into a NaN.  Positions are expected in pixels.
  *
  * Selection.  The valid hypothesis with the most inliers wins, ties to the
  * lowest k.  With n < 8 (no hypothesis is drawn: every sample index is -1) or
@@ -1377,7 +1381,13 @@ int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* 
  * scaled to unit Frobenius norm (ss = sum H[i]*H[i] over i = 0..8 in index
  * order, H[i] = H[i] / sqrtf(ss)).  Then w0 = (h6*qx0 + h7*qy0) + h8 for sample
  * 0's raw query position; if w0 < 0 every entry of H is negated.  The hypothesis
- * is invalid when any entry is non-finite or w0 == 0.  An invalid hypothesis has
+ * is invalid when any entry is non-finite or w0 == 0, and -- the own-sample
+ * rule -- when one of its own four pairs fails the score's predicate below
+ * under H and the call's max_error: where the horizon of H (w = 0) passes next
+ * to a sample's query position, the float32 rounding of px and py divided by w
+ * is worth pixels and no float32 H reproduces that pair (samples that hold an
+ * unrelated pair do this about once in 300).  So every valid hypothesis counts
+ * at least its own 4 matches.  An invalid hypothesis has
  * H all zero and inlier count 0.  There is no refit on the inliers and no
  * h8 = 1 scaling: divide by H[8] for OpenCV's convention;
  * sift_amd.cv.homography_lstsq refits on the host.
@@ -1388,7 +1398,8 @@ int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* 
  *   w > 0  &&  dx*dx + dy*dy <= (max_error*max_error) * (w*w)
  * -- the forward transfer error (OpenCV's reprojection error) <= max_error,
  * inclusive, division-free, with the chirality test the sign rule makes
- * meaningful.  A NaN is an inlier of nothing.
+ * meaningful.  A NaN is an inlier of nothing; an overflow of both sides to
+ * +inf is an inlier, as for the fundamental matrix.
  *
  * Selection and output.  As above: most inliers among the valid hypotheses,
  * ties to the lowest k; with n < 4 or no valid hypothesis hypothesis = -1,
