@@ -20,15 +20,21 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             $(if $(strip $(EXTRA_HIPFLAGS)),-DSIFT_AB_FLAGS='"$(strip $(EXTRA_HIPFLAGS))"')
 CXXFLAGS := -O2 -std=c++17 -fPIC -Iinclude -Wall -Wextra
 
-HIP_SRCS := $(SRC)/detector.hip $(SRC)/lanes.hip $(SRC)/datagen.hip $(SRC)/matcher_api.hip $(SRC)/pyramid.hip $(SRC)/keypoints.hip $(SRC)/descriptor.hip $(SRC)/match.hip \
+HIP_SRCS := $(SRC)/detector.hip $(SRC)/lanes.hip $(SRC)/datagen.hip $(SRC)/matcher_api.hip $(SRC)/keypoints.hip $(SRC)/descriptor.hip \
+            $(SRC)/upsample.hip $(SRC)/blur.hip $(SRC)/blur_tail.hip $(SRC)/extrema.hip \
+            $(SRC)/match.hip $(SRC)/match_select.hip $(SRC)/match_knn.hip \
             $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/refit.hip $(SRC)/pose.hip $(SRC)/verify_api.hip $(SRC)/rootsift.hip
 HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OUT)/obj/%.o,$(HIP_SRCS)) $(OUT)/obj/synth_frame.o
 
 all: $(OUT)/libsift_hip.so $(OUT)/libsift_cuda.so tools
 
-$(OUT)/obj/%.o: $(SRC)/%.hip $(SRC)/detector_state.h $(SRC)/sift_kernels.h $(SRC)/sift_math.h $(SRC)/sift_match.h $(SRC)/sift_refine.h $(SRC)/sift_desc_rows.h $(SRC)/sift_rootsift.h $(SRC)/sift_epipolar.h $(SRC)/sift_verify.h $(SRC)/sift_verify_dev.h $(SRC)/sift_jacobi_dev.h include/sift_hip.h
+# Each object's headers come from the dependency file the compiler writes beside it (-MMD -MP), so a unit is rebuilt
+# when a header it includes changes and not otherwise.
+$(OUT)/obj/%.o: $(SRC)/%.hip include/sift_hip.h
 	@mkdir -p $(OUT)/obj
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
+
+-include $(HIP_OBJS:.o=.d)
 
 $(OUT)/obj/synth_frame.o: $(SRC)/synth_frame.cpp include/sift_hip.h
 	@mkdir -p $(OUT)/obj
@@ -95,6 +101,7 @@ clean:
 .PHONY: all tools oracle asan clean
 
 # Isolated kernel timing (tools/kernel_bench.hip), not part of `all`.
-tools/kernel_bench: tools/kernel_bench.hip $(OUT)/obj/pyramid.o $(OUT)/obj/synth_frame.o
+KBENCH_OBJS := $(OUT)/obj/blur.o $(OUT)/obj/extrema.o $(OUT)/obj/synth_frame.o
+tools/kernel_bench: tools/kernel_bench.hip $(KBENCH_OBJS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o tools/kernel_bench.o
-	$(HIPCC) --offload-arch=$(ARCH) -o $@ tools/kernel_bench.o $(OUT)/obj/pyramid.o $(OUT)/obj/synth_frame.o
+	$(HIPCC) --offload-arch=$(ARCH) -o $@ tools/kernel_bench.o $(KBENCH_OBJS)

@@ -1,5 +1,6 @@
 // Matcher handle (sift_hip_matcher_*, sift_hip_match_*) and the descriptor
-// sidecar registry of libsift_hip.so; the kernels are match.hip.  Replaces
+// sidecar registry of libsift_hip.so; the kernels are match.hip, match_select.hip
+// and match_knn.hip.  Replaces
 // /root/reference/sift_cuda/sift_func/Match.cu:8-33 (matchBruteForce).
 //
 // Every match entry point fills one MatchCall and hands it to run(): one

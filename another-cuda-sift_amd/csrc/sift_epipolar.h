@@ -1,5 +1,5 @@
 // The epipolar predicate (the rule is in include/sift_hip.h), shared by the
-// matcher's epipolar gate (match.hip, k_match_epipolar) and the two-view
+// matcher's epipolar gate (sift_match_dev.h; match.hip's k_match_epipolar, match_knn.hip) and the two-view
 // verifier's score (verify.hip): one statement of the float32 operation order.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -83,7 +83,7 @@ struct Counters {
 // a keypoint without a peak leaves a hole (bucket kHoleBucket, response 0).
 constexpr unsigned kHoleBucket = 0xffffffffu;
 
-// --- launch wrappers (implemented in pyramid.hip / keypoints.hip / match.hip) --
+// --- launch wrappers (implemented in upsample.hip / blur.hip / blur_tail.hip / extrema.hip / keypoints.hip) --
 // sfs: byte stride between the nf source frames (the caller's frames or arenas).
 void launch_upsample2x(const float* src, int spitch, int W, int H, float* dst, int dpitch, const Frames& fr, long sfs,
                        hipStream_t s);
@@ -126,7 +126,7 @@ struct BlurDesc {
     const Taps* taps;
 };
 bool launch_blur_pair(const BlurDesc& a, const BlurDesc& b, const Frames& fr, hipStream_t s);
-// Pyramid tail (pyramid.hip): planes 1..L+2 of octaves o0..nOct-1 of each
+// Pyramid tail (blur_tail.hip): planes 1..L+2 of octaves o0..nOct-1 of each
 // frame in one workgroup, in LDS, from octave o0's base plane (already in
 // HBM).  tail_first_octave: the first octave from which every later octave
 // fits (nOct: none).  taps[i] = the blur of plane i (i = 1..L+2).
@@ -304,7 +304,7 @@ void launch_bucket_rank(const PyrDesc& pyr, const OriKpt* kpts, unsigned* bcount
 // Matcher sidecar of a descriptor buffer (written by the descriptor kernels
 // beside the fp16 rows): per keypoint p its int8 codes c = v - 128 (128 B,
 // row-major) and the key bias -(256 |c|^2 + (p & 255)) that the matcher's
-// prep kernel would compute (match.hip).  sift_hip_match_* use it for
+// prep kernel would compute (k_match_prep, match.hip).  sift_hip_match_* use it for
 // detector-produced buffers instead of converting the fp16 rows.
 struct Sidecar {
     int8_t* codes;

@@ -1,4 +1,4 @@
-// Matcher launch interface: the launchers of match.hip as matcher_api.hip's host path (the C ABI) calls them.
+// Matcher launch interface: the launchers of match.hip, match_select.hip and match_knn.hip as matcher_api.hip's host path (the C ABI) calls them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

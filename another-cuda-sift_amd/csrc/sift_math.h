@@ -76,6 +76,18 @@ __device__ __forceinline__ int reflect101(int p, int len) {
     return p;
 }
 
+// Packed-float vectors of the pyramid kernels.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// A wave's neighbour lanes by DPP (the 2x upsample's and the extrema strips' columns across lane edges).
+__device__ __forceinline__ float dpp_left_or(float own, float v) {  // lane i <- lane i-1, lane 0 <- own
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dpp_right_or(float own, float v) {  // lane i <- lane i+1, lane 63 <- own
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own), __float_as_int(v), 0x130, 0xf, 0xf, false));
+}
+
 // XCD-aware tile order.  Workgroups are dispatched round-robin over the 8
 // XCDs (linear id b -> XCD b % 8) and each XCD has its own 4 MiB L2, so a
 // raster tile order scatters neighbouring tiles -- whose halos overlap --

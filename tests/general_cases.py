@@ -1,7 +1,7 @@
 """Inputs and float64 references shared by the general-path matcher tests (tests/test_match_general_cases.py on the
 CPU, tests/test_gpu_match_general.py on the GPU) and by tools/general_path_accuracy.py.
 
-The general path of the matcher (match_f16_block in csrc/match.hip) takes every set that holds a value which is not
+The general path of the matcher (match_f16_block in csrc/sift_match_dev.h) takes every set that holds a value which is not
 an integer 0..255.  The other matcher tests feed it values for which fp32 arithmetic is exact; the two families here
 make fp32 round:
 

@@ -1,5 +1,5 @@
 """The fused single-pair matcher's fp16 -> int8 code conversion
-(another-cuda-sift_amd/csrc/match.hip, codes16), restated in numpy over every
+(another-cuda-sift_amd/csrc/sift_match_dev.h, codes16), restated in numpy over every
 fp16 bit pattern: v + 1024 puts an integer 0..255 in the low mantissa byte,
 the low byte ^ 0x80 is the int8 code v - 128, and a value is accepted only if
 the high byte is 0x64 and (v + 1024) - 1024 gives v back bit for bit.  Exactly

@@ -1,7 +1,7 @@
 """What tests/threshold_cases.py's frames do to the detector (no GPU): each
 has, by the oracle, the property its GPU test in test_gpu_thresholds.py relies
 on.  Capacities are the library's (Detector.capacities(), host-only); the
-tile and list sizes mirror another-cuda-sift_amd/csrc/pyramid.hip (EX4_LIST,
+tile and list sizes mirror another-cuda-sift_amd/csrc/extrema.hip (EX4_LIST,
 EX4_COLS and the 2-row / 12-row strips of extrema_block and launch_extrema_all;
 EX_LIST, EX_TW x EX_TH of k_extrema) as named constants of threshold_cases.
 

@@ -21,7 +21,7 @@ import numpy as np
 
 import oracle_binding as oracle
 
-# Extrema geometry of another-cuda-sift_amd/csrc/pyramid.hip, mirrored:
+# Extrema geometry of another-cuda-sift_amd/csrc/extrema.hip, mirrored:
 #   k_extrema_all (L <= 6): a workgroup is four waves over a strip of EX4_COLS
 #   = 256 columns; a wave takes 2 rows (EX4_TR = 2), or 12 (6 * kExStream) in
 #   launches of many strips, so a workgroup's tile is 256 x 8 or 256 x 48, all

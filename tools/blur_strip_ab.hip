@@ -4,7 +4,7 @@
 // owns 64 output columns x SEG rows, keeps the row-blurred rows in an LDS ring
 // and streams 8 input rows per step (loaded one step ahead into registers), so
 // no input row is read twice vertically inside a segment.  Same arithmetic as
-// the product (pyramid.hip header comment): outputs compared bit for bit.
+// the product (blur.hip header comment): outputs compared bit for bit.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
 //     -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -Ianother-cuda-sift_amd/csrc \

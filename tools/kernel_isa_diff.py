@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
-"""Compare the kernels of two device-assembly builds of one HIP source.
+"""Compare the kernels of two device-assembly builds of the same HIP code.
 
     hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o a.s   (old tree)
     hipcc <HIPFLAGS of the Makefile> --cuda-device-only -S file.hip -o b.s   (new tree)
     tools/kernel_isa_diff.py a.s b.s [--json out.json] [--count v_mfma ds_read ...] [--rename OLD=NEW ...]
 
-Per kernel (symbol .. function-end label) the text is compared after the local
-label numbers (.LBB<n>_, BB<n>_ in comments) are normalised; the resources are
-read from the compiler's own summary after the function.  A kernel of one build
-only is listed with its resources.  Exit status 1 when a kernel's text differs
-or a kernel is in one build only.  --rename OLD=NEW compares kernel OLD of the
+Either side may be the `cat` of several units' assembly (a source split into, or
+merged from, several translation units): kernels are matched by name, wherever
+they stand.  Per kernel (symbol .. function-end label) the text is compared
+after the local label numbers (.LBB<n>_) are normalised and every line's
+trailing `;` comment and trailing whitespace are removed (the comments and
+their padding depend on a function's ordinal in its file; comment-only lines
+drop out); the resources are read from the compiler's own summary after the
+function.  A kernel of one build only is listed with its resources.  Exit
+status 1 when a kernel's text differs, a kernel is in one build only, or a name
+occurs twice on one side (a kernel instantiated in two units).
+
+--rename OLD=NEW compares kernel OLD of the
 old build with kernel NEW of the new one (a kernel whose template parameters or
 argument types were renamed): OLD is replaced by NEW in the old build's name and
 text first, and the report keeps the old name under "renamed_from".
@@ -32,10 +39,14 @@ def kernels(path):
             continue
         if name is not None:
             if line.startswith(".Lfunc_end"):
+                if name in out:
+                    sys.exit(f"{path}: kernel {name} occurs twice (instantiated in two units?)")
                 out[name] = {"text": body}
                 tail, name = out[name], None
             else:
-                body.append(re.sub(r"BB\d+_", "BB_", line.split("; %bb.")[0]).rstrip())
+                text = re.sub(r"BB\d+_", "BB_", line.split(";")[0]).rstrip()
+                if text:
+                    body.append(text)
             continue
         if tail is not None:
             for k, pat in RES.items():

@@ -22,14 +22,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build(name):
-    tmp = tempfile.mkdtemp()
-    shutil.copy(os.path.join(ROOT, "Makefile"), tmp)
-    shutil.copytree(os.path.join(ROOT, "include"), os.path.join(tmp, "include"))
-    shutil.copytree(os.path.join(ROOT, "another-cuda-sift_amd", "csrc"), os.path.join(tmp, "another-cuda-sift_amd", "csrc"))
-    path = os.path.join(tmp, "another-cuda-sift_amd", "csrc", "match.hip")
-    s = open(path).read()
+def patch(s):
+    """The text of csrc/match.hip with the stamps added to k_match_batch; every anchor must be found."""
     anchor_ns = "namespace sift_amd {\n"
+    assert s.count(anchor_ns) == 1
     s = s.replace(anchor_ns, anchor_ns + """
 __device__ unsigned long long g_wg_stamps[16384][6];
 __device__ __forceinline__ void wg_stamp(int slot) {
@@ -42,10 +38,10 @@ __device__ __forceinline__ void wg_stamp(int slot) {
     }
 }
 """, 1)
-    a1 = "    const int q0w = q0 + 64 * w;\n    Top2 res[2];\n    if (flags[pr.qset] != epoch"
+    a1 = "    const int q0w = q0 + 32 * QBW * w;\n    Top2 res[QBW];\n    // flags == nullptr: code sets handed over ready"
     assert s.count(a1) == 1
     s = s.replace(a1, "    wg_stamp(0);\n" + a1)
-    a2 = "        res[0] = match_f16_block(pr, q0w, tb, te, col, h);\n        res[1] = match_f16_block(pr, q0w + 32, tb, te, col, h);\n    }\n"
+    a2 = "        for (int qb = 0; qb < QBW; qb++) res[qb] = match_f16_block(pr, NoGate{}, q0w + 32 * qb, tb, te, col, h);\n    }\n"
     assert s.count(a2) == 1
     s = s.replace(a2, a2 + "    wg_stamp(1);\n")
     a3 = "    merge_contribution(s_res, &s_last, keys + 2 * ((size_t)p * nq_stride + q0)"
@@ -53,7 +49,7 @@ __device__ __forceinline__ void wg_stamp(int slot) {
     i3 = s.index(a3)
     e3 = s.index(";\n}\n", i3)
     s = s[:e3] + ";\n    wg_stamp(2);\n}\n" + s[e3 + 4:]
-    a4 = "        if (qv) write_top2(s_res[tid], o, ratio, ratio_on_squared, idx2, d2out, match);\n        return;\n"
+    a4 = "        if (qv) write_top2(s_res[tid], o, out);\n        return;\n"
     i4 = s.rindex(a4, 0, i3)  # the S == 1 exit of k_match_batch
     s = s[:i4] + a4.replace("        return;\n", "        wg_stamp(2);\n        return;\n") + s[i4 + len(a4):]
     s += """
@@ -61,7 +57,16 @@ extern "C" int sift_hip_debug_wg_stamps(void* dst, size_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sift_amd::g_wg_stamps), bytes, 0, hipMemcpyDeviceToHost);
 }
 """
-    open(path, "w").write(s)
+    return s
+
+
+def build(name):
+    tmp = tempfile.mkdtemp()
+    shutil.copy(os.path.join(ROOT, "Makefile"), tmp)
+    shutil.copytree(os.path.join(ROOT, "include"), os.path.join(tmp, "include"))
+    shutil.copytree(os.path.join(ROOT, "another-cuda-sift_amd", "csrc"), os.path.join(tmp, "another-cuda-sift_amd", "csrc"))
+    path = os.path.join(tmp, "another-cuda-sift_amd", "csrc", "match.hip")
+    open(path, "w").write(patch(open(path).read()))
     r = subprocess.run(["make", "-C", tmp, "-j8", "another-cuda-sift_amd/lib/libsift_hip.so"], capture_output=True,
                        text=True)
     if r.returncode:
