@@ -150,6 +150,40 @@ void launch_pose_select(const List& list, const float4* pts, const uint8_t* mask
                         float max_depth, float max_cos_parallax, PoseResult* pose, uint8_t* mask_out, float* points,
                         MatchRecord* out, int* out_count, hipStream_t s);
 
+// The relative pose from a verified homography (pose_homography.hip; sift_hip_recover_pose_homography_*, the rule is
+// in include/sift_hip.h).  The same two launches on the gathered list:
+// k_plane_decompose: one wave per pair.  A = Kt^-1 H Kq of the pair's record under its two cameras, the eigenvectors of
+//   A^T A by the refit's Jacobi routine, and the two (R, t, N, distance) of the four candidates into the verifier's
+//   scratch record cand[p] (usable = 0: an empty or unusable record, or an A without a decomposition); the four
+//   candidates rounded to float32 into candidates[4 p ..] when that is not null (all zero when usable = 0).
+// k_plane_select: one workgroup per pair.  k_pose_select with a translation per rotation and w > 0 under H in the fit
+//   test; the winner's plane follows its pose in pose[p].
+struct PlanePoseResult {  // sift_hip_plane_pose_result's layout: a PoseResult, then the plane
+    PoseResult pose;
+    float normal[3], distance;
+};
+static_assert(sizeof(PlanePoseResult) == 96, "sift_hip_plane_pose_result layout");
+struct PlaneCandidate {  // sift_hip_plane_candidate's layout
+    float R[9], t[3], normal[3], distance;
+};
+static_assert(sizeof(PlaneCandidate) == 64, "sift_hip_plane_candidate layout");
+struct PlaneCandidates {  // k_plane_select reads the 43 leading doubles as an array
+    double R[2][9];  // R+, R- row-major; the candidates are (R+, t+, N+), (R-, t-, N-), (R+, -t+, -N+), (R-, -t-, -N-)
+    double t[2][3];
+    double kq[4], kt[4];  // the cameras' fx, fy, cx, cy
+    double h3[3];         // the third row of H as the record holds it: w = (h3[0] qx + h3[1] qy) + h3[2]
+    double N[2][3];
+    double distance[2];
+    int usable, pad;
+};
+static_assert(offsetof(PlaneCandidates, usable) == 43 * sizeof(double), "k_plane_select's view of the record");
+void launch_plane_decompose(const PoseCameras& cams, int P, const VerifyResult* result, PlaneCandidates* cand,
+                            PlaneCandidate* candidates, hipStream_t s);
+template <class List>
+void launch_plane_select(const List& list, const float4* pts, const uint8_t* mask, const PlaneCandidates* cand,
+                         float max_depth, float max_cos_parallax, PlanePoseResult* pose, uint8_t* mask_out, float* points,
+                         MatchRecord* out, int* out_count, hipStream_t s);
+
 // k_project_homography: out[i * out_stride + {0, 1}] = row i of xy (n rows of
 // `stride` floats) through the device matrix H, NaN x 2 where w is not > 0.
 void launch_project_homography(const float* H, const float* xy, int stride, int n, float* out, int out_stride,

@@ -30,6 +30,9 @@ struct sift_hip_verifier {
     PoseCandidates* dPoseCand = nullptr;  // the pose calls' candidates per pair (sift_hip_recover_pose_*), maxP records
     PoseResult* dPose = nullptr;          // sift_hip_recover_pose_*_host: maxP pose records and maxM x 3 point floats
     float* dPoints = nullptr;
+    PlaneCandidates* dPlaneCand = nullptr;  // the plane pose calls' candidates per pair (sift_hip_recover_pose_homography_*)
+    PlanePoseResult* dPlanePose = nullptr;  // their host forms: maxP pose records and 4 x maxP candidates
+    PlaneCandidate* dPlaneOut = nullptr;
     int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
     int lastModel = 0;           // its VerifyModel, 0: none
     bool lastBatch = false;      // it was a batched call (the getters read one pair's scratch layout)
@@ -37,7 +40,7 @@ struct sift_hip_verifier {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
                         (void*)dOut, (void*)dMask, (void*)dCand, (void*)dRefineInts, (void*)dPoseCand, (void*)dPose,
-                        (void*)dPoints})
+                        (void*)dPoints, (void*)dPlaneCand, (void*)dPlanePose, (void*)dPlaneOut})
             if (p) (void)hipFree(p);
     }
 };
@@ -49,6 +52,10 @@ static_assert(sizeof(sift_hip_homography_result) == sizeof(VerifyResult) &&
 static_assert(sizeof(sift_hip_pose_result) == sizeof(PoseResult) &&
                   offsetof(sift_hip_pose_result, candidate) == offsetof(PoseResult, candidate),
               "the pose record is written by the kernel");
+static_assert(sizeof(sift_hip_plane_pose_result) == sizeof(PlanePoseResult) &&
+                  offsetof(sift_hip_plane_pose_result, normal) == offsetof(PlanePoseResult, normal) &&
+                  sizeof(sift_hip_plane_candidate) == sizeof(PlaneCandidate),
+              "the plane pose record and the candidates are written by the kernels");
 static_assert(sizeof(sift_hip_camera) == sizeof(PoseCamera), "the cameras go to the kernel as they are");
 
 namespace {
@@ -84,6 +91,7 @@ struct Call {
     void* pose;
     uint8_t* mask_out;
     float* points;
+    void* candidates;  // plane pose: 4 P candidates, nullable
     void* stream;
 };
 
@@ -167,9 +175,11 @@ struct Outputs {
     uint8_t* mask;
     int* accepted;
     hipStream_t stream;
-    PoseResult* pose = nullptr;  // the pose calls' outputs; result and mask are then read only
+    // the pose calls' outputs; result and mask are then read only
+    void* pose = nullptr;  // PoseResult records, or PlanePoseResult records for the homography
     uint8_t* mask_out = nullptr;
     float* points = nullptr;
+    PlaneCandidate* candidates = nullptr;  // the homography's four per pair
 };
 
 // The runners, one per operation, over the list type (VerifyInput or VerifyBatch): one launch per step for all the
@@ -225,9 +235,17 @@ int pose_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs
         cams.t[p] = PoseCamera{c.cams_t[p].fx, c.cams_t[p].fy, c.cams_t[p].cx, c.cams_t[p].cy};
     }
     launch_verify_gather(list, v->dPts, o.stream);
-    launch_pose_decompose(cams, c.P, o.result, v->dPoseCand, o.stream);
-    launch_pose_select(list, v->dPts, o.mask, v->dPoseCand, c.pose_params->max_depth, c.pose_params->max_cos_parallax,
-                       o.pose, o.mask_out, o.points, o.out, o.out_counts, o.stream);
+    if (c.model == VerifyModel::Homography) {
+        launch_plane_decompose(cams, c.P, o.result, v->dPlaneCand, o.candidates, o.stream);
+        launch_plane_select(list, v->dPts, o.mask, v->dPlaneCand, c.pose_params->max_depth,
+                            c.pose_params->max_cos_parallax, static_cast<PlanePoseResult*>(o.pose), o.mask_out, o.points,
+                            o.out, o.out_counts, o.stream);
+    } else {
+        launch_pose_decompose(cams, c.P, o.result, v->dPoseCand, o.stream);
+        launch_pose_select(list, v->dPts, o.mask, v->dPoseCand, c.pose_params->max_depth,
+                           c.pose_params->max_cos_parallax, static_cast<PoseResult*>(o.pose), o.mask_out, o.points, o.out,
+                           o.out_counts, o.stream);
+    }
     HIPCHK(hipGetLastError());
     return SIFT_HIP_OK;
 }
@@ -283,7 +301,13 @@ int refine_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch&
 int pose_to_host(const sift_hip_verifier* v, const Call& c, const VerifyBatch& b) {
     int n[kVerifyMaxPairs];
     HIPCHK(hipMemcpy(n, v->dRefineInts, sizeof(int) * (size_t)b.P, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c.pose, v->dPose, sizeof(PoseResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+    if (c.model == VerifyModel::Homography) {
+        HIPCHK(hipMemcpy(c.pose, v->dPlanePose, sizeof(PlanePoseResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+        if (c.candidates)
+            HIPCHK(hipMemcpy(c.candidates, v->dPlaneOut, sizeof(PlaneCandidate) * 4 * (size_t)b.P, hipMemcpyDeviceToHost));
+    } else {
+        HIPCHK(hipMemcpy(c.pose, v->dPose, sizeof(PoseResult) * (size_t)b.P, hipMemcpyDeviceToHost));
+    }
     if (c.mask_out && b.rows > 0) HIPCHK(hipMemcpy(c.mask_out, v->dMask, (size_t)b.rows, hipMemcpyDeviceToHost));
     if (c.points && b.rows > 0) {
         int counts[kVerifyMaxPairs];
@@ -313,7 +337,9 @@ int run(sift_hip_verifier* v, const Call& c) {
                        : Outputs{static_cast<VerifyResult*>(c.result), reinterpret_cast<MatchRecord*>(c.out), c.out_counts,
                                  c.mask, c.accepted, (hipStream_t)c.stream};
     if (pose) {  // a host form writes the in-front mask over the uploaded mask, which the call allows
-        o.pose = c.host ? v->dPose : static_cast<PoseResult*>(c.pose);
+        const bool plane = c.model == VerifyModel::Homography;
+        o.pose = !c.host ? c.pose : plane ? (void*)v->dPlanePose : (void*)v->dPose;
+        o.candidates = !c.host ? static_cast<PlaneCandidate*>(c.candidates) : c.candidates ? v->dPlaneOut : nullptr;
         o.mask_out = !c.host ? c.mask_out : c.mask_out ? v->dMask : nullptr;
         o.points = !c.host ? c.points : c.points ? v->dPoints : nullptr;
     }
@@ -403,6 +429,9 @@ int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypoth
         hipMalloc((void**)&v->dPoseCand, sizeof(PoseCandidates) * (size_t)max_pairs) != hipSuccess ||
         hipMalloc((void**)&v->dPose, sizeof(PoseResult) * (size_t)max_pairs) != hipSuccess ||
         hipMalloc((void**)&v->dPoints, sizeof(float) * 3 * M) != hipSuccess ||
+        hipMalloc((void**)&v->dPlaneCand, sizeof(PlaneCandidates) * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dPlanePose, sizeof(PlanePoseResult) * (size_t)max_pairs) != hipSuccess ||
+        hipMalloc((void**)&v->dPlaneOut, sizeof(PlaneCandidate) * 4 * (size_t)max_pairs) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         delete v;
         return fail(SIFT_HIP_ERR_NOMEM, "verifier allocation failed");
@@ -470,36 +499,49 @@ SIFT_VERIFIER_ENTRIES(fundamental_batched, VerifyModel::Fundamental, sift_hip_ve
 SIFT_VERIFIER_ENTRIES(homography_batched, VerifyModel::Homography, sift_hip_homography_result, SIFT_BATCH, SIFT_BATCH_LIST)
 #undef SIFT_VERIFIER_ENTRIES
 
-// The four pose entry points: {one pair, batch} x {device, host}.
-#define SIFT_POSE_ENTRIES(name, LIST_ARGS, LIST)                                                                        \
+// The eight pose entry points: {from F, from H} x {one pair, batch} x {device, host}.  The plane pose calls carry one
+// more argument, the nullable candidates, at the end (CAND_ARG, CAND_SET).
+#define SIFT_POSE_ENTRIES(name, MODEL, RESULT, POSE, LIST_ARGS, LIST, CAND_ARG, CAND_SET)                               \
     int sift_hip_recover_pose##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,          \
-                                             const sift_hip_verify_result* result, const uint8_t* mask,                 \
+                                             const RESULT* result, const uint8_t* mask,                                 \
                                              const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,        \
-                                             const sift_hip_pose_params* params, sift_hip_pose_result* pose,            \
-                                             uint8_t* mask_out, float* points, sift_hip_dmatch* out, int* out_count,    \
+                                             const sift_hip_pose_params* params, POSE* pose, uint8_t* mask_out,         \
+                                             float* points, sift_hip_dmatch* out, int* out_count CAND_ARG,              \
                                              void* stream) {                                                            \
-        Call c = make_call(Op::Pose, VerifyModel::Fundamental, false, matches, query_stride, train_stride);             \
+        Call c = make_call(Op::Pose, MODEL, false, matches, query_stride, train_stride);                                \
         LIST(c);                                                                                                        \
-        c.result = const_cast<sift_hip_verify_result*>(result), c.mask = const_cast<uint8_t*>(mask);                    \
+        c.result = const_cast<RESULT*>(result), c.mask = const_cast<uint8_t*>(mask);                                    \
         c.cams_q = cam_query, c.cams_t = cam_train, c.pose_params = params, c.pose = pose, c.mask_out = mask_out;       \
         c.points = points, c.out = out, c.out_counts = out_count, c.stream = stream;                                    \
+        CAND_SET;                                                                                                       \
         return run(v, c);                                                                                               \
     }                                                                                                                   \
     int sift_hip_recover_pose##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,            \
-                                           const sift_hip_verify_result* result_host, const uint8_t* mask_host,         \
+                                           const RESULT* result_host, const uint8_t* mask_host,                         \
                                            const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,          \
-                                           const sift_hip_pose_params* params, sift_hip_pose_result* pose_host,         \
-                                           uint8_t* mask_out_host, float* points_host, sift_hip_dmatch* out_host,       \
-                                           int* out_count_host) {                                                       \
-        Call c = make_call(Op::Pose, VerifyModel::Fundamental, true, matches, query_stride, train_stride);              \
+                                           const sift_hip_pose_params* params, POSE* pose_host, uint8_t* mask_out_host, \
+                                           float* points_host, sift_hip_dmatch* out_host,                               \
+                                           int* out_count_host CAND_ARG) {                                              \
+        Call c = make_call(Op::Pose, MODEL, true, matches, query_stride, train_stride);                                 \
         LIST(c);                                                                                                        \
-        c.result = const_cast<sift_hip_verify_result*>(result_host), c.mask = const_cast<uint8_t*>(mask_host);          \
+        c.result = const_cast<RESULT*>(result_host), c.mask = const_cast<uint8_t*>(mask_host);                          \
         c.cams_q = cam_query, c.cams_t = cam_train, c.pose_params = params, c.pose = pose_host;                         \
         c.mask_out = mask_out_host, c.points = points_host, c.out = out_host, c.out_counts = out_count_host;            \
+        CAND_SET;                                                                                                       \
         return run(v, c);                                                                                               \
     }
-SIFT_POSE_ENTRIES(, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
-SIFT_POSE_ENTRIES(_batched, SIFT_BATCH, SIFT_BATCH_LIST)
+#define SIFT_NO_CAND
+#define SIFT_CAND_ARG , sift_hip_plane_candidate* candidates
+SIFT_POSE_ENTRIES(, VerifyModel::Fundamental, sift_hip_verify_result, sift_hip_pose_result, SIFT_ONE_PAIR,
+                  SIFT_ONE_PAIR_LIST, SIFT_NO_CAND, (void)0)
+SIFT_POSE_ENTRIES(_batched, VerifyModel::Fundamental, sift_hip_verify_result, sift_hip_pose_result, SIFT_BATCH,
+                  SIFT_BATCH_LIST, SIFT_NO_CAND, (void)0)
+SIFT_POSE_ENTRIES(_homography, VerifyModel::Homography, sift_hip_homography_result, sift_hip_plane_pose_result,
+                  SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST, SIFT_CAND_ARG, c.candidates = candidates)
+SIFT_POSE_ENTRIES(_homography_batched, VerifyModel::Homography, sift_hip_homography_result, sift_hip_plane_pose_result,
+                  SIFT_BATCH, SIFT_BATCH_LIST, SIFT_CAND_ARG, c.candidates = candidates)
+#undef SIFT_CAND_ARG
+#undef SIFT_NO_CAND
 #undef SIFT_POSE_ENTRIES
 #undef SIFT_BATCH_LIST
 #undef SIFT_BATCH

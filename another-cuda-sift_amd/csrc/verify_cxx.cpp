@@ -33,6 +33,15 @@ static_assert(sizeof(PoseResult) == sizeof(sift_hip_pose_result) &&
                   offsetof(PoseResult, counts) == offsetof(sift_hip_pose_result, counts) &&
                   offsetof(PoseResult, candidate) == offsetof(sift_hip_pose_result, candidate),
               "sift_cuda::PoseResult is sift_hip_pose_result");
+static_assert(sizeof(PlanePoseResult) == sizeof(sift_hip_plane_pose_result) &&
+                  offsetof(PlanePoseResult, candidate) == offsetof(sift_hip_plane_pose_result, candidate) &&
+                  offsetof(PlanePoseResult, normal) == offsetof(sift_hip_plane_pose_result, normal) &&
+                  offsetof(PlanePoseResult, distance) == offsetof(sift_hip_plane_pose_result, distance),
+              "sift_cuda::PlanePoseResult is sift_hip_plane_pose_result");
+static_assert(sizeof(PlaneCandidate) == sizeof(sift_hip_plane_candidate) &&
+                  offsetof(PlaneCandidate, normal) == offsetof(sift_hip_plane_candidate, normal) &&
+                  offsetof(PlaneCandidate, distance) == offsetof(sift_hip_plane_candidate, distance),
+              "sift_cuda::PlaneCandidate is sift_hip_plane_candidate");
 static_assert(sizeof(Camera) == sizeof(sift_hip_camera) && offsetof(Camera, cx) == offsetof(sift_hip_camera, cx),
               "sift_cuda::Camera is sift_hip_camera");
 
@@ -251,6 +260,41 @@ std::vector<RelativePose> recoverPoseHostT(sift_hip_verifier* h, const char* wha
     return out;
 }
 
+auto planePoseDevice(const OnePair&) { return sift_hip_recover_pose_homography_device; }
+auto planePoseDevice(const Batch&) { return sift_hip_recover_pose_homography_batched_device; }
+auto planePoseHost(const OnePair&) { return sift_hip_recover_pose_homography_host; }
+auto planePoseHost(const Batch&) { return sift_hip_recover_pose_homography_batched_host; }
+
+// The plane pose calls' host form over either list, as recoverPoseHostT.
+template <class List>
+std::vector<PlanePose> recoverPlanePoseHostT(sift_hip_verifier* h, const char* what, const List& l, size_t rows,
+                                             const std::vector<size_t>& caps, const sift_hip_homography_result* results,
+                                             const std::vector<uint8_t>& mask, const Camera* cq, const Camera* ct,
+                                             const PoseParams& params) {
+    const sift_hip_pose_params p = toAbi(params);
+    const size_t P = caps.size();
+    std::vector<sift_hip_plane_pose_result> poses(P ? P : 1);
+    std::vector<sift_hip_plane_candidate> cands(4 * (P ? P : 1));
+    std::vector<uint8_t> front(rows);
+    std::vector<float> points(3 * rows, std::numeric_limits<float>::quiet_NaN());
+    std::vector<DMatch> list(rows);
+    std::vector<int> n(P ? P : 1);
+    check_throw(abiCall(planePoseHost(l), h, l, results, mask.empty() ? nullptr : mask.data(), abi(cq), abi(ct), &p,
+                        poses.data(), front.data(), points.data(), abi(list.data()), n.data(), cands.data()),
+                what);
+    std::vector<PlanePose> out(P);
+    size_t row0 = 0;
+    for (size_t i = 0; i < P; i++) {
+        std::memcpy(&out[i].pose, &poses[i], sizeof(PlanePoseResult));
+        std::memcpy(out[i].candidates, &cands[4 * i], 4 * sizeof(PlaneCandidate));
+        out[i].mask.assign(front.begin() + row0, front.begin() + row0 + caps[i]);
+        out[i].points.assign(points.begin() + 3 * row0, points.begin() + 3 * (row0 + caps[i]));
+        out[i].inliers.assign(list.begin() + row0, list.begin() + row0 + (size_t)n[i]);
+        row0 += caps[i];
+    }
+    return out;
+}
+
 // The convenience call on a host list: a verifier sized to it (the argument rules come first, they need no device
 // memory), the list uploaded, the host form, and with refit > 0 that many refit rounds on its record and mask.
 template <class M>
@@ -391,6 +435,65 @@ std::vector<RelativePose> Verifier::recoverPoseBatchedHost(BATCH_ARGS, const std
                             reinterpret_cast<const sift_hip_verify_result*>(results.data()), mask, cams_query.data(),
                             cams_train.data(), params);
 }
+
+void Verifier::recoverPoseHomographyDevice(ONE_PAIR_ARGS, const HomographyResult* result, const uint8_t* mask,
+                                           const Camera& cam_query, const Camera& cam_train, const PoseParams& params,
+                                           PlanePoseResult* pose, uint8_t* mask_out, float* points, DMatch* out,
+                                           int* out_count, PlaneCandidate* candidates, void* stream) {
+    const sift_hip_pose_params p = toAbi(params);
+    const OnePair l = ONE_PAIR;
+    check_throw(abiCall(planePoseDevice(l), m_handle, l, reinterpret_cast<const sift_hip_homography_result*>(result), mask,
+                        abi(&cam_query), abi(&cam_train), &p, reinterpret_cast<sift_hip_plane_pose_result*>(pose),
+                        mask_out, points, abi(out), out_count, reinterpret_cast<sift_hip_plane_candidate*>(candidates),
+                        stream),
+                "Verifier::recoverPoseHomographyDevice");
+}
+
+void Verifier::recoverPoseHomographyBatchedDevice(BATCH_ARGS, const HomographyResult* results, const uint8_t* mask,
+                                                  const std::vector<Camera>& cams_query,
+                                                  const std::vector<Camera>& cams_train, const PoseParams& params,
+                                                  PlanePoseResult* poses, uint8_t* mask_out, float* points, DMatch* out,
+                                                  int* out_counts, PlaneCandidate* candidates, void* stream) {
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument("Verifier::recoverPoseHomographyBatchedDevice: one camera per pair and side");
+    const sift_hip_pose_params p = toAbi(params);
+    const Batch l = BATCH;
+    check_throw(abiCall(planePoseDevice(l), m_handle, l, reinterpret_cast<const sift_hip_homography_result*>(results),
+                        mask, abi(cams_query.data()), abi(cams_train.data()), &p,
+                        reinterpret_cast<sift_hip_plane_pose_result*>(poses), mask_out, points, abi(out), out_counts,
+                        reinterpret_cast<sift_hip_plane_candidate*>(candidates), stream),
+                "Verifier::recoverPoseHomographyBatchedDevice");
+}
+
+PlanePose Verifier::recoverPoseHomographyHost(ONE_PAIR_ARGS, const HomographyResult& result,
+                                              const std::vector<uint8_t>& mask, const Camera& cam_query,
+                                              const Camera& cam_train, const PoseParams& params) {
+    const char* what = "Verifier::recoverPoseHomographyHost";
+    const bool sized = cap >= 0 && cap <= 65536;
+    if (sized) check_mask(mask, (size_t)cap, what);
+    const size_t rows = sized ? (size_t)cap : 0;
+    return recoverPlanePoseHostT(m_handle, what, ONE_PAIR, rows, {rows},
+                                 reinterpret_cast<const sift_hip_homography_result*>(&result), mask, &cam_query,
+                                 &cam_train, params)[0];
+}
+
+std::vector<PlanePose> Verifier::recoverPoseHomographyBatchedHost(BATCH_ARGS, const std::vector<HomographyResult>& results,
+                                                                  const std::vector<uint8_t>& mask,
+                                                                  const std::vector<Camera>& cams_query,
+                                                                  const std::vector<Camera>& cams_train,
+                                                                  const PoseParams& params) {
+    const char* what = "Verifier::recoverPoseHomographyBatchedHost";
+    if (results.size() != pairs.size()) throw std::invalid_argument(std::string(what) + ": one result record per pair");
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument(std::string(what) + ": one camera per pair and side");
+    const size_t rows = batchRows(pairs);
+    if (rows > 0) check_mask(mask, rows, what);
+    std::vector<size_t> caps;
+    for (const VerifyPair& p : pairs) caps.push_back(rows > 0 && p.cap > 0 ? (size_t)p.cap : 0);
+    return recoverPlanePoseHostT(m_handle, what, BATCH, rows, caps,
+                                 reinterpret_cast<const sift_hip_homography_result*>(results.data()), mask,
+                                 cams_query.data(), cams_train.data(), params);
+}
 #undef BATCH
 #undef BATCH_ARGS
 #undef ONE_PAIR
@@ -437,6 +540,24 @@ RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_
     return v.recoverPoseHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
                              nt, r, mask.empty() ? std::vector<uint8_t>(matches.size(), 1) : mask, cam_query, cam_train,
                              params);
+}
+
+PlanePose recoverPoseHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const float (&H)[9], const std::vector<uint8_t>& mask, const Camera& cam_query,
+                                const Camera& cam_train, const PoseParams& params, int query_stride, int train_stride) {
+    const int n = (int)matches.size();
+    if (!mask.empty() && mask.size() != matches.size())
+        throw std::invalid_argument("recoverPoseHomography: mask must hold one byte per match, or none");
+    Verifier v(n > 0 ? n : 1, 1);
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0)
+        check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), "recoverPoseHomography");
+    HomographyResult r{};
+    for (int i = 0; i < 9; i++) r.H[i] = H[i];
+    r.matches = n;
+    return v.recoverPoseHomographyHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy,
+                                       train_stride, nt, r, mask.empty() ? std::vector<uint8_t>(matches.size(), 1) : mask,
+                                       cam_query, cam_train, params);
 }
 
 void projectHomographyDevice(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

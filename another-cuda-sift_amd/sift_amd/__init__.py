@@ -207,6 +207,11 @@ class _PoseParams(ctypes.Structure):
 POSE_RESULT_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("in_front", "<i4"), ("with_parallax", "<i4"),
                               ("counts", "<i4", (4,)), ("candidate", "<i4"), ("fit", "<i4")])
 assert POSE_RESULT_DTYPE.itemsize == 80
+# sift_hip_plane_pose_result: a pose record as it lies, then the winner's plane; sift_hip_plane_candidate: one of the
+# four (R, t, n, distance) of a homography's decomposition.
+PLANE_POSE_RESULT_DTYPE = np.dtype(POSE_RESULT_DTYPE.descr + [("normal", "<f4", (3,)), ("distance", "<f4")])
+PLANE_CANDIDATE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("normal", "<f4", (3,)), ("distance", "<f4")])
+assert PLANE_POSE_RESULT_DTYPE.itemsize == 96 and PLANE_CANDIDATE_DTYPE.itemsize == 64
 
 
 def _cameras(cams, P: int):
@@ -409,6 +414,19 @@ def lib() -> ctypes.CDLL:
         "sift_hip_recover_pose_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
                                                    ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
                                                    ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp]),
+        "sift_hip_recover_pose_homography_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp,
+                                                        ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                        ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp, vp]),
+        "sift_hip_recover_pose_homography_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp,
+                                                      ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                      ctypes.POINTER(_PoseParams), vp, vp, vp, vp, ip, vp]),
+        "sift_hip_recover_pose_homography_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp,
+                                                                vp, ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                                ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp,
+                                                                vp]),
+        "sift_hip_recover_pose_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
+                                                              ctypes.POINTER(_Camera), ctypes.POINTER(_Camera),
+                                                              ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp]),
         "sift_synth_frame": (i, [ctypes.c_uint, i, i, vp]),
         "sift_hip_device_count": (i, [ip]),
         "sift_hip_set_device": (i, [i]),
@@ -1937,6 +1955,99 @@ class Verifier:
                  out[row0[i]: row0[i] + n_out[i]].copy()) for i in range(P)]
 
 
+    # --- the relative pose from a verified homography (sift_hip_recover_pose_homography_*; the rule: include/sift_hip.h,
+    # in numpy sift_amd.cv.recover_pose_homography).  Argument for argument the pose calls above, on what the
+    # homography verify and refine calls wrote, with the 96-byte record and the optional four candidates per pair.
+
+    def recover_pose_homography_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int,
+                                       t_xy_ptr: int, nt: int, result_ptr: int, mask_ptr: int, cam_q, cam_t, pose_ptr: int,
+                                       mask_out_ptr: int = 0, points_ptr: int = 0, out_ptr: int = 0, out_count_ptr: int = 0,
+                                       candidates_ptr: int = 0, max_depth: float = 50.0,
+                                       max_cos_parallax: float = 0.99998, q_stride: int = 3, t_stride: int = 3,
+                                       stream: Optional[int] = None) -> None:
+        """Enqueue the plane pose of the pair (sift_hip_recover_pose_homography_device); every pointer is device memory.
+        pose_ptr: a PLANE_POSE_RESULT_DTYPE record; candidates_ptr: four PLANE_CANDIDATE_DTYPE records, or 0; the other
+        optional outputs as for recover_pose_device."""
+        p = _PoseParams(max_depth, max_cos_parallax)
+        _check(lib().sift_hip_recover_pose_homography_device(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride,
+            nt, result_ptr or None, mask_ptr or None, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p),
+            pose_ptr or None, mask_out_ptr or None, points_ptr or None, out_ptr or None, out_count_ptr or None,
+            candidates_ptr or None, stream), "recover_pose_homography_device")
+
+    def recover_pose_homography_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int,
+                                     t_xy_ptr: int, nt: int, result, mask, cam_q, cam_t, max_depth: float = 50.0,
+                                     max_cos_parallax: float = 0.99998, q_stride: int = 3, t_stride: int = 3):
+        """Synchronous (sift_hip_recover_pose_homography_host): result (a HOMOGRAPHY_RESULT_DTYPE record) and mask (cap
+        bytes) are host values; the list and positions are device memory.  Returns (the PLANE_POSE_RESULT_DTYPE record,
+        the in-front mask, the points (cap, 3) float32, the in-front records, the four PLANE_CANDIDATE_DTYPE records)."""
+        res = np.array([result], HOMOGRAPHY_RESULT_DTYPE)
+        mask = np.array(np.asarray(mask, np.uint8).reshape(-1), np.uint8)
+        if len(mask) != max(cap, 0):
+            raise ValueError("one mask byte per row of the list (cap)")
+        p = _PoseParams(max_depth, max_cos_parallax)
+        pose = np.zeros(1, PLANE_POSE_RESULT_DTYPE)
+        mask_out = np.zeros(max(cap, 0), np.uint8)
+        points = np.full((max(cap, 0), 3), np.nan, np.float32)
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        n_out = ctypes.c_int(0)
+        cands = np.zeros(4, PLANE_CANDIDATE_DTYPE)
+        _check(lib().sift_hip_recover_pose_homography_host(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None, t_stride,
+            nt, _ptr(res), _ptr(mask) if cap > 0 else None, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p),
+            _ptr(pose), _ptr(mask_out), _ptr(points), _ptr(out), ctypes.byref(n_out), _ptr(cands)),
+            "recover_pose_homography_host")
+        return pose[0], mask_out, points, out[: n_out.value], cands
+
+    def recover_pose_homography_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                               mask_ptr: int, cams_q, cams_t, poses_ptr: int, mask_out_ptr: int = 0,
+                                               points_ptr: int = 0, out_ptr: int = 0, out_counts_ptr: int = 0,
+                                               candidates_ptr: int = 0, max_depth: float = 50.0,
+                                               max_cos_parallax: float = 0.99998, q_stride: int = 3, t_stride: int = 3,
+                                               stream: Optional[int] = None) -> None:
+        """Enqueue the plane pose of every pair (sift_hip_recover_pose_homography_batched_device) on what
+        verify_homography_batched_device and refine_homography_batched_device wrote; poses_ptr: len(pairs)
+        PLANE_POSE_RESULT_DTYPE records; candidates_ptr: 4 x len(pairs) PLANE_CANDIDATE_DTYPE records, or 0.  Pair p's
+        bytes are the single call's."""
+        p = _PoseParams(max_depth, max_cos_parallax)
+        table, _ = self._pairs(pairs)
+        P = len(pairs)
+        _check(lib().sift_hip_recover_pose_homography_batched_device(
+            self._v, matches_ptr or None, counts_ptr or None, P, table, q_stride, t_stride, results_ptr or None,
+            mask_ptr or None, _cameras(cams_q, P), _cameras(cams_t, P), ctypes.byref(p), poses_ptr or None,
+            mask_out_ptr or None, points_ptr or None, out_ptr or None, out_counts_ptr or None, candidates_ptr or None,
+            stream), "recover_pose_homography_batched_device")
+
+    def recover_pose_homography_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, verified: Sequence,
+                                             cams_q, cams_t, max_depth: float = 50.0, max_cos_parallax: float = 0.99998,
+                                             q_stride: int = 3, t_stride: int = 3) -> list:
+        """Synchronous (sift_hip_recover_pose_homography_batched_host): verified holds per pair a tuple with the
+        HOMOGRAPHY_RESULT_DTYPE record first and the mask (cap bytes) last; per pair what recover_pose_homography_host
+        returns."""
+        table, caps = self._pairs(pairs)
+        P = len(pairs)
+        if len(verified) != P:
+            raise ValueError("one verified (record, ..., mask) per pair")
+        row0 = np.concatenate([[0], np.cumsum([c if 0 <= c <= 65536 else 0 for c in caps])]).astype(int)
+        res = np.array([v[0] for v in verified], HOMOGRAPHY_RESULT_DTYPE) if P else np.zeros(1, HOMOGRAPHY_RESULT_DTYPE)
+        mask = np.zeros(row0[-1], np.uint8)
+        for i, v in enumerate(verified):
+            mask[row0[i]: row0[i + 1]] = np.asarray(v[-1], np.uint8).reshape(-1)
+        p = _PoseParams(max_depth, max_cos_parallax)
+        poses = np.zeros(max(P, 1), PLANE_POSE_RESULT_DTYPE)
+        mask_out = np.zeros(row0[-1], np.uint8)
+        points = np.full((row0[-1], 3), np.nan, np.float32)
+        out = np.zeros(row0[-1], DMATCH_DTYPE)
+        n_out = np.zeros(max(P, 1), np.int32)
+        cands = np.zeros((max(P, 1), 4), PLANE_CANDIDATE_DTYPE)
+        _check(lib().sift_hip_recover_pose_homography_batched_host(
+            self._v, matches_ptr or None, counts_ptr or None, P, table, q_stride, t_stride, _ptr(res),
+            _ptr(mask) if len(mask) else None, _cameras(cams_q, P), _cameras(cams_t, P), ctypes.byref(p), _ptr(poses),
+            _ptr(mask_out), _ptr(points), _ptr(out), _ptr(n_out), _ptr(cands)), "recover_pose_homography_batched_host")
+        return [(poses[i].copy(), mask_out[row0[i]: row0[i + 1]].copy(), points[row0[i]: row0[i + 1]].copy(),
+                 out[row0[i]: row0[i] + n_out[i]].copy(), cands[i].copy()) for i in range(P)]
+
+
 def _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit):
     if len(matches_per_pair) != len(xy_per_pair):
         raise ValueError("one (des_xy, src_xy) per match list")
@@ -2048,6 +2159,50 @@ def recoverPoseBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequ
                                       max_depth, max_cos_parallax, 2, 2)
     return [(pose["R"].reshape(3, 3).copy(), pose["t"].copy(), mask_out, points, pose)
             for pose, mask_out, points, _ in got]
+
+
+def recoverPoseHomography(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, result, mask, cam_q, cam_t,
+                          max_depth: float = 50.0, max_cos_parallax: float = 0.99998, des_stride: int = 3,
+                          src_stride: int = 3):
+    """cv::decomposeHomographyMat and the choice by visible points on a verified pair: the arguments are recoverPose's,
+    with result a HOMOGRAPHY_RESULT_DTYPE record or H as 9 floats (3 x 3, signed as verifyHomography signs it).
+    Returns (R, t, the in-front mask, the points, the PLANE_POSE_RESULT_DTYPE record, the four PLANE_CANDIDATE_DTYPE
+    candidates); the record's normal and distance are the plane n^T X_des = distance, in baselines.  Two equal entries
+    at the top of the record's counts: the plane has two valid poses, and the first is returned."""
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE)).reshape(-1)
+    if not (isinstance(result, np.void) or (isinstance(result, np.ndarray) and result.dtype == HOMOGRAPHY_RESULT_DTYPE)):
+        rec = np.zeros(1, HOMOGRAPHY_RESULT_DTYPE)
+        rec["H"][0] = np.asarray(result, np.float32).reshape(9)
+        rec["matches"][0] = len(m)
+        result = rec[0]
+    mask = np.ones(len(m), np.uint8) if mask is None else mask
+    v = Verifier(max(len(m), 1), 1)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    pose, mask_out, points, _, cands = v.recover_pose_homography_host(
+        d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src, result, mask, cam_q, cam_t, max_depth,
+        max_cos_parallax, des_stride, src_stride)
+    return pose["R"].reshape(3, 3).copy(), pose["t"].copy(), mask_out, points, pose, cands
+
+
+def recoverPoseHomographyBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, results: Sequence,
+                                 masks: Sequence, cams_q, cams_t, max_depth: float = 50.0,
+                                 max_cos_parallax: float = 0.99998) -> list:
+    """recoverPoseHomography for P pairs in one pass; the arguments are recoverPoseBatched's with
+    HOMOGRAPHY_RESULT_DTYPE records.  A list of what recoverPoseHomography returns per pair."""
+    if not (len(matches_per_pair) == len(xy_per_pair) == len(results) == len(masks)):
+        raise ValueError("one (des_xy, src_xy), record and mask per match list")
+    lists = [np.ascontiguousarray(np.asarray(m, DMATCH_DTYPE)).reshape(-1) for m in matches_per_pair]
+    xy = [[np.ascontiguousarray(np.asarray(a, np.float32)[:, :2]) for a in qt] for qt in xy_per_pair]
+    rows = sum(len(m) for m in lists)
+    v = Verifier(max(rows, 1), 1, max(len(lists), 1))
+    d = DeviceArray.from_numpy(np.concatenate(lists) if lists else np.zeros(0, DMATCH_DTYPE))
+    dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
+    pairs = [(dq.value, len(q), dt.value, len(t), len(m)) for m, (q, t), (dq, dt) in zip(lists, xy, dxy)]
+    got = v.recover_pose_homography_batched_host(d.value if rows else 0, 0, pairs, list(zip(results, masks)), cams_q,
+                                                 cams_t, max_depth, max_cos_parallax, 2, 2)
+    return [(pose["R"].reshape(3, 3).copy(), pose["t"].copy(), mask_out, points, pose, cands)
+            for pose, mask_out, points, _, cands in got]
 
 
 def project_homography_device(H_ptr: int, xy_ptr: int, n: int, out_ptr: int, stride: int = 3, out_stride: int = 2,

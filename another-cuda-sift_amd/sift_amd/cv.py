@@ -1206,6 +1206,154 @@ def recover_pose(matches, q_xy, t_xy, result, mask, cam_q, cam_t, max_depth=POSE
     return out
 
 
+# --- Relative pose from a verified homography: the rule of sift_hip_recover_pose_homography_* (include/sift_hip.h,
+# "Relative pose from a verified homography") in numpy float64, written as the rule above is: one IEEE operation per
+# operation written, the header's associations, outputs rounded to float32 once.
+
+def calibrated_homography(H, cam_q, cam_t) -> np.ndarray:
+    """A = Kt^-1 H Kq (3 x 3 float64) for skew-free cameras (fx, fy, cx, cy): G = H Kq column by column as in
+    essential_from_fundamental, then the rows of Kt^-1, each entry in the header's association.  H keeps its sign."""
+    h = np.asarray(H, np.float32).reshape(-1)
+    if h.size != 9:
+        raise ValueError("H must have 9 entries (3 x 3, row-major)")
+    h = [float(v) for v in h]
+    fxq, fyq, cxq, cyq = _camera(cam_q, "cam_q")
+    fxt, fyt, cxt, cyt = _camera(cam_t, "cam_t")
+    G = [[h[3 * r] * fxq, h[3 * r + 1] * fyq, (h[3 * r] * cxq + h[3 * r + 1] * cyq) + h[3 * r + 2]] for r in range(3)]
+    A = np.zeros((3, 3), np.float64)
+    with np.errstate(all="ignore"):
+        for c in range(3):
+            A[0, c] = np.float64(G[0][c] - cxt * G[2][c]) / np.float64(fxt)
+            A[1, c] = np.float64(G[1][c] - cyt * G[2][c]) / np.float64(fyt)
+            A[2, c] = G[2][c]
+    return A
+
+
+def decompose_homography(A, sweeps: int = REFIT_SWEEPS) -> list:
+    """The four (R, t, n, distance) candidates of a calibrated homography A ~ R + t n^T / distance (Ma, Soatto, Kosecka,
+    Sastry, 5.3.3), in the order 0 = (R+, t+, N+), 1 = (R-, t-, N-), 2 = (R+, -t+, -N+), 3 = (R-, -t-, -N-): R (3, 3),
+    t (3,) with |t| = 1, n (3,) with |n| = 1, all float64, and distance a float64 scalar, the plane's distance from the
+    query camera in baselines (X_train = R X_query + t, n^T X_query = distance on the plane).  [] when A^T A has rank
+    <= 1, when its largest and smallest eigenvalue do not differ, or when a translation has no length.  The
+    eigenvectors of A^T A come from the refit's Jacobi routine (3 x 3, `sweeps` sweeps)."""
+    A = [[float(np.asarray(A, np.float64).reshape(3, 3)[r, c]) for c in range(3)] for r in range(3)]
+    S = [[(A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c] for c in range(3)] for r in range(3)]
+    with np.errstate(all="ignore"):
+        V, d = _jacobi_full(S, sweeps)
+    i1 = 0
+    for i in (1, 2):
+        if d[i] > d[i1]:
+            i1 = i
+    i2 = -1
+    for i in range(3):
+        if i != i1 and (i2 < 0 or d[i] > d[i2]):
+            i2 = i
+    i3 = 3 - i1 - i2
+    w1, w2, w3 = np.float64(d[i1]), np.float64(d[i2]), np.float64(d[i3])
+    with np.errstate(all="ignore"):
+        if not (np.isfinite(w2) and w2 > 0):
+            return []
+        span = w1 - w3
+        if not span > 0:
+            return []
+        s = np.sqrt(w2)
+        Hn = [[float(np.float64(A[r][c]) / s) for c in range(3)] for r in range(3)]
+        d23, d12 = w2 - w3, w1 - w2
+        d23 = d23 if d23 > 0 else np.float64(0.0)
+        d12 = d12 if d12 > 0 else np.float64(0.0)
+        a, b = float(np.sqrt(d23 / span)), float(np.sqrt(d12 / span))
+    v1, v2 = [V[k][i1] for k in range(3)], [V[k][i2] for k in range(3)]
+    v3 = _cross(v1, v2)
+    half = []
+    for u in ([a * v1[k] + b * v3[k] for k in range(3)], [a * v1[k] - b * v3[k] for k in range(3)]):
+        N = _cross(v2, u)
+        hv = [(Hn[r][0] * v2[0] + Hn[r][1] * v2[1]) + Hn[r][2] * v2[2] for r in range(3)]
+        hu = [(Hn[r][0] * u[0] + Hn[r][1] * u[1]) + Hn[r][2] * u[2] for r in range(3)]
+        hc = _cross(hv, hu)
+        R = [[(hv[r] * v2[c] + hu[r] * u[c]) + hc[r] * N[c] for c in range(3)] for r in range(3)]
+        T = [((Hn[r][0] - R[r][0]) * N[0] + (Hn[r][1] - R[r][1]) * N[1]) + (Hn[r][2] - R[r][2]) * N[2]
+             for r in range(3)]
+        with np.errstate(all="ignore"):
+            norm = np.sqrt(np.float64((T[0] * T[0] + T[1] * T[1]) + T[2] * T[2]))
+            if not (np.isfinite(norm) and norm > 0):
+                return []
+            t = np.array([np.float64(T[r]) / norm for r in range(3)], np.float64)
+            dist = np.float64(1.0) / norm
+        half.append((np.array(R, np.float64), t, np.array(N, np.float64), dist))
+    return half + [(R, -t, -N, dist) for R, t, N, dist in half]
+
+
+def recover_pose_homography(matches, q_xy, t_xy, result, mask, cam_q, cam_t, max_depth=POSE_MAX_DEPTH,
+                            max_cos_parallax=POSE_MAX_COS_PARALLAX, sweeps: int = REFIT_SWEEPS) -> dict:
+    """The whole plane pose operation (sift_hip_recover_pose_homography_*) in numpy.  The arguments are recover_pose's,
+    with result a ransac_homography / refine_homography dict or a HOMOGRAPHY_RESULT_DTYPE record (read: H,
+    hypothesis).  Returns recover_pose's dict -- the fit set here also asks for w = (h6 qx + h7 qy) + h8 > 0 -- plus
+    normal (3,) float32, distance (float32) of the winner and candidates, four PLANE_CANDIDATE_DTYPE records (all zero
+    when H has no decomposition, filled also when no record is in front).  counts shows a tie between two candidates;
+    the first of them is the winner."""
+    from . import DMATCH_DTYPE, PLANE_CANDIDATE_DTYPE
+
+    matches = np.asarray(matches, DMATCH_DTYPE).reshape(-1)
+    n = len(matches)
+    mask = np.asarray(mask, np.uint8).reshape(-1)[:n]
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    kq, kt = _camera(cam_q, "cam_q"), _camera(cam_t, "cam_t")
+    md, mc = np.float32(max_depth), np.float32(max_cos_parallax)
+    if not md > 0:
+        raise ValueError("max_depth must be > 0")
+    if not (mc >= -1 and mc <= 1):
+        raise ValueError("max_cos_parallax must lie in [-1, 1]")
+    md, mc = np.float64(md), np.float64(mc)
+    pts = _match_points(matches, q_xy, t_xy)
+    h = np.asarray(result["H"], np.float32).reshape(-1)
+    p = pts.astype(np.float64)
+    with np.errstate(all="ignore"):
+        w = (np.float64(h[6]) * p[:, 0] + np.float64(h[7]) * p[:, 1]) + np.float64(h[8])
+        fit = (mask != 0) & np.isfinite(pts).all(1) & (w > 0)
+    out = {"R": np.zeros(9, np.float32), "t": np.zeros(3, np.float32), "in_front": 0, "with_parallax": 0,
+           "counts": np.zeros(4, np.int32), "candidate": -1, "fit": int(fit.sum()), "normal": np.zeros(3, np.float32),
+           "distance": np.float32(0), "candidates": np.zeros(4, PLANE_CANDIDATE_DTYPE), "mask": np.zeros(n, np.uint8),
+           "points": np.full((n, 3), POSE_NAN, np.float32), "list": matches[:0].copy()}
+    if not (int(result["hypothesis"]) >= 0 and geometry_usable(h)):
+        return out
+    cands = decompose_homography(calibrated_homography(h, cam_q, cam_t), sweeps)
+    if not cands:
+        return out
+    for k, (R, t, N, dist) in enumerate(cands):
+        out["candidates"][k] = (R.reshape(9).astype(np.float32), t.astype(np.float32), N.astype(np.float32),
+                                np.float32(dist))
+    with np.errstate(all="ignore"):
+        xq = np.stack([(p[:, 0] - kq[2]) / kq[0], (p[:, 1] - kq[3]) / kq[1]], 1)
+        xt = np.stack([(p[:, 2] - kt[2]) / kt[0], (p[:, 3] - kt[3]) / kt[1]], 1)
+        front, parallax, depth = [], [], []
+        for R, t, _, _ in cands:
+            a, b, det, cosine = triangulate_depths(R, t, xq, xt)
+            ok = fit & (det > 0) & (a > 0) & (b > 0) & (a < md) & (b < md)
+            front.append(ok)
+            parallax.append(ok & (cosine < mc))
+            depth.append(a)
+    counts = np.array([int(k.sum()) for k in front], np.int32)
+    out["counts"] = counts
+    best = 0
+    for k in range(1, 4):
+        if counts[k] > counts[best]:
+            best = k
+    if counts[best] == 0:
+        return out
+    keep = front[best]
+    with np.errstate(all="ignore"):
+        a = depth[best]
+        X = np.stack([a * xq[:, 0], a * xq[:, 1], a], 1).astype(np.float32)
+    out["points"][keep] = X[keep]
+    R, t, N, dist = cands[best]
+    out.update(R=R.reshape(9).astype(np.float32), t=t.astype(np.float32), in_front=int(counts[best]),
+               with_parallax=int(parallax[best].sum()), candidate=best, normal=N.astype(np.float32),
+               distance=np.float32(dist), mask=keep.astype(np.uint8), list=matches[keep])
+    assert out["R"].dtype == np.float32 and out["points"].dtype == np.float32
+    return out
+
+
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     import cv2
 

@@ -93,6 +93,38 @@ struct RelativePose {
     std::vector<DMatch> inliers;
 };
 
+// sift_hip_plane_pose_result (device form): a PoseResult as it lies, then the winner's plane n^T X_query = distance
+// (|normal| = 1, distance in baselines); candidate = -1 is the empty result (all zero).  Two equal top entries in
+// counts: the plane has two valid poses and the first is reported (include/sift_hip.h, "Relative pose from a verified
+// homography").
+struct PlanePoseResult {
+    float R[9];
+    float t[3];
+    int in_front, with_parallax;
+    int counts[4];
+    int candidate, fit;
+    float normal[3];
+    float distance;
+};
+
+// sift_hip_plane_candidate: one of the four (R, t, n, distance) of a homography's decomposition.
+struct PlaneCandidate {
+    float R[9];
+    float t[3];
+    float normal[3];
+    float distance;
+};
+
+// What the plane pose host forms return: RelativePose's members with the plane pose record, and the four candidates
+// (all zero when H has no decomposition).
+struct PlanePose {
+    PlanePoseResult pose{};
+    PlaneCandidate candidates[4] = {};
+    std::vector<uint8_t> mask;
+    std::vector<float> points;
+    std::vector<DMatch> inliers;
+};
+
 // A verifier owns the scratch of its calls; calls on one verifier must be
 // ordered.  What the ABI refuses (sift_hip_verify_fundamental_device) throws
 // std::invalid_argument; a failed allocation or HIP call std::runtime_error.
@@ -218,6 +250,36 @@ public:
                                                      const std::vector<Camera>& cams_query,
                                                      const std::vector<Camera>& cams_train, const PoseParams& params = {});
 
+    // The relative pose from a verified homography (sift_hip_recover_pose_homography_*; the rule: include/sift_hip.h,
+    // "Relative pose from a verified homography"): argument for argument the four calls above on what the homography
+    // verify and refine calls wrote, with the plane pose record and the trailing candidates (4 device records per
+    // pair, nullable).
+    void recoverPoseHomographyDevice(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                     int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                     const HomographyResult* result, const uint8_t* mask, const Camera& cam_query,
+                                     const Camera& cam_train, const PoseParams& params, PlanePoseResult* pose,
+                                     uint8_t* mask_out = nullptr, float* points = nullptr, DMatch* out = nullptr,
+                                     int* out_count = nullptr, PlaneCandidate* candidates = nullptr,
+                                     void* stream = nullptr);
+    PlanePose recoverPoseHomographyHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                        int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                        const HomographyResult& result, const std::vector<uint8_t>& mask,
+                                        const Camera& cam_query, const Camera& cam_train, const PoseParams& params = {});
+    void recoverPoseHomographyBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                            int query_stride, int train_stride, const HomographyResult* results,
+                                            const uint8_t* mask, const std::vector<Camera>& cams_query,
+                                            const std::vector<Camera>& cams_train, const PoseParams& params,
+                                            PlanePoseResult* poses, uint8_t* mask_out = nullptr, float* points = nullptr,
+                                            DMatch* out = nullptr, int* out_counts = nullptr,
+                                            PlaneCandidate* candidates = nullptr, void* stream = nullptr);
+    std::vector<PlanePose> recoverPoseHomographyBatchedHost(const DMatch* matches, const int* counts,
+                                                            const std::vector<VerifyPair>& pairs, int query_stride,
+                                                            int train_stride, const std::vector<HomographyResult>& results,
+                                                            const std::vector<uint8_t>& mask,
+                                                            const std::vector<Camera>& cams_query,
+                                                            const std::vector<Camera>& cams_train,
+                                                            const PoseParams& params = {});
+
     sift_hip_verifier* handle() const { return m_handle; }
 
 private:
@@ -249,6 +311,14 @@ RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_
                          const float (&F)[9], const std::vector<uint8_t>& mask, const Camera& cam_query,
                          const Camera& cam_train, const PoseParams& params = {}, int query_stride = 3,
                          int train_stride = 3);
+
+// The all-in-one beside verifyHomography: uploads the list and recovers the pose and the plane of a verified H (9
+// floats, row-major, x_train ~ H x_query, signed as verifyHomography signs it) over the records `mask` marks (empty:
+// every record).
+PlanePose recoverPoseHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const float (&H)[9], const std::vector<uint8_t>& mask, const Camera& cam_query,
+                                const Camera& cam_train, const PoseParams& params = {}, int query_stride = 3,
+                                int train_stride = 3);
 
 // Enqueued on `stream`, not synchronised (sift_hip_project_homography_device): row i of out_xy = row i of xy carried
 // over by H, NaN where it lands behind the camera.  H: 9 floats of device memory (a HomographyResult's address); xy /

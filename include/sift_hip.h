@@ -1158,8 +1158,8 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
 /* --- The verifier's refusals ----------------------------------------------------
  *
  * Every verifier call that takes a match list (sift_hip_verify_*, sift_hip_score_*,
- * sift_hip_refine_* and sift_hip_recover_pose_*, single-pair and batched, device
- * and host form) judges
+ * sift_hip_refine_*, sift_hip_recover_pose_* and sift_hip_recover_pose_homography_*,
+ * single-pair and batched, device and host form) judges
  * its arguments in ONE order and reports the first rule broken, with nothing
  * launched and nothing written.  First what needs no look at the verifier:
  *   a null verifier; null pairs; a null params or result (the score calls: a
@@ -1168,8 +1168,9 @@ int sift_hip_match_plan(int max_query, int max_train, int pairs, int* splits, in
  *   null matches with a row to read; max_error not > 0 and finite; out
  *   overlapping matches (device forms); the refine calls' null mask, then rounds
  *   outside 1..8;
- *   the pose calls, which have no params or result among the first rules and no
- *   max_error, after the list rules (null matches): a null camera pointer; pair
+ *   the pose calls (from F and from H alike), which have no params or result
+ *   among the first rules and no max_error, after the list rules (null
+ *   matches): a null camera pointer; pair
  *   by pair, query camera first, fx or fy not > 0 and finite, then cx or cy not
  *   finite; a null params, result or pose; max_depth not > 0 (+inf is allowed, a
  *   NaN is refused); max_cos_parallax outside [-1, 1]; a null mask with a row to
@@ -1863,7 +1864,169 @@ int sift_hip_recover_pose_batched_host(sift_hip_verifier_t v, const sift_hip_dma
                                        uint8_t* mask_out_host, float* points_host, sift_hip_dmatch* out_host,
                                        int* out_counts_host);
 
-/* --- Multi-GPU (the reference binds one Detector to the current
+/* --- Relative pose from a verified homography -----------------------------------
+ *
+ * What a calibrated caller does with a verified H of a plane
+ * (cv::decomposeHomographyMat and cv::filterHomographyDecompByVisibleRefpoints,
+ * ORB-SLAM's ReconstructH): A = Kt^-1 H Kq = s (R + t n^T / d), its four
+ * (R, t, n, d) candidates, the inliers triangulated under each, and the candidate
+ * that puts them in front of both cameras.  These are the cases in which the pose
+ * from F is degenerate: planar targets, floors and facades, low parallax.  A plane
+ * pose call does it on the device from what a homography verify or refine call
+ * left there, on the caller's stream, with no read-back.  The numpy mirror
+ * sift_amd.cv.calibrated_homography / decompose_homography / triangulate_depths
+ * (the steps) and recover_pose_homography (the operation) is the specification:
+ * the device equals it byte for byte.
+ *
+ * Arithmetic and inputs: as for "Relative pose from a verified fundamental
+ * matrix" above, with the record's first nine floats read as H (x_train ~ H
+ * x_query).  The decomposition is the one of Ma, Soatto, Kosecka, Sastry, "An
+ * Invitation to 3-D Vision", 5.3.3: it needs the eigen-decomposition of a
+ * symmetric 3 x 3 matrix and nothing else.
+ *
+ * The rule.
+ *   1. Usable record: hypothesis >= 0 and nine floats that are finite and not all
+ *      zero (the refit's test).  Otherwise the result is empty.
+ *   2. A = Kt^-1 H Kq for skew-free K, row r and column c from 0:
+ *        G[r][0] = H[r][0] fxq;  G[r][1] = H[r][1] fyq;
+ *        G[r][2] = (H[r][0] cxq + H[r][1] cyq) + H[r][2];
+ *        A[0][c] = (G[0][c] - cxt G[2][c]) / fxt;
+ *        A[1][c] = (G[1][c] - cyt G[2][c]) / fyt;  A[2][c] = G[2][c].
+ *      H is used with the sign it has.  The verify and refine calls sign H so that
+ *      every record they count has w = (H[2][0] qx + H[2][1] qy) + H[2][2] > 0, and
+ *      the third row of A applied to the normalised query ray is that same w.
+ *   3. S = A^T A with S[r][c] = (A[0][r] A[0][c] + A[1][r] A[1][c]) + A[2][r] A[2][c].
+ *      Its eigen-decomposition by the refit's Jacobi routine (3 x 3, V = I, 8
+ *      sweeps, the same pivot order).  i1 = the index of the largest diagonal
+ *      entry, i2 of the largest of the other two, ties to the lower index both
+ *      times, i3 the remaining one; w1 >= w2 >= w3 those entries, v1, v2 the
+ *      columns i1, i2 of V, v3 = v1 x v2 (the cross product as written above).
+ *      The result is empty when w2 is not finite or not > 0 (rank <= 1), or when
+ *      w1 - w3 is not > 0.  No other threshold is set.
+ *   4. Hn[r][c] = A[r][c] / sqrt(w2).  With max0(x) = x when x > 0, else 0:
+ *        a = sqrt(max0(w2 - w3) / (w1 - w3));  b = sqrt(max0(w1 - w2) / (w1 - w3));
+ *        u+[k] = a v1[k] + b v3[k];  u-[k] = a v1[k] - b v3[k].
+ *      (The formulas are scale-free in w: nothing is renormalised first.)
+ *   5. Per u (u+ gives R+, t+, N+, d+; u- gives R-, t-, N-, d-):
+ *        N = v2 x u;
+ *        hv[r] = (Hn[r][0] v2[0] + Hn[r][1] v2[1]) + Hn[r][2] v2[2];
+ *        hu[r] = (Hn[r][0] u[0] + Hn[r][1] u[1]) + Hn[r][2] u[2];  hc = hv x hu;
+ *        R[r][c] = (hv[r] v2[c] + hu[r] u[c]) + hc[r] N[c]
+ *      -- R = W U^T with U = (v2, u, N) and W = (Hn v2, Hn u, Hn v2 x Hn u) --;
+ *        T[r] = ((Hn[r][0] - R[r][0]) N[0] + (Hn[r][1] - R[r][1]) N[1])
+ *               + (Hn[r][2] - R[r][2]) N[2];
+ *        |T| = sqrt((T[0] T[0] + T[1] T[1]) + T[2] T[2]);
+ *      the result is empty when either |T| is not finite or not > 0;
+ *        t = T / |T|;  d = 1 / |T|,
+ *      the plane's distance from the query camera in baselines:
+ *      Hn = R + (t / d) N^T.
+ *   6. Candidates, in this order: 0 = (R+, t+, N+, d+), 1 = (R-, t-, N-, d-),
+ *      2 = (R+, -t+, -N+, d+), 3 = (R-, -t-, -N-, d-).  X_train = R X_query + t,
+ *      |t| = 1 and |n| = 1 up to rounding, n^T X_query = d on the plane.
+ *   7. Fit set: the records j < n with mask[j] != 0 whose four gathered coordinates
+ *      are finite (the refit's set) and whose w (step 2, in float64 from the
+ *      float32 entries and positions) is > 0; fit their number.  It is counted
+ *      from the record's floats as they are, also when the record is not usable.
+ *      A wrongly signed H therefore gives fit = 0 and the empty result, visibly.
+ *   8. Depths, the IN FRONT test and the PARALLAX test: step 6 of the rule for F,
+ *      word for word, per fit record and candidate (R, t).  Negating t negates
+ *      both depths exactly, so the four candidates cost two evaluations.
+ *   9. Winner: the candidate with the most records in front, ties to the lowest
+ *      index.  A winning count of 0 gives the empty result.
+ *  10. Outputs.  The plane pose record: the pose record of the rule for F, filled
+ *      the same way, then normal and distance of the winner, rounded to float32.
+ *      mask_out, points, out and out_count: as for F.  candidates (4 records per
+ *      pair, nullable): R, t, normal, distance of the candidates 0..3 rounded to
+ *      float32, written whenever steps 1 to 5 gave a decomposition -- also when no
+ *      record is in front -- and all zero otherwise.
+ * The empty result: the pose record as for F (zero, candidate = -1, fit still
+ * counted), normal and distance zero, mask_out all zero, every points row j < n
+ * NaN, an empty list.  It is a success, not an error.
+ *
+ * A TIE IS NOT AN ACCIDENT HERE.  A plane seen from two views has, in general,
+ * two physically valid decompositions: both put every point in front of both
+ * cameras.  ORB-SLAM gives up in that case and OpenCV returns both.  This call
+ * reports and does not hide: counts[4] shows two equal top counts, the winner is
+ * the first of them (the rule above, not a judgement), and candidates holds all
+ * four.  The caller decides with a prior on the normal, a third view, or
+ * ORB-SLAM's bar (the second count below 0.75 of the first).
+ *
+ * A near-pure rotation (|t| much smaller than d) leaves w1, w2 and w3 equal up to
+ * rounding.  When w1 - w3 rounds to 0 the result is empty; otherwise R is still
+ * the rotation, distance is very large (of order 1e7) and t and normal are
+ * directions of rounding noise.  The call sets no threshold for this: distance
+ * and with_parallax tell.
+ *
+ * Consequences.  The output is a function of the inputs alone: the same bytes in
+ * every run, and in the single and batched forms. */
+typedef struct {
+    float R[9]; /* the first 80 bytes: a sift_hip_pose_result as it lies */
+    float t[3];
+    int in_front;
+    int with_parallax;
+    int counts[4];
+    int candidate; /* 0..3, -1: the empty result */
+    int fit;
+    float normal[3]; /* the plane n^T X_query = distance, |n| = 1 */
+    float distance;  /* in baselines */
+} sift_hip_plane_pose_result;
+
+typedef struct {
+    float R[9];
+    float t[3];
+    float normal[3];
+    float distance;
+} sift_hip_plane_candidate;
+#ifdef __cplusplus
+static_assert(sizeof(sift_hip_plane_pose_result) == 96, "sift_hip_plane_pose_result is 96 bytes");
+static_assert(sizeof(sift_hip_plane_candidate) == 64, "sift_hip_plane_candidate is 64 bytes");
+#else
+typedef char sift_hip_plane_pose_result_is_96_bytes[sizeof(sift_hip_plane_pose_result) == 96 ? 1 : -1];
+typedef char sift_hip_plane_candidate_is_64_bytes[sizeof(sift_hip_plane_candidate) == 64 ? 1 : -1];
+#endif
+
+/* Argument for argument the pose calls above, with the homography's record, the
+ * plane pose record and the trailing nullable candidates (device form: device
+ * memory, 4 records; host form: host memory; batched: 4 P records, pair p's at
+ * 4 p).  Device forms: two launches after the gather, no allocation, not
+ * synchronised, capturable, the hypothesis scratch untouched; refusals by the
+ * rules and in the order of "The verifier's refusals", with nothing launched and
+ * nothing written. */
+int sift_hip_recover_pose_homography_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count,
+                                            int cap, const float* query_xy, int query_stride, int nq,
+                                            const float* train_xy, int train_stride, int nt,
+                                            const sift_hip_homography_result* result, const uint8_t* mask,
+                                            const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                            const sift_hip_pose_params* params, sift_hip_plane_pose_result* pose,
+                                            uint8_t* mask_out, float* points, sift_hip_dmatch* out, int* out_count,
+                                            sift_hip_plane_candidate* candidates, void* stream);
+int sift_hip_recover_pose_homography_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                          const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                          int train_stride, int nt, const sift_hip_homography_result* result_host,
+                                          const uint8_t* mask_host, const sift_hip_camera* cam_query,
+                                          const sift_hip_camera* cam_train, const sift_hip_pose_params* params,
+                                          sift_hip_plane_pose_result* pose_host, uint8_t* mask_out_host,
+                                          float* points_host, sift_hip_dmatch* out_host, int* out_count_host,
+                                          sift_hip_plane_candidate* candidates_host);
+int sift_hip_recover_pose_homography_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches,
+                                                    const int* counts, int P, const sift_hip_verify_pair* pairs,
+                                                    int query_stride, int train_stride,
+                                                    const sift_hip_homography_result* results, const uint8_t* mask,
+                                                    const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                                    const sift_hip_pose_params* params,
+                                                    sift_hip_plane_pose_result* poses, uint8_t* mask_out, float* points,
+                                                    sift_hip_dmatch* out, int* out_counts,
+                                                    sift_hip_plane_candidate* candidates, void* stream);
+int sift_hip_recover_pose_homography_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                                  int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                                  int train_stride, const sift_hip_homography_result* results_host,
+                                                  const uint8_t* mask_host, const sift_hip_camera* cam_query,
+                                                  const sift_hip_camera* cam_train, const sift_hip_pose_params* params,
+                                                  sift_hip_plane_pose_result* poses_host, uint8_t* mask_out_host,
+                                                  float* points_host, sift_hip_dmatch* out_host, int* out_counts_host,
+                                                  sift_hip_plane_candidate* candidates_host);
+
+/* --- Multi-GPU(the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
 
 /* Binds the calling host thread to `device` (a thread per GPU drives its own
