@@ -511,8 +511,11 @@ void enqueue_extrema(sift_hip_detector* d, int nf) {
     hipStream_t s = d->stream;
     const int L = d->L;
     const Frames fr{nf, d->afs};
+    // k_extrema_all (L <= 6) streams the planes G1 .. G(L+1) and reads the two outer planes only around provisional
+    // hits; the LDS-staged k_extrema reads all L + 3.
+    const int planes = L <= 6 ? L + 1 : L + 3;
     double exBytes = 0;
-    for (int o = 0; o < d->nOct; o++) exBytes += (double)d->pyr.oct[o].W * d->pyr.oct[o].H * 4 * (L + 3) * nf;
+    for (int o = 0; o < d->nOct; o++) exBytes += (double)d->pyr.oct[o].W * d->pyr.oct[o].H * 4 * planes * nf;
     d->timed("extrema", exBytes, [&] {
         if (!launch_extrema_all(d->pyr, d->threshold, d->dCand, d->dCtr, d->capCand, fr, s))
             for (int o = 0; o < d->nOct; o++)

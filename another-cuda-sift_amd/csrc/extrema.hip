@@ -140,7 +140,8 @@ __global__ __launch_bounds__(256) void k_extrema(OctGeom g, int L, int o, float 
 // flight, with
 // 16-byte loads (one buffer_load_dwordx4 per row and plane), plus one dword
 // per row and plane for the strip's outer neighbours (lane 0: column x0-1,
-// lane 63: column x0+256).  Per row the 5 DoG planes are formed in registers
+// lane 63: column x0+256).  Only the planes G1 .. G(L+1) are streamed: per row
+// the L inner DoG layers D1 .. DL are formed in registers
 // and kept in a 3-row ring; a tested row takes the vertical max/min of its
 // three rows per column, then the horizontal 3-max in-lane, with the columns
 // across lane boundaries brought in by one DPP move each (lane 0 / 63 keep
@@ -148,6 +149,14 @@ __global__ __launch_bounds__(256) void k_extrema(OctGeom g, int L, int o, float 
 // is exactly "v == max of the 3x3x3 block" (the block contains v), so the
 // decision per pixel is OpenCV's and the oracle's: |v| > threshold and
 // v >= (<=) all 26, with no LDS staging.
+//
+// The outer DoG layers D0 = G1 - G0 and D(L+1) = G(L+2) - G(L+1) are compared
+// against by layer 1 and layer L alone, so G0 and G(L+2) are not streamed (a
+// third of the bytes at L = 3).  The stream tests layers 1 and L against the
+// inner layers only: such a hit is provisional (~0.6 % of the pixels), and the
+// nine outer values it still has to dominate are loaded and compared when the
+// workgroup's list is flushed (outer_ok) -- the same float subtraction and the
+// same comparisons as in the stream, so the candidate set is the same.
 // ---------------------------------------------------------------------------
 constexpr int EX4_LIST = 2048;  // per-workgroup candidate list (LDS): a 256 x 32 x L block can hold
                                 // ~7 % extrema on textured frames; overflow spills to HBM
@@ -167,8 +176,10 @@ constexpr int EX4_COLS = 64 * kExCpl;  // columns per wave
 template <int LT, bool FLAT, int EX4_TR, int EX4_AHEAD, int NB = 1, int CPL = kExCpl>
 __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr, uint2* __restrict__ cand,
                                               Counters* __restrict__ ctr, unsigned cap, int tile, int strips,
-                                              uint2* s_list, unsigned& s_cnt, unsigned& s_base) {
-    constexpr int NG = LT + 3, ND = LT + 2;
+                                              uint2* s_list, unsigned& s_cnt, unsigned& s_keep, unsigned& s_base) {
+    // NG planes in the octave; the stream reads NP of them (G1 .. G(LT+1)) and
+    // forms the ND inner DoG layers (index d: layer d + 1).
+    constexpr int NG = LT + 3, NP = LT + 1, ND = LT;
     static_assert(CPL * LT <= 31 && (CPL == 2 || CPL == 4), "hit bits per row");
     static_assert(NB == 1 || (EX4_TR % 3 == 0 && EX4_TR % (EX4_AHEAD + 1) == 0),
                   "multi-step streams: the ring and the load sets repeat every EX4_TR rows");
@@ -182,7 +193,7 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
     const int xe = min(max(lane == 0 ? x0 - 1 : x0 + EX4_COLS, 0), W - 1);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         g.base, 0, (int)min((long)NG * g.planeStride * 4, 0x7fffffffL), 0x00020000);
-    if (tid == 0) s_cnt = 0;
+    if (tid == 0) s_cnt = s_keep = 0;
     __syncthreads();
 
     bool colOK[CPL];
@@ -194,8 +205,8 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
     float re[3][ND];
     // Raw rows in flight: EX4_AHEAD + 1 register sets, loads issued EX4_AHEAD
     // rows ahead of the row being formed.
-    f4 rv[EX4_AHEAD + 1][NG];
-    float rev[EX4_AHEAD + 1][NG];
+    f4 rv[EX4_AHEAD + 1][NP];
+    float rev[EX4_AHEAD + 1][NP];
     // Lanes whose columns start past the octave's width (the last strip of a
     // row overhangs it: 1920 = 7.5 strips) and the lanes that do not use the
     // outer column (all but lanes 0 and 63) load from an offset past the
@@ -205,7 +216,7 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
 #else
     const bool l4 = xl < W, le = lane == 0 || lane == 63;
 #endif
-    auto issue_row = [&](int y, f4 (&v)[NG], float (&e)[NG]) {
+    auto issue_row = [&](int y, f4 (&v)[NP], float (&e)[NP]) {
 #if defined(SIFT_EX_DIAG) && (SIFT_EX_DIAG == 2 || SIFT_EX_DIAG == 3)  // traffic variants: halo rows -> the wave's own rows
         y = min(max(y, y0), y0 + TR - 1);
 #endif
@@ -213,14 +224,76 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
         const unsigned off4 = l4 ? (unsigned)(yc * pitch + xl) * 4u : 0x80000000u;
         const unsigned offe = le ? (unsigned)(yc * pitch + xe) * 4u : 0x80000000u;
 #pragma unroll
-        for (int d = 0; d < NG; d++) {
-            const int so = (int)((long)d * g.planeStride * 4);
+        for (int d = 0; d < NP; d++) {
+            const int so = (int)((long)(d + 1) * g.planeStride * 4);
             if constexpr (CPL == 4)
                 v[d] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off4, so, 0));
             else
                 v[d] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off4, so, 0));
             e[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, offe, so, 0));
         }
+    };
+    // The outer-layer half of the test for a provisional hit (layer 1: against
+    // D0; layer LT: against D(LT+1); LT = 1: both): v > 0 stays iff v >= the
+    // nine outer values, v < 0 iff v <= them.  A hit is >= 5 pixels from every
+    // border, so the 3x3 patches are inside the planes.  Every row of a patch
+    // is a cache line of its own in both planes, and by now the rows the block
+    // streamed have left the L2, so the test goes in two steps: the centre row
+    // first (with v: three lines; it rejects 57 % of the C2 frame's provisional
+    // hits, the whole patch 77 %), then the rows above and below for the lanes
+    // still in.  The loads of a step are all issued before the first is used
+    // and none is conditional (a conditional load is a branch plus a full
+    // wait): a lane with nothing to test loads from past the buffer (0, no
+    // memory request).  Returns `true` for a hit that is not provisional.
+    auto outer_ok = [&](bool have, int l, unsigned rc) -> bool {
+        const unsigned ps4 = (unsigned)(g.planeStride * 4);
+        const unsigned at = (unsigned)((int)(rc >> 16) * pitch + (int)(rc & 0xffffu)) * 4u;
+        constexpr unsigned kPast = 0x90000000u;  // stays past the buffer with the patch and plane offsets added
+        constexpr int NO = LT == 1 ? 2 : 1;      // outer layers to compare against
+        const bool prov = have && (l == 1 || l == LT);
+        unsigned lo[NO];  // byte offset of (r, c) in the lower plane of each outer DoG layer
+        if constexpr (LT == 1) {
+            lo[0] = at;
+            lo[1] = at + 2u * ps4;
+        } else {
+            lo[0] = at + (l == 1 ? 0u : (unsigned)(LT + 1) * ps4);
+        }
+        auto ld = [&](unsigned off) {
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+        };
+        // Rows r + dy (dy in DY) of the outer layers, as `form` makes them: one float subtraction.
+        auto rows = [&](bool on, const int (&DY)[2], int ndy, float& mx, float& mn) {
+            float a[NO][2][3], b[NO][2][3];
+#pragma unroll
+            for (int n = 0; n < NO; n++)
+#pragma unroll
+                for (int j = 0; j < ndy; j++)
+#pragma unroll
+                    for (int dx = 0; dx < 3; dx++) {
+                        const unsigned off = on ? lo[n] + (unsigned)(DY[j] * pitch + dx - 1) * 4u : kPast;
+                        a[n][j][dx] = ld(off);
+                        b[n][j][dx] = ld(off + ps4);
+                    }
+            mx = mn = b[0][0][0] - a[0][0][0];
+#pragma unroll
+            for (int n = 0; n < NO; n++)
+#pragma unroll
+                for (int j = 0; j < ndy; j++)
+#pragma unroll
+                    for (int dx = 0; dx < 3; dx++) {
+                        const float dv = b[n][j][dx] - a[n][j][dx];
+                        mx = fmaxf(mx, dv);
+                        mn = fminf(mn, dv);
+                    }
+        };
+        const unsigned vo = prov ? at + (unsigned)l * ps4 : kPast;
+        const float v0 = ld(vo), v1 = ld(vo + ps4);
+        float mx, mn;
+        rows(prov, {0, 0}, 1, mx, mn);
+        const float v = v1 - v0;
+        const bool in = prov && (v > 0 ? mx <= v : mn >= v);
+        rows(in, {-1, 1}, 2, mx, mn);
+        return !prov || (in && (v > 0 ? mx <= v : mn >= v));
     };
     // Candidates of one tested row: one LDS reservation per row with hits;
     // each lane's slot offset is the exclusive prefix of the per-lane hit
@@ -243,7 +316,7 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
             const uint2 q = make_uint2((unsigned)(o << 8 | l), (unsigned)(r << 16 | (xl + c)));
             if (pos < EX4_LIST) {
                 s_list[pos] = q;
-            } else {  // plateau-heavy tile: spill straight to the global list
+            } else if (outer_ok(true, l, q.y)) {  // plateau-heavy tile: spill straight to the global list
                 const unsigned gp = atomicAdd(&ctr->cand, 1u);
                 if (gp < cap)
                     cand[gp] = q;
@@ -282,10 +355,13 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
         for (int l = 1; l <= LT; l++)
 #pragma unroll
             for (int c = 0; c < CPL; c++) {
-                const float v = rd[B][l][c];
-                const float M = fmaxf(fmaxf(hx[l - 1][c], hx[l][c]), hx[l + 1][c]);
-                const float m = fminf(fminf(hn[l - 1][c], hn[l][c]), hn[l + 1][c]);
-                // M >= v >= m always (v is one of the 27), so "v >= all" is v == M;
+                // Layer l is index l - 1; its neighbours among the inner layers
+                // (layers 1 and LT lack one: provisional, outer_ok has the rest).
+                const float v = rd[B][l - 1][c];
+                float M = hx[l - 1][c], m = hn[l - 1][c];
+                if (l > 1) M = fmaxf(M, hx[l - 2][c]), m = fminf(m, hn[l - 2][c]);
+                if (l < LT) M = fmaxf(M, hx[l][c]), m = fminf(m, hn[l][c]);
+                // M >= v >= m always (v is one of them), so "v >= all" is v == M;
                 // |v| > thr >= 0 excludes v == 0, and the sign picks the test.
                 bool h = rowOK && colOK[c] && fabsf(v) > thr && v == (v > 0 ? M : m);
                 // FLAT (the launches with thr = 0): a hit whose in-layer 3x3 block
@@ -299,7 +375,7 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
                 // 16-frame C2 launch when always on, so launches with thr >= 1,
                 // where such a block would have to be constant at |v| > 1, run
                 // without it.
-                if constexpr (FLAT) h = h && hx[l][c] != hn[l][c];
+                if constexpr (FLAT) h = h && hx[l - 1][c] != hn[l - 1][c];
                 hits |= (unsigned)h << ((l - 1) * CPL + c);
             }
         return hits;
@@ -353,13 +429,34 @@ __device__ __forceinline__ void extrema_block(const OctGeom& g, int o, float thr
         }
     }
     __syncthreads();
+    // Flush.  Pass 1 resolves the provisional entries: a survivor takes its
+    // slot among the workgroup's survivors (ballot per wave, one LDS add) into
+    // the free upper half of its first word (o << 8 | l < 2^16, slot <
+    // EX4_LIST <= 2^16); a rejected entry becomes ~0.  Then one global atomic
+    // reserves the survivors' run, and pass 2 writes them.
+    static_assert(EX4_LIST <= 65536 && kMaxOctaves <= 256, "slot and o << 8 | l share a word");
     const unsigned nl = min(s_cnt, (unsigned)EX4_LIST);
-    if (tid == 0) s_base = nl ? atomicAdd(&ctr->cand, nl) : 0u;
+    for (unsigned k0 = 0; k0 < nl; k0 += 256) {  // uniform
+        const unsigned k = k0 + tid;
+        const bool have = k < nl;
+        const uint2 q = have ? s_list[k] : make_uint2(0u, 0u);
+        const bool keep = outer_ok(have, (int)(q.x & 0xffu), q.y) && have;
+        const unsigned long long km = __ballot(keep);
+        unsigned base = 0;
+        if (lane == 0 && km) base = atomicAdd(&s_keep, (unsigned)__popcll(km));
+        const unsigned slot = __builtin_amdgcn_readfirstlane(base) +
+                              __builtin_amdgcn_mbcnt_hi((unsigned)(km >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)km, 0u));
+        if (have) s_list[k].x = keep ? q.x | slot << 16 : ~0u;
+    }
+    __syncthreads();
+    if (tid == 0) s_base = s_keep ? atomicAdd(&ctr->cand, s_keep) : 0u;
     __syncthreads();
     for (unsigned k = tid; k < nl; k += 256) {
-        const unsigned pos = s_base + k;
+        const uint2 q = s_list[k];
+        if (q.x == ~0u) continue;
+        const unsigned pos = s_base + (q.x >> 16);
         if (pos < cap)
-            cand[pos] = s_list[k];
+            cand[pos] = make_uint2(q.x & 0xffffu, q.y);
         else
             atomicOr(&ctr->overflow, 1u);
     }
@@ -382,7 +479,7 @@ template <int LT, bool FLAT>
 __global__ __launch_bounds__(256) void k_extrema_all(PyrDesc pyr, ExtremaPlan plan, float thr,
                                                      uint2* __restrict__ cand, Counters* __restrict__ ctr,
                                                      unsigned cap, long fs) {
-    __shared__ unsigned s_cnt, s_base;
+    __shared__ unsigned s_cnt, s_keep, s_base;
     __shared__ uint2 s_list[EX4_LIST];
     // Frame-major block order over all frames, XCD-aware: each XCD takes a
     // contiguous run of (frame, octave, strip block), so vertically adjacent
@@ -398,9 +495,9 @@ __global__ __launch_bounds__(256) void k_extrema_all(PyrDesc pyr, ExtremaPlan pl
     ctr = fptr(ctr, f * fs);
     const int blk = b - plan.start[o];
     if (plan.tall[o])
-        extrema_block<LT, FLAT, 6, 2, kExStream>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
+        extrema_block<LT, FLAT, 6, 2, kExStream>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_keep, s_base);
     else
-        extrema_block<LT, FLAT, 2, 2>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_base);
+        extrema_block<LT, FLAT, 2, 2>(g, o, thr, cand, ctr, cap, blk, plan.strips[o], s_list, s_cnt, s_keep, s_base);
 }
 
 // Octave o alone, for L > 6 (LDS-staged k_extrema).

@@ -245,7 +245,7 @@ int main(int argc, char** argv) {
     const float thr = std::floor(0.5 * 0.04 / L * 255);
     {
         double bytes = 0;
-        for (int o = 0; o < 3; o++) bytes += 4.0 * (L + 3) * pyr.oct[o].W * pyr.oct[o].H;
+        for (int o = 0; o < 3; o++) bytes += 4.0 * (L + 1) * pyr.oct[o].W * pyr.oct[o].H;  // the dense stream: G1 .. G(L+1)
         us = time_us(iters, s, [&] {
             CK(hipMemsetAsync(dCtr, 0, sizeof(Counters), s));
             launch_extrema_all(pyr, thr, dCand, dCtr, 1u << 20, kOne, s);
