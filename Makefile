@@ -70,7 +70,7 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_pose_args $(ASAN_DIR)/test_pose_homography_args $(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_affine_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_pose_args $(ASAN_DIR)/test_pose_homography_args $(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
@@ -80,8 +80,9 @@ $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/
 
 # Argument validation of the verifier's C++ surface (verify_cxx.cpp), CPU only: test_verify_args (run by
 # tests/test_verify_asan.py), test_homography_args for the homography calls and the projection, test_verify_batched_args
-# for the batched calls, test_refit_args for the refit calls, test_pose_args for the pose calls and
-# test_pose_homography_args for the plane pose calls, each with its tests/test_*_asan.py.
+# for the batched calls, test_refit_args for the refit calls, test_pose_args for the pose calls,
+# test_pose_homography_args for the plane pose calls and test_affine_args for the affine and similarity calls, each
+# with its tests/test_*_asan.py.
 $(ASAN_DIR)/test_%_args: tests/cpp/test_%_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ $< $(SRC)/verify_cxx.cpp \

@@ -10,9 +10,12 @@
 //                  in LDS -- the four disjoint rotations of a round side by side, one lane per updated row or
 //                  block (jacobi, sift_jacobi_dev.h) --, the 3 x 3 problem of the rank-2 step the same way, and the
 //                  denormalisation; lane 0 writes the candidate.
+//  k_refit_fit_a   the affine map and the similarity (sift_hip_refine_affine_*): the same fit set and summation order,
+//                  two passes (means, the seven sums of centred products) and a closed-form solve by one thread; no
+//                  Jacobi, the problem is linear and centred.  Mirrored by sift_amd.cv.refit_affine.
 //  k_refit_accept  one 1024-thread workgroup per pair: the candidate's count over the n records (ballot + popcount),
 //                  the accept decision, and k_verify_select's mask and ordered compaction.
-// Both are templates over the list, as the verify kernels are.  The fit is float64 with -ffp-contract=off: every
+// All are templates over the list, as the verify kernels are.  The fit is float64 with -ffp-contract=off: every
 // operation is the one written, in the order written; float64 division and square root are correctly rounded.
 #include <limits.h>
 
@@ -273,6 +276,112 @@ __global__ __launch_bounds__(kRefitThreads) void k_refit_fit(List list, const fl
     if (lane == 0) *cand = out;
 }
 
+// The affine map and the similarity: k_refit_fit's fit set and summation order, the means, the seven sums of centred
+// products and the closed-form solution of the normal equations -- the problem is linear and centred, so there is no
+// normalisation and no Jacobi.  Every thread holds the sums; thread 0 solves.
+template <VerifyModel Model, class List>
+__global__ __launch_bounds__(kRefitThreads) void k_refit_fit_a(List list, const float4* __restrict__ pts,
+                                                              const uint8_t* __restrict__ mask,
+                                                              const VerifyResult* __restrict__ result,
+                                                              RefitCandidate* __restrict__ cand) {
+#pragma clang fp contract(off)
+    __shared__ double s_red[kRefitWaves][45];
+    __shared__ int s_cnt[kRefitWaves];
+    if constexpr (kBatched<List>) {
+        const int p = pair_of(list), row0 = row0_of(list);
+        pts += row0, mask += row0, result += p, cand += p;
+    }
+    const VerifyInput in = list_of(list);
+    const int n = verify_n(in.count, in.cap);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+
+    // The current record: empty, or a model the guided matchers would refuse, is left alone.
+    bool usable = result->hypothesis >= 0, any = false;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const float f = result->F[i];
+        usable = usable && finite_f(f);
+        any = any || f != 0.f;
+    }
+    usable = usable && any;
+
+    // Pass 1: the fit set's size and coordinate sums.
+    int cnt = 0;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = tid; j < n; j += kRefitThreads) {
+        const float4 p = pts[j];
+        if (mask[j] != 0 && finite_f(p.x) && finite_f(p.y) && finite_f(p.z) && finite_f(p.w)) {
+            cnt++;
+            sum[0] = sum[0] + (double)p.x;
+            sum[1] = sum[1] + (double)p.y;
+            sum[2] = sum[2] + (double)p.z;
+            sum[3] = sum[3] + (double)p.w;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    if (lane == 0) s_cnt[w] = cnt;
+    block_tree<4>(sum, s_red, lane, w);  // its barriers publish s_cnt too
+    int m = 0;
+#pragma unroll
+    for (int i = 0; i < kRefitWaves; i++) m += s_cnt[i];
+
+    const RefitCandidate none{{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0};
+    if (!(usable && m >= sample_size(Model))) {  // workgroup-uniform
+        if (tid == 0) *cand = none;
+        return;
+    }
+    const double dm = (double)m;
+    const double mqx = sum[0] / dm, mqy = sum[1] / dm, mtx = sum[2] / dm, mty = sum[3] / dm;
+
+    // Pass 2: Sxx, Sxy, Syy, Txx, Txy, Tyx, Tyy of the centred coordinates.
+    double S[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = tid; j < n; j += kRefitThreads) {
+        const float4 p = pts[j];
+        if (mask[j] != 0 && finite_f(p.x) && finite_f(p.y) && finite_f(p.z) && finite_f(p.w)) {
+            const double x = (double)p.x - mqx, y = (double)p.y - mqy;
+            const double u = (double)p.z - mtx, v = (double)p.w - mty;
+            S[0] = S[0] + x * x;
+            S[1] = S[1] + x * y;
+            S[2] = S[2] + y * y;
+            S[3] = S[3] + u * x;
+            S[4] = S[4] + u * y;
+            S[5] = S[5] + v * x;
+            S[6] = S[6] + v * y;
+        }
+    }
+    block_tree<7>(S, s_red, lane, w);
+    if (tid != 0) return;  // no barrier below
+
+    const double Sxx = S[0], Sxy = S[1], Syy = S[2], Txx = S[3], Txy = S[4], Tyx = S[5], Tyy = S[6];
+    double a, b, c, d;
+    bool ok;
+    if constexpr (Model == VerifyModel::Affine) {
+        const double det = Sxx * Syy - Sxy * Sxy;
+        ok = finite_d(det) && det > 0.0;
+        a = (Txx * Syy - Txy * Sxy) / det;
+        b = (Txy * Sxx - Txx * Sxy) / det;
+        c = (Tyx * Syy - Tyy * Sxy) / det;
+        d = (Tyy * Sxx - Tyx * Sxy) / det;
+    } else {
+        const double den = Sxx + Syy;
+        ok = finite_d(den) && den > 0.0;
+        a = (Txx + Tyy) / den;
+        c = (Tyx - Txy) / den;
+        b = -c, d = a;
+    }
+    const double R[6] = {a, b, mtx - (a * mqx + b * mqy), c, d, mty - (c * mqx + d * mqy)};
+    RefitCandidate out = none;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        out.m[i] = (float)R[i];
+        ok = ok && finite_f(out.m[i]);
+    }
+    out.m[8] = 1.f;
+    out.valid = 1;
+    *cand = ok ? out : none;
+}
+
 template <class Pass, class List>
 __global__ __launch_bounds__(kAcceptThreads) void k_refit_accept(List list, const float4* __restrict__ pts,
                                                                  const RefitCandidate* __restrict__ cand, float e2,
@@ -355,6 +464,11 @@ void launch_refit_fit(VerifyModel model, const List& list, const float4* pts, co
     const dim3 grid(1, list_pairs(list)), block(kRefitThreads);
     if (model == VerifyModel::Homography)
         hipLaunchKernelGGL((k_refit_fit<VerifyModel::Homography, List>), grid, block, 0, s, list, pts, mask, result, cand);
+    else if (model == VerifyModel::Affine)
+        hipLaunchKernelGGL((k_refit_fit_a<VerifyModel::Affine, List>), grid, block, 0, s, list, pts, mask, result, cand);
+    else if (model == VerifyModel::Similarity)
+        hipLaunchKernelGGL((k_refit_fit_a<VerifyModel::Similarity, List>), grid, block, 0, s, list, pts, mask, result,
+                           cand);
     else
         hipLaunchKernelGGL((k_refit_fit<VerifyModel::Fundamental, List>), grid, block, 0, s, list, pts, mask, result, cand);
 }
@@ -366,6 +480,9 @@ void launch_refit_accept(VerifyModel model, const List& list, const float4* pts,
     const dim3 grid(1, list_pairs(list)), block(kAcceptThreads);
     if (model == VerifyModel::Homography)
         hipLaunchKernelGGL((k_refit_accept<TransferPass, List>), grid, block, 0, s, list, pts, cand, e2, result, mask, out,
+                           out_count, accepted, first_round ? 1 : 0);
+    else if (is_affine(model))
+        hipLaunchKernelGGL((k_refit_accept<AffinePass, List>), grid, block, 0, s, list, pts, cand, e2, result, mask, out,
                            out_count, accepted, first_round ? 1 : 0);
     else
         hipLaunchKernelGGL((k_refit_accept<SampsonPass, List>), grid, block, 0, s, list, pts, cand, e2, result, mask, out,

@@ -70,19 +70,26 @@ void launch_verify_gather(const List& list, float4* pts, hipStream_t s);
 
 // The model a verify call fits: it selects the hypothesis kernel and the
 // predicate the score and select kernels are instantiated with.
-enum class VerifyModel { Fundamental = 1, Homography = 2 };
+// Affine (6 degrees of freedom, 3-point samples) and Similarity (4, 2-point samples) store their 2 x 3 matrix as
+// the 3 x 3 {m0 .. m5, 0, 0, 1} in the homography's record and share one predicate (AffinePass).
+enum class VerifyModel { Fundamental = 1, Homography = 2, Affine = 3, Similarity = 4 };
+constexpr bool is_affine(VerifyModel m) { return m == VerifyModel::Affine || m == VerifyModel::Similarity; }
+// The matches a hypothesis of the model draws: the stride of its rows in the samples scratch.
+constexpr int sample_size(VerifyModel m) {
+    return m == VerifyModel::Fundamental ? 8 : m == VerifyModel::Homography ? 4 : m == VerifyModel::Affine ? 3 : 2;
+}
 
-// k_verify_hypotheses / k_verify_hypotheses_h: hypothesis k in [0, K) draws its
-// m matches (m = 8 for the fundamental matrix, 4 for the homography;
+// k_verify_hypotheses / k_verify_hypotheses_h / k_verify_hypotheses_a: hypothesis k in [0, K) draws its
+// m matches (m = 8 for the fundamental matrix, 4 for the homography, 3 for the affine map, 2 for the similarity;
 // samples[m k ..], -1 when n < m) and solves them: F[9 k ..] and valid[k] (an
 // invalid hypothesis has F all zero).  e2 = max_error^2 serves the homography's
-// own-sample rule; the fundamental kernel does not read it.
+// own-sample rule; the other kernels do not read it.
 template <class List>
 void launch_verify_hypotheses(VerifyModel model, const List& list, const float4* pts, int K, unsigned seed, float e2,
                               int* samples, float* F, int* valid, hipStream_t s);
 
 // k_verify_score: counts[k] = the matches j < n that pass the model's predicate
-// (Sampson distance / forward transfer error) under F[9 k ..] with
+// (Sampson distance / forward transfer error / affine transfer error) under F[9 k ..] with
 // e2 = max_error^2; 0 where valid (nullable) says the hypothesis is invalid.
 template <class List>
 void launch_verify_score(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid, int K,

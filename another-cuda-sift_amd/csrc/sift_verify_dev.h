@@ -1,5 +1,5 @@
 // Device-side pieces the verifier's kernels share (verify.hip, refit.hip): how a kernel finds its list -- the call's
-// own, or pair blockIdx.y's of a batch -- and the two models' predicates.  Included by .hip files only.
+// own, or pair blockIdx.y's of a batch -- and the models' predicates.  Included by .hip files only.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -55,6 +55,17 @@ struct TransferPass {
         const float w = (h[6] * p.x + h[7] * p.y) + h[8];
         const float dx = px - p.z * w, dy = py - p.w * w;
         return (w > 0.f) & (dx * dx + dy * dy <= e2 * (w * w));
+    }
+};
+// Affine map and similarity: the transfer error of {m0 .. m5, 0, 0, 1}.  TransferPass on the same nine floats gives
+// the same answer (its w is exactly 1); this one does not form w.
+struct AffinePass {
+    static __device__ __forceinline__ bool pass(const float (&m)[9], const float4 p, float e2) {
+#pragma clang fp contract(off)
+        const float px = (m[0] * p.x + m[1] * p.y) + m[2];
+        const float py = (m[3] * p.x + m[4] * p.y) + m[5];
+        const float dx = px - p.z, dy = py - p.w;
+        return dx * dx + dy * dy <= e2;
     }
 };
 

@@ -1,9 +1,11 @@
 // Two-view verification: a fixed-budget RANSAC over a match list, on the device,
-// for the fundamental matrix (sift_hip_verify_fundamental_*) and the homography
-// (sift_hip_verify_homography_*), and the projection of positions through a
+// for the fundamental matrix (sift_hip_verify_fundamental_*), the homography
+// (sift_hip_verify_homography_*) and the affine map and similarity
+// (sift_hip_verify_affine_*), and the projection of positions through a
 // homography (sift_hip_project_homography_device).  The rules -- sampler,
 // solver, score, selection -- are written out in include/sift_hip.h and
-// mirrored in numpy by sift_amd.cv.ransac_fundamental / ransac_homography.
+// mirrored in numpy by sift_amd.cv.ransac_fundamental / ransac_homography /
+// ransac_affine.
 //
 //  k_verify_gather        record j -> (qx, qy, tx, ty) in scratch, NaN for a
 //                         record whose index lies outside its position array:
@@ -17,6 +19,8 @@
 //  k_verify_hypotheses_h  the same for the homography: 4 matches, the
 //                         orientation test, the 8 x 9 DLT system through the
 //                         same elimination (solve_8x9), the sign of w.
+//  k_verify_hypotheses_a  the affine map (3 matches) and the similarity (2):
+//                         the closed-form solve in registers, no LDS.
 //  k_verify_score         the hot path, K x n predicate evaluations: one wave
 //                         per hypothesis, the workgroup's waves share an
 //                         LDS-staged tile of the gathered matches, lanes stride
@@ -24,7 +28,8 @@
 //                         hypothesis.  One body for both models: the predicate
 //                         is a template parameter (SampsonPass: sift_epipolar.h's,
 //                         the matcher's own; TransferPass: the forward transfer
-//                         error with the chirality test).
+//                         error with the chirality test; AffinePass: the
+//                         same error where w is 1).
 //  k_verify_select        one 1024-thread workgroup: argmax with the tie rule,
 //                         the winner rescored into the mask, and the ordered
 //                         compaction of k_match_select (prefix sums, no atomics:
@@ -410,7 +415,65 @@ __global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_h(List list, 
 }
 #undef VA
 
-constexpr int kScoreWaves = 4;     // hypotheses per workgroup
+// The affine map (3 matches) and the similarity (2 matches): the closed-form solve on the raw sample coordinates, all
+// in registers -- no LDS, no elimination, no normalisation.  The model is {m0 .. m5, 0, 0, 1}.
+template <VerifyModel Model, class List>
+__global__ __launch_bounds__(kHypThreads) void k_verify_hypotheses_a(List list, const float4* __restrict__ pts, int K,
+                                                                    unsigned seed, int* __restrict__ samples,
+                                                                    float* __restrict__ Aout, int* __restrict__ valid) {
+#pragma clang fp contract(off)
+    constexpr int M = sample_size(Model);
+    if constexpr (kBatched<List>) {
+        const size_t k0 = (size_t)K * pair_of(list);
+        pts += row0_of(list), seed += (unsigned)pair_of(list), samples += M * k0, Aout += 9 * k0, valid += k0;
+    }
+    const VerifyInput in = list_of(list);
+    const int k = blockIdx.x * kHypThreads + threadIdx.x;
+    if (k >= K) return;
+    const int n = verify_n(in.count, in.cap);
+
+    bool ok = n >= M;
+    int pick[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) pick[j] = -1;
+    float g[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (ok) {
+        draw<M>(seed, k, n, pick);
+        float4 p[M];
+#pragma unroll
+        for (int j = 0; j < M; j++) p[j] = pts[pick[j]];
+        const float d1x = p[1].x - p[0].x, d1y = p[1].y - p[0].y, e1x = p[1].z - p[0].z, e1y = p[1].w - p[0].w;
+        if constexpr (Model == VerifyModel::Affine) {
+            const float d2x = p[2].x - p[0].x, d2y = p[2].y - p[0].y, e2x = p[2].z - p[0].z, e2y = p[2].w - p[0].w;
+            const float det = d1x * d2y - d1y * d2x, dett = e1x * e2y - e1y * e2x;
+            const float s = det * dett;  // zero: a collinear triple or a repeated position on either side; or a NaN
+            ok = s > 0.f || s < 0.f;
+            g[0] = (e1x * d2y - e2x * d1y) / det;
+            g[1] = (e2x * d1x - e1x * d2x) / det;
+            g[3] = (e1y * d2y - e2y * d1y) / det;
+            g[4] = (e2y * d1x - e1y * d2x) / det;
+        } else {
+            const float den = d1x * d1x + d1y * d1y, dent = e1x * e1x + e1y * e1y;
+            ok = den > 0.f && dent > 0.f;
+            const float a = (d1x * e1x + d1y * e1y) / den, b = (d1x * e1y - d1y * e1x) / den;
+            g[0] = a, g[1] = -b, g[3] = b, g[4] = a;
+        }
+        g[2] = p[0].z - (g[0] * p[0].x + g[1] * p[0].y);
+        g[5] = p[0].w - (g[3] * p[0].x + g[4] * p[0].y);
+#pragma unroll
+        for (int i = 0; i < 6; i++) ok = ok && finite_f(g[i]);
+    }
+#pragma unroll
+    for (int j = 0; j < M; j++) samples[M * (size_t)k + j] = pick[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++) Aout[9 * (size_t)k + i] = ok ? g[i] : 0.f;
+    Aout[9 * (size_t)k + 6] = 0.f;
+    Aout[9 * (size_t)k + 7] = 0.f;
+    Aout[9 * (size_t)k + 8] = ok ? 1.f : 0.f;
+    valid[k] = ok ? 1 : 0;
+}
+
+constexpr int kScoreWaves = 4;    // hypotheses per workgroup
 constexpr int kScoreUnroll = 4;    // matches per lane and loop iteration
 constexpr int kScoreTile = 2048;   // matches per LDS tile (32 KiB): 2000 matches are one tile
 
@@ -591,6 +654,12 @@ void launch_verify_hypotheses(VerifyModel model, const List& list, const float4*
     const dim3 grid((K + kHypThreads - 1) / kHypThreads, list_pairs(list)), block(kHypThreads);
     if (model == VerifyModel::Homography)
         hipLaunchKernelGGL(k_verify_hypotheses_h<List>, grid, block, 0, s, list, pts, K, seed, e2, samples, F, valid);
+    else if (model == VerifyModel::Affine)
+        hipLaunchKernelGGL((k_verify_hypotheses_a<VerifyModel::Affine, List>), grid, block, 0, s, list, pts, K, seed,
+                           samples, F, valid);
+    else if (model == VerifyModel::Similarity)
+        hipLaunchKernelGGL((k_verify_hypotheses_a<VerifyModel::Similarity, List>), grid, block, 0, s, list, pts, K, seed,
+                           samples, F, valid);
     else
         hipLaunchKernelGGL(k_verify_hypotheses<List>, grid, block, 0, s, list, pts, K, seed, samples, F, valid);
 }
@@ -601,6 +670,8 @@ void launch_verify_score(VerifyModel model, const List& list, const float4* pts,
     const dim3 grid((K + kScoreWaves - 1) / kScoreWaves, list_pairs(list)), block(64 * kScoreWaves);
     if (model == VerifyModel::Homography)
         hipLaunchKernelGGL((k_verify_score<TransferPass, List>), grid, block, 0, s, list, pts, F, valid, K, e2, counts);
+    else if (is_affine(model))
+        hipLaunchKernelGGL((k_verify_score<AffinePass, List>), grid, block, 0, s, list, pts, F, valid, K, e2, counts);
     else
         hipLaunchKernelGGL((k_verify_score<SampsonPass, List>), grid, block, 0, s, list, pts, F, valid, K, e2, counts);
 }
@@ -612,6 +683,9 @@ void launch_verify_select(VerifyModel model, const List& list, const float4* pts
     const dim3 grid(1, list_pairs(list)), block(kVSelThreads);
     if (model == VerifyModel::Homography)
         hipLaunchKernelGGL((k_verify_select<TransferPass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
+                           result, out, out_count, mask);
+    else if (is_affine(model))
+        hipLaunchKernelGGL((k_verify_select<AffinePass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
                            result, out, out_count, mask);
     else
         hipLaunchKernelGGL((k_verify_select<SampsonPass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,

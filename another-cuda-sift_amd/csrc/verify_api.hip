@@ -17,8 +17,9 @@ struct sift_hip_verifier {
     int device = 0;
     int maxM = 0, maxK = 0, maxP = 0;
     float4* dPts = nullptr;      // the gathered matches (qx, qy, tx, ty), maxM rows
-    int* dSamples = nullptr;     // 8 per hypothesis (the homography uses 4), maxP x maxK hypotheses as are dF .. dCounts
-    float* dF = nullptr;         // 9 per hypothesis (F, or H)
+    int* dSamples = nullptr;     // 8 per hypothesis (the homography uses 4, the affine map 3, the similarity 2), maxP x
+                                 // maxK hypotheses as are dF .. dCounts
+    float* dF = nullptr;         // 9 per hypothesis (F, H, or the affine matrix over 0 0 1)
     int* dValid = nullptr;
     int* dCounts = nullptr;
     // the outputs of sift_hip_verify_fundamental_host / _homography_host and their batched forms
@@ -49,6 +50,7 @@ static_assert(sizeof(sift_hip_verify_result) == sizeof(VerifyResult), "the resul
 static_assert(sizeof(sift_hip_homography_result) == sizeof(VerifyResult) &&
                   offsetof(sift_hip_homography_result, inliers) == offsetof(VerifyResult, inliers),
               "both models' result records share the kernel's layout");
+static_assert(sizeof(sift_hip_affine_result) == sizeof(VerifyResult), "the affine models reuse the homography's record");
 static_assert(sizeof(sift_hip_pose_result) == sizeof(PoseResult) &&
                   offsetof(sift_hip_pose_result, candidate) == offsetof(PoseResult, candidate),
               "the pose record is written by the kernel");
@@ -109,10 +111,13 @@ int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
     const auto refuse = [](const std::string& msg) { return fail(SIFT_HIP_ERR_INVALID, msg); };
     const bool refine = c.op == Op::Refine, pose = c.op == Op::Pose;
     if (!v) return refuse("null verifier");
+    if ((int)c.model == 0) return refuse("verify: model must be SIFT_HIP_MODEL_AFFINE or SIFT_HIP_MODEL_SIMILARITY");
     if (!c.pairs) return refuse("verify: null pairs");
     if (c.op == Op::Score) {
         if (!c.models || !c.scores)
-            return refuse(c.model == VerifyModel::Homography ? "verify: null H or counts" : "verify: null F or counts");
+            return refuse(c.model == VerifyModel::Homography ? "verify: null H or counts"
+                          : is_affine(c.model)               ? "verify: null A or counts"
+                                                             : "verify: null F or counts");
     } else if (!pose && (!c.params || !c.result)) {
         return refuse(refine && c.single ? "refine: null result" : "verify: null params or result");
     }
@@ -358,7 +363,7 @@ int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples
     if (v->lastK == 0) return fail(SIFT_HIP_ERR_STATE, "no verify call has run on this verifier");
     if (v->lastBatch) return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was a batch");
     if (v->lastModel != (int)model)
-        return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was of the other model");
+        return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was of the other model");  // or of another
     const size_t K = (size_t)std::min(cap, v->lastK);
     if (K == 0) return SIFT_HIP_OK;
     HIPCHK(hipSetDevice(v->device));
@@ -376,6 +381,13 @@ bool rows_overlap(const float* xy, int stride, const float* out_xy, int out_stri
     const uintptr_t ibytes = sizeof(float) * ((size_t)(n - 1) * (size_t)stride + 2);
     const uintptr_t obytes = sizeof(float) * ((size_t)(n - 1) * (size_t)out_stride + 2);
     return !(ib == ob && stride == out_stride) && (ib <= ob ? ob - ib < ibytes : ib - ob < obytes);
+}
+
+// The affine calls' model argument; anything else is VerifyModel{0}, which check() refuses.
+VerifyModel affine_model(int model) {
+    return model == SIFT_HIP_MODEL_AFFINE       ? VerifyModel::Affine
+           : model == SIFT_HIP_MODEL_SIMILARITY ? VerifyModel::Similarity
+                                                : VerifyModel{0};
 }
 
 }  // namespace
@@ -445,8 +457,9 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
     return SIFT_HIP_OK;
 }
 
-// The sixteen verify and refine entry points: {fundamental, homography} x {one pair, batch} x {verify, refine} x
-// {device, host}.  Each fills the call record and runs it.
+// The twenty-four verify and refine entry points: {fundamental, homography, affine} x {one pair, batch} x
+// {verify, refine} x {device, host}.  Each fills the call record and runs it.  The affine calls carry one more
+// argument, the model (affine map or similarity), behind the handle (MODEL_ARG).
 #define SIFT_ONE_PAIR                                                                                               \
     const int* count, int cap, const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride, \
         int nt
@@ -456,8 +469,8 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
 #define SIFT_BATCH const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride
 #define SIFT_BATCH_LIST(c) c.single = false, c.counts = counts, c.P = P, c.pairs = pairs
 
-#define SIFT_VERIFIER_ENTRIES(name, MODEL, RESULT, LIST_ARGS, LIST)                                                      \
-    int sift_hip_verify_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                \
+#define SIFT_VERIFIER_ENTRIES(name, MODEL_ARG, MODEL, RESULT, LIST_ARGS, LIST)                                           \
+    int sift_hip_verify_##name##_device(sift_hip_verifier_t v, MODEL_ARG const sift_hip_dmatch* matches, LIST_ARGS,      \
                                         const sift_hip_verify_params* params, RESULT* result, sift_hip_dmatch* out,      \
                                         int* out_count, uint8_t* mask, void* stream) {                                   \
         Call c = make_call(Op::Verify, MODEL, false, matches, query_stride, train_stride);                               \
@@ -465,7 +478,7 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
         c.params = params, c.result = result, c.out = out, c.out_counts = out_count, c.mask = mask, c.stream = stream;   \
         return run(v, c);                                                                                                \
     }                                                                                                                    \
-    int sift_hip_verify_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                  \
+    int sift_hip_verify_##name##_host(sift_hip_verifier_t v, MODEL_ARG const sift_hip_dmatch* matches, LIST_ARGS,        \
                                       const sift_hip_verify_params* params, RESULT* result_host,                         \
                                       sift_hip_dmatch* out_host, uint8_t* mask_host) {                                   \
         Call c = make_call(Op::Verify, MODEL, true, matches, query_stride, train_stride);                                \
@@ -473,7 +486,7 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
         c.params = params, c.result = result_host, c.out = out_host, c.mask = mask_host;                                 \
         return run(v, c);                                                                                                \
     }                                                                                                                    \
-    int sift_hip_refine_##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,                \
+    int sift_hip_refine_##name##_device(sift_hip_verifier_t v, MODEL_ARG const sift_hip_dmatch* matches, LIST_ARGS,      \
                                         float max_error, int rounds, RESULT* result, uint8_t* mask, sift_hip_dmatch* out, \
                                         int* out_count, int* accepted, void* stream) {                                   \
         const sift_hip_verify_params params{1, 0u, max_error}; /* the one-hypothesis budget every verifier has */        \
@@ -483,8 +496,9 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
         c.accepted = accepted, c.stream = stream;                                                                        \
         return run(v, c);                                                                                                \
     }                                                                                                                    \
-    int sift_hip_refine_##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS, float max_error, \
-                                      int rounds, RESULT* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,    \
+    int sift_hip_refine_##name##_host(sift_hip_verifier_t v, MODEL_ARG const sift_hip_dmatch* matches, LIST_ARGS,        \
+                                      float max_error, int rounds, RESULT* result_host, uint8_t* mask_host,              \
+                                      sift_hip_dmatch* out_host,                                                         \
                                       int* out_count_host, int* accepted_host) {                                         \
         const sift_hip_verify_params params{1, 0u, max_error};                                                           \
         Call c = make_call(Op::Refine, MODEL, true, matches, query_stride, train_stride);                                \
@@ -493,10 +507,22 @@ int sift_hip_verifier_destroy(sift_hip_verifier_t v) {
         c.out_counts = out_count_host, c.accepted = accepted_host;                                                       \
         return run(v, c);                                                                                                \
     }
-SIFT_VERIFIER_ENTRIES(fundamental, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
-SIFT_VERIFIER_ENTRIES(homography, VerifyModel::Homography, sift_hip_homography_result, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
-SIFT_VERIFIER_ENTRIES(fundamental_batched, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_BATCH, SIFT_BATCH_LIST)
-SIFT_VERIFIER_ENTRIES(homography_batched, VerifyModel::Homography, sift_hip_homography_result, SIFT_BATCH, SIFT_BATCH_LIST)
+#define SIFT_NO_MODEL_ARG
+#define SIFT_MODEL_ARG int model,
+SIFT_VERIFIER_ENTRIES(fundamental, SIFT_NO_MODEL_ARG, VerifyModel::Fundamental, sift_hip_verify_result, SIFT_ONE_PAIR,
+                      SIFT_ONE_PAIR_LIST)
+SIFT_VERIFIER_ENTRIES(homography, SIFT_NO_MODEL_ARG, VerifyModel::Homography, sift_hip_homography_result, SIFT_ONE_PAIR,
+                      SIFT_ONE_PAIR_LIST)
+SIFT_VERIFIER_ENTRIES(affine, SIFT_MODEL_ARG, affine_model(model), sift_hip_affine_result, SIFT_ONE_PAIR,
+                      SIFT_ONE_PAIR_LIST)
+SIFT_VERIFIER_ENTRIES(fundamental_batched, SIFT_NO_MODEL_ARG, VerifyModel::Fundamental, sift_hip_verify_result,
+                      SIFT_BATCH, SIFT_BATCH_LIST)
+SIFT_VERIFIER_ENTRIES(homography_batched, SIFT_NO_MODEL_ARG, VerifyModel::Homography, sift_hip_homography_result,
+                      SIFT_BATCH, SIFT_BATCH_LIST)
+SIFT_VERIFIER_ENTRIES(affine_batched, SIFT_MODEL_ARG, affine_model(model), sift_hip_affine_result, SIFT_BATCH,
+                      SIFT_BATCH_LIST)
+#undef SIFT_MODEL_ARG
+#undef SIFT_NO_MODEL_ARG
 #undef SIFT_VERIFIER_ENTRIES
 
 // The eight pose entry points: {from F, from H} x {one pair, batch} x {device, host}.  The plane pose calls carry one
@@ -565,6 +591,14 @@ int sift_hip_score_homography_device(sift_hip_verifier_t v, const sift_hip_dmatc
     SIFT_ONE_PAIR_LIST(c);
     return score_entry(v, c, H, K, max_error, counts, stream);
 }
+
+// The predicate is both affine models' own, so the call takes no model argument.
+int sift_hip_score_affine_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, SIFT_ONE_PAIR, const float* A,
+                                 int K, float max_error, int* counts, void* stream) {
+    Call c = make_call(Op::Score, VerifyModel::Affine, false, matches, query_stride, train_stride);
+    SIFT_ONE_PAIR_LIST(c);
+    return score_entry(v, c, A, K, max_error, counts, stream);
+}
 #undef SIFT_ONE_PAIR_LIST
 #undef SIFT_ONE_PAIR
 
@@ -574,6 +608,14 @@ int sift_hip_verify_hypotheses_host(sift_hip_verifier_t v, int* samples, float* 
 
 int sift_hip_verify_homography_hypotheses_host(sift_hip_verifier_t v, int* samples, float* H, int* counts, int cap) {
     return hypotheses_host(v, VerifyModel::Homography, 4, samples, H, counts, cap);
+}
+
+int sift_hip_verify_affine_hypotheses_host(sift_hip_verifier_t v, int model, int* samples, float* A, int* counts,
+                                           int cap) {
+    const VerifyModel m = affine_model(model);
+    if (v && (int)m == 0)
+        return fail(SIFT_HIP_ERR_INVALID, "verify: model must be SIFT_HIP_MODEL_AFFINE or SIFT_HIP_MODEL_SIMILARITY");
+    return hypotheses_host(v, m, sample_size(m), samples, A, counts, cap);
 }
 
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

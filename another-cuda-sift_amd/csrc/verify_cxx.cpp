@@ -1,4 +1,4 @@
-// sift_cuda::Verifier / verifyFundamental / verifyHomography / projectHomographyDevice
+// sift_cuda::Verifier / verifyFundamental / verifyHomography / verifyAffine / projectHomographyDevice
 // (include/sift_cuda/Verify.hh) over the
 // C ABI in include/sift_hip.h.  Plain C++ (g++): no HIP headers, no device code.
 #include "sift_cuda/Verify.hh"
@@ -132,6 +132,38 @@ int abiCall(Fn fn, sift_hip_verifier* h, const Batch& l, Rest... rest) {
 SIFT_MODEL(Fundamental, fundamental, , sift_hip_verify_result, VerifyResult, TwoViewGeometry, F)
 SIFT_MODEL(Planar, homography, Homography, sift_hip_homography_result, HomographyResult, PlanarGeometry, H)
 #undef SIFT_MODEL
+
+// The affine models: one set of entry points that carry the model behind the handle.  Bound to it here, they have the
+// other models' shape, and the method templates below serve them as they are.
+template <int MODEL, class Fn>
+auto bound(Fn fn) {
+    return [fn](sift_hip_verifier* h, auto... rest) { return fn(h, MODEL, rest...); };
+}
+template <int MODEL>
+struct AffineMap {
+    using Record = sift_hip_affine_result;
+    using Result = AffineResult;
+    using Geometry = PlanarGeometry;
+    static constexpr const char* verifyHostName = "Verifier::verifyAffineHost";
+    static constexpr const char* refineHostName = "Verifier::refineAffineHost";
+    static const float (&matrix(const Record& r))[9] { return r.H; }
+    static float (&matrix(Geometry& g))[9] { return g.H; }
+    static auto verifyDevice(const OnePair&) { return bound<MODEL>(sift_hip_verify_affine_device); }
+    static auto verifyDevice(const Batch&) { return bound<MODEL>(sift_hip_verify_affine_batched_device); }
+    static auto verifyHost(const OnePair&) { return bound<MODEL>(sift_hip_verify_affine_host); }
+    static auto verifyHost(const Batch&) { return bound<MODEL>(sift_hip_verify_affine_batched_host); }
+    static auto refineDevice(const OnePair&) { return bound<MODEL>(sift_hip_refine_affine_device); }
+    static auto refineDevice(const Batch&) { return bound<MODEL>(sift_hip_refine_affine_batched_device); }
+    static auto refineHost(const OnePair&) { return bound<MODEL>(sift_hip_refine_affine_host); }
+    static auto refineHost(const Batch&) { return bound<MODEL>(sift_hip_refine_affine_batched_host); }
+};
+// f(the model's struct) for the model an affine method was given.
+template <class F>
+auto byModel(AffineModel model, const char* what, F f) {
+    if (model == AffineModel::Similarity) return f(AffineMap<SIFT_HIP_MODEL_SIMILARITY>{});
+    if (model != AffineModel::Affine) throw std::invalid_argument(std::string(what) + ": model must be Affine or Similarity");
+    return f(AffineMap<SIFT_HIP_MODEL_AFFINE>{});
+}
 
 template <class M>
 typename M::Record* abi(typename M::Result* r) {
@@ -382,6 +414,61 @@ SIFT_VERIFIER_METHODS(Fundamental, )
 SIFT_VERIFIER_METHODS(Planar, Homography)
 #undef SIFT_VERIFIER_METHODS
 
+// The affine methods: the same shapes, the model chosen at run time.
+void Verifier::verifyAffineDevice(ONE_PAIR_ARGS, AffineModel model, const VerifyParams& params, AffineResult* result,
+                                  DMatch* out, int* out_count, uint8_t* mask, void* stream) {
+    const char* what = "Verifier::verifyAffineDevice";
+    byModel(model, what, [&](auto m) {
+        verifyDeviceT<decltype(m)>(m_handle, what, ONE_PAIR, params, result, out, out_count, mask, stream);
+    });
+}
+void Verifier::verifyAffineBatchedDevice(BATCH_ARGS, AffineModel model, const VerifyParams& params, AffineResult* results,
+                                         DMatch* out, int* out_counts, uint8_t* mask, void* stream) {
+    const char* what = "Verifier::verifyAffineBatchedDevice";
+    byModel(model, what, [&](auto m) {
+        verifyDeviceT<decltype(m)>(m_handle, what, BATCH, params, results, out, out_counts, mask, stream);
+    });
+}
+PlanarGeometry Verifier::verifyAffineHost(ONE_PAIR_ARGS, AffineModel model, const VerifyParams& params) {
+    const char* what = "Verifier::verifyAffineHost";
+    return byModel(model, what, [&](auto m) { return verifyHostT<decltype(m)>(m_handle, what, ONE_PAIR, params); });
+}
+std::vector<PlanarGeometry> Verifier::verifyAffineBatchedHost(BATCH_ARGS, AffineModel model, const VerifyParams& params) {
+    const char* what = "Verifier::verifyAffineBatchedHost";
+    return byModel(model, what, [&](auto m) { return verifyBatchedHostT<decltype(m)>(m_handle, what, BATCH, params); });
+}
+void Verifier::refineAffineDevice(ONE_PAIR_ARGS, AffineModel model, float max_error, int rounds, AffineResult* result,
+                                  uint8_t* mask, DMatch* out, int* out_count, int* accepted, void* stream) {
+    const char* what = "Verifier::refineAffineDevice";
+    byModel(model, what, [&](auto m) {
+        refineDeviceT<decltype(m)>(m_handle, what, ONE_PAIR, max_error, rounds, result, mask, out, out_count, accepted,
+                                   stream);
+    });
+}
+void Verifier::refineAffineBatchedDevice(BATCH_ARGS, AffineModel model, float max_error, int rounds, AffineResult* results,
+                                         uint8_t* mask, DMatch* out, int* out_counts, int* accepted, void* stream) {
+    const char* what = "Verifier::refineAffineBatchedDevice";
+    byModel(model, what, [&](auto m) {
+        refineDeviceT<decltype(m)>(m_handle, what, BATCH, max_error, rounds, results, mask, out, out_counts, accepted,
+                                   stream);
+    });
+}
+int Verifier::refineAffineHost(ONE_PAIR_ARGS, AffineModel model, float max_error, int rounds, AffineResult& result,
+                               std::vector<uint8_t>& mask, std::vector<DMatch>* inliers) {
+    const char* what = "Verifier::refineAffineHost";
+    return byModel(model, what, [&](auto m) {
+        return refineHostT<decltype(m)>(m_handle, what, ONE_PAIR, max_error, rounds, result, mask, inliers);
+    });
+}
+std::vector<int> Verifier::refineAffineBatchedHost(BATCH_ARGS, AffineModel model, float max_error, int rounds,
+                                                   std::vector<AffineResult>& results, std::vector<uint8_t>& mask,
+                                                   std::vector<DMatch>* out, std::vector<int>* out_counts) {
+    const char* what = "Verifier::refineAffineBatchedHost";
+    return byModel(model, what, [&](auto m) {
+        return refineBatchedHostT<decltype(m)>(m_handle, what, BATCH, max_error, rounds, results, mask, out, out_counts);
+    });
+}
+
 void Verifier::recoverPoseDevice(ONE_PAIR_ARGS, const VerifyResult* result, const uint8_t* mask, const Camera& cam_query,
                                  const Camera& cam_train, const PoseParams& params, PoseResult* pose, uint8_t* mask_out,
                                  float* points, DMatch* out, int* out_count, void* stream) {
@@ -540,6 +627,16 @@ RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_
     return v.recoverPoseHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
                              nt, r, mask.empty() ? std::vector<uint8_t>(matches.size(), 1) : mask, cam_query, cam_train,
                              params);
+}
+
+PlanarGeometry verifyAffine(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                            int nt, AffineModel model, const VerifyParams& params, int query_stride, int train_stride,
+                            int refit) {
+    return byModel(model, "verifyAffine", [&](auto m) {
+        return verifyT<decltype(m)>("verifyAffine", matches,
+                                    OnePair{nullptr, nullptr, 0, query_xy, query_stride, nq, train_xy, train_stride, nt},
+                                    params, refit);
+    });
 }
 
 PlanePose recoverPoseHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,

@@ -191,6 +191,9 @@ class _HomographyResult(ctypes.Structure):
 HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("matches", "<i4"),
                                     ("valid_hypotheses", "<i4")])
 assert HOMOGRAPHY_RESULT_DTYPE.itemsize == ctypes.sizeof(_HomographyResult)
+# sift_hip_affine_result is the homography's record: H holds {a, b, tx, c, d, ty, 0, 0, 1}.
+AFFINE_RESULT_DTYPE = HOMOGRAPHY_RESULT_DTYPE
+MODEL_AFFINE, MODEL_SIMILARITY = 0, 1  # SIFT_HIP_MODEL_*
 
 
 class _Camera(ctypes.Structure):
@@ -403,6 +406,22 @@ def lib() -> ctypes.CDLL:
                                                           vp, vp, vp, vp]),
         "sift_hip_refine_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
                                                         vp, vp, vp]),
+        "sift_hip_verify_affine_device": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams), vp,
+                                              vp, vp, vp, vp]),
+        "sift_hip_verify_affine_host": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams),
+                                            ctypes.POINTER(_HomographyResult), vp, vp]),
+        "sift_hip_score_affine_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, i, f, vp, vp]),
+        "sift_hip_verify_affine_hypotheses_host": (i, [vp, i, vp, vp, vp, i]),
+        "sift_hip_verify_affine_batched_device": (i, [vp, i, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                      ctypes.POINTER(_VerifyParams), vp, vp, vp, vp, vp]),
+        "sift_hip_verify_affine_batched_host": (i, [vp, i, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i,
+                                                    ctypes.POINTER(_VerifyParams), vp, vp, vp]),
+        "sift_hip_refine_affine_device": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, vp, vp, vp]),
+        "sift_hip_refine_affine_host": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, f, i, vp, vp, vp, ip, ip]),
+        "sift_hip_refine_affine_batched_device": (i, [vp, i, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                      vp, vp, vp, vp]),
+        "sift_hip_refine_affine_batched_host": (i, [vp, i, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
+                                                    vp, vp, vp]),
         "sift_hip_default_pose_params": (None, [ctypes.POINTER(_PoseParams)]),
         "sift_hip_recover_pose_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp, ctypes.POINTER(_Camera),
                                              ctypes.POINTER(_Camera), ctypes.POINTER(_PoseParams), vp, vp, vp, vp, vp, vp]),
@@ -1553,6 +1572,7 @@ class Verifier:
         self.max_matches, self.max_hypotheses, self.max_pairs = max_matches, max_hypotheses, max_pairs
         self._hypotheses = 0
         self._h_hypotheses = 0
+        self._a_hypotheses = 0
 
     def __del__(self):
         v = getattr(self, "_v", None)
@@ -1866,6 +1886,111 @@ class Verifier:
                                          HOMOGRAPHY_RESULT_DTYPE, matches_ptr, counts_ptr, pairs, verified, max_error,
                                          rounds, q_stride, t_stride)
 
+    # --- the affine map and the similarity (sift_hip_verify_affine_* / sift_hip_refine_affine_*; the rule:
+    # include/sift_hip.h, in numpy sift_amd.cv.ransac_affine / refine_affine).  The homography methods argument for
+    # argument, with similarity choosing the 4-degree-of-freedom model (2-point samples) over the affine map (3-point
+    # samples); the record is the homography's, H = {a, b, tx, c, d, ty, 0, 0, 1}, so project_homography_device and the
+    # window-gated matchers take it as it lies.
+
+    @staticmethod
+    def _affine(fn, similarity):
+        """fn with the model argument, which follows the handle, bound."""
+        model = MODEL_SIMILARITY if similarity else MODEL_AFFINE
+        return lambda v, *args: fn(v, model, *args)
+
+    def verify_affine_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                             nt: int, result_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0, mask_ptr: int = 0,
+                             max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                             t_stride: int = 3, stream: Optional[int] = None, similarity: bool = False) -> None:
+        """verify_homography_device for the affine map or the similarity (sift_hip_verify_affine_device); result_ptr:
+        an AFFINE_RESULT_DTYPE record."""
+        self._device(self._affine(lib().sift_hip_verify_affine_device, similarity), "verify_affine_device", matches_ptr,
+                     count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, out_ptr, out_count_ptr, mask_ptr, max_error,
+                     hypotheses, seed, q_stride, t_stride, stream)
+        self._a_hypotheses = hypotheses
+
+    def verify_affine_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                           nt: int, max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                           t_stride: int = 3, full: bool = False, similarity: bool = False):
+        """Synchronous (sift_hip_verify_affine_host): (A 3 x 3 float32 with the last row 0 0 1, the inlier records as a
+        DMATCH_DTYPE array, the winning hypothesis or -1).  full: (the AFFINE_RESULT_DTYPE record, the records, the
+        mask of cap bytes)."""
+        got = self._host(self._affine(lib().sift_hip_verify_affine_host, similarity), "verify_affine_host",
+                         _HomographyResult, AFFINE_RESULT_DTYPE, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt,
+                         max_error, hypotheses, seed, q_stride, t_stride, full)
+        self._a_hypotheses = hypotheses
+        return got
+
+    def score_affine_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                            nt: int, A_ptr: int, K: int, max_error: float, counts_ptr: int, q_stride: int = 3,
+                            t_stride: int = 3, stream: Optional[int] = None, similarity: bool = False) -> None:
+        """The affine score alone on the caller's K models (device, K x 9 floats, the last row 0 0 1): counts (device,
+        K ints).  The predicate is both models' own: similarity changes nothing."""
+        self._score(lib().sift_hip_score_affine_device, "score_affine_device", matches_ptr, count_ptr, cap, q_xy_ptr, nq,
+                    t_xy_ptr, nt, A_ptr, K, max_error, counts_ptr, q_stride, t_stride, stream)
+
+    def affine_hypotheses(self, similarity: bool = False):
+        """What the last verify call drew, solved and counted, when it was a call of this model: (samples (K, 3) --
+        similarity: (K, 2) -- int32, A (K, 9) float32, valid (K,) bool -- an invalid hypothesis has A all zero --,
+        counts (K,) int32).  Synchronises the device."""
+        K, m = self._a_hypotheses, 2 if similarity else 3
+        samples, A, counts = np.zeros((K, m), np.int32), np.zeros((K, 9), np.float32), np.zeros(K, np.int32)
+        _check(lib().sift_hip_verify_affine_hypotheses_host(self._v, MODEL_SIMILARITY if similarity else MODEL_AFFINE,
+                                                            _ptr(samples), _ptr(A), _ptr(counts), K),
+               "verify_affine_hypotheses_host")
+        return samples, A, A.any(1), counts
+
+    def verify_affine_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                     out_ptr: int = 0, out_counts_ptr: int = 0, mask_ptr: int = 0,
+                                     max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, q_stride: int = 3,
+                                     t_stride: int = 3, stream: Optional[int] = None, similarity: bool = False) -> None:
+        """verify_batched_device for the affine models (sift_hip_verify_affine_batched_device)."""
+        self._batched_device(self._affine(lib().sift_hip_verify_affine_batched_device, similarity),
+                             "verify_affine_batched_device", matches_ptr, counts_ptr, pairs, results_ptr, out_ptr,
+                             out_counts_ptr, mask_ptr, max_error, hypotheses, seed, q_stride, t_stride, stream)
+
+    def verify_affine_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, max_error: float = 1.5,
+                                   hypotheses: int = 1024, seed: int = 0, q_stride: int = 3, t_stride: int = 3,
+                                   full: bool = False, similarity: bool = False) -> list:
+        """verify_batched_host for the affine models (sift_hip_verify_affine_batched_host)."""
+        return self._batched_host(self._affine(lib().sift_hip_verify_affine_batched_host, similarity),
+                                  "verify_affine_batched_host", AFFINE_RESULT_DTYPE, matches_ptr, counts_ptr, pairs,
+                                  max_error, hypotheses, seed, q_stride, t_stride, full)
+
+    def refine_affine_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                             nt: int, result_ptr: int, mask_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0,
+                             accepted_ptr: int = 0, max_error: float = 1.5, rounds: int = 1, q_stride: int = 3,
+                             t_stride: int = 3, stream: Optional[int] = None, similarity: bool = False) -> None:
+        """refine_device for the affine models (sift_hip_refine_affine_device)."""
+        self._refine_device(self._affine(lib().sift_hip_refine_affine_device, similarity), "refine_affine_device",
+                            matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result_ptr, mask_ptr, out_ptr,
+                            out_count_ptr, accepted_ptr, max_error, rounds, q_stride, t_stride, stream)
+
+    def refine_affine_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                           nt: int, result, mask, max_error: float = 1.5, rounds: int = 1, q_stride: int = 3,
+                           t_stride: int = 3, similarity: bool = False):
+        """refine_host for the affine models (sift_hip_refine_affine_host; an AFFINE_RESULT_DTYPE record)."""
+        return self._refine_host(self._affine(lib().sift_hip_refine_affine_host, similarity), "refine_affine_host",
+                                 AFFINE_RESULT_DTYPE, matches_ptr, count_ptr, cap, q_xy_ptr, nq, t_xy_ptr, nt, result,
+                                 mask, max_error, rounds, q_stride, t_stride)
+
+    def refine_affine_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, results_ptr: int,
+                                     mask_ptr: int, out_ptr: int = 0, out_counts_ptr: int = 0, accepted_ptr: int = 0,
+                                     max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3,
+                                     stream: Optional[int] = None, similarity: bool = False) -> None:
+        """refine_batched_device for the affine models (sift_hip_refine_affine_batched_device)."""
+        self._refine_batched_device(self._affine(lib().sift_hip_refine_affine_batched_device, similarity),
+                                    "refine_affine_batched_device", matches_ptr, counts_ptr, pairs, results_ptr, mask_ptr,
+                                    out_ptr, out_counts_ptr, accepted_ptr, max_error, rounds, q_stride, t_stride, stream)
+
+    def refine_affine_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, verified: Sequence,
+                                   max_error: float = 1.5, rounds: int = 1, q_stride: int = 3, t_stride: int = 3,
+                                   similarity: bool = False) -> list:
+        """refine_batched_host for the affine models (sift_hip_refine_affine_batched_host)."""
+        return self._refine_batched_host(self._affine(lib().sift_hip_refine_affine_batched_host, similarity),
+                                         "refine_affine_batched_host", AFFINE_RESULT_DTYPE, matches_ptr, counts_ptr, pairs,
+                                         verified, max_error, rounds, q_stride, t_stride)
+
     # --- the relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
     # in numpy sift_amd.cv.recover_pose).  The list, count, cap and positions are the verify call's; result(s) and mask
     # are what it (or a refine call) wrote and are only read.  A camera is (fx, fy, cx, cy).
@@ -2081,6 +2206,19 @@ def verifyHomographyBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair:
                            matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit)
 
 
+def verifyAffineBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, similarity: bool = False,
+                        max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, refit: int = 0) -> list:
+    """verifyFundamentalBatched for the affine map or, with similarity, the similarity: per pair what verifyAffine
+    returns."""
+    def host(v, *args):
+        return v.verify_affine_batched_host(*args, similarity=similarity)
+
+    def refine(v, *args):
+        return v.refine_affine_batched_host(*args, similarity=similarity)
+
+    return _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit)
+
+
 def verifyFundamental(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, max_error: float = 1.5,
                       hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3, refit: int = 0):
     """Geometric verification of a match list (matchList's output): (F 3 x 3 float32 with x_src^T F x_des = 0, the
@@ -2115,6 +2253,26 @@ def verifyHomography(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int
         return v.verify_homography_host(*args, max_error, hypotheses, seed, des_stride, src_stride)
     r, _, mask = v.verify_homography_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True)
     r, recs, _, _ = v.refine_homography_host(*args, r, mask, max_error, refit, des_stride, src_stride)
+    return r["H"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
+
+
+def verifyAffine(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, similarity: bool = False,
+                 max_error: float = 1.5, hypotheses: int = 1024, seed: int = 0, des_stride: int = 3, src_stride: int = 3,
+                 refit: int = 0):
+    """verifyFundamental for the affine map (cv::estimateAffine2D) or, with similarity, the similarity
+    (cv::estimateAffinePartial2D): (A 3 x 3 float32 with x_src = A x_des and the last row 0 0 1, the inlier records
+    in input order, the winning hypothesis or -1 when there are fewer than 3 / 2 matches or no sample was valid).
+    refit: as for verifyFundamental (Verifier.refine_affine_host) -- worth more here than for the other models, a
+    minimal model through 2 or 3 grid-rounded points being rough."""
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
+    v = Verifier(max(len(m), 1), hypotheses)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    args = (d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src)
+    if not refit:
+        return v.verify_affine_host(*args, max_error, hypotheses, seed, des_stride, src_stride, similarity=similarity)
+    r, _, mask = v.verify_affine_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True, similarity)
+    r, recs, _, _ = v.refine_affine_host(*args, r, mask, max_error, refit, des_stride, src_stride, similarity)
     return r["H"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
 
 

@@ -1040,6 +1040,226 @@ def refine_homography(matches, q_xy, t_xy, result, max_error=1.5, rounds: int = 
     return _refine("H", _transfer_pass, matches, q_xy, t_xy, result, max_error, rounds)
 
 
+# --- Affine and similarity verification: the rule of sift_hip_verify_affine_* / sift_hip_refine_affine_*
+# (include/sift_hip.h, "Affine and similarity verification") in numpy, on the conventions above: the minimal solve and
+# the score in float32, the refit in float64, one rounded operation per array operation in the header's order.  The
+# model is x_train = A x_query + t, stored as the nine floats {a, b, tx, c, d, ty, 0, 0, 1} -- a homography record.
+
+
+def affine_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the affine rule: (K, 3) int32, ransac_samples' draw with 3 indices.  n < 3: every entry -1."""
+    return _samples(n, K, seed, 3)
+
+
+def similarity_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the similarity rule: (K, 2) int32, ransac_samples' draw with 2 indices.  n < 2: every entry -1."""
+    return _samples(n, K, seed, 2)
+
+
+def _affine_rows(a, b, c, d, q0, t0, ok):
+    """The nine floats of (K,) matrix entries and the first sample (K, 2) each side; invalid rows all zero."""
+    tx = t0[:, 0] - (a * q0[:, 0] + b * q0[:, 1])
+    ty = t0[:, 1] - (c * q0[:, 0] + d * q0[:, 1])
+    zero, one = np.zeros_like(a), np.ones_like(a)
+    A = np.stack([a, b, tx, c, d, ty, zero, zero, one], 1)
+    assert A.dtype == np.float32
+    ok = ok & np.isfinite(A).all(1)
+    A[~ok] = 0
+    return A, ok
+
+
+def affine_from_3(q_xy3, t_xy3):
+    """The solver of the affine rule: the map through 3 pairs, in closed form on the raw coordinates.  q_xy3 / t_xy3:
+    (3, 2) -> (A (9,) float32, valid bool), or (K, 3, 2) -> (A (K, 9), valid (K,)).  An invalid hypothesis (a collinear
+    triple or a repeated position on either side, a NaN, a non-finite entry) has A all zero; a reflection is valid."""
+    q = np.asarray(q_xy3, np.float32)
+    t = np.asarray(t_xy3, np.float32)
+    single = q.ndim == 2
+    q, t = q.reshape(-1, 3, 2), t.reshape(-1, 3, 2)
+    with np.errstate(all="ignore"):
+        d1, d2, e1, e2 = q[:, 1] - q[:, 0], q[:, 2] - q[:, 0], t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]
+        det = d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0]
+        dett = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        p = det * dett
+        ok = (p > 0) | (p < 0)
+        a = (e1[:, 0] * d2[:, 1] - e2[:, 0] * d1[:, 1]) / det
+        b = (e2[:, 0] * d1[:, 0] - e1[:, 0] * d2[:, 0]) / det
+        c = (e1[:, 1] * d2[:, 1] - e2[:, 1] * d1[:, 1]) / det
+        d = (e2[:, 1] * d1[:, 0] - e1[:, 1] * d2[:, 0]) / det
+        A, ok = _affine_rows(a, b, c, d, q[:, 0], t[:, 0], ok)
+    assert p.dtype == np.float32
+    return (A[0], bool(ok[0])) if single else (A, ok)
+
+
+def similarity_from_2(q_xy2, t_xy2):
+    """The solver of the similarity rule: the rotation, scale and translation through 2 pairs, [a, -b, tx; b, a, ty].
+    q_xy2 / t_xy2: (2, 2) -> (A (9,) float32, valid bool), or (K, 2, 2) -> (A (K, 9), valid (K,)).  An invalid
+    hypothesis (a repeated position on either side, a NaN, a non-finite entry) has A all zero."""
+    q = np.asarray(q_xy2, np.float32)
+    t = np.asarray(t_xy2, np.float32)
+    single = q.ndim == 2
+    q, t = q.reshape(-1, 2, 2), t.reshape(-1, 2, 2)
+    with np.errstate(all="ignore"):
+        dq, dt = q[:, 1] - q[:, 0], t[:, 1] - t[:, 0]
+        den = dq[:, 0] * dq[:, 0] + dq[:, 1] * dq[:, 1]
+        dent = dt[:, 0] * dt[:, 0] + dt[:, 1] * dt[:, 1]
+        ok = (den > 0) & (dent > 0)
+        a = (dq[:, 0] * dt[:, 0] + dq[:, 1] * dt[:, 1]) / den
+        b = (dq[:, 0] * dt[:, 1] - dq[:, 1] * dt[:, 0]) / den
+        A, ok = _affine_rows(a, -b, b, a, q[:, 0], t[:, 0], ok)
+    assert den.dtype == np.float32
+    return (A[0], bool(ok[0])) if single else (A, ok)
+
+
+def _affine_pass(pts, A, max_error) -> np.ndarray:
+    """(K, n) bool: the affine predicate of every match (qx, qy, tx, ty) under each of the K rows of A (K, 9):
+    dx dx + dy dy <= max_error max_error, inclusive, with dx = px - tx, dy = py - ty.  The last row is not read."""
+    m = np.asarray(A, np.float32).reshape(-1, 9)[:, :, None]
+    e = np.float32(max_error)
+    qx, qy, tx, ty = (pts[None, :, i] for i in range(4))
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        px = (m[:, 0] * qx + m[:, 1] * qy) + m[:, 2]
+        py = (m[:, 3] * qx + m[:, 4] * qy) + m[:, 5]
+        dx = px - tx
+        dy = py - ty
+        near = dx * dx + dy * dy <= e * e
+    assert dx.dtype == np.float32 and dy.dtype == np.float32
+    return near
+
+
+def affine_inliers(matches, q_xy, t_xy, A, max_error) -> np.ndarray:
+    """The score of the affine and similarity rules: a bool per DMATCH_DTYPE record, True where the record's query
+    position, carried over by A (9 floats, the last row 0 0 1), lies within max_error pixels of its train position,
+    inclusive -- transfer_inliers' answer on the same nine floats.  A record with an index outside its position array,
+    or a NaN position, is an inlier of nothing."""
+    a = np.asarray(A, np.float32).reshape(-1)
+    if a.size != 9:
+        raise ValueError("A must have 9 entries (3 x 3, row-major, the last row 0 0 1)")
+    return _affine_pass(_match_points(matches, q_xy, t_xy), a, max_error)[0]
+
+
+def ransac_affine(matches, q_xy, t_xy, max_error=1.5, K: int = 1024, seed: int = 0, similarity: bool = False) -> dict:
+    """The whole operation (sift_hip_verify_affine_*) in numpy, for the affine map or, with similarity, the similarity.
+    Returns ransac_homography's dict, keys H and Hs included (the record is a homography record); samples is (K, 3) or
+    (K, 2)."""
+    from . import DMATCH_DTYPE
+
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    m = 2 if similarity else 3
+    pts = _match_points(matches, q_xy, t_xy)
+    samples = _samples(n, K, seed, m)
+    if n >= m:
+        solve = similarity_from_2 if similarity else affine_from_3
+        Hs, valid = solve(pts[samples][:, :, :2], pts[samples][:, :, 2:])
+        passes = _affine_pass(pts, Hs, max_error) & valid[:, None]
+    else:
+        Hs, valid, passes = np.zeros((K, 9), np.float32), np.zeros(K, bool), np.zeros((K, n), bool)
+    counts = passes.sum(1).astype(np.int32)
+    hyp = -1
+    if valid.any():
+        hyp = int(np.argmax(np.where(valid, counts, -1)))  # the first of the largest: ties to the lowest k
+    mask = passes[hyp].astype(np.uint8) if hyp >= 0 else np.zeros(n, np.uint8)
+    return dict(H=Hs[hyp].copy() if hyp >= 0 else np.zeros(9, np.float32), inliers=int(counts[hyp]) if hyp >= 0 else 0,
+                hypothesis=hyp, matches=n, valid_hypotheses=int(valid.sum()), mask=mask, list=matches[mask != 0],
+                samples=samples, Hs=Hs, valid=valid, counts=counts)
+
+
+def _refit_affine(pts, mask, similarity: bool):
+    """One fit of the affine refit rule on gathered points (n, 4) float32 and their mask: (A (9,) float32, valid)."""
+    assert pts.dtype == np.float32
+    n = len(pts)
+    mask = np.asarray(mask).reshape(-1)[:n]
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    zero = np.zeros(9, np.float32)
+    fit = (mask != 0) & np.isfinite(pts).all(1)
+    m = int(fit.sum())
+    if m < (2 if similarity else 3):
+        return zero, False
+    p = pts.astype(np.float64)
+    with np.errstate(all="ignore"):
+        mean = _slot_sum(p, fit) / np.float64(m)                       # (mqx, mqy, mtx, mty)
+        c = p - mean
+        x, y, u, v = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+        Sxx, Sxy, Syy, Txx, Txy, Tyx, Tyy = _slot_sum(np.stack([x * x, x * y, y * y, u * x, u * y, v * x, v * y], 1), fit)
+        if similarity:
+            den = Sxx + Syy
+            ok = bool(np.isfinite(den) and den > 0)
+            a = (Txx + Tyy) / den
+            c_ = (Tyx - Txy) / den
+            b, d = -c_, a
+        else:
+            det = Sxx * Syy - Sxy * Sxy
+            ok = bool(np.isfinite(det) and det > 0)
+            a = (Txx * Syy - Txy * Sxy) / det
+            b = (Txy * Sxx - Txx * Sxy) / det
+            c_ = (Tyx * Syy - Tyy * Sxy) / det
+            d = (Tyy * Sxx - Tyx * Sxy) / det
+        R = np.array([a, b, mean[2] - (a * mean[0] + b * mean[1]), c_, d, mean[3] - (c_ * mean[0] + d * mean[1]),
+                      0.0, 0.0, 1.0], np.float64)
+        out = R.astype(np.float32)
+    ok = ok and bool(np.isfinite(out).all())
+    return (out, True) if ok else (zero, False)
+
+
+def refit_affine(pts_or_matches, q_xy=None, t_xy=None, mask=None, similarity: bool = False):
+    """One fit of the affine refit rule (include/sift_hip.h): the least-squares affine map -- or similarity -- of the
+    records mask marks, (A (9,) float32 over the row 0 0 1, valid), from the means and the seven sums of centred
+    products in the refit's summation order.  pts_or_matches: as for refit_fundamental.  An invalid fit (fewer than 3
+    / 2 fit records, a fit set on one line or at one point, a non-finite result) has A all zero."""
+    pts = _refit_points(pts_or_matches, q_xy, t_xy)
+    return _refit_affine(pts, np.ones(len(pts), np.uint8) if mask is None else mask, similarity)
+
+
+def refine_affine(matches, q_xy, t_xy, result, max_error=1.5, rounds: int = 1, similarity: bool = False) -> dict:
+    """refine_fundamental for a ransac_affine dict (sift_hip_refine_affine_*)."""
+    from . import DMATCH_DTYPE
+
+    if not 1 <= int(rounds) <= REFIT_MAX_ROUNDS:
+        raise ValueError("rounds must lie in 1..8")
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    out = dict(result)
+    cur = np.asarray(result["H"], np.float32).reshape(9).copy()
+    mask = np.asarray(result["mask"], np.uint8).reshape(-1)[:n].copy()
+    if len(mask) != n:
+        raise ValueError("one mask byte per record")
+    inliers = int(result["inliers"])
+    accepted = 0
+    pts = _match_points(matches, q_xy, t_xy)
+    if int(result["hypothesis"]) >= 0 and geometry_usable(cur):
+        for _ in range(int(rounds)):
+            cand, ok = _refit_affine(pts, mask, similarity)
+            if not ok:
+                break  # the state is unchanged, so every later round fails the same way
+            keep = _affine_pass(pts, cand, max_error)[0]
+            if int(keep.sum()) < inliers:
+                break
+            cur, mask, inliers = cand, keep.astype(np.uint8), int(keep.sum())
+            accepted += 1
+    assert cur.dtype == np.float32 and mask.dtype == np.uint8
+    out["H"], out["mask"], out["inliers"], out["list"] = cur, mask, inliers, matches[mask != 0]
+    out["accepted"] = accepted
+    return out
+
+
+def affine_lstsq(q_pts, t_pts, similarity: bool = False) -> np.ndarray:
+    """A reference, not part of the device rule: the float64 least-squares affine map (or similarity) of n >= 3 (2)
+    pairs through np.linalg.lstsq, as 3 x 3 with the last row 0 0 1 -- the truth the tests hold the rule against."""
+    q = np.asarray(q_pts, np.float64).reshape(len(q_pts), -1)[:, :2]
+    t = np.asarray(t_pts, np.float64).reshape(len(t_pts), -1)[:, :2]
+    if len(q) != len(t) or len(q) < (2 if similarity else 3):
+        raise ValueError("affine_lstsq needs the same number (>= 3, similarity: >= 2) of points on both sides")
+    one, nil = np.ones(len(q)), np.zeros(len(q))
+    if similarity:  # unknowns (a, b, tx, ty): u = a x - b y + tx, v = b x + a y + ty
+        M = np.r_[np.stack([q[:, 0], -q[:, 1], one, nil], 1), np.stack([q[:, 1], q[:, 0], nil, one], 1)]
+        a, b, tx, ty = np.linalg.lstsq(M, np.r_[t[:, 0], t[:, 1]], rcond=None)[0]
+        return np.array([[a, -b, tx], [b, a, ty], [0, 0, 1]])
+    sol = np.linalg.lstsq(np.stack([q[:, 0], q[:, 1], one], 1), t, rcond=None)[0]  # (3, 2)
+    return np.r_[sol.T, [[0.0, 0.0, 1.0]]]
+
+
 # --- Relative pose from a verified fundamental matrix: the rule of sift_hip_recover_pose_* (include/sift_hip.h,
 # "Relative pose from a verified fundamental matrix") in numpy float64.  As in the refit: every operation below is one
 # IEEE float64 operation in the header's association -- products and sums are written out elementwise, no @, dot,

@@ -1,6 +1,6 @@
-// sift_cuda::Verifier / verifyFundamental / verifyHomography: two-view
-// verification of a match list (a fixed-budget RANSAC for the fundamental matrix
-// or the homography on the device) and projectHomographyDevice, over
+// sift_cuda::Verifier / verifyFundamental / verifyHomography / verifyAffine: two-view
+// verification of a match list (a fixed-budget RANSAC for the fundamental matrix,
+// the homography, the affine map or the similarity on the device) and projectHomographyDevice, over
 // sift_hip_verify_* and sift_hip_project_homography_device of
 // include/sift_hip.h, where the rules are written out.
 // Plain C++: no HIP headers.
@@ -52,6 +52,12 @@ struct HomographyResult {
     float H[9];
     int inliers, hypothesis, matches, valid_hypotheses;
 };
+
+// The affine models (sift_hip_verify_affine_*): the 6-degree-of-freedom affine map from 3-point samples
+// (cv::estimateAffine2D) or the 4-degree-of-freedom similarity from 2-point samples (cv::estimateAffinePartial2D).
+// Their record is the homography's, H = {a, b, tx, c, d, ty, 0, 0, 1}: projectHomographyDevice takes it as it lies.
+enum class AffineModel { Affine = 0, Similarity = 1 };
+using AffineResult = HomographyResult;
 
 // sift_hip_verify_pair: one pair of a batched call -- its device position rows (nq / nt rows) and cap, its number of
 // rows in the call's matches, out and mask arrays, where its rows start at the sum of the caps before it.
@@ -219,6 +225,40 @@ public:
                                                  std::vector<uint8_t>& mask, std::vector<DMatch>* out = nullptr,
                                                  std::vector<int>* out_counts = nullptr);
 
+    // The affine map and the similarity (sift_hip_verify_affine_* / sift_hip_refine_affine_*; the rule:
+    // include/sift_hip.h, "Affine and similarity verification"): the homography's verify and refine calls argument for
+    // argument, with the model behind the list.  The geometry's H holds the 2 x 3 matrix over the row 0 0 1.
+    void verifyAffineDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                            int nq, const float* train_xy, int train_stride, int nt, AffineModel model,
+                            const VerifyParams& params, AffineResult* result, DMatch* out = nullptr,
+                            int* out_count = nullptr, uint8_t* mask = nullptr, void* stream = nullptr);
+    PlanarGeometry verifyAffineHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                    int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                    AffineModel model, const VerifyParams& params = {});
+    void verifyAffineBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                   int query_stride, int train_stride, AffineModel model, const VerifyParams& params,
+                                   AffineResult* results, DMatch* out = nullptr, int* out_counts = nullptr,
+                                   uint8_t* mask = nullptr, void* stream = nullptr);
+    std::vector<PlanarGeometry> verifyAffineBatchedHost(const DMatch* matches, const int* counts,
+                                                        const std::vector<VerifyPair>& pairs, int query_stride,
+                                                        int train_stride, AffineModel model,
+                                                        const VerifyParams& params = {});
+    void refineAffineDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                            int nq, const float* train_xy, int train_stride, int nt, AffineModel model, float max_error,
+                            int rounds, AffineResult* result, uint8_t* mask, DMatch* out = nullptr,
+                            int* out_count = nullptr, int* accepted = nullptr, void* stream = nullptr);
+    int refineAffineHost(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride, int nq,
+                         const float* train_xy, int train_stride, int nt, AffineModel model, float max_error, int rounds,
+                         AffineResult& result, std::vector<uint8_t>& mask, std::vector<DMatch>* inliers = nullptr);
+    void refineAffineBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                   int query_stride, int train_stride, AffineModel model, float max_error, int rounds,
+                                   AffineResult* results, uint8_t* mask, DMatch* out = nullptr, int* out_counts = nullptr,
+                                   int* accepted = nullptr, void* stream = nullptr);
+    std::vector<int> refineAffineBatchedHost(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                             int query_stride, int train_stride, AffineModel model, float max_error,
+                                             int rounds, std::vector<AffineResult>& results, std::vector<uint8_t>& mask,
+                                             std::vector<DMatch>* out = nullptr, std::vector<int>* out_counts = nullptr);
+
     // The relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
     // "Relative pose from a verified fundamental matrix"): cv::recoverPose on the list, count and positions of the
     // verify call that wrote *result and mask (device memory, read only).  pose: a device record; mask_out (cap bytes,
@@ -304,6 +344,12 @@ TwoViewGeometry verifyFundamental(const std::vector<DMatch>& matches, const floa
                                   int train_stride, int refit);
 PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                                 int nt, const VerifyParams& params, int query_stride, int train_stride, int refit);
+
+// The one shot for the affine map or the similarity, with `refit` refit rounds (0: the minimal-sample winner): the
+// matrix in H, over the row 0 0 1.
+PlanarGeometry verifyAffine(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                            int nt, AffineModel model, const VerifyParams& params = {}, int query_stride = 3,
+                            int train_stride = 3, int refit = 0);
 
 // The all-in-one beside verifyFundamental: uploads the list and recovers the pose of a verified F (9 floats, row-major,
 // x_train^T F x_query = 0) over the records `mask` marks (empty: every record).

@@ -1696,6 +1696,153 @@ int sift_hip_refine_homography_batched_host(sift_hip_verifier_t v, const sift_hi
                                             uint8_t* mask_host, sift_hip_dmatch* out_host, int* out_counts_host,
                                             int* accepted_host);
 
+/* --- Affine and similarity verification: 3- and 2-point RANSAC ------------------
+ *
+ * The models of motions that are a 2-D affine map (6 degrees of freedom:
+ * cv::estimateAffine2D) or a similarity (4: cv::estimateAffinePartial2D) --
+ * video stabilisation, aerial and satellite strips, scanned sheets, microscope
+ * mosaics, a fronto-parallel object instance, a tracker's frame-to-frame motion.
+ * The same fixed budget of K hypotheses on the same verifier, but a sample is 3
+ * or 2 matches instead of 4, and the chance that a sample is clean falls with
+ * the power of its size: at 20 % planted pairs a 2-point sample is clean once in
+ * 25 draws, a 3-point sample once in 125, a 4-point sample once in 625.  One
+ * call argument, `model`, selects between the two.
+ *
+ * The result is stored as the 3 x 3 matrix [a b tx; c d ty; 0 0 1] in the
+ * homography's 52-byte record (sift_hip_affine_result is that type), so
+ * everything downstream of a homography -- sift_hip_project_homography_device,
+ * its batched form, the window-gated matchers on projected positions -- takes it
+ * as it lies.
+ *
+ * The rule.  x_train = A x_query + t.  The conventions are the verifier's:
+ * float32, every operation rounded to nearest, one at a time, in the written
+ * order; nothing fused; division correctly rounded.  The refit is float64 in one
+ * written association.  sift_amd.cv.ransac_affine / refine_affine is the same
+ * rule in numpy; the device equals it byte for byte.
+ *
+ * Input.  As for the other models: n, the positions (qx, qy, tx, ty) of match j,
+ * and the four NaNs of a record with an index outside [0, nq) / [0, nt).
+ *
+ * Sampling.  The sampler of the fundamental rule with m = 3 draws (affine) or
+ * m = 2 (similarity): j = 0..m-1, the same base, h and r, the same skip of
+ * earlier picks.  With n < m nothing is drawn and every sample index is -1.
+ *
+ * Affine from 3, on the raw sample coordinates (q_i, t_i the query and train
+ * position of sample i).  d1 = q1 - q0, d2 = q2 - q0, e1 = t1 - t0, e2 = t2 - t0.
+ *   det = d1x*d2y - d1y*d2x;  dett = e1x*e2y - e1y*e2x;  p = det * dett
+ * The sample is degenerate when p is neither > 0 nor < 0: a collinear triple on
+ * either side, a repeated position, or a NaN.  A negative p -- a reflection --
+ * is allowed, as in OpenCV.
+ *   a = (e1x*d2y - e2x*d1y) / det;  b = (e2x*d1x - e1x*d2x) / det
+ *   c = (e1y*d2y - e2y*d1y) / det;  d = (e2y*d1x - e1y*d2x) / det
+ *   tx = t0x - (a*q0x + b*q0y);     ty = t0y - (c*q0x + d*q0y)
+ *
+ * Similarity from 2.  dq = q1 - q0, dt = t1 - t0.
+ *   den = dqx*dqx + dqy*dqy;  dent = dtx*dtx + dty*dty
+ * The sample is degenerate unless den > 0 and dent > 0.
+ *   a = (dqx*dtx + dqy*dty) / den;  b = (dqx*dty - dqy*dtx) / den
+ * The matrix is [a, -b, tx; b, a, ty] with
+ *   tx = t0x - (a*q0x - b*q0y);     ty = t0y - (b*q0x + a*q0y)
+ * (the negation is exact, and x - y is x + (-y): one formula serves both models).
+ *
+ * Model record.  Nine floats {m0, m1, m2, m3, m4, m5, 0, 0, 1}; the last row is
+ * exact and there is no unit-norm scaling.  A hypothesis is invalid when its
+ * sample is degenerate or one of m0..m5 is not finite; its row is then all zero
+ * (the 1 included) and its count 0.  There is no own-sample rule.
+ *
+ * Score.  Match (qx, qy, tx, ty) is an inlier of a valid hypothesis when
+ *   px = (m0*qx + m1*qy) + m2;  py = (m3*qx + m4*qy) + m5
+ *   dx = px - tx;  dy = py - ty
+ *   dx*dx + dy*dy <= max_error*max_error
+ * inclusive; a NaN is an inlier of nothing.  This is the homography's predicate
+ * on the same nine floats (its w is exactly 1 for every finite position), so
+ * the record is interchangeable with a homography record, and
+ * sift_hip_score_affine_device needs no model argument.
+ *
+ * Selection and output.  Word for word the other models': most inliers among the
+ * valid hypotheses, ties to the lowest k; with n < m or no valid hypothesis
+ * hypothesis = -1, inliers = 0, a zero model, an empty list and a zero mask,
+ * status success; the 52-byte record, the records in input order, their count,
+ * the cap-byte mask; no atomics, the same bytes in every run.
+ *
+ * Refit (sift_hip_refine_affine_*).  One round refits the model on the records
+ * the mask marks: the refit rule's fit set (step 1, with m >= 3 for the affine
+ * map and m >= 2 for the similarity), arithmetic (step 2) and summation order
+ * (step 3), then
+ *   pass 1: m and the means mqx, mqy, mtx, mty (each sum / m);
+ *   pass 2: with x = qx - mqx, y = qy - mqy, u = tx - mtx, v = ty - mty the seven
+ *     sums Sxx = sum x x, Sxy = sum x y, Syy = sum y y, Txx = sum u x,
+ *     Txy = sum u y, Tyx = sum v x, Tyy = sum v y;
+ *   affine: det = Sxx*Syy - Sxy*Sxy must be finite and > 0;
+ *     a = (Txx*Syy - Txy*Sxy) / det;  b = (Txy*Sxx - Txx*Sxy) / det
+ *     c = (Tyx*Syy - Tyy*Sxy) / det;  d = (Tyy*Sxx - Tyx*Sxy) / det
+ *   similarity: den = Sxx + Syy must be finite and > 0;
+ *     a = (Txx + Tyy) / den;  c = (Tyx - Txy) / den;  b = -c;  d = a
+ *   translation: tx = mtx - (a*mqx + b*mqy);  ty = mty - (c*mqx + d*mqy)
+ * rounded to float32 once, over the row 0 0 1; a non-finite entry is invalid.
+ * There is no normalisation and no Jacobi: the problem is linear and centred.
+ * The accept step is the refit rule's step 9 with the predicate above, `rounds`
+ * is 1..8, and a rejected round changes no byte. */
+#define SIFT_HIP_MODEL_AFFINE 0      /* 6 degrees of freedom, 3-point samples */
+#define SIFT_HIP_MODEL_SIMILARITY 1  /* 4 degrees of freedom, 2-point samples */
+
+/* The homography's record, reused: H holds {m0 .. m5, 0, 0, 1}, and
+ * valid_hypotheses counts the samples that were not degenerate. */
+typedef sift_hip_homography_result sift_hip_affine_result;
+
+/* The homography calls, argument for argument, with `model` behind the handle.
+ * The same arguments are refused, with nothing launched, and so is a model that
+ * is neither constant above; cap == 0 succeeds with the empty result. */
+int sift_hip_verify_affine_device(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches, const int* count,
+                                  int cap, const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                  int train_stride, int nt, const sift_hip_verify_params* params,
+                                  sift_hip_affine_result* result, sift_hip_dmatch* out, int* out_count, uint8_t* mask,
+                                  void* stream);
+int sift_hip_verify_affine_host(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches, const int* count,
+                                int cap, const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                int train_stride, int nt, const sift_hip_verify_params* params,
+                                sift_hip_affine_result* result_host, sift_hip_dmatch* out_host, uint8_t* mask_host);
+/* The score alone on the caller's K models (K x 9 floats, rows 0 0 1 last); the
+ * predicate is both models' own, so there is no model argument. */
+int sift_hip_score_affine_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                 const float* query_xy, int query_stride, int nq, const float* train_xy, int train_stride,
+                                 int nt, const float* A, int K, float max_error, int* counts, void* stream);
+/* samples (K x 3 for the affine map, K x 2 for the similarity), A (K x 9, zero
+ * rows: invalid hypotheses) and counts (K).  SIFT_HIP_ERR_STATE unless the
+ * verifier's last verify call was a single-pair call of this very model; the
+ * two getters above refuse after an affine call in the same way. */
+int sift_hip_verify_affine_hypotheses_host(sift_hip_verifier_t v, int model, int* samples, float* A, int* counts,
+                                           int cap);
+int sift_hip_verify_affine_batched_device(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches,
+                                          const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                          int train_stride, const sift_hip_verify_params* params,
+                                          sift_hip_affine_result* results, sift_hip_dmatch* out, int* out_counts,
+                                          uint8_t* mask, void* stream);
+int sift_hip_verify_affine_batched_host(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches,
+                                        const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                        int train_stride, const sift_hip_verify_params* params,
+                                        sift_hip_affine_result* results_host, sift_hip_dmatch* out_host,
+                                        uint8_t* mask_host);
+int sift_hip_refine_affine_device(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches, const int* count,
+                                  int cap, const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                  int train_stride, int nt, float max_error, int rounds, sift_hip_affine_result* result,
+                                  uint8_t* mask, sift_hip_dmatch* out, int* out_count, int* accepted, void* stream);
+int sift_hip_refine_affine_host(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches, const int* count,
+                                int cap, const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                int train_stride, int nt, float max_error, int rounds,
+                                sift_hip_affine_result* result_host, uint8_t* mask_host, sift_hip_dmatch* out_host,
+                                int* out_count_host, int* accepted_host);
+int sift_hip_refine_affine_batched_device(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches,
+                                          const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                          int train_stride, float max_error, int rounds, sift_hip_affine_result* results,
+                                          uint8_t* mask, sift_hip_dmatch* out, int* out_counts, int* accepted,
+                                          void* stream);
+int sift_hip_refine_affine_batched_host(sift_hip_verifier_t v, int model, const sift_hip_dmatch* matches,
+                                        const int* counts, int P, const sift_hip_verify_pair* pairs, int query_stride,
+                                        int train_stride, float max_error, int rounds,
+                                        sift_hip_affine_result* results_host, uint8_t* mask_host,
+                                        sift_hip_dmatch* out_host, int* out_counts_host, int* accepted_host);
+
 /* --- Relative pose from a verified fundamental matrix ---------------------------
  *
  * What a calibrated caller does with a verified F (cv::recoverPose, ORB-SLAM's
