@@ -23,7 +23,7 @@ CXXFLAGS := -O2 -std=c++17 -fPIC -Iinclude -Wall -Wextra
 HIP_SRCS := $(SRC)/detector.hip $(SRC)/lanes.hip $(SRC)/datagen.hip $(SRC)/matcher_api.hip $(SRC)/keypoints.hip $(SRC)/descriptor.hip \
             $(SRC)/upsample.hip $(SRC)/blur.hip $(SRC)/blur_tail.hip $(SRC)/extrema.hip \
             $(SRC)/match.hip $(SRC)/match_select.hip $(SRC)/match_knn.hip \
-            $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/refit.hip $(SRC)/pose.hip $(SRC)/pose_homography.hip $(SRC)/verify_api.hip $(SRC)/rootsift.hip
+            $(SRC)/multi.hip $(SRC)/verify.hip $(SRC)/essential.hip $(SRC)/refit.hip $(SRC)/pose.hip $(SRC)/pose_homography.hip $(SRC)/verify_api.hip $(SRC)/rootsift.hip
 HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OUT)/obj/%.o,$(HIP_SRCS)) $(OUT)/obj/synth_frame.o
 
 all: $(OUT)/libsift_hip.so $(OUT)/libsift_cuda.so tools
@@ -70,7 +70,7 @@ oracle:
 ASAN_DIR  := $(OUT)/asan
 SANFLAGS  := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined
 
-asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_affine_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_pose_args $(ASAN_DIR)/test_pose_homography_args $(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args
+asan: $(ASAN_DIR)/test_multi $(ASAN_DIR)/test_verify_args $(ASAN_DIR)/test_homography_args $(ASAN_DIR)/test_affine_args $(ASAN_DIR)/test_essential_args $(ASAN_DIR)/test_verify_batched_args $(ASAN_DIR)/test_refit_args $(ASAN_DIR)/test_pose_args $(ASAN_DIR)/test_pose_homography_args $(ASAN_DIR)/test_match_knn_args $(ASAN_DIR)/test_match_knn_gated_args
 	$(MAKE) -C oracle asan
 
 $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
@@ -81,8 +81,8 @@ $(ASAN_DIR)/test_multi: tests/cpp/test_multi.cpp $(CXX_SRCS) $(wildcard include/
 # Argument validation of the verifier's C++ surface (verify_cxx.cpp), CPU only: test_verify_args (run by
 # tests/test_verify_asan.py), test_homography_args for the homography calls and the projection, test_verify_batched_args
 # for the batched calls, test_refit_args for the refit calls, test_pose_args for the pose calls,
-# test_pose_homography_args for the plane pose calls and test_affine_args for the affine and similarity calls, each
-# with its tests/test_*_asan.py.
+# test_pose_homography_args for the plane pose calls, test_affine_args for the affine and similarity calls and
+# test_essential_args for the essential calls, each with its tests/test_*_asan.py.
 $(ASAN_DIR)/test_%_args: tests/cpp/test_%_args.cpp $(SRC)/verify_cxx.cpp $(wildcard include/sift_cuda/*.hh) include/sift_hip.h $(OUT)/libsift_hip.so
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) -std=c++17 -Iinclude -Wall -Wextra $(SANFLAGS) -pthread -o $@ $< $(SRC)/verify_cxx.cpp \

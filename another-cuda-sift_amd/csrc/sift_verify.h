@@ -72,12 +72,21 @@ void launch_verify_gather(const List& list, float4* pts, hipStream_t s);
 // predicate the score and select kernels are instantiated with.
 // Affine (6 degrees of freedom, 3-point samples) and Similarity (4, 2-point samples) store their 2 x 3 matrix as
 // the 3 x 3 {m0 .. m5, 0, 0, 1} in the homography's record and share one predicate (AffinePass).
-enum class VerifyModel { Fundamental = 1, Homography = 2, Affine = 3, Similarity = 4 };
+// Essential (essential.hip): 5-point samples under two cameras, ten model slots per sample, each a pixel-space
+// fundamental matrix -- the score and the select then run over 10 K slots with the fundamental matrix's predicate.
+enum class VerifyModel { Fundamental = 1, Homography = 2, Affine = 3, Similarity = 4, Essential = 5 };
 constexpr bool is_affine(VerifyModel m) { return m == VerifyModel::Affine || m == VerifyModel::Similarity; }
 // The matches a hypothesis of the model draws: the stride of its rows in the samples scratch.
 constexpr int sample_size(VerifyModel m) {
-    return m == VerifyModel::Fundamental ? 8 : m == VerifyModel::Homography ? 4 : m == VerifyModel::Affine ? 3 : 2;
+    return m == VerifyModel::Fundamental  ? 8
+           : m == VerifyModel::Homography ? 4
+           : m == VerifyModel::Affine     ? 3
+           : m == VerifyModel::Essential  ? 5
+                                          : 2;
 }
+// The model slots a sample owns: the rows of the model, valid and count scratch per sample.
+constexpr int kEssentialSlots = 10;
+constexpr int model_slots(VerifyModel m) { return m == VerifyModel::Essential ? kEssentialSlots : 1; }
 
 // k_verify_hypotheses / k_verify_hypotheses_h / k_verify_hypotheses_a: hypothesis k in [0, K) draws its
 // m matches (m = 8 for the fundamental matrix, 4 for the homography, 3 for the affine map, 2 for the similarity;
@@ -103,6 +112,17 @@ template <class List>
 void launch_verify_select(VerifyModel model, const List& list, const float4* pts, const float* F, const int* valid,
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s);
+
+// k_verify_hypotheses_e (essential.hip): sample k in [0, K) draws 5 matches (samples[5 k ..], -1 when n < 5), turns
+// them into calibrated rays under the pair's two cameras and solves the 5-point problem: up to ten real roots, root r
+// in ascending order in slot 10 k + r as the pixel-space F = Kt^-T E Kq^-1 of unit norm (F[9 (10 k + r) ..]) with
+// valid[10 k + r]; every other slot is zero and invalid.  A batch: pair p's samples at 5 K p, its slots at 10 K p,
+// and its cameras go through cam_scratch (2 kVerifyMaxPairs records, device; a single call does not touch it).
+struct PoseCameras;
+struct PoseCamera;
+template <class List>
+void launch_verify_hypotheses_e(const List& list, const float4* pts, int K, unsigned seed, const PoseCameras& cams,
+                                PoseCamera* cam_scratch, int* samples, float* F, int* valid, hipStream_t s);
 
 // The refit of a verified model on its inliers (refit.hip; sift_hip_refine_*, the rule is in include/sift_hip.h).
 // One round is two launches, both with one workgroup per pair:

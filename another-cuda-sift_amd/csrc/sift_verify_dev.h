@@ -1,5 +1,6 @@
-// Device-side pieces the verifier's kernels share (verify.hip, refit.hip): how a kernel finds its list -- the call's
-// own, or pair blockIdx.y's of a batch -- and the models' predicates.  Included by .hip files only.
+// Device-side pieces the verifier's kernels share (verify.hip, essential.hip, refit.hip): how a kernel finds its list
+// -- the call's own, or pair blockIdx.y's of a batch --, the counter-based sampler and the models' predicates.  Included
+// by .hip files only.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -18,6 +19,41 @@ __device__ __forceinline__ int verify_n(const int* count, int cap) {
 }
 
 __device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < INFINITY; }
+
+// lowbias32 (the header writes it out).
+__device__ __forceinline__ unsigned mix32(unsigned h) {
+    h ^= h >> 16;
+    h *= 0x7feb352du;
+    h ^= h >> 15;
+    h *= 0x846ca68bu;
+    h ^= h >> 16;
+    return h;
+}
+
+// The draw of hypothesis k: M distinct indices of [0, n), n >= M, a function of (seed, k, n).
+template <int M>
+__device__ __forceinline__ void draw(unsigned seed, int k, int n, int (&pick)[M]) {
+    const unsigned base = mix32(seed ^ mix32((unsigned)k));
+    int sorted[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+        const unsigned h = mix32(base + 0x9e3779b9u * (unsigned)(j + 1));
+        int r = (int)(((unsigned long long)h * (unsigned long long)(unsigned)(n - j)) >> 32);
+#pragma unroll
+        for (int i = 0; i < j; i++)
+            if (r >= sorted[i]) r++;
+        pick[j] = r;
+        int v = r;
+#pragma unroll
+        for (int i = 0; i < j; i++)
+            if (sorted[i] > v) {
+                const int t = sorted[i];
+                sorted[i] = v;
+                v = t;
+            }
+        sorted[j] = v;
+    }
+}
 
 // The list a workgroup works on: the call's own, or pair blockIdx.y's rows of the batch's match buffer, its counter
 // and its positions.

@@ -33,7 +33,9 @@
 //  k_verify_select        one 1024-thread workgroup: argmax with the tie rule,
 //                         the winner rescored into the mask, and the ordered
 //                         compaction of k_match_select (prefix sums, no atomics:
-//                         the same bytes in every run).  The same template.
+//                         the same bytes in every run).  The same template; its key
+//                         width is a parameter (the essential matrix's 10 K slots
+//                         need 16 bits of index: a 64-bit key).
 //  k_project_homography   one thread per position row.
 // The four verify kernels are templates over the list they take.  VerifyInput:
 // the single-pair call's list.  VerifyBatch (sift_hip_verify_*_batched_*): all P
@@ -46,6 +48,8 @@
 #include <float.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "sift_epipolar.h"
 #include "sift_verify.h"
 #include "sift_verify_dev.h"
@@ -53,41 +57,6 @@
 namespace sift_amd {
 
 namespace {
-
-// lowbias32 (the header writes it out).
-__device__ __forceinline__ unsigned mix32(unsigned h) {
-    h ^= h >> 16;
-    h *= 0x7feb352du;
-    h ^= h >> 15;
-    h *= 0x846ca68bu;
-    h ^= h >> 16;
-    return h;
-}
-
-// The draw of hypothesis k: M distinct indices of [0, n), n >= M, a function of (seed, k, n).
-template <int M>
-__device__ __forceinline__ void draw(unsigned seed, int k, int n, int (&pick)[M]) {
-    const unsigned base = mix32(seed ^ mix32((unsigned)k));
-    int sorted[M];
-#pragma unroll
-    for (int j = 0; j < M; j++) {
-        const unsigned h = mix32(base + 0x9e3779b9u * (unsigned)(j + 1));
-        int r = (int)(((unsigned long long)h * (unsigned long long)(unsigned)(n - j)) >> 32);
-#pragma unroll
-        for (int i = 0; i < j; i++)
-            if (r >= sorted[i]) r++;
-        pick[j] = r;
-        int v = r;
-#pragma unroll
-        for (int i = 0; i < j; i++)
-            if (sorted[i] > v) {
-                const int t = sorted[i];
-                sorted[i] = v;
-                v = t;
-            }
-        sorted[j] = v;
-    }
-}
 
 // Hartley normalisation of one side of a sample of M points: x, y become the
 // normalised coordinates, (s, ox, oy) the similarity x' = s x + ox, (mx, my) the
@@ -519,8 +488,11 @@ __global__ __launch_bounds__(64 * kScoreWaves) void k_verify_score(List list, co
 
 constexpr int kVSelThreads = 1024, kVSelWaves = kVSelThreads / 64;
 
+// kSlotBits is the width of the hypothesis index in the argmax key: 12 for the models with one slot per sample
+// (K <= 4096, an int key, the code as it was before the parameter), 16 for the essential matrix's ten slots per sample
+// (10 K <= 40960, a 64-bit key).
 // A batch: one workgroup per pair, result and out_count its entries, out and mask (each nullable) its rows.
-template <class Pass, class List>
+template <class Pass, class List, int kSlotBits = 12>
 __global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const float4* __restrict__ pts,
                                                                 const float* __restrict__ F,
                                                                 const int* __restrict__ valid,
@@ -528,7 +500,10 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const
                                                                 VerifyResult* __restrict__ result,
                                                                 MatchRecord* __restrict__ out, int* __restrict__ out_count,
                                                                 uint8_t* __restrict__ mask) {
-    __shared__ int s_key[kVSelWaves], s_nv[kVSelWaves], s_wave[kVSelWaves];
+    using Key = std::conditional_t<(kSlotBits > 12), long long, int>;
+    constexpr int kSlots = 1 << kSlotBits;
+    __shared__ Key s_key[kVSelWaves];
+    __shared__ int s_nv[kVSelWaves], s_wave[kVSelWaves];
     if constexpr (kBatched<List>) {
         const int p = pair_of(list), row0 = row0_of(list);
         const size_t k0 = (size_t)K * p;
@@ -541,12 +516,13 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const
     const int n = verify_n(in.count, in.cap);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // The winner: most inliers among the valid hypotheses, ties to the lowest k, as the largest key
-    // count * 4096 + (4095 - k) (count <= 65536, k < 4096); -1: none.
-    int key = -1, nv = 0;
+    // count * 4096 + (4095 - k) (count <= 65536, k < 4096; 65536 and 65535 - k for the wide key); -1: none.
+    Key key = -1;
+    int nv = 0;
     for (int k = tid; k < K; k += kVSelThreads)
         if (valid[k]) {
             nv++;
-            key = max(key, counts[k] * 4096 + (4095 - k));
+            key = max(key, (Key)counts[k] * kSlots + (kSlots - 1 - k));
         }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -561,7 +537,7 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const
         key = max(key, s_key[i]);
         nv += s_nv[i];
     }
-    const int hyp = key < 0 ? -1 : 4095 - (key & 4095);
+    const int hyp = key < 0 ? -1 : kSlots - 1 - (int)(key & (kSlots - 1));
     float f[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) f[i] = hyp < 0 ? 0.f : F[9 * (size_t)hyp + i];
@@ -569,7 +545,7 @@ __global__ __launch_bounds__(kVSelThreads) void k_verify_select(List list, const
         VerifyResult r;
 #pragma unroll
         for (int i = 0; i < 9; i++) r.F[i] = f[i];
-        r.inliers = key < 0 ? 0 : key >> 12;
+        r.inliers = key < 0 ? 0 : (int)(key >> kSlotBits);
         r.hypothesis = hyp;
         r.matches = n;
         r.valid_hypotheses = nv;
@@ -681,7 +657,10 @@ void launch_verify_select(VerifyModel model, const List& list, const float4* pts
                           const int* counts, int K, float e2, VerifyResult* result, MatchRecord* out, int* out_count,
                           uint8_t* mask, hipStream_t s) {
     const dim3 grid(1, list_pairs(list)), block(kVSelThreads);
-    if (model == VerifyModel::Homography)
+    if (model == VerifyModel::Essential)
+        hipLaunchKernelGGL((k_verify_select<SampsonPass, List, 16>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
+                           result, out, out_count, mask);
+    else if (model == VerifyModel::Homography)
         hipLaunchKernelGGL((k_verify_select<TransferPass, List>), grid, block, 0, s, list, pts, F, valid, counts, K, e2,
                            result, out, out_count, mask);
     else if (is_affine(model))

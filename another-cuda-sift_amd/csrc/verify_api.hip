@@ -34,6 +34,14 @@ struct sift_hip_verifier {
     PlaneCandidates* dPlaneCand = nullptr;  // the plane pose calls' candidates per pair (sift_hip_recover_pose_homography_*)
     PlanePoseResult* dPlanePose = nullptr;  // their host forms: maxP pose records and 4 x maxP candidates
     PlaneCandidate* dPlaneOut = nullptr;
+    // The essential calls' hypothesis scratch (sift_hip_verifier_reserve_essential): maxP x essK samples of 5 indices
+    // and ten model slots each.  essK = 0: not reserved.
+    int essK = 0;
+    int* dEssSamples = nullptr;
+    float* dEssF = nullptr;
+    int* dEssValid = nullptr;
+    int* dEssCounts = nullptr;
+    PoseCamera* dEssCams = nullptr;  // a batch's cameras on their way to the hypothesis kernel
     int lastK = 0;               // hypotheses of the last verify call (sift_hip_verify_*hypotheses_host)
     int lastModel = 0;           // its VerifyModel, 0: none
     bool lastBatch = false;      // it was a batched call (the getters read one pair's scratch layout)
@@ -41,7 +49,8 @@ struct sift_hip_verifier {
         (void)hipSetDevice(device);
         for (void* p : {(void*)dPts, (void*)dSamples, (void*)dF, (void*)dValid, (void*)dCounts, (void*)dResult,
                         (void*)dOut, (void*)dMask, (void*)dCand, (void*)dRefineInts, (void*)dPoseCand, (void*)dPose,
-                        (void*)dPoints, (void*)dPlaneCand, (void*)dPlanePose, (void*)dPlaneOut})
+                        (void*)dPoints, (void*)dPlaneCand, (void*)dPlanePose, (void*)dPlaneOut, (void*)dEssSamples,
+                        (void*)dEssF, (void*)dEssValid, (void*)dEssCounts, (void*)dEssCams})
             if (p) (void)hipFree(p);
     }
 };
@@ -88,7 +97,8 @@ struct Call {
     const float* models;  // score: the K models to count under, and their counts
     int* scores;
     const sift_hip_camera* cams_q;  // pose: P cameras per side (host memory), the thresholds, the P pose records and
-    const sift_hip_camera* cams_t;  // the optional mask and points; `result` and `mask` are the inputs
+    const sift_hip_camera* cams_t;  // the optional mask and points; `result` and `mask` are the inputs.  An essential
+                                    // verify call carries the cameras too.
     const sift_hip_pose_params* pose_params;
     void* pose;
     uint8_t* mask_out;
@@ -110,6 +120,7 @@ Call make_call(Op op, VerifyModel model, bool host, const sift_hip_dmatch* match
 int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
     const auto refuse = [](const std::string& msg) { return fail(SIFT_HIP_ERR_INVALID, msg); };
     const bool refine = c.op == Op::Refine, pose = c.op == Op::Pose;
+    const bool essential = c.op == Op::Verify && c.model == VerifyModel::Essential;
     if (!v) return refuse("null verifier");
     if ((int)c.model == 0) return refuse("verify: model must be SIFT_HIP_MODEL_AFFINE or SIFT_HIP_MODEL_SIMILARITY");
     if (!c.pairs) return refuse("verify: null pairs");
@@ -136,15 +147,19 @@ int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
         max_cap = std::max(max_cap, e.cap);
     }
     if (rows > 0 && !c.matches) return refuse("verify: null matches");
-    if (pose) {  // the pose calls' own rules stand where max_error stands for the others
-        if (!c.cams_q || !c.cams_t) return refuse("pose: null camera pointer");
+    if (pose || essential) {  // the cameras' rules, the pose calls' and the essential calls' alike
+        const std::string who = pose ? "pose" : "verify";
+        if (!c.cams_q || !c.cams_t) return refuse(who + ": null camera pointer");
         for (int p = 0; p < c.P; p++)
             for (const sift_hip_camera* k : {c.cams_q + p, c.cams_t + p}) {
                 const auto at = [&] { return c.single ? std::string() : " (pair " + std::to_string(p) + ")"; };
                 if (!(k->fx > 0.f) || !(k->fy > 0.f) || !std::isfinite(k->fx) || !std::isfinite(k->fy))
-                    return refuse("pose: fx and fy must be > 0 and finite" + at());
-                if (!std::isfinite(k->cx) || !std::isfinite(k->cy)) return refuse("pose: cx and cy must be finite" + at());
+                    return refuse(who + ": fx and fy must be > 0 and finite" + at());
+                if (!std::isfinite(k->cx) || !std::isfinite(k->cy))
+                    return refuse(who + ": cx and cy must be finite" + at());
             }
+    }
+    if (pose) {  // the pose calls' own rules stand where max_error stands for the others
         if (!c.pose_params || !c.result || !c.pose) return refuse("pose: null params or result");
         if (!(c.pose_params->max_depth > 0.f)) return refuse("pose: max_depth must be > 0");
         if (!(c.pose_params->max_cos_parallax >= -1.f && c.pose_params->max_cos_parallax <= 1.f))
@@ -159,11 +174,17 @@ int check(const sift_hip_verifier* v, const Call& c, VerifyBatch& b) {
     if (refine && (c.rounds < 1 || c.rounds > kRefineMaxRounds))
         return refuse("refine: rounds must lie in 1.." + std::to_string(kRefineMaxRounds));
     const int K = pose ? 1 : c.params->hypotheses;  // a pose call draws nothing
-    if (K < 1 || K > kVerifyMaxHypotheses || K > v->maxK) return refuse("verify: hypotheses outside 1..max_hypotheses");
+    if (K < 1 || K > kVerifyMaxHypotheses || (!essential && K > v->maxK))
+        return refuse("verify: hypotheses outside 1..max_hypotheses");
     if (c.P > v->maxP) return refuse("verify: more pairs than the verifier's max_pairs");
     if (rows > v->maxM)
         return refuse(c.single ? "verify: cap exceeds the verifier's max_matches"
                                : "verify: the caps' sum exceeds the verifier's max_matches");
+    // An essential call draws its samples into the scratch of sift_hip_verifier_reserve_essential: a matter of the
+    // handle's state, judged when the arguments themselves are in order.
+    if (essential && v->essK == 0)
+        return fail(SIFT_HIP_ERR_STATE, "verify: no essential scratch (sift_hip_verifier_reserve_essential)");
+    if (essential && K > v->essK) return fail(SIFT_HIP_ERR_STATE, "verify: hypotheses above the essential reservation");
     if (!c.single) std::fill(b.pair + c.P, b.pair + kVerifyMaxPairs, VerifyBatchPair{});  // the table goes by value
     b.matches = reinterpret_cast<const MatchRecord*>(c.matches);
     b.counts = c.counts;
@@ -187,17 +208,37 @@ struct Outputs {
     PlaneCandidate* candidates = nullptr;  // the homography's four per pair
 };
 
+// The cameras of a pose or an essential call as the kernels take them, by value.
+PoseCameras cameras_of(const Call& c) {
+    PoseCameras cams{};
+    for (int p = 0; p < c.P; p++) {
+        cams.q[p] = PoseCamera{c.cams_q[p].fx, c.cams_q[p].fy, c.cams_q[p].cx, c.cams_q[p].cy};
+        cams.t[p] = PoseCamera{c.cams_t[p].fx, c.cams_t[p].fy, c.cams_t[p].cx, c.cams_t[p].cy};
+    }
+    return cams;
+}
+
 // The runners, one per operation, over the list type (VerifyInput or VerifyBatch): one launch per step for all the
-// list's pairs.  Every index stays inside the handle's scratch: rows <= maxM, P <= maxP and K <= maxK were checked.
+// list's pairs.  Every index stays inside the handle's scratch: rows <= maxM, P <= maxP and K <= maxK (an essential
+// call: K <= essK, in its own scratch) were checked.
 template <class List>
 int verify_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
     const int K = c.params->hypotheses;
     const float e2 = c.params->max_error * c.params->max_error;
     launch_verify_gather(list, v->dPts, o.stream);
-    launch_verify_hypotheses(c.model, list, v->dPts, K, c.params->seed, e2, v->dSamples, v->dF, v->dValid, o.stream);
-    launch_verify_score(c.model, list, v->dPts, v->dF, v->dValid, K, e2, v->dCounts, o.stream);
-    launch_verify_select(c.model, list, v->dPts, v->dF, v->dValid, v->dCounts, K, e2, o.result, o.out, o.out_counts,
-                         o.mask, o.stream);
+    if (c.model == VerifyModel::Essential) {  // K samples; their 10 K model slots are scored and selected as F
+        const int S = kEssentialSlots * K;
+        launch_verify_hypotheses_e(list, v->dPts, K, c.params->seed, cameras_of(c), v->dEssCams, v->dEssSamples,
+                                   v->dEssF, v->dEssValid, o.stream);
+        launch_verify_score(c.model, list, v->dPts, v->dEssF, v->dEssValid, S, e2, v->dEssCounts, o.stream);
+        launch_verify_select(c.model, list, v->dPts, v->dEssF, v->dEssValid, v->dEssCounts, S, e2, o.result, o.out,
+                             o.out_counts, o.mask, o.stream);
+    } else {
+        launch_verify_hypotheses(c.model, list, v->dPts, K, c.params->seed, e2, v->dSamples, v->dF, v->dValid, o.stream);
+        launch_verify_score(c.model, list, v->dPts, v->dF, v->dValid, K, e2, v->dCounts, o.stream);
+        launch_verify_select(c.model, list, v->dPts, v->dF, v->dValid, v->dCounts, K, e2, o.result, o.out, o.out_counts,
+                             o.mask, o.stream);
+    }
     HIPCHK(hipGetLastError());
     v->lastK = K;
     v->lastModel = (int)c.model;
@@ -234,11 +275,7 @@ int refine_on(sift_hip_verifier* v, const Call& c, const List& list, const Outpu
 // cameras travel by value; the verifier's hypothesis scratch is not touched.
 template <class List>
 int pose_on(sift_hip_verifier* v, const Call& c, const List& list, const Outputs& o) {
-    PoseCameras cams{};
-    for (int p = 0; p < c.P; p++) {
-        cams.q[p] = PoseCamera{c.cams_q[p].fx, c.cams_q[p].fy, c.cams_q[p].cx, c.cams_q[p].cy};
-        cams.t[p] = PoseCamera{c.cams_t[p].fx, c.cams_t[p].fy, c.cams_t[p].cx, c.cams_t[p].cy};
-    }
+    const PoseCameras cams = cameras_of(c);
     launch_verify_gather(list, v->dPts, o.stream);
     if (c.model == VerifyModel::Homography) {
         launch_plane_decompose(cams, c.P, o.result, v->dPlaneCand, o.candidates, o.stream);
@@ -364,13 +401,15 @@ int hypotheses_host(sift_hip_verifier* v, VerifyModel model, int m, int* samples
     if (v->lastBatch) return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was a batch");
     if (v->lastModel != (int)model)
         return fail(SIFT_HIP_ERR_STATE, "the verifier's last verify call was of the other model");  // or of another
-    const size_t K = (size_t)std::min(cap, v->lastK);
+    const size_t K = (size_t)std::min(cap, v->lastK), S = K * (size_t)model_slots(model);  // samples, model slots
     if (K == 0) return SIFT_HIP_OK;
+    const bool ess = model == VerifyModel::Essential;
     HIPCHK(hipSetDevice(v->device));
     HIPCHK(hipDeviceSynchronize());
-    if (samples) HIPCHK(hipMemcpy(samples, v->dSamples, sizeof(int) * (size_t)m * K, hipMemcpyDeviceToHost));
-    if (M) HIPCHK(hipMemcpy(M, v->dF, sizeof(float) * 9 * K, hipMemcpyDeviceToHost));
-    if (counts) HIPCHK(hipMemcpy(counts, v->dCounts, sizeof(int) * K, hipMemcpyDeviceToHost));
+    if (samples)
+        HIPCHK(hipMemcpy(samples, ess ? v->dEssSamples : v->dSamples, sizeof(int) * (size_t)m * K, hipMemcpyDeviceToHost));
+    if (M) HIPCHK(hipMemcpy(M, ess ? v->dEssF : v->dF, sizeof(float) * 9 * S, hipMemcpyDeviceToHost));
+    if (counts) HIPCHK(hipMemcpy(counts, ess ? v->dEssCounts : v->dCounts, sizeof(int) * S, hipMemcpyDeviceToHost));
     return SIFT_HIP_OK;
 }
 
@@ -449,6 +488,29 @@ int sift_hip_verifier_create_batched(int device, int max_matches, int max_hypoth
         return fail(SIFT_HIP_ERR_NOMEM, "verifier allocation failed");
     }
     *out = v;
+    return SIFT_HIP_OK;
+}
+
+int sift_hip_verifier_reserve_essential(sift_hip_verifier_t v, int max_samples) {
+    if (!v) return fail(SIFT_HIP_ERR_INVALID, "null verifier");
+    if (max_samples < 1 || max_samples > kVerifyMaxHypotheses)
+        return fail(SIFT_HIP_ERR_INVALID, "reserve: max_samples outside 1.." + std::to_string(kVerifyMaxHypotheses));
+    if (v->essK != 0) return fail(SIFT_HIP_ERR_STATE, "reserve: the verifier has its essential scratch");
+    const size_t K = (size_t)max_samples * (size_t)v->maxP, S = K * kEssentialSlots;
+    if (hipSetDevice(v->device) != hipSuccess || hipMalloc((void**)&v->dEssSamples, sizeof(int) * 5 * K) != hipSuccess ||
+        hipMalloc((void**)&v->dEssF, sizeof(float) * 9 * S) != hipSuccess ||
+        hipMalloc((void**)&v->dEssValid, sizeof(int) * S) != hipSuccess ||
+        hipMalloc((void**)&v->dEssCounts, sizeof(int) * S) != hipSuccess ||
+        hipMalloc((void**)&v->dEssCams, sizeof(PoseCamera) * 2 * kVerifyMaxPairs) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        for (void** p : {(void**)&v->dEssSamples, (void**)&v->dEssF, (void**)&v->dEssValid, (void**)&v->dEssCounts,
+                         (void**)&v->dEssCams}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return fail(SIFT_HIP_ERR_NOMEM, "essential scratch allocation failed");
+    }
+    v->essK = max_samples;
     return SIFT_HIP_OK;
 }
 
@@ -569,6 +631,34 @@ SIFT_POSE_ENTRIES(_homography_batched, VerifyModel::Homography, sift_hip_homogra
 #undef SIFT_CAND_ARG
 #undef SIFT_NO_CAND
 #undef SIFT_POSE_ENTRIES
+
+// The four essential entry points: {one pair, batch} x {device, host}.  The verify calls' arguments with the cameras in
+// front of the params.
+#define SIFT_ESSENTIAL_ENTRIES(name, LIST_ARGS, LIST)                                                                   \
+    int sift_hip_verify_essential##name##_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,      \
+                                                 const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,    \
+                                                 const sift_hip_verify_params* params, sift_hip_verify_result* result,  \
+                                                 sift_hip_dmatch* out, int* out_count, uint8_t* mask, void* stream) {   \
+        Call c = make_call(Op::Verify, VerifyModel::Essential, false, matches, query_stride, train_stride);             \
+        LIST(c);                                                                                                        \
+        c.cams_q = cam_query, c.cams_t = cam_train;                                                                     \
+        c.params = params, c.result = result, c.out = out, c.out_counts = out_count, c.mask = mask, c.stream = stream;  \
+        return run(v, c);                                                                                               \
+    }                                                                                                                   \
+    int sift_hip_verify_essential##name##_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, LIST_ARGS,        \
+                                               const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,      \
+                                               const sift_hip_verify_params* params,                                    \
+                                               sift_hip_verify_result* result_host, sift_hip_dmatch* out_host,          \
+                                               uint8_t* mask_host) {                                                    \
+        Call c = make_call(Op::Verify, VerifyModel::Essential, true, matches, query_stride, train_stride);              \
+        LIST(c);                                                                                                        \
+        c.cams_q = cam_query, c.cams_t = cam_train;                                                                     \
+        c.params = params, c.result = result_host, c.out = out_host, c.mask = mask_host;                                \
+        return run(v, c);                                                                                               \
+    }
+SIFT_ESSENTIAL_ENTRIES(, SIFT_ONE_PAIR, SIFT_ONE_PAIR_LIST)
+SIFT_ESSENTIAL_ENTRIES(_batched, SIFT_BATCH, SIFT_BATCH_LIST)
+#undef SIFT_ESSENTIAL_ENTRIES
 #undef SIFT_BATCH_LIST
 #undef SIFT_BATCH
 
@@ -616,6 +706,11 @@ int sift_hip_verify_affine_hypotheses_host(sift_hip_verifier_t v, int model, int
     if (v && (int)m == 0)
         return fail(SIFT_HIP_ERR_INVALID, "verify: model must be SIFT_HIP_MODEL_AFFINE or SIFT_HIP_MODEL_SIMILARITY");
     return hypotheses_host(v, m, sample_size(m), samples, A, counts, cap);
+}
+
+// samples: cap x 5, F: 10 cap x 9, counts: 10 cap.
+int sift_hip_verify_essential_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap) {
+    return hypotheses_host(v, VerifyModel::Essential, 5, samples, F, counts, cap);
 }
 
 int sift_hip_project_homography_device(const float* H, const float* xy, int stride, int n, float* out_xy, int out_stride,

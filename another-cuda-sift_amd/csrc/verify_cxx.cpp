@@ -469,6 +469,65 @@ std::vector<int> Verifier::refineAffineBatchedHost(BATCH_ARGS, AffineModel model
     });
 }
 
+// The essential methods: the fundamental model's record and geometry, the cameras in front of the params.
+void Verifier::reserveEssential(int max_samples) {
+    check_throw(sift_hip_verifier_reserve_essential(m_handle, max_samples), "Verifier::reserveEssential");
+}
+
+void Verifier::verifyEssentialDevice(ONE_PAIR_ARGS, const Camera& cam_query, const Camera& cam_train,
+                                     const VerifyParams& params, VerifyResult* result, DMatch* out, int* out_count,
+                                     uint8_t* mask, void* stream) {
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(abiCall(sift_hip_verify_essential_device, m_handle, ONE_PAIR, abi(&cam_query), abi(&cam_train), &p,
+                        abi<Fundamental>(result), abi(out), out_count, mask, stream),
+                "Verifier::verifyEssentialDevice");
+}
+
+void Verifier::verifyEssentialBatchedDevice(BATCH_ARGS, const std::vector<Camera>& cams_query,
+                                            const std::vector<Camera>& cams_train, const VerifyParams& params,
+                                            VerifyResult* results, DMatch* out, int* out_counts, uint8_t* mask,
+                                            void* stream) {
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument("Verifier::verifyEssentialBatchedDevice: one camera per pair and side");
+    const sift_hip_verify_params p = toAbi(params);
+    check_throw(abiCall(sift_hip_verify_essential_batched_device, m_handle, BATCH, abi(cams_query.data()),
+                        abi(cams_train.data()), &p, abi<Fundamental>(results), abi(out), out_counts, mask, stream),
+                "Verifier::verifyEssentialBatchedDevice");
+}
+
+TwoViewGeometry Verifier::verifyEssentialHost(ONE_PAIR_ARGS, const Camera& cam_query, const Camera& cam_train,
+                                              const VerifyParams& params) {
+    const sift_hip_verify_params p = toAbi(params);
+    sift_hip_verify_result r{};
+    std::vector<DMatch> list(cap > 0 ? (size_t)cap : 0);
+    check_throw(abiCall(sift_hip_verify_essential_host, m_handle, ONE_PAIR, abi(&cam_query), abi(&cam_train), &p, &r,
+                        abi(list.data()), nullptr),
+                "Verifier::verifyEssentialHost");
+    list.resize((size_t)r.inliers);
+    return geometry<Fundamental>(r, std::move(list));
+}
+
+std::vector<TwoViewGeometry> Verifier::verifyEssentialBatchedHost(BATCH_ARGS, const std::vector<Camera>& cams_query,
+                                                                  const std::vector<Camera>& cams_train,
+                                                                  const VerifyParams& params) {
+    const char* what = "Verifier::verifyEssentialBatchedHost";
+    if (cams_query.size() != pairs.size() || cams_train.size() != pairs.size())
+        throw std::invalid_argument(std::string(what) + ": one camera per pair and side");
+    const sift_hip_verify_params p = toAbi(params);
+    std::vector<sift_hip_verify_result> r(pairs.size());
+    std::vector<DMatch> list(batchRows(pairs));
+    check_throw(abiCall(sift_hip_verify_essential_batched_host, m_handle, BATCH, abi(cams_query.data()),
+                        abi(cams_train.data()), &p, r.data(), abi(list.data()), nullptr),
+                what);
+    std::vector<TwoViewGeometry> out(pairs.size());
+    size_t row0 = 0;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        out[i] = geometry<Fundamental>(r[i], {list.begin() + row0, list.begin() + row0 + (size_t)r[i].inliers});
+        row0 += (size_t)pairs[i].cap;
+    }
+    return out;
+}
+
 void Verifier::recoverPoseDevice(ONE_PAIR_ARGS, const VerifyResult* result, const uint8_t* mask, const Camera& cam_query,
                                  const Camera& cam_train, const PoseParams& params, PoseResult* pose, uint8_t* mask_out,
                                  float* points, DMatch* out, int* out_count, void* stream) {
@@ -627,6 +686,31 @@ RelativePose recoverPose(const std::vector<DMatch>& matches, const float* query_
     return v.recoverPoseHost(static_cast<const DMatch*>(d.p), nullptr, n, query_xy, query_stride, nq, train_xy, train_stride,
                              nt, r, mask.empty() ? std::vector<uint8_t>(matches.size(), 1) : mask, cam_query, cam_train,
                              params);
+}
+
+TwoViewGeometry verifyEssential(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const Camera& cam_query, const Camera& cam_train, const VerifyParams& params,
+                                int query_stride, int train_stride, int refit) {
+    const char* what = "verifyEssential";
+    const int n = (int)matches.size();
+    Verifier v(n > 0 ? n : 1, 1);
+    v.reserveEssential(params.hypotheses);  // refuses a sample count outside 1..4096
+    DeviceBlock d(sizeof(DMatch) * matches.size());
+    if (n > 0) check_throw(sift_hip_memcpy_h2d(d.p, matches.data(), sizeof(DMatch) * matches.size()), what);
+    const DMatch* dm = static_cast<const DMatch*>(d.p);
+    if (refit == 0)
+        return v.verifyEssentialHost(dm, nullptr, n, query_xy, query_stride, nq, train_xy, train_stride, nt, cam_query,
+                                     cam_train, params);
+    const sift_hip_verify_params p = toAbi(params);
+    VerifyResult r{};
+    std::vector<uint8_t> mask(matches.size());
+    const OnePair l{dm, nullptr, n, query_xy, query_stride, nq, train_xy, train_stride, nt};
+    check_throw(abiCall(sift_hip_verify_essential_host, v.handle(), l, abi(&cam_query), abi(&cam_train), &p,
+                        abi<Fundamental>(&r), nullptr, mask.empty() ? nullptr : mask.data()),
+                what);
+    std::vector<DMatch> inliers;
+    refineHostT<Fundamental>(v.handle(), Fundamental::refineHostName, l, params.max_error, refit, r, mask, &inliers);
+    return geometry<Fundamental>(*abi<Fundamental>(&r), std::move(inliers));
 }
 
 PlanarGeometry verifyAffine(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,

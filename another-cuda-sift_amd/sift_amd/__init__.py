@@ -406,6 +406,16 @@ def lib() -> ctypes.CDLL:
                                                           vp, vp, vp, vp]),
         "sift_hip_refine_homography_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, f, i, vp, vp,
                                                         vp, vp, vp]),
+        "sift_hip_verifier_reserve_essential": (i, [vp, i]),
+        "sift_hip_verify_essential_device": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp, ctypes.POINTER(_VerifyParams),
+                                                 vp, vp, vp, vp, vp]),
+        "sift_hip_verify_essential_host": (i, [vp, vp, vp, i, vp, i, i, vp, i, i, vp, vp, ctypes.POINTER(_VerifyParams),
+                                               ctypes.POINTER(_VerifyResult), vp, vp]),
+        "sift_hip_verify_essential_batched_device": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
+                                                         ctypes.POINTER(_VerifyParams), vp, vp, vp, vp, vp]),
+        "sift_hip_verify_essential_batched_host": (i, [vp, vp, vp, i, ctypes.POINTER(_VerifyPair), i, i, vp, vp,
+                                                       ctypes.POINTER(_VerifyParams), vp, vp, vp]),
+        "sift_hip_verify_essential_hypotheses_host": (i, [vp, vp, vp, vp, i]),
         "sift_hip_verify_affine_device": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams), vp,
                                               vp, vp, vp, vp]),
         "sift_hip_verify_affine_host": (i, [vp, i, vp, vp, i, vp, i, i, vp, i, i, ctypes.POINTER(_VerifyParams),
@@ -1559,9 +1569,11 @@ class Verifier:
     ransac_homography).  Owns all scratch of its calls -- for lists of up to max_matches records and up to
     max_hypotheses hypotheses -- so a device call only launches kernels.  Calls on one verifier must be ordered."""
 
-    def __init__(self, max_matches: int, max_hypotheses: int = 1024, max_pairs: int = 1, device: int = -1):
+    def __init__(self, max_matches: int, max_hypotheses: int = 1024, max_pairs: int = 1, device: int = -1,
+                 essential_samples: int = 0):
         """max_pairs > 1: a verifier for the batched calls (sift_hip_verifier_create_batched) of up to max_pairs pairs
-        whose caps sum to at most max_matches (up to 64 x 65536)."""
+        whose caps sum to at most max_matches (up to 64 x 65536).  essential_samples > 0: the scratch of the essential
+        calls for up to that many samples (sift_hip_verifier_reserve_essential), ten model slots each."""
         self._v = ctypes.c_void_p()
         if max_pairs == 1:
             _check(lib().sift_hip_verifier_create(device, max_matches, max_hypotheses, ctypes.byref(self._v)),
@@ -1573,6 +1585,16 @@ class Verifier:
         self._hypotheses = 0
         self._h_hypotheses = 0
         self._a_hypotheses = 0
+        self._e_hypotheses = 0
+        self.essential_samples = 0
+        if essential_samples:
+            self.reserve_essential(essential_samples)
+
+    def reserve_essential(self, max_samples: int) -> None:
+        """sift_hip_verifier_reserve_essential: allocates, once, what essential calls of up to max_samples (1..4096)
+        samples need for the verifier's max_pairs.  Not capturable; the essential calls after it are."""
+        _check(lib().sift_hip_verifier_reserve_essential(self._v, max_samples), "verifier_reserve_essential")
+        self.essential_samples = max_samples
 
     def __del__(self):
         v = getattr(self, "_v", None)
@@ -1991,6 +2013,82 @@ class Verifier:
                                          "refine_affine_batched_host", AFFINE_RESULT_DTYPE, matches_ptr, counts_ptr, pairs,
                                          verified, max_error, rounds, q_stride, t_stride)
 
+    # --- the essential matrix (sift_hip_verify_essential_*; the rule: include/sift_hip.h, "Essential-matrix
+    # verification", in numpy sift_amd.cv.ransac_essential).  The fundamental methods argument for argument with the two
+    # cameras (fx, fy, cx, cy) behind the positions; `hypotheses` counts 5-point samples, each owning ten model slots,
+    # and is bound by the reservation (essential_samples), not by max_hypotheses.  The record is a VERIFY_RESULT_DTYPE
+    # record whose F is the winner's pixel-space matrix: recover_pose_device, refine_device and the epipolar matchers
+    # take it as it lies.
+
+    def verify_essential_device(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                                nt: int, cam_q, cam_t, result_ptr: int, out_ptr: int = 0, out_count_ptr: int = 0,
+                                mask_ptr: int = 0, max_error: float = 1.5, hypotheses: int = 256, seed: int = 0,
+                                q_stride: int = 3, t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """verify_device for the essential matrix (sift_hip_verify_essential_device): `hypothesis` in the record is the
+        winning slot 10 k + r, valid_hypotheses the number of valid slots; max_error stays in pixels."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        _check(lib().sift_hip_verify_essential_device(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+            t_stride, nt, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p), result_ptr or None, out_ptr or None,
+            out_count_ptr or None, mask_ptr or None, stream), "verify_essential_device")
+        self._e_hypotheses = hypotheses
+
+    def verify_essential_host(self, matches_ptr: int, count_ptr: int, cap: int, q_xy_ptr: int, nq: int, t_xy_ptr: int,
+                              nt: int, cam_q, cam_t, max_error: float = 1.5, hypotheses: int = 256, seed: int = 0,
+                              q_stride: int = 3, t_stride: int = 3, full: bool = False):
+        """Synchronous (sift_hip_verify_essential_host): what verify_host returns -- (F 3 x 3 float32, the inlier
+        records, the winning slot or -1), or with full (the VERIFY_RESULT_DTYPE record, the records, the mask)."""
+        p = _VerifyParams(hypotheses, seed, max_error)
+        r = _VerifyResult()
+        out = np.zeros(max(cap, 0), DMATCH_DTYPE)
+        mask = np.zeros(max(cap, 0), np.uint8)
+        _check(lib().sift_hip_verify_essential_host(
+            self._v, matches_ptr or None, count_ptr or None, cap, q_xy_ptr or None, q_stride, nq, t_xy_ptr or None,
+            t_stride, nt, _cameras(cam_q, 1), _cameras(cam_t, 1), ctypes.byref(p), ctypes.byref(r), _ptr(out),
+            _ptr(mask)), "verify_essential_host")
+        self._e_hypotheses = hypotheses
+        if full:
+            return np.frombuffer(bytes(r), VERIFY_RESULT_DTYPE)[0], out[: r.inliers], mask
+        return np.array(r.F, np.float32).reshape(3, 3), out[: r.inliers], r.hypothesis
+
+    def essential_hypotheses(self):
+        """What the last verify call drew, solved and counted, when it was an essential call of K samples: (samples
+        (K, 5) int32, F (10 K, 9) float32, valid (10 K,) bool -- an invalid slot has F all zero --, counts (10 K,)
+        int32).  Synchronises the device."""
+        K = self._e_hypotheses
+        samples, F, counts = np.zeros((K, 5), np.int32), np.zeros((10 * K, 9), np.float32), np.zeros(10 * K, np.int32)
+        _check(lib().sift_hip_verify_essential_hypotheses_host(self._v, _ptr(samples), _ptr(F), _ptr(counts), K),
+               "verify_essential_hypotheses_host")
+        return samples, F, F.any(1), counts
+
+    def verify_essential_batched_device(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, cams_q, cams_t,
+                                        results_ptr: int, out_ptr: int = 0, out_counts_ptr: int = 0, mask_ptr: int = 0,
+                                        max_error: float = 1.5, hypotheses: int = 256, seed: int = 0, q_stride: int = 3,
+                                        t_stride: int = 3, stream: Optional[int] = None) -> None:
+        """verify_batched_device for the essential matrix (sift_hip_verify_essential_batched_device): one camera per
+        pair and side."""
+        p = _VerifyParams(hypotheses, seed & 0xFFFFFFFF, max_error)
+        table, _ = self._pairs(pairs)
+        P = len(pairs)
+        _check(lib().sift_hip_verify_essential_batched_device(
+            self._v, matches_ptr or None, counts_ptr or None, P, table, q_stride, t_stride, _cameras(cams_q, P),
+            _cameras(cams_t, P), ctypes.byref(p), results_ptr or None, out_ptr or None, out_counts_ptr or None,
+            mask_ptr or None, stream), "verify_essential_batched_device")
+
+    def verify_essential_batched_host(self, matches_ptr: int, counts_ptr: int, pairs: Sequence, cams_q, cams_t,
+                                      max_error: float = 1.5, hypotheses: int = 256, seed: int = 0, q_stride: int = 3,
+                                      t_stride: int = 3, full: bool = False) -> list:
+        """verify_batched_host for the essential matrix (sift_hip_verify_essential_batched_host)."""
+        P = len(pairs)
+        cq, ct = _cameras(cams_q, P), _cameras(cams_t, P)
+
+        def fn(v, matches, counts, n, table, qs, ts, params, res, out, mask):
+            return lib().sift_hip_verify_essential_batched_host(v, matches, counts, n, table, qs, ts, cq, ct, params, res,
+                                                                out, mask)
+
+        return self._batched_host(fn, "verify_essential_batched_host", VERIFY_RESULT_DTYPE, matches_ptr, counts_ptr,
+                                  pairs, max_error, hypotheses, seed, q_stride, t_stride, full)
+
     # --- the relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
     # in numpy sift_amd.cv.recover_pose).  The list, count, cap and positions are the verify call's; result(s) and mask
     # are what it (or a refine call) wrote and are only read.  A camera is (fx, fy, cx, cy).
@@ -2173,13 +2271,14 @@ class Verifier:
                  out[row0[i]: row0[i] + n_out[i]].copy(), cands[i].copy()) for i in range(P)]
 
 
-def _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit):
+def _verify_batched(host, refine, matches_per_pair, xy_per_pair, max_error, hypotheses, seed, refit,
+                    max_hypotheses=None):
     if len(matches_per_pair) != len(xy_per_pair):
         raise ValueError("one (des_xy, src_xy) per match list")
     lists = [np.ascontiguousarray(np.asarray(m, DMATCH_DTYPE)).reshape(-1) for m in matches_per_pair]
     xy = [[np.ascontiguousarray(np.asarray(a, np.float32)[:, :2]) for a in qt] for qt in xy_per_pair]
     rows = sum(len(m) for m in lists)
-    v = Verifier(max(rows, 1), hypotheses, max(len(lists), 1))
+    v = Verifier(max(rows, 1), max_hypotheses or hypotheses, max(len(lists), 1))
     d = DeviceArray.from_numpy(np.concatenate(lists) if lists else np.zeros(0, DMATCH_DTYPE))
     dxy = [[DeviceArray.from_numpy(a) for a in qt] for qt in xy]
     pairs = [(dq.value, len(q), dt.value, len(t), len(m)) for m, (q, t), (dq, dt) in zip(lists, xy, dxy)]
@@ -2274,6 +2373,48 @@ def verifyAffine(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, si
     r, _, mask = v.verify_affine_host(*args, max_error, hypotheses, seed, des_stride, src_stride, True, similarity)
     r, recs, _, _ = v.refine_affine_host(*args, r, mask, max_error, refit, des_stride, src_stride, similarity)
     return r["H"].reshape(3, 3).copy(), recs, int(r["hypothesis"])
+
+
+def verifyEssential(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, cam_q, cam_t, max_error: float = 1.5,
+                    hypotheses: int = 256, seed: int = 0, des_stride: int = 3, src_stride: int = 3, refit: int = 0):
+    """cv::findEssentialMat on a match list: verifyFundamental with 5-point samples under the two cameras
+    (fx, fy, cx, cy) of the des and the src side.  Returns what verifyFundamental returns -- (F 3 x 3 float32 in pixel
+    space, the inlier records in input order, the winning slot 10 k + r or -1 when there are fewer than 5 matches or no
+    sample had a solution) -- and E = Kt^T F Kq (3 x 3 float64, cv.essential_from_fundamental).  `hypotheses` counts
+    samples.  refit = 1..8: Verifier.refine_host on the record -- the 8-point least-squares F, not an essential refit;
+    skip it on near-planar scenes, where that fit is ill-conditioned and can still be accepted."""
+    from . import cv
+
+    m = np.ascontiguousarray(np.asarray(matches, DMATCH_DTYPE))
+    v = Verifier(max(len(m), 1), 1, essential_samples=hypotheses)
+    d = DeviceArray.from_numpy(m)
+    qxy, txy = (p.data() if isinstance(p, DeviceBuffer) else int(p or 0) for p in (des_xy, src_xy))
+    args = (d.value if len(m) else 0, 0, len(m), qxy, n_des, txy, n_src)
+    if not refit:
+        F, recs, hyp = v.verify_essential_host(*args, cam_q, cam_t, max_error, hypotheses, seed, des_stride, src_stride)
+    else:
+        r, _, mask = v.verify_essential_host(*args, cam_q, cam_t, max_error, hypotheses, seed, des_stride, src_stride,
+                                             True)
+        r, recs, _, _ = v.refine_host(*args, r, mask, max_error, refit, des_stride, src_stride)
+        F, hyp = r["F"].reshape(3, 3).copy(), int(r["hypothesis"])
+    return F, recs, hyp, cv.essential_from_fundamental(F, cam_q, cam_t)
+
+
+def verifyEssentialBatched(matches_per_pair: Sequence[np.ndarray], xy_per_pair: Sequence, cams_q, cams_t,
+                           max_error: float = 1.5, hypotheses: int = 256, seed: int = 0, refit: int = 0) -> list:
+    """verifyFundamentalBatched for the essential matrix: cams_q / cams_t one (fx, fy, cx, cy) per pair; per pair what
+    verifyEssential returns."""
+    from . import cv
+
+    def host(v, *args):
+        if not v.essential_samples:
+            v.reserve_essential(hypotheses)
+        return v.verify_essential_batched_host(*args[:3], cams_q, cams_t, *args[3:])
+
+    got = _verify_batched(host, Verifier.refine_batched_host, matches_per_pair, xy_per_pair, max_error, hypotheses, seed,
+                          refit, max_hypotheses=1)
+    cq, ct = np.asarray(cams_q, np.float32).reshape(-1, 4), np.asarray(cams_t, np.float32).reshape(-1, 4)
+    return [(F, recs, hyp, cv.essential_from_fundamental(F, cq[p], ct[p])) for p, (F, recs, hyp) in enumerate(got)]
 
 
 def recoverPose(matches: np.ndarray, des_xy, src_xy, n_des: int, n_src: int, result, mask, cam_q, cam_t,

@@ -1574,6 +1574,321 @@ def recover_pose_homography(matches, q_xy, t_xy, result, mask, cam_q, cam_t, max
     return out
 
 
+# --- Essential-matrix verification: the rule of sift_hip_verify_essential_* (include/sift_hip.h, "Essential-matrix
+# verification") in numpy.  The 5-point solve is float64 from the calibrated rays to the unit-norm pixel-space F, one
+# IEEE operation per array operation in the header's association (no @, dot, einsum, polynomial or linalg routine),
+# vectorised across the samples; the models are rounded to float32 once, and the score is ransac_fundamental's.
+
+ESSENTIAL_SLOTS = 10        # model slots per sample: the degree of the polynomial in z
+ESSENTIAL_BISECTIONS = 48   # bisection steps per bracket with a sign change
+ESSENTIAL_NEWTON = 3        # Newton steps after them, each kept only inside the bracket
+
+# The variables of a constraint polynomial are indexed 0 = x, 1 = y, 2 = z, 3 = 1.  A quadratic's ten coefficients are
+# those of the pairs i <= j in lexicographic order; a cubic's twenty are stored in Nister's column order.
+_ESS_PAIRS = [(i, j) for i in range(4) for j in range(i, 4)]
+_ESS_COLUMNS = ["xxx", "yyy", "xxy", "xyy", "xxz", "xx", "yyz", "yy", "xyz", "xy",
+                "xzz", "xz", "x", "yzz", "yz", "y", "zzz", "zz", "z", ""]
+_ESS_T2 = [[_ESS_PAIRS.index((min(i, j), max(i, j))) for j in range(4)] for i in range(4)]
+_ESS_T3 = [[_ESS_COLUMNS.index("".join("xyz"[v] for v in sorted(_ESS_PAIRS[m] + (k,)) if v < 3)) for k in range(4)]
+           for m in range(10)]
+
+
+def essential_samples(n: int, K: int, seed: int = 0) -> np.ndarray:
+    """The sampler of the essential rule: (K, 5) int32, ransac_samples' draw with 5 indices.  n < 5: every entry -1."""
+    return _samples(n, K, seed, 5)
+
+
+def _ess_first_largest(mag):
+    """The pivot scan on (K, m) magnitudes: the first of the largest, starting from entry 0 and moving on a strictly
+    larger value only (nothing is larger than a NaN at entry 0, and a NaN is larger than nothing)."""
+    flat = np.argmax(np.where(np.isnan(mag), -1.0, mag), axis=1)
+    return np.where(np.isnan(mag[:, 0]), 0, flat)
+
+
+def _ess_null_space(A):
+    """Gauss-Jordan with full pivoting on (K, 5, 9) float64 systems (changed in place): (B (K, 4, 9), ok (K,)), B[:, f]
+    the solution with the free variable at position 5 + f set to 1, the column permutation undone."""
+    K = len(A)
+    ar = np.arange(K)
+    perm = np.tile(np.arange(9), (K, 1))
+    ok = np.ones(K, bool)
+    for c in range(5):
+        flat = _ess_first_largest(np.abs(A[:, c:, c:]).reshape(K, -1))
+        pr, pc = c + flat // (9 - c), c + flat % (9 - c)
+        tmp = A[ar, c, :].copy()
+        A[ar, c, :] = A[ar, pr, :]
+        A[ar, pr, :] = tmp
+        tmp = A[ar, :, c].copy()
+        A[ar, :, c] = A[ar, :, pc]
+        A[ar, :, pc] = tmp
+        tmp = perm[ar, c].copy()
+        perm[ar, c] = perm[ar, pc]
+        perm[ar, pc] = tmp
+        p = A[:, c, c]
+        ok &= (p != 0) & np.isfinite(p)
+        for r in range(5):
+            if r != c:
+                m = A[:, r, c] / p
+                A[:, r, c + 1:] = A[:, r, c + 1:] - m[:, None] * A[:, c, c + 1:]
+    B = np.zeros((K, 4, 9), np.float64)
+    for f in range(4):
+        y = np.zeros((K, 9), np.float64)
+        y[:, 5 + f] = 1
+        for i in range(5):
+            y[:, i] = (-A[:, i, 5 + f]) / A[:, i, i]
+        B[ar[:, None], f, perm] = y
+    return B, ok
+
+
+def _ess_mul11(a, b):
+    """(K, 4) x (K, 4) linear polynomials -> (K, 10) quadratic, each coefficient summed from zero in loop order."""
+    c = np.zeros((len(a), 10), np.float64)
+    for i in range(4):
+        for j in range(4):
+            c[:, _ESS_T2[i][j]] = c[:, _ESS_T2[i][j]] + a[:, i] * b[:, j]
+    return c
+
+
+def _ess_mul21(a, b):
+    """(K, 10) quadratic x (K, 4) linear -> (K, 20) cubic in Nister's column order, summed from zero in loop order."""
+    c = np.zeros((len(a), 20), np.float64)
+    for m in range(10):
+        for k in range(4):
+            c[:, _ESS_T3[m][k]] = c[:, _ESS_T3[m][k]] + a[:, m] * b[:, k]
+    return c
+
+
+def _ess_constraints(B):
+    """The (K, 10, 20) coefficient matrix of det E = 0 (row 0) and of the nine entries of (E E^T - tr(E E^T) / 2) E = 0
+    (rows 1 .. 9, row-major) for E = x X + y Y + z Z + W."""
+    e = [[np.stack([B[:, 0, 3 * r + c], B[:, 1, 3 * r + c], B[:, 2, 3 * r + c], B[:, 3, 3 * r + c]], 1)
+          for c in range(3)] for r in range(3)]
+    M = np.zeros((len(B), 10, 20), np.float64)
+    m0 = _ess_mul11(e[1][1], e[2][2]) - _ess_mul11(e[1][2], e[2][1])
+    m1 = _ess_mul11(e[1][0], e[2][2]) - _ess_mul11(e[1][2], e[2][0])
+    m2 = _ess_mul11(e[1][0], e[2][1]) - _ess_mul11(e[1][1], e[2][0])
+    M[:, 0] = (_ess_mul21(m0, e[0][0]) - _ess_mul21(m1, e[0][1])) + _ess_mul21(m2, e[0][2])
+    G = [[None] * 3 for _ in range(3)]
+    for i in range(3):
+        for j in range(i, 3):
+            G[i][j] = (_ess_mul11(e[i][0], e[j][0]) + _ess_mul11(e[i][1], e[j][1])) + _ess_mul11(e[i][2], e[j][2])
+            G[j][i] = G[i][j]
+    half = 0.5 * ((G[0][0] + G[1][1]) + G[2][2])
+    L = [[G[i][j] - half if i == j else G[i][j] for j in range(3)] for i in range(3)]
+    for i in range(3):
+        for j in range(3):
+            M[:, 1 + 3 * i + j] = (_ess_mul21(L[i][0], e[0][j]) + _ess_mul21(L[i][1], e[1][j])) + _ess_mul21(L[i][2], e[2][j])
+    return M
+
+
+def _ess_reduce(M):
+    """Gauss-Jordan on the first ten columns of (K, 10, 20) with row pivoting (changed in place): (R (K, 6, 10), ok),
+    R the right-hand ten columns of rows 4 .. 9, each divided by its pivot."""
+    K = len(M)
+    ar = np.arange(K)
+    ok = np.ones(K, bool)
+    for c in range(10):
+        pr = c + _ess_first_largest(np.abs(M[:, c:, c]))
+        tmp = M[ar, c, :].copy()
+        M[ar, c, :] = M[ar, pr, :]
+        M[ar, pr, :] = tmp
+        p = M[:, c, c]
+        ok &= (p != 0) & np.isfinite(p)
+        for r in range(10):
+            if r != c:
+                m = M[:, r, c] / p
+                M[:, r, c + 1:] = M[:, r, c + 1:] - m[:, None] * M[:, c, c + 1:]
+    R = np.zeros((K, 6, 10), np.float64)
+    for r in range(6):
+        R[:, r] = M[:, 4 + r, 10:] / M[:, 4 + r, 4 + r][:, None]
+    return R, ok
+
+
+def _ess_conv(a, b):
+    """The product of two polynomials in z, coefficients ascending, (K, la) x (K, lb), summed from zero in loop order."""
+    c = np.zeros((len(a), a.shape[1] + b.shape[1] - 1), np.float64)
+    for i in range(a.shape[1]):
+        for j in range(b.shape[1]):
+            c[:, i + j] = c[:, i + j] + a[:, i] * b[:, j]
+    return c
+
+
+def _ess_horner(c, d, z):
+    """sum c[k] z^k for k <= d: acc = c[d], then acc = acc z + c[k] downwards."""
+    acc = c[:, d]
+    for k in range(d - 1, -1, -1):
+        acc = acc * z + c[:, k]
+    return acc
+
+
+def _ess_value(c, d, z):
+    """_ess_horner where z is finite; at z = -inf / +inf a value with the polynomial's sign there (c[d], negated at
+    -inf for an odd d)."""
+    lead = c[:, d]
+    return np.where(z == -np.inf, -lead if d % 2 else lead, np.where(z == np.inf, lead, _ess_horner(c, d, z)))
+
+
+def _ess_z(s):
+    """The point of the real line that s in [-1, 1] stands for: s / (1 - |s|)."""
+    return s / (1.0 - np.abs(s))
+
+
+def _ess_roots(c):
+    """The real roots of the (K, 11) polynomials by the derivative chain: (z (K, 10), has (K, 10), ok (K,)) -- bracket i
+    of the last level, its root where has, in ascending order.  Brackets are bisected in s = z / (1 + |z|)."""
+    K = len(c)
+    ok = (c[:, 10] != 0) & np.isfinite(c).all(1)
+    D = [None] * 11
+    D[10] = c
+    for d in range(10, 0, -1):
+        D[d - 1] = np.stack([D[d][:, k + 1] * float(k + 1) for k in range(d)], 1)
+    ns = [np.full(K, -1.0), np.full(K, 1.0)]
+    nz = [np.full(K, -np.inf), np.full(K, np.inf)]
+    has = []
+    for d in range(1, 11):
+        f = [_ess_value(D[d], d, z) for z in nz]
+        new_s, new_z, has = [ns[0]], [nz[0]], []
+        for i in range(d):
+            flo, fhi = f[i], f[i + 1]
+            h = ((flo < 0) & (fhi >= 0)) | ((flo > 0) & (fhi <= 0))
+            a, b = ns[i], ns[i + 1]
+            for _ in range(ESSENTIAL_BISECTIONS):
+                mid = 0.5 * (a + b)
+                fm = _ess_value(D[d], d, _ess_z(mid))
+                same = np.where(flo < 0, fm < 0, fm > 0)
+                a, b = np.where(same, mid, a), np.where(same, b, mid)
+            z, za, zb = _ess_z(0.5 * (a + b)), _ess_z(a), _ess_z(b)
+            for _ in range(ESSENTIAL_NEWTON):
+                zn = z - _ess_horner(D[d], d, z) / _ess_horner(D[d - 1], d - 1, z)
+                z = np.where((zn >= za) & (zn <= zb), zn, z)
+            s = z / (1.0 + np.abs(z))
+            s = np.where(s < a, a, s)
+            s = np.where(s > b, b, s)
+            new_s.append(np.where(h, s, ns[i]))
+            new_z.append(np.where(h, z, nz[i]))
+            has.append(h)
+        new_s.append(ns[-1])
+        new_z.append(nz[-1])
+        ns, nz = new_s, new_z
+    assert len(nz) == 12 and nz[1].shape == (K,)
+    return np.stack(nz[1:11], 1), np.stack(has, 1), ok
+
+
+def _essential_from_5(q, t, cam_q, cam_t):
+    """(K, 5, 2) float32 pairs -> (F (K, 10, 9) float32, valid (K, 10), E (K, 10, 9) float64, z (K, 10) float64)."""
+    fxq, fyq, cxq, cyq = cam_q
+    fxt, fyt, cxt, cyt = cam_t
+    K = len(q)
+    with np.errstate(all="ignore"):
+        qx = (q[:, :, 0].astype(np.float64) - cxq) / fxq
+        qy = (q[:, :, 1].astype(np.float64) - cyq) / fyq
+        tx = (t[:, :, 0].astype(np.float64) - cxt) / fxt
+        ty = (t[:, :, 1].astype(np.float64) - cyt) / fyt
+        A = np.stack([tx * qx, tx * qy, tx, ty * qx, ty * qy, ty, qx, qy, np.ones_like(qx)], axis=2)  # (K, 5, 9)
+        B, ok = _ess_null_space(A)
+        R, ok2 = _ess_reduce(_ess_constraints(B))
+        ok &= ok2
+        # The 3 x 3 matrix in z over (x, y, 1): row i from rows e = R[2 i], f = R[2 i + 1] as e - z f.
+        P = [[np.stack([e[:, 3 * v + 2], e[:, 3 * v + 1] - f[:, 3 * v + 2], e[:, 3 * v] - f[:, 3 * v + 1], -f[:, 3 * v]], 1)
+              for v in range(2)] +
+             [np.stack([e[:, 9], e[:, 8] - f[:, 9], e[:, 7] - f[:, 8], e[:, 6] - f[:, 7], -f[:, 6]], 1)]
+             for e, f in ((R[:, 0], R[:, 1]), (R[:, 2], R[:, 3]), (R[:, 4], R[:, 5]))]
+        det = (_ess_conv(_ess_conv(P[1][1], P[2][2]) - _ess_conv(P[1][2], P[2][1]), P[0][0])
+               - _ess_conv(_ess_conv(P[1][0], P[2][2]) - _ess_conv(P[1][2], P[2][0]), P[0][1])) \
+            + _ess_conv(_ess_conv(P[1][0], P[2][1]) - _ess_conv(P[1][1], P[2][0]), P[0][2])
+        zs, has, ok3 = _ess_roots(det)
+        ok &= ok3
+        F = np.zeros((K, 10, 9), np.float32)
+        Es = np.zeros((K, 10, 9), np.float64)
+        Z = np.zeros((K, 10), np.float64)
+        valid = np.zeros((K, 10), bool)
+        slot = np.zeros(K, np.int64)
+        for i in range(10):
+            z = zs[:, i]
+            b = [[_ess_horner(P[r][v], 3 if v < 2 else 4, z) for v in range(3)] for r in range(3)]
+            # Cramer's rule on the row pair (0, 1), (0, 2) or (1, 2) with the largest |d|, the first on a tie.
+            d = x = y = None
+            for u, v in ((0, 1), (0, 2), (1, 2)):
+                du = b[u][0] * b[v][1] - b[u][1] * b[v][0]
+                xu = b[u][1] * b[v][2] - b[u][2] * b[v][1]
+                yu = b[u][2] * b[v][0] - b[u][0] * b[v][2]
+                if d is None:
+                    d, x, y = du, xu, yu
+                else:
+                    better = np.abs(du) > np.abs(d)
+                    d, x, y = np.where(better, du, d), np.where(better, xu, x), np.where(better, yu, y)
+            x, y = x / d, y / d
+            E = ((x[:, None] * B[:, 0] + y[:, None] * B[:, 1]) + z[:, None] * B[:, 2]) + B[:, 3]
+            # F = Kt^-T E Kq^-1: M = E Kq^-1 column by column, then Kt^-T M row by row.
+            M = np.zeros((K, 3, 3), np.float64)
+            E3 = E.reshape(K, 3, 3)
+            M[:, :, 0] = E3[:, :, 0] / fxq
+            M[:, :, 1] = E3[:, :, 1] / fyq
+            M[:, :, 2] = E3[:, :, 2] - (M[:, :, 0] * cxq + M[:, :, 1] * cyq)
+            G = np.zeros((K, 3, 3), np.float64)
+            G[:, 0] = M[:, 0] / fxt
+            G[:, 1] = M[:, 1] / fyt
+            G[:, 2] = M[:, 2] - (G[:, 0] * cxt + G[:, 1] * cyt)
+            G = G.reshape(K, 9)
+            ss = G[:, 0] * G[:, 0]
+            for j in range(1, 9):
+                ss = ss + G[:, j] * G[:, j]
+            f32 = (G / np.sqrt(ss)[:, None]).astype(np.float32)
+            use = ok & has[:, i]
+            good = use & np.isfinite(f32).all(1)
+            rows = np.nonzero(good)[0]
+            F[rows, slot[rows]] = f32[rows]
+            Es[rows, slot[rows]] = E[rows]
+            Z[rows, slot[rows]] = z[rows]
+            valid[rows, slot[rows]] = True
+            slot = slot + use
+    assert A.dtype == np.float64 and det.dtype == np.float64 and det.shape == (K, 11)
+    return F, valid, Es, Z
+
+
+def essential_from_5(q_xy5, t_xy5, cam_q, cam_t, calibrated: bool = False):
+    """The solver of the essential rule: the up to ten pixel-space models F = Kt^-T E Kq^-1 (unit Frobenius norm,
+    float32) of 5 pairs under the two cameras (fx, fy, cx, cy).  q_xy5 / t_xy5: (5, 2) -> (F (10, 9), valid (10,)), or
+    (K, 5, 2) -> (F (K, 10, 9), valid (K, 10)).  Slot r holds the r-th real root in ascending order; a slot without a
+    root, a non-finite model and every slot of a sample without a solution are zero and invalid.  With `calibrated`
+    the float64 E of every slot (as solved: x X + y Y + z Z + W, not normalised) and its root z follow."""
+    cq, ct = _camera(cam_q, "cam_q"), _camera(cam_t, "cam_t")
+    q = np.asarray(q_xy5, np.float32)
+    t = np.asarray(t_xy5, np.float32)
+    single = q.ndim == 2
+    out = _essential_from_5(q.reshape(-1, 5, 2), t.reshape(-1, 5, 2), cq, ct)
+    out = out if calibrated else out[:2]
+    return tuple(o[0] for o in out) if single else out
+
+
+def ransac_essential(matches, q_xy, t_xy, cam_q, cam_t, max_error=1.5, K: int = 256, seed: int = 0) -> dict:
+    """The whole operation (sift_hip_verify_essential_*) in numpy.  Returns ransac_fundamental's dict over the 10 K
+    model slots: F (the winner's pixel-space matrix), inliers, hypothesis (the slot 10 k + r, -1: none), matches,
+    valid_hypotheses (valid slots), mask, list, samples (K, 5), Fs (10 K, 9), valid (10 K,), counts (10 K,)."""
+    from . import DMATCH_DTYPE
+
+    cq, ct = _camera(cam_q, "cam_q"), _camera(cam_t, "cam_t")
+    matches = np.asarray(matches, DMATCH_DTYPE)
+    n = len(matches)
+    S = ESSENTIAL_SLOTS * K
+    pts = _match_points(matches, q_xy, t_xy)
+    samples = essential_samples(n, K, seed)
+    if n >= 5:
+        Fs, valid, _, _ = _essential_from_5(pts[samples][:, :, :2], pts[samples][:, :, 2:], cq, ct)
+        Fs, valid = Fs.reshape(S, 9), valid.reshape(S)
+        passes = _sampson_pass(pts, Fs, max_error) & valid[:, None]
+    else:
+        Fs, valid, passes = np.zeros((S, 9), np.float32), np.zeros(S, bool), np.zeros((S, n), bool)
+    counts = passes.sum(1).astype(np.int32)
+    hyp = -1
+    if valid.any():
+        hyp = int(np.argmax(np.where(valid, counts, -1)))  # the first of the largest: ties to the lowest slot
+    mask = passes[hyp].astype(np.uint8) if hyp >= 0 else np.zeros(n, np.uint8)
+    return dict(F=Fs[hyp].copy() if hyp >= 0 else np.zeros(9, np.float32), inliers=int(counts[hyp]) if hyp >= 0 else 0,
+                hypothesis=hyp, matches=n, valid_hypotheses=int(valid.sum()), mask=mask, list=matches[mask != 0],
+                samples=samples, Fs=Fs, valid=valid, counts=counts)
+
+
 def to_cv_keypoints(final_kpts, final_features, size: int = -1):
     import cv2
 

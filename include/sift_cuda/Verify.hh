@@ -259,6 +259,32 @@ public:
                                              int rounds, std::vector<AffineResult>& results, std::vector<uint8_t>& mask,
                                              std::vector<DMatch>* out = nullptr, std::vector<int>* out_counts = nullptr);
 
+    // The essential matrix (sift_hip_verify_essential_*; the rule: include/sift_hip.h, "Essential-matrix
+    // verification"): the fundamental verify calls argument for argument with the two cameras behind the list.
+    // params.hypotheses counts 5-point samples; each owns ten model slots, and the record's hypothesis is the winning
+    // slot 10 k + r.  The record's F is the winner's pixel-space matrix, so recoverPose*, refine* and the epipolar
+    // matchers take it as it lies.  reserveEssential(max_samples), 1..4096, allocates the calls' scratch once (not
+    // capturable); a call without it, or with more samples than it, throws.
+    void reserveEssential(int max_samples);
+    void verifyEssentialDevice(const DMatch* matches, const int* count, int cap, const float* query_xy, int query_stride,
+                               int nq, const float* train_xy, int train_stride, int nt, const Camera& cam_query,
+                               const Camera& cam_train, const VerifyParams& params, VerifyResult* result,
+                               DMatch* out = nullptr, int* out_count = nullptr, uint8_t* mask = nullptr,
+                               void* stream = nullptr);
+    TwoViewGeometry verifyEssentialHost(const DMatch* matches, const int* count, int cap, const float* query_xy,
+                                        int query_stride, int nq, const float* train_xy, int train_stride, int nt,
+                                        const Camera& cam_query, const Camera& cam_train, const VerifyParams& params = {});
+    void verifyEssentialBatchedDevice(const DMatch* matches, const int* counts, const std::vector<VerifyPair>& pairs,
+                                      int query_stride, int train_stride, const std::vector<Camera>& cams_query,
+                                      const std::vector<Camera>& cams_train, const VerifyParams& params,
+                                      VerifyResult* results, DMatch* out = nullptr, int* out_counts = nullptr,
+                                      uint8_t* mask = nullptr, void* stream = nullptr);
+    std::vector<TwoViewGeometry> verifyEssentialBatchedHost(const DMatch* matches, const int* counts,
+                                                            const std::vector<VerifyPair>& pairs, int query_stride,
+                                                            int train_stride, const std::vector<Camera>& cams_query,
+                                                            const std::vector<Camera>& cams_train,
+                                                            const VerifyParams& params = {});
+
     // The relative pose from a verified fundamental matrix (sift_hip_recover_pose_*; the rule: include/sift_hip.h,
     // "Relative pose from a verified fundamental matrix"): cv::recoverPose on the list, count and positions of the
     // verify call that wrote *result and mask (device memory, read only).  pose: a device record; mask_out (cap bytes,
@@ -350,6 +376,13 @@ PlanarGeometry verifyHomography(const std::vector<DMatch>& matches, const float*
 PlanarGeometry verifyAffine(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
                             int nt, AffineModel model, const VerifyParams& params = {}, int query_stride = 3,
                             int train_stride = 3, int refit = 0);
+
+// The one shot for the essential matrix (cv::findEssentialMat): the geometry's F is the pixel-space matrix of the
+// winning slot, E = Kt^T F Kq.  `refit` rounds of Verifier::refineHost follow -- the 8-point least-squares F, not an
+// essential refit; skip it on near-planar scenes.
+TwoViewGeometry verifyEssential(const std::vector<DMatch>& matches, const float* query_xy, int nq, const float* train_xy,
+                                int nt, const Camera& cam_query, const Camera& cam_train, const VerifyParams& params = {},
+                                int query_stride = 3, int train_stride = 3, int refit = 0);
 
 // The all-in-one beside verifyFundamental: uploads the list and recovers the pose of a verified F (9 floats, row-major,
 // x_train^T F x_query = 0) over the records `mask` marks (empty: every record).

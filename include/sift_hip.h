@@ -2173,6 +2173,167 @@ int sift_hip_recover_pose_homography_batched_host(sift_hip_verifier_t v, const s
                                                   float* points_host, sift_hip_dmatch* out_host, int* out_counts_host,
                                                   sift_hip_plane_candidate* candidates_host);
 
+/* --- Essential-matrix verification: 5-point RANSAC -------------------------------
+ *
+ * The model of a calibrated pair (cv::findEssentialMat, the call OpenCV documents
+ * in front of cv::recoverPose).  The same fixed budget of K samples, but a sample
+ * is 5 matches instead of 8 -- at 30 % true pairs a 5-point sample is clean once
+ * in about 400 draws, an 8-point sample once in about 15,000 -- and the solver is
+ * not degenerate on a dominant plane with some structure off it.  The cameras
+ * are the pose calls' sift_hip_camera, host memory, one per side (one per pair
+ * and side in the batched form), under the pose calls' rules.
+ *
+ * A sample has up to ten solutions, so it owns ten model slots: slot 10 k + r is
+ * root r of sample k.  Every slot holds a pixel-space fundamental matrix
+ * F = Kt^-T E Kq^-1, so max_error stays in pixels, the score and the selection
+ * are the fundamental rule's over the 10 K slots, and the record is a
+ * sift_hip_verify_result that sift_hip_recover_pose_*, sift_hip_refine_fundamental_*
+ * and the epipolar matchers take as it lies.
+ *
+ * The rule.  float64 from the rays to the unit-norm F, every operation rounded to
+ * nearest, one at a time, in the written association; nothing fused; division and
+ * square root correctly rounded and no other function; no iteration whose length
+ * depends on the data.  sift_amd.cv.ransac_essential is the same rule in numpy;
+ * the device equals it byte for byte.
+ *
+ * Input and sampling.  As for the other models; the sampler of the fundamental
+ * rule with m = 5 draws.  With n < 5 nothing is drawn, every sample index is -1
+ * and every slot is invalid.
+ *
+ * Rays.  With the cameras' float32 values widened to float64, for sample i
+ *   qx = (qx - cxq) / fxq;  qy = (qy - cyq) / fyq;  likewise tx, ty under cam_train.
+ *
+ * Null space.  Row i of the 5 x 9 system is the 8-point system's row
+ *   (tx*qx, tx*qy, tx, ty*qx, ty*qy, ty, qx, qy, 1).
+ * Gauss-Jordan with full pivoting: at step c = 0..4 the pivot is the largest
+ * |entry| of rows >= c and columns >= c, the scan starting at (c, c) in row-major
+ * order and moving on a strictly larger value only (solve_8x9's rule); rows c and
+ * pr are exchanged, then columns c and pc (and the permutation); a pivot that is
+ * zero or not finite: no model from this sample; then for every row r != c
+ *   m = A[r][c] / p;  A[r][j] = A[r][j] - m * A[c][j],  j > c.
+ * The basis vector of free position 5 + f (f = 0..3) is y[5 + f] = 1, the other
+ * free positions 0, y[i] = (-A[i][5 + f]) / A[i][i] for i < 5, with the column
+ * permutation undone.  f = 0..3 are X, Y, Z, W (row-major 3 x 3); no SVD, no
+ * orthonormalisation.
+ *
+ * Constraints.  E = x X + y Y + z Z + W: entry i is the linear polynomial
+ * (X[i], Y[i], Z[i], W[i]) over the variables 0 = x, 1 = y, 2 = z, 3 = 1.  A
+ * product of two linear polynomials a, b is the quadratic c over the pairs u <= v
+ * in lexicographic order: c = 0, then for u = 0..3, v = 0..3 in that order
+ *   c[pair(u, v)] = c[pair(u, v)] + a[u] * b[v].
+ * A quadratic a times a linear b is the cubic c, likewise from zero over the
+ * quadratic's index m = 0..9 and v = 0..3, stored in Nister's column order
+ *   x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.
+ * Sums and differences of polynomials are coefficient by coefficient.  The ten
+ * rows of the 10 x 20 matrix:
+ *   row 0 (det E):  (m0 E00 - m1 E01) + m2 E02  with  m0 = E11 E22 - E12 E21,
+ *     m1 = E10 E22 - E12 E20,  m2 = E10 E21 - E11 E20;
+ *   G = E E^T:  G[i][j] = (Ei0 Ej0 + Ei1 Ej1) + Ei2 Ej2 for i <= j, G[j][i] = G[i][j];
+ *   h = 0.5 * ((G00 + G11) + G22);  L = G with h subtracted on the diagonal;
+ *   row 1 + 3 i + j:  (Li0 E0j + Li1 E1j) + Li2 E2j
+ * -- the nine entries of (E E^T - tr(E E^T) / 2) E, half of 2 E E^T E - tr(E E^T) E.
+ * Gauss-Jordan on the first ten columns with row pivoting: at step c = 0..9 the
+ * pivot is the largest |entry| of column c in rows >= c, the scan starting at row
+ * c and moving on a strictly larger value only; the same exchange, pivot test
+ * and elimination of every other row over the columns j > c.  Rows 4..9 (x^2z,
+ * x^2, y^2z, y^2, xyz, xy) then give, with u = row 4 + 2 i and v = row 5 + 2 i,
+ * each right-hand entry divided by its row's pivot, row i = u - z v of the 3 x 3
+ * polynomial matrix B(z) over (x, y, 1), coefficients ascending in z:
+ *   Bi0 = (u[12], u[11] - v[12], u[10] - v[11], -v[10])
+ *   Bi1 = (u[15], u[14] - v[15], u[13] - v[14], -v[13])
+ *   Bi2 = (u[19], u[18] - v[19], u[17] - v[18], u[16] - v[17], -v[16]).
+ * A product of polynomials in z is c = 0, then c[i + j] = c[i + j] + a[i] * b[j]
+ * for i over a, j over b.  The degree-10 polynomial is
+ *   p = ((B11 B22 - B12 B21) B00 - (B10 B22 - B12 B20) B01) + (B10 B21 - B11 B20) B02
+ * with every product in the written order of its factors.
+ *
+ * Real roots, by the derivative chain.  A p whose p_10 is zero, or with a
+ * coefficient that is not finite: no model from this sample.  Each derivative's
+ * coefficient is the previous one's times its exponent.  A polynomial c of degree
+ * d is evaluated by Horner's rule, acc = c[d], then acc = acc * z + c[k]
+ * downwards; at z = +inf its value is c[d] and at z = -inf c[d], negated for an
+ * odd d (only the sign is used).  The real line is searched through
+ * s = z / (1 + |z|) in [-1, 1], z(s) = s / (1 - |s|): bisection in s needs no
+ * root bound and resolves a root of any magnitude to the same relative width.
+ * For d = 1..10, with c the derivative of degree d (d = 10: p itself) and the
+ * nodes -inf (s = -1), the d - 1 results of level d - 1, +inf (s = 1): bracket
+ * i = 0..d-1 is (lo, hi] = (node i, node i + 1] and holds a root when
+ * (c(lo) < 0 and c(hi) >= 0) or (c(lo) > 0 and c(hi) <= 0).  Then
+ *   a = s(lo), b = s(hi); 48 times: mid = 0.5 * (a + b); when c(z(mid)) has
+ *     c(lo)'s strict sign a = mid, else b = mid;
+ *   z = z(0.5 * (a + b)), za = z(a), zb = z(b); 3 times: zn = z - c(z) / c'(z),
+ *     kept when za <= zn <= zb;
+ * and the bracket's result is z, with s = z / (1 + |z|) held into [a, b]; a
+ * bracket without a root hands lo on, so the nodes stay sorted and every later
+ * bracket is still one on which c is monotonic.  The roots of p are the results
+ * of the brackets of level 10 that held one, in bracket order, which is
+ * ascending.  No Sturm chain, no companion matrix, no convergence test.
+ *
+ * Back-substitution.  For root z with b_rc = B_rc(z), on the row pair (u, v) of
+ * (0, 1), (0, 2), (1, 2) with the largest |d|, the first on a tie:
+ *   d = bu0*bv1 - bu1*bv0;  x = (bu1*bv2 - bu2*bv1) / d;  y = (bu2*bv0 - bu0*bv2) / d
+ *   E[i] = ((x*X[i] + y*Y[i]) + z*Z[i]) + W[i]
+ *   M = E Kq^-1:  M[r][0] = E[r][0] / fxq;  M[r][1] = E[r][1] / fyq;
+ *                 M[r][2] = E[r][2] - (M[r][0]*cxq + M[r][1]*cyq)
+ *   F = Kt^-T M:  F[0][c] = M[0][c] / fxt;  F[1][c] = M[1][c] / fyt;
+ *                 F[2][c] = M[2][c] - (F[0][c]*cxt + F[1][c]*cyt)
+ * scaled to unit Frobenius norm (the squares summed in index order) and rounded
+ * to float32.  The r-th root found goes to slot 10 k + r; a root whose F is not
+ * finite keeps its slot, zero and invalid; slots past the last root, and every
+ * slot of a sample without a model, are zero and invalid.
+ *
+ * Score, selection and output.  The fundamental rule's over the 10 K slots:
+ * `hypothesis` is the winning slot 10 k + r (sample k = hypothesis / 10),
+ * valid_hypotheses the number of valid slots, ties go to the lowest slot; n < 5
+ * gives the empty result, status success.
+ *
+ * Scratch.  A verifier serves essential calls after
+ * sift_hip_verifier_reserve_essential(v, max_samples), 1 <= max_samples <= 4096,
+ * which allocates the samples and the 10-slot model, flag and count arrays for
+ * the verifier's max_pairs, once (a second call is SIFT_HIP_ERR_STATE; not
+ * capturable).  After it an essential call allocates nothing and is capturable
+ * like the rest.  An essential call on a verifier that has not reserved, or with
+ * params->hypotheses above the reservation, is SIFT_HIP_ERR_STATE with nothing
+ * written; params->hypotheses counts samples and is not bound by the verifier's
+ * max_hypotheses.  The other calls and their scratch are untouched.
+ *
+ * Not here: an essential refit.  sift_hip_refine_fundamental_* on the record is
+ * the 8-point least-squares F, accepted when it counts at least as many records;
+ * on a near-planar scene that fit is ill-conditioned and can still pass, because
+ * it explains the plane.  Planar callers should skip it. */
+int sift_hip_verifier_reserve_essential(sift_hip_verifier_t v, int max_samples);
+/* The fundamental calls, argument for argument, with the two cameras in front of
+ * the params.  The same arguments are refused, with nothing launched, and so are
+ * a null camera pointer, fx or fy not > 0 or not finite, cx or cy not finite. */
+int sift_hip_verify_essential_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                     const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                     int train_stride, int nt, const sift_hip_camera* cam_query,
+                                     const sift_hip_camera* cam_train, const sift_hip_verify_params* params,
+                                     sift_hip_verify_result* result, sift_hip_dmatch* out, int* out_count, uint8_t* mask,
+                                     void* stream);
+int sift_hip_verify_essential_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* count, int cap,
+                                   const float* query_xy, int query_stride, int nq, const float* train_xy,
+                                   int train_stride, int nt, const sift_hip_camera* cam_query,
+                                   const sift_hip_camera* cam_train, const sift_hip_verify_params* params,
+                                   sift_hip_verify_result* result_host, sift_hip_dmatch* out_host, uint8_t* mask_host);
+/* Pair p under cam_query[p] / cam_train[p] with the seed `seed + p`: its bytes
+ * are the single call's. */
+int sift_hip_verify_essential_batched_device(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                             int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                             const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                             const sift_hip_verify_params* params, sift_hip_verify_result* results,
+                                             sift_hip_dmatch* out, int* out_counts, uint8_t* mask, void* stream);
+int sift_hip_verify_essential_batched_host(sift_hip_verifier_t v, const sift_hip_dmatch* matches, const int* counts,
+                                           int P, const sift_hip_verify_pair* pairs, int query_stride, int train_stride,
+                                           const sift_hip_camera* cam_query, const sift_hip_camera* cam_train,
+                                           const sift_hip_verify_params* params, sift_hip_verify_result* results_host,
+                                           sift_hip_dmatch* out_host, uint8_t* mask_host);
+/* samples (cap x 5), F (10 cap x 9, zero rows: invalid slots) and counts (10 cap)
+ * of the first min(cap, K) samples.  SIFT_HIP_ERR_STATE unless the verifier's
+ * last verify call was a single-pair essential call; the other getters refuse
+ * after one in the same way. */
+int sift_hip_verify_essential_hypotheses_host(sift_hip_verifier_t v, int* samples, float* F, int* counts, int cap);
+
 /* --- Multi-GPU(the reference binds one Detector to the current
  * device, Detector.hh:26-29, and has no multi-GPU path) ----------------------- */
 
